@@ -86,7 +86,8 @@ def cpu_baseline(sample_iters=3):
         pass
     # kind "port": /root/reference does not exist on the GPU box, so what is timed is oracle/unet3d_oracle.py — the reference's
     # module graph restated on the same ATen CPU operators.  tests/test_oracle.py::test_port_and_live_reference_same_speed times
-    # both side by side in the build container (same numerics to 1e-6, same throughput within noise).
+    # it side by side with this project's drop-in module tree on the CPU (same numerics to 1e-6, same throughput within noise);
+    # the drop-in is pinned to the reference numerically by the golden tests, the reference's own speed is not measured there.
     return {"value": round(1.0 / med, 4), "unit": "patches/s", "cores": torch.get_num_threads(), "kind": "port",
             "sample": f"PORT of the reference path (oracle/unet3d_oracle.py, not the reference module tree itself): batch "
                       f"1x1x{PATCH[0]}x{PATCH[1]}x{PATCH[2]} fwd+bwd, 1 warm-up + {sample_iters} timed iterations (median {med:.3f} s), "
@@ -109,6 +110,21 @@ def pmc_traffic(family):
         return round(fam["bytes_per_launch"]), os.path.relpath(files[-1], ROOT)
     except Exception:
         return None, None
+
+
+def dump_outputs(out_dir, probs, logits, loss, model):
+    """--dump-outputs: what one timed step hands its caller (probabilities, logits, loss) and leaves in the model (each parameter's
+    gradient and its value after the optimizer step), as float32 .npy files named after the array."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"probs": probs, "logits": logits, "loss": loss}
+    for k, p in model.named_parameters():
+        arrays["param." + k] = p
+        if p.grad is not None:
+            arrays["grad." + k] = p.grad
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().float().cpu().numpy())
 
 
 def self_launch(n):
@@ -144,7 +160,14 @@ def main():
     ap.add_argument("--compute-dtype", default="fp32", choices=["fp32", "fp32_split"],
                     help="arithmetic of the TIMED model (default fp32 = fp32 MFMA; fp32_split is reported as an extra leg anyway)")
     ap.add_argument("--no-extras", action="store_true", help="skip the extra legs outside the contract (reference step order, fp32_split, partial bf16)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the LAST timed step computed as DIR/<name>.npy (float32): probs, logits, "
+                         "loss, and per parameter its gradient (grad.<name>) and its value after the Adam update (param.<name>); "
+                         "~47 MB at the default batch.  Under --gpus N only rank 0 writes: probs / logits / loss of its own shard "
+                         "(seed 1000 + rank), parameters and gradients after the all-reduce.  Inputs and initial weights are seeded, so two builds compare output for output")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -200,7 +223,9 @@ def main():
     ab_copy = int(os.environ.get("U3D_AB_COPY", "0"))
     ab_buf = torch.empty((2, ab_copy << 18), device=dev) if ab_copy else None
 
-    def step():
+    kept = []  # (probs, logits) of the step run with keep=True: the last timed step when --dump-outputs is given
+
+    def step(keep=False):
         if ab_sleep:
             torch.cuda._sleep(ab_sleep)
         if ab_buf is not None:
@@ -210,6 +235,8 @@ def main():
         opt.zero_grad(set_to_none=True)
         loss.backward()
         opt.step()
+        if keep:
+            kept[:] = [probs, logits]
         return loss
 
     # u3d_conv3d_ex is u3d_conv3d with a scratch buffer, u3d_conv3d_ex_reps that with replica rows of the statistics table (same kernels):
@@ -290,7 +317,7 @@ def main():
     for i_step in range(args.steps):
         if prof is not None:
             nat.profiler = prof if i_step % bracket_every == bracket_phase else None
-        loss = step()
+        loss = step(keep=args.dump_outputs is not None and i_step == args.steps - 1)
         if os.environ.get("U3D_BENCH_HOST_TRACE") == "1":
             host_marks.append(time.perf_counter() - t0)  # (debugging aid: when each step's launches were all enqueued)
     barrier()
@@ -298,6 +325,10 @@ def main():
     if host_marks and rank == 0:
         print("host enqueue marks (ms):", [round(1000 * v, 1) for v in host_marks], "elapsed", round(1000 * elapsed, 1), file=sys.stderr)
     nat.profiler = None
+    if args.dump_outputs is not None and rank == 0:
+        # copied out now, before any untimed step below (profiler table, extra legs) changes the model or reuses a buffer
+        dump_outputs(args.dump_outputs, kept[0], kept[1], loss, model)
+    kept.clear()
     if use_dist:
         tmax = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)

@@ -13,7 +13,7 @@ from pytorch3dunet_amd import _native as nat
 from pytorch3dunet_amd.unet3d import buildingblocks as bb
 from pytorch3dunet_amd.unet3d import model as M
 from pytorch3dunet_amd.unet3d.utils import get_class, number_of_features_per_level
-from ref_import import import_reference, reference_available
+from reference_records import STATE_DICT_CFGS, misc, state_dict_id
 
 ALL_CFGS = [
     dict(name="UNet3D", in_channels=1, out_channels=1, f_maps=16),
@@ -129,20 +129,22 @@ def test_golden_state_dict_loads_strict_and_cpu_forward_matches(name):
     assert torch.equal(single, probs)
 
 
-@pytest.mark.skipif(not reference_available(), reason="/root/reference only exists in the build container")
 @pytest.mark.parametrize("cfg", ALL_CFGS, ids=lambda c: c["name"] + str(c["in_channels"]))
 def test_state_dict_keys_shapes_match_reference(cfg):
-    ref = import_reference()
-    torch.manual_seed(0)
-    r = ref.get_model(dict(cfg))
+    """key order, shapes and the bytes of the seeded initialisation (SHA-256) of the reference's state_dict, recorded by
+    tests/golden/make_reference_records.py; a state_dict with exactly those keys and shapes loads strictly"""
+    import hashlib
+
+    assert cfg in STATE_DICT_CFGS
+    rs = misc("sd/" + state_dict_id(cfg))  # [[key, shape, sha256 of the tensor's bytes], ...]
     torch.manual_seed(0)
     m = M.get_model(dict(cfg))
-    rs, ms = r.state_dict(), m.state_dict()
-    assert list(rs.keys()) == list(ms.keys())
-    for k in rs:
-        assert rs[k].shape == ms[k].shape
-        assert torch.equal(rs[k], ms[k]), f"seeded init differs at {k}"
-    m.load_state_dict(rs, strict=True)
+    ms = m.state_dict()
+    assert [k for k, _, _ in rs] == list(ms.keys())
+    for k, shape, digest in rs:
+        assert list(ms[k].shape) == shape
+        assert hashlib.sha256(ms[k].contiguous().numpy().tobytes()).hexdigest() == digest, f"seeded init differs at {k}"
+    m.load_state_dict({k: torch.zeros(shape, dtype=ms[k].dtype) for k, shape, _ in rs}, strict=True)
 
 
 def test_reference_property_tests_on_cpu():

@@ -173,38 +173,3 @@ def test_fused_bce_dice_vs_cpu_oracle(shape):
     # run-to-run reproducible loss value (f64 accumulation)
     val2 = L.BCEDiceLoss(alpha=0.7)(x.detach(), target.cuda())
     assert abs(val2.item() - val.item()) <= 1e-7 * max(1.0, abs(val.item()))
-
-
-@pytest.mark.skipif(not os.path.isdir("/root/reference/pytorch3dunet"), reason="live reference only in the build container")
-def test_live_reference_factory_with_the_fused_family_patched_in():
-    """the imported reference's `get_loss_criterion` (losses.py:273-345) after `install_fused`: the fused classes for the three
-    fused names (also inside its own wrappers), its own classes for every other name, its own error for unknown names"""
-    import importlib
-    import sys
-
-    from ref_import import import_reference
-
-    import_reference()
-    sys.modules.pop("pytorch3dunet.unet3d.losses", None)
-    R = importlib.import_module("pytorch3dunet.unet3d.losses")
-    assert R is not L and R.BCEDiceLoss is not L.BCEDiceLoss
-    try:
-        a = L.get_loss_criterion({"device": "cpu", "loss": {"name": "BCEDiceLoss", "alpha": 0.3}})
-        assert type(a) is L.BCEDiceLoss and a.alpha == 0.3 and R.BCEDiceLoss is L.BCEDiceLoss and R.DiceLoss is L.DiceLoss
-        w = R.get_loss_criterion({"device": "cpu", "loss": {"name": "DiceLoss", "ignore_index": -1, "skip_last_target": True}})
-        assert type(w) is R.SkipLastTargetChannelWrapper and type(w.loss) is R.MaskingLossWrapper and type(w.loss.loss) is L.DiceLoss
-        x = torch.randn(1, 2, 3, 4, 4)
-        t = (torch.rand(1, 3, 3, 4, 4) > 0.5).float()
-        t[0, 0, 0, 0, 0] = -1
-        assert torch.isfinite(w(x, t))
-        b = R.get_loss_criterion({"device": "cpu", "loss": {"name": "BCEWithLogitsLoss", "pos_weight": [2.0]}})
-        assert type(b) is L.BCEWithLogitsLoss and float(b.pos_weight) == 2.0
-        for n in ("CrossEntropyLoss", "WeightedCrossEntropyLoss", "GeneralizedDiceLoss", "MSELoss", "SmoothL1Loss", "L1Loss"):
-            c = L.get_loss_criterion({"device": "cpu", "loss": {"name": n}})
-            assert type(c).__module__ in (R.__name__, "torch.nn.modules.loss"), (n, type(c))
-        with pytest.raises(RuntimeError):
-            L.get_loss_criterion({"device": "cpu", "loss": {"name": "NoSuchLoss"}})
-        with pytest.raises(AssertionError):
-            L.get_loss_criterion({"loss": {"name": "DiceLoss"}})
-    finally:
-        sys.modules.pop("pytorch3dunet.unet3d.losses", None)  # later tests import a fresh, unpatched reference module

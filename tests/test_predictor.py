@@ -1,6 +1,6 @@
 """Sliding-window inference: pytorch3dunet_amd.predictor against the host-side restatement of the
-reference's StandardPredictor loop (oracle/predictor_oracle.py), the patch grid / padding helpers against the LIVE
-reference when /root/reference is present, and — on the GPU — the native forward path inside the loop."""
+reference's StandardPredictor loop (oracle/predictor_oracle.py), the patch grid / padding helpers against the reference's
+recorded results (tests/golden/make_reference_records.py), and — on the GPU — the native forward path inside the loop."""
 import numpy as np
 import pytest
 import torch
@@ -8,7 +8,7 @@ import torch
 import predictor_oracle as porc
 from pytorch3dunet_amd import predictor as P
 from pytorch3dunet_amd.unet3d.model import UNet3D, get_model
-from ref_import import import_reference, reference_available
+from reference_records import misc, predictor_inputs
 
 
 @pytest.mark.parametrize("i,k,s", [(10, 4, 2), (10, 4, 3), (7, 7, 1), (100, 32, 20), (65, 64, 64), (9, 3, 9)])
@@ -18,24 +18,24 @@ def test_gen_indices_restatements_agree(i, k, s):
     assert idx[0] == 0 and idx[-1] == i - k and all(b > a for a, b in zip(idx, idx[1:]))
 
 
-@pytest.mark.skipif(not reference_available(), reason="needs /root/reference (build container only)")
 def test_grid_and_padding_match_live_reference():
-    import importlib
-
-    import_reference()
-    ru = importlib.import_module("pytorch3dunet.datasets.utils")
+    """SliceBuilder._build_slices, mirror_pad and remove_padding of the reference (datasets/utils.py), recorded"""
     rng = np.random.default_rng(0)
-    for shape, patch, stride in [((20, 70, 90), (8, 64, 64), (4, 32, 40)), ((16, 64, 64), (16, 64, 64), (8, 8, 8)),
-                                 ((33, 100, 81), (10, 64, 70), (7, 30, 11))]:
-        vol = rng.standard_normal(shape).astype(np.float32)
-        ref = ru.SliceBuilder._build_slices(vol, patch, stride)
-        assert [tuple(s) for s in ref] == P.build_slices(shape, patch, stride)
+    for i, (shape, patch, stride) in enumerate([((20, 70, 90), (8, 64, 64), (4, 32, 40)), ((16, 64, 64), (16, 64, 64), (8, 8, 8)),
+                                                ((33, 100, 81), (10, 64, 70), (7, 30, 11))]):
+        rng.standard_normal(shape).astype(np.float32)  # (the volume the reference's SliceBuilder was given: keeps the draws aligned)
+        rec = misc(f"grid/{i}")
+        assert (tuple(rec["shape"]), tuple(rec["patch"]), tuple(rec["stride"])) == (shape, patch, stride)
+        ref = [tuple(slice(a, b) for a, b in t) for t in rec["slices"]]
+        assert ref == P.build_slices(shape, patch, stride)
     vol = rng.standard_normal((2, 9, 11, 13)).astype(np.float32)
-    for halo in [(0, 0, 0), (2, 3, 4), (1, 0, 5)]:
-        ref = ru.mirror_pad(vol, halo)
+    assert np.array_equal(vol, misc("pad/vol"))
+    for i, halo in enumerate([(0, 0, 0), (2, 3, 4), (1, 0, 5)]):
+        assert tuple(misc(f"pad/{i}/halo")) == halo
+        ref = misc(f"pad/{i}/padded")
         got = P.mirror_pad(torch.from_numpy(vol), halo).numpy()
         assert np.array_equal(ref, got)
-        assert np.array_equal(ru.remove_padding(ref, halo), P.remove_padding(torch.from_numpy(ref), halo).numpy())
+        assert np.array_equal(misc(f"pad/{i}/removed"), P.remove_padding(torch.from_numpy(ref), halo).numpy())
     with pytest.raises(ValueError):
         P.mirror_pad(torch.zeros(1, 4, 4, 4), (1, -1, 0))
 
@@ -99,12 +99,13 @@ class _MemTestDataset(torch.utils.data.Dataset):
     """what StandardPredictor needs from an AbstractHDF5Dataset in the test phase (datasets/hdf5.py:70-113,154-173): file_path,
     volume_shape, halo_shape and (standardised padded patch, unpadded spatial index) items"""
 
-    def __init__(self, raw, patch, stride, halo, file_path):
+    def __init__(self, raw, patch, stride, halo, file_path, mean=None, std=None):
         self.file_path = file_path
         self.halo_shape = tuple(halo)
         vol = raw if raw.ndim == 4 else raw[None]
         self.volume_shape = vol.shape[1:]
-        self.mean, self.std = float(raw.mean()), float(raw.std())
+        self.mean = float(raw.mean()) if mean is None else mean
+        self.std = float(raw.std()) if std is None else std
         self.padded = np.pad(vol, [(0, 0)] + [(p, p) for p in halo], mode="reflect") if any(halo) else vol
         self.slices = porc.build_slices(self.volume_shape, patch, stride)
 
@@ -171,22 +172,35 @@ def test_predictor_classes_native_forward_on_device(name, cin, cout, halo, kw):
     assert nat.launch_count > n0
 
 
-@pytest.mark.skipif(not reference_available(), reason="needs /root/reference (build container only)")
-@pytest.mark.timeout(300)
 def test_drop_in_predictors_equal_the_unmodified_reference_predictors():
-    """tests/drive_reference_predictor.py: reference StandardPredictor / LazyPredictor == ours == the oracle's loop, bit for bit
-    (probabilities, prediction_channel, multi- and single-channel segmentation, the dice metric branch)"""
-    import json
-    import os
-    import subprocess
-    import sys
+    """the reference's unmodified StandardPredictor / LazyPredictor (recorded by tests/golden/make_reference_records.py, fed by the
+    reference's own dataset code) == ours == the oracle's loop, bit for bit: probabilities with a halo, prediction_channel, multi-
+    and single-channel segmentation, and the value of the dice metric branch"""
+    import fake_h5py
+    from pytorch3dunet_amd.unet3d import predictor as MP
+    from reference_records import record
 
-    from conftest import ROOT
-
-    proc = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "drive_reference_predictor.py")], capture_output=True,
-                          text=True, timeout=280, env=dict(os.environ, OMP_NUM_THREADS="4"))
-    assert proc.returncode == 0, proc.stderr[-3000:]
-    r = json.loads([ln for ln in proc.stdout.splitlines() if ln.startswith("RESULT ")][-1][7:])
-    for case in ("probs", "channel", "segm_multi", "segm_single"):
-        assert all(r[case][k] for k in ("ref_standard", "ref_lazy", "our_standard", "our_lazy", "oracle")), (case, r[case])
-    assert r["dice_equal"] and r["names"]
+    z = record("r5_reference_predictors")
+    fake_h5py.install()
+    cases, dice = predictor_inputs()
+    for case, (model, cout, raw, patch, stride, halo, mean, std, kw) in cases.items():
+        ref = z[f"pred/{case}/ref_standard"]
+        lazy = z[f"pred/{case}/ref_lazy"]
+        assert lazy.shape == ref.shape and lazy.dtype == ref.dtype and np.array_equal(lazy, ref), case
+        loader = torch.utils.data.DataLoader(_MemTestDataset(raw, patch, stride, halo, f"/mem/{case}.h5", mean, std), batch_size=3,
+                                             num_workers=0, collate_fn=_collate)
+        outs = {}
+        for tag, cls in (("our_standard", MP.StandardPredictor), ("our_lazy", MP.LazyPredictor)):
+            cls(model, f"/mem/{tag}", cout, "cpu", output_dataset="predictions", **kw)(loader)
+            outs[tag] = fake_h5py.STORE[f"/mem/{tag}/{case}_predictions.h5"]["predictions"]
+        outs["oracle"] = porc.standard_predict(model, raw, patch, stride, halo, batch_size=3, mean=mean, std=std, **kw)
+        for tag, v in outs.items():
+            assert v.shape == ref.shape and v.dtype == ref.dtype and np.array_equal(v, ref), (case, tag)
+    model, raw, patch, stride, halo, mean, std, gt = dice
+    fake_h5py.STORE["/mem/gt.h5"] = {"label": gt}
+    loader = torch.utils.data.DataLoader(_MemTestDataset(raw, patch, stride, halo, "/mem/gt.h5", mean, std), batch_size=2,
+                                         collate_fn=_collate)
+    b = MP.StandardPredictor(model, "/mem/m_our", 2, "cpu", performance_metric="dice", gt_internal_path="label")(loader)
+    assert np.allclose(np.array(b, dtype=np.float64), z["dice/ref"], rtol=0, atol=0)
+    # the class lookup of predict.get_predictor (predict.py:20-40) resolves by name in whatever module carries that name
+    assert all(hasattr(MP, n) for n in ("AbstractPredictor", "StandardPredictor", "LazyPredictor", "mean_iou", "dice_score"))
