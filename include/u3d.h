@@ -768,6 +768,48 @@ int u3d_se_bwd_apply_b16(int device, u3d_stream_t stream, const void* dout, cons
                          const float* ws, const float* dls, const float* ds, int N, int64_t V, int C, int mode, int relu_mask,
                          void* out);
 
+/* ---- 2-D path: Conv2d 3x3 and MaxPool2d(2) of UNet2D (`native_2d: true`; csrc/u3d_conv2d.hip) -------------------------------
+ * Activations are NHWC fp32 — the NDHWC layout above with D = 1 — so the statistics, GroupNorm / BatchNorm, apply, virtual-concat,
+ * head, loss and optimizer entry points take them with D = 1 unchanged.  A virtual source (u3d_src_t with C1 > 0) has D1 == 1 and
+ * reads its low-res half through ymap / xmap (zmap is not read).
+ *
+ * Weight images: u3d_pack_weights2d packs a (Cout, Cin, 3, 3) weight; mode 0 = forward image (B[k = ci][n = co] = w[co][ci][tap]),
+ * mode 1 = data-gradient image (roles swapped, taps flipped: B[k = co][n = ci] = w[co][ci][8 - tap]); u3d_packed_weight2d_floats
+ * gives its size in floats. */
+size_t u3d_packed_weight2d_floats(int Cin, int Cout, int mode);
+int u3d_pack_weights2d(int device, u3d_stream_t stream, const float* w, int Cout, int Cin, int mode, float* packed);
+/* Replaces nn.Conv2d(in, out, 3, padding=1, bias=False) (buildingblocks.py:55-58) forward, and — called with the mode-1 image on dy —
+ * its data gradient.  Implicit GEMM on v_mfma_f32_32x32x2_f32: M = 16 x 16-pixel tile, N = 32 / 64 output channels, K = 9 * Cin;
+ * the input halo is staged through LDS with the affine of src fused (padding stays 0).  Any Cin, Cout >= 1; any H, W >= 1.
+ *   out        (N,H,W,Cout) fp32; relu: max(v, 0) in the epilogue
+ *   out_stats  optional double[stat_reps][N][Cout][2] += (sum, sum of squares) of the written outputs (as u3d_conv3d_ex_reps)
+ *   gx/gstats  optional (data-gradient use): gx = the layer's forward input (Cout channels here, virtual concat allowed, affine
+ *              ignored); gstats double[stat_reps][N][Cout][2] += (sum dg, sum dg * x)
+ *   workspace  optional, u3d_conv2d_workspace_floats() floats (0 for shapes that never split): grids with fewer blocks than CUs
+ *              split the channel reduction and add the partial sums in a fixed order (statistics then go to replica row 0).
+ * Zeroing the statistics tables is the caller's job; the library never allocates and never synchronises. */
+long long u3d_conv2d_workspace_floats(int N, int H, int W, int Cin, int Cout);
+int u3d_conv2d_ex_reps(int device, u3d_stream_t stream, const u3d_src_t* src, const float* packed_w, float* out, int N, int H, int W,
+                       int Cout, int relu, double* out_stats, const u3d_src_t* gx, double* gstats, float* workspace,
+                       long long workspace_floats, int stat_reps);
+/* Weight gradient of the same convolution (autograd of nn.Conv2d, buildingblocks.py:55-58): dw[cout][cin][ky][kx] =
+ * sum_{n,y,x} dz[n,y,x,cout] * g[n, y+ky-1, x+kx-1, cin], g = src with its affine, zero padded.  dw is written (not accumulated) in the
+ * reference layout (Cout,Cin,3,3).  Blocks own 32 x 32 channels x 9 taps over a pixel range; their partial sums are added in a fixed
+ * order, so the same inputs give a bitwise-identical dw.  workspace: u3d_wgrad2d_workspace_floats() floats (0: none needed). */
+size_t u3d_wgrad2d_workspace_floats(int N, int H, int W, int Cin, int Cout);
+int u3d_conv2d_wgrad(int device, u3d_stream_t stream, const u3d_src_t* src, const float* dz, float* dw, int N, int H, int W, int Cout,
+                     float* workspace, size_t workspace_floats);
+/* MaxPool2d(kernel_size=2) (buildingblocks.py:358): stride 2, floor.  The 2-D twins of u3d_maxpool2_fwd / _bwd_merge / _bwd_merge_gn
+ * (same arguments without D): argmax byte = 2 * dy + dx of the first maximum in (y, x) scan order (ATen); H, W >= 2. */
+int u3d_maxpool2d_fwd(int device, u3d_stream_t stream, const float* x, int N, int H, int W, int C, float* out, uint8_t* argmax,
+                      double* out_stats);
+int u3d_maxpool2d_bwd_merge(int device, u3d_stream_t stream, const float* dg, const float* pooled, const uint8_t* argmax,
+                            const float* coef, const float* skip_grad, const float* e, int N, int H, int W, int C, int relu_mask,
+                            float* out);
+int u3d_maxpool2d_bwd_merge_gn(int device, u3d_stream_t stream, const float* dg, const float* pooled, const uint8_t* argmax,
+                               const float* coef, const float* skip_dg, int Cdg, const float* skip_coef, int Ctot, const float* e, int N,
+                               int H, int W, int C, int relu_mask, float* out);
+
 /* ---- layout: NCDHW <-> NDHWC for multi-channel model inputs ------------------------------------ */
 int u3d_ncdhw_to_ndhwc(int device, u3d_stream_t stream, const float* src, float* dst, int N, int C, int64_t V);
 int u3d_ndhwc_to_ncdhw(int device, u3d_stream_t stream, const float* src, float* dst, int N, int C, int64_t V);

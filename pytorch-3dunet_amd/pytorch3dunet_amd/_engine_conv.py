@@ -137,7 +137,7 @@ class ConvLayers:
     def _subpixel_layers(self, size):
         """decoder first convs whose low-res input is upsampled by exactly 2 — or, round 5, from n to 2n + 1 voxels — in every dimension at
         this input size: {id(weight): (C0, C1)} (+ `.plus`: the ids with an n -> 2n + 1 axis) — per-call state, handed down as `sub`"""
-        if not self.subpixel or any(ct is not None for ct in self.dec_up) or any(self.dec_interp):
+        if not self.subpixel or getattr(self, "is2d", False) or any(ct is not None for ct in self.dec_up) or any(self.dec_interp):
             return _SubLayers()  # (a transposed convolution yields 2n-1 voxels, resized to the skip: never an exact 2x replication)
         dims = [tuple(size)]
         for has_pool, _, _ in self.enc:
@@ -277,9 +277,12 @@ class ConvLayers:
         "f32s": "_fwd_f32s",          # u3d_bf16.hip: compute_dtype fp32_split
         "bf16": "_fwd_bf16",          # u3d_bf16.hip: compute_dtype bf16 (fp32 or bf16 activation storage)
         "fp32": "_fwd_fp32",          # u3d_conv.hip: fp32 MFMA (persistent / generic / split-K chosen by the library)
+        "conv2d": "_fwd_conv2d",      # u3d_conv2d.hip: 3x3 convolutions of a 2-D net (native_2d), every layer and only those
     }
 
     def _fwd_family(self, c: "_ConvCall", residual) -> str:
+        if getattr(self, "is2d", False):
+            return "conv2d"
         if self.small_cin and c.src.t1 is None and c.Ctot <= 4 and c.Cout <= 32 and residual is None and not c.b16:
             return "small"
         if c.src.t1 is not None and residual is None and id(c.conv.weight) in c.sub:
@@ -355,6 +358,18 @@ class ConvLayers:
         nat.call("u3d_conv3d_bf16_ex" + ("_b16" if c.b16 else ""), c.dev.index, _stream(c.dev), _p(c.src.t0), _p(c.affine),
                  _p(self._packed_bf16(c.conv.weight, 0, c.dev)), _p(c.y), c.N, c.D, c.H, c.W, c.Ctot, c.Cout, c.relu, _p(ystats), None, None,
                  _p(c.residual), _p(kws), need, flops=c.flops)
+        return ystats
+
+    def _fwd_conv2d(self, c: "_ConvCall"):
+        # fp32 MFMA 3x3 implicit GEMM on the D = 1 tensors (virtual concat, fused affine, ReLU and statistics as the 3-D kernels)
+        assert c.residual is None and c.D == 1
+        wp = self._packed2d(c.conv.weight, 0, c.dev)
+        ystats = c.take_stats(self.stat_reps)
+        s = c.src.struct(c.affine)
+        need = nat.get_lib().u3d_conv2d_workspace_floats(c.N, c.H, c.W, c.Ctot, c.Cout)  # split-K scratch on small grids
+        kws = _empty(need, dtype=_F32, device=c.dev) if need > 0 else None
+        nat.call("u3d_conv2d_ex_reps", c.dev.index, _stream(c.dev), ctypes.byref(s), _p(wp), _p(c.y), c.N, c.H, c.W, c.Cout, c.relu,
+                 _p(ystats), None, None, _p(kws), need, _reps(ystats), flops=18.0 * c.Ctot * c.Cout * c.N * c.H * c.W)
         return ystats
 
     def _fwd_fp32(self, c: "_ConvCall"):
@@ -497,15 +512,19 @@ class ConvLayers:
         "subpixel": "_wgrad_subpixel",  # u3d_subpix.hip (upsampled channels) + u3d_conv.hip strided (skip channels)
         "fp32_side": "_wgrad_fp32_side",  # u3d_conv.hip on the side stream (U3D_SIDE_VOXELS, off by default)
         "fp32": "_wgrad_fp32",          # u3d_conv.hip
+        "conv2d": "_wgrad_conv2d",      # u3d_conv2d.hip (2-D nets)
     }
     _DGRAD_KERNELS = {
         "subpixel": "_dgrad_subpixel",  # skip half at full resolution + upsampled half directly at LOW resolution
         "f32s": "_dgrad_f32s",
         "bf16": "_dgrad_bf16",
         "fp32": "_dgrad_fp32",
+        "conv2d": "_dgrad_conv2d",  # u3d_conv2d.hip (2-D nets)
     }
 
     def _wgrad_family(self, c: "_BwdCall") -> str:
+        if getattr(self, "is2d", False):
+            return "conv2d"
         if c.bf16 and c.Cout % 32 == 0:  # (Cout % 64 == 32 since round 4: 64-column blocks with a zero upper half)
             return "bf16"
         if c.rec.sub is not None:
@@ -515,6 +534,8 @@ class ConvLayers:
         return "fp32"
 
     def _dgrad_family(self, c: "_BwdCall") -> str:
+        if getattr(self, "is2d", False):
+            return "conv2d"
         if c.rec.sub is not None:
             return "subpixel"
         if c.src.t1 is None and not c.rec.small and self._split_dgrad(c.src.C, c.Cout):
@@ -667,6 +688,24 @@ class ConvLayers:
                  None, _p(kws), need, flops=c.flops)
         return dg, gst
 
+    def _wgrad_conv2d(self, c: "_BwdCall"):
+        # (takes no GroupNorm-backward job: c.job stays set and _conv_bwd runs the reduction on its own)
+        cx, dev, src, rec, ws = c.cx, c.cx.dev, c.src, c.rec, c.cx.ws
+        s_aff = src.struct(rec.affine)
+        nat.call("u3d_conv2d_wgrad", dev.index, _stream(dev), ctypes.byref(s_aff), _p(c.dz), _p(cx.gview(rec.idx_w)), c.N, c.H, c.W,
+                 c.Cout, _p(ws), ws.numel(), flops=18.0 * src.C * c.Cout * c.N * c.H * c.W)
+
+    def _dgrad_conv2d(self, c: "_BwdCall"):
+        cx, dev, src, rec, ws = c.cx, c.cx.dev, c.src, c.rec, c.cx.ws
+        wpd = self._packed2d(rec.conv_w, 1, dev)
+        dg = _empty((c.N, c.D, c.H, c.W, src.C), dtype=_F32, device=dev)
+        gst = _take_reps(cx.pool, c.N * src.C * 2, c.greps)
+        s_dz = VSrc(c.dz).struct()
+        s_x = src.struct()
+        nat.call("u3d_conv2d_ex_reps", dev.index, _stream(dev), ctypes.byref(s_dz), _p(wpd), _p(dg), c.N, c.H, c.W, src.C, 0, None,
+                 ctypes.byref(s_x), _p(gst), _p(ws), ws.numel(), _reps(gst), flops=18.0 * src.C * c.Cout * c.N * c.H * c.W)
+        return dg, gst
+
     def _dgrad_fp32(self, c: "_BwdCall"):
         cx, dev, src, rec, ws = c.cx, c.cx.dev, c.src, c.rec, c.cx.ws
         wpd = self._packed(rec.conv_w, 1, dev)
@@ -772,6 +811,8 @@ class ConvLayers:
     def _layer_ws_floats(self, N, D, H, W, Cin, Cout, sub=None, small=False, virtual=False):
         """scratch floats one 3x3x3 layer's backward needs from the shared buffer, for the kernels it will actually run"""
         lib = nat.get_lib()
+        if getattr(self, "is2d", False):  # weight gradient + the data gradient's split-K scratch (roles swapped)
+            return max(lib.u3d_wgrad2d_workspace_floats(N, H, W, Cin, Cout), lib.u3d_conv2d_workspace_floats(N, H, W, Cout, Cin))
         if small:
             return lib.u3d_small_cin_bwd_workspace_floats(N, D, H, W, Cin, Cout)
         if sub is not None:  # skip slice (fp32 kernels) + sub-pixel slice + the slab boxes of an n -> 2n + 1 level

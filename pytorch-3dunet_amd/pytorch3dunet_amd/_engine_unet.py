@@ -33,12 +33,15 @@ class UNet3DEngine(WeightImages, ConvLayers):
         self.grad_sync = None  # set by parallel.GradSync (RCCL all-reduce overlapped with the encoder backward)
         self.debug = None  # dict -> backward stores clones of per-layer dz / dg (tools/gpu_layer_diag.py)
         self.fused_stats = True
+        # UNet2D under `native_2d` (unet3d/model.py): (N,C,H,W) runs as (N,C,1,H,W) — every 3x3 convolution on the 2-D kernel family
+        # (csrc/u3d_conv2d.hip, `conv2d` in the family tables), 2x2 pooling, no sub-pixel decoder kernels
+        self.is2d = bool(getattr(model, "native_2d", False))
         # replica rows of the statistics tables the persistent fp32 convolutions write (u3d_conv3d_ex_reps; 1 = plain tables)
         self.stat_reps = max(1, min(64, int(os.environ.get("U3D_STAT_REPS", "8"))))
         self.small_cin = True  # dedicated kernels for the in_channels<=4 first layer
         self.overlap_small_wgrad = True  # weight gradients of small layers on a second HIP stream (see _BwdCtx)
         # decoder first convs over an exact-2x upsampling: sub-pixel convolution of the upsampled half (csrc/u3d_subpix.hip)
-        self.subpixel = os.environ.get("U3D_SUBPIXEL", "1") != "0"
+        self.subpixel = os.environ.get("U3D_SUBPIXEL", "1") != "0" and not self.is2d
         # ... and over a level that upsamples n -> 2n + 1 along some axes (an odd skip size: 42 -> 85 in the shipped 80 x 170 x 170 patch):
         # sub-pixel kernels on a shifted window + the general kernels on the near-boundary slab (round 5; U3D_SUBPIXEL_PLUS=0: such
         # levels keep the 27-tap virtual-concat kernels)
@@ -154,6 +157,9 @@ class UNet3DEngine(WeightImages, ConvLayers):
         outputs in the reference's NCDHW layout."""
         m = self.model
         dev = x.device
+        if self.is2d:
+            assert x.dim() == 4, "the 2-D executor takes (N,C,H,W)"
+            x = x.unsqueeze(2)  # (N,C,1,H,W): NHWC is NDHWC with D = 1
         N, Cin, D, H, W = x.shape
         x = x.contiguous()
         if Cin == 1:
@@ -193,13 +199,17 @@ class UNet3DEngine(WeightImages, ConvLayers):
         for i, (has_pool, c1, c2) in enumerate(self.enc):
             if has_pool:
                 Np, Dp, Hp, Wp, Cp = cur.shape
-                pooled = _empty((Np, Dp // 2, Hp // 2, Wp // 2, Cp), dtype=_F32, device=dev)
+                Dq = Dp if self.is2d else Dp // 2  # (2-D: MaxPool2d, D stays 1)
+                pooled = _empty((Np, Dq, Hp // 2, Wp // 2, Cp), dtype=_F32, device=dev)
                 argmax = _empty(pooled.shape, dtype=torch.uint8, device=dev)
                 pst = None if self.post_norm else _take_reps(pool, Np * Cp * 2, self.stat_reps)
-                nat.call("u3d_maxpool2_fwd", dev.index, _stream(dev), _p(cur), Np, Dp, Hp, Wp, Cp, _p(pooled), _p(argmax), None)
+                if self.is2d:
+                    nat.call("u3d_maxpool2d_fwd", dev.index, _stream(dev), _p(cur), Np, Hp, Wp, Cp, _p(pooled), _p(argmax), None)
+                else:
+                    nat.call("u3d_maxpool2_fwd", dev.index, _stream(dev), _p(cur), Np, Dp, Hp, Wp, Cp, _p(pooled), _p(argmax), None)
                 if pst is not None:  # (the pooled tensor's statistics: a pass of its own — fused into the pool it was slower — into replica rows)
                     s_p = VSrc(pooled).struct()
-                    nat.call("u3d_chan_stats_reps", dev.index, _stream(dev), ctypes.byref(s_p), Np, Dp // 2, Hp // 2, Wp // 2, _p(pst),
+                    nat.call("u3d_chan_stats_reps", dev.index, _stream(dev), ctypes.byref(s_p), Np, Dq, Hp // 2, Wp // 2, _p(pst),
                              _reps(pst))
                 if tape is not None:
                     tape.pools.append((pooled, argmax, cur))
@@ -276,6 +286,9 @@ class UNet3DEngine(WeightImages, ConvLayers):
             tape.head_x = cur
             if self.debug is not None:
                 self.debug["tape"] = tape
+        if self.is2d:  # (N,Cout,H,W), the reference's 2-D layout
+            logits = logits.view(N, Co, H, W)
+            probs = probs.view(N, Co, H, W) if probs is not None else None
         return logits, probs, tape
 
     # -- backward -----------------------------------------------------------------------------------
@@ -421,13 +434,16 @@ class UNet3DEngine(WeightImages, ConvLayers):
                 Ne, De, He, We, Ce = e_in.shape
                 out = _empty_like(e_in)
                 sk = skip_grad.pop(i - 1, None)
+                # (2-D: the same merges over 2x2 windows, u3d_maxpool2d_*)
+                pdims = (Ne, He, We, Ce) if self.is2d else (Ne, De, He, We, Ce)
+                sfx = "2d" if self.is2d else "2"
                 if sk is None:
-                    nat.call("u3d_maxpool2_bwd_merge", dev.index, _stream(dev), _p(dg1), _p(pooled), _p(argmax), _p(coef1), None,
-                             _p(e_in), Ne, De, He, We, Ce, mk, _p(out))
+                    nat.call(f"u3d_maxpool{sfx}_bwd_merge", dev.index, _stream(dev), _p(dg1), _p(pooled), _p(argmax), _p(coef1), None,
+                             _p(e_in), *pdims, mk, _p(out))
                 else:
                     sdg, sCdg, scoef, sCt = sk
-                    nat.call("u3d_maxpool2_bwd_merge_gn", dev.index, _stream(dev), _p(dg1), _p(pooled), _p(argmax), _p(coef1),
-                             _p(sdg), sCdg, _p(scoef), sCt, _p(e_in), Ne, De, He, We, Ce, mk, _p(out))
+                    nat.call(f"u3d_maxpool{sfx}_bwd_merge_gn", dev.index, _stream(dev), _p(dg1), _p(pooled), _p(argmax), _p(coef1),
+                             _p(sdg), sCdg, _p(scoef), sCt, _p(e_in), *pdims, mk, _p(out))
                     del sk, sdg, scoef
                 self._unact(dev, out, e_in)
                 dz = out
@@ -446,4 +462,6 @@ class UNet3DEngine(WeightImages, ConvLayers):
             else:
                 dx = _empty((N, Cin, D, H, W), dtype=_F32, device=dev)
                 nat.call("u3d_ndhwc_to_ncdhw", dev.index, _stream(dev), _p(dx0), _p(dx), N, Cin, V)
+            if self.is2d:
+                dx = dx.view(N, Cin, H, W)
         return flat, dx

@@ -140,6 +140,8 @@ class WeightImages:
         for mod in self.model.modules():
             if isinstance(mod, torch.nn.Conv3d) and mod.kernel_size == (3, 3, 3):
                 out.append(mod.weight)
+            elif isinstance(mod, torch.nn.Conv2d) and mod.kernel_size == (3, 3):  # (UNet2D under native_2d)
+                out.append(mod.weight)
         return out
 
     # pack modes: 0 forward, 1 data gradient (u3d_pack_weights).  Layers in self._sub (sub-pixel path) use instead: 10 / 11 =
@@ -254,6 +256,11 @@ class WeightImages:
         ws = getattr(self, "_cw", None)
         if ws is None:
             ws = self._cw = self._conv_weights()
+        if getattr(self, "is2d", False):
+            for w in ws:  # 2-D images: one small launch per weight and mode (u3d_pack_weights2d)
+                for mode in modes:
+                    self._packed2d(w, mode, dev)
+            return
         if self.bf16:
             self._repack_bf16_all(dev, modes, ws)
         stale = []
@@ -336,6 +343,20 @@ class WeightImages:
             hit = (self._ver(w), buf)
             self._pack_cache[(id(w), mode)] = hit
         return hit[1]
+
+    def _packed2d(self, w: torch.Tensor, mode: int, dev) -> torch.Tensor:
+        """forward (0) / data-gradient (1) image of a (Cout, Cin, 3, 3) weight for csrc/u3d_conv2d.hip, cached per parameter version"""
+        key = (id(w), 40 + mode)
+        ver = self._ver(w)
+        hit = self._pack_cache.get(key)
+        if hit is not None and hit[0] == ver:
+            return hit[1]
+        Cout, Cin = w.shape[0], w.shape[1]
+        n = nat.get_lib().u3d_packed_weight2d_floats(Cin, Cout, mode)
+        out = hit[1] if hit is not None and hit[1].numel() == n and hit[1].device == dev else _empty(n, dtype=_F32, device=dev)
+        nat.call("u3d_pack_weights2d", dev.index, _stream(dev), _p(w.detach()), Cout, Cin, mode, _p(out))
+        self._pack_cache[key] = (ver, out)
+        return out
 
     def _packed(self, w: torch.Tensor, mode: int, dev) -> torch.Tensor:
         key = (id(w), mode)

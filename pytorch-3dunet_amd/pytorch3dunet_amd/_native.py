@@ -406,6 +406,19 @@ _PROTOS = {
     "u3d_pair_stats": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p]),
     "u3d_cvt_f64_f32": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int64]),
     "u3d_cvt_f64_f32_sum": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int64, c_int]),
+    # 2-D path (csrc/u3d_conv2d.hip)
+    "u3d_packed_weight2d_floats": (c_size_t, [c_int, c_int, c_int]),
+    "u3d_pack_weights2d": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "u3d_conv2d_workspace_floats": (c_int64, [c_int, c_int, c_int, c_int, c_int]),
+    "u3d_conv2d_ex_reps": (c_int, [c_int, c_void_p, POINTER(U3DSrc), c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                                   POINTER(U3DSrc), c_void_p, c_void_p, c_int64, c_int]),
+    "u3d_wgrad2d_workspace_floats": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "u3d_conv2d_wgrad": (c_int, [c_int, c_void_p, POINTER(U3DSrc), c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t]),
+    "u3d_maxpool2d_fwd": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "u3d_maxpool2d_bwd_merge": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                        c_int, c_int, c_void_p]),
+    "u3d_maxpool2d_bwd_merge_gn": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int,
+                                           c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "u3d_ncdhw_to_ndhwc": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64]),
     "u3d_ndhwc_to_ncdhw": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64]),
 }

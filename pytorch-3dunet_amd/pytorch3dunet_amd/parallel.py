@@ -180,6 +180,10 @@ def attach(model: torch.nn.Module, process_group=None, broadcast: bool = True, f
         broadcast_parameters(model, 0, process_group)
     first = next(iter(model.parameters()), None)
     native = bool(getattr(model, "native_supported", False)) and first is not None and first.is_cuda
+    if native and getattr(model, "native_2d", False):
+        # (the 2-D executor's gradient exchange is not built or tested: refuse rather than train unsynchronised)
+        raise NotImplementedError("u3d: data-parallel training of a native_2d model is not supported; train it on one GPU or "
+                                  "without native_2d")
     old = getattr(model, "_u3d_grad_sync", None)
     if isinstance(old, TreeSync):
         old.detach()

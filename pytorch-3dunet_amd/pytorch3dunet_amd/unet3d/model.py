@@ -13,7 +13,8 @@ libu3d_hip.so is missing (no silent fallback).  CPU tensors (`device: cpu`) run 
 made of.  ONE backend: a 3-D model variant the executor does not cover (layer orders outside engine.layer_spec's grammar,
 conv kernels other than 3/pad 1, `pool_type: avg`) RAISES on a HIP device; U3D_ALLOW_TORCH_FALLBACK=1 opts into running
 the same module tree through stock PyTorch-ROCm operators after a one-time warning (never counted as covered).  2-D
-models are outside the 3-D path and keep that warning path by default; U3D_STRICT=1 makes them an error too.  Covered since round 2: every layer order with at most one
+models are outside the 3-D path and keep that warning path by default (opt-in since round 7: `native_2d: true` / U3D_NATIVE_2D=1 runs a
+fp32 UNet2D with nearest upsampling on the 2-D kernels of csrc/u3d_conv2d.hip); U3D_STRICT=1 makes them an error too.  Covered since round 2: every layer order with at most one
 GroupNorm / BatchNorm, one non-linearity and a trailing dropout, every `upsample` value the reference itself can run
 on a 3-D net, nn.DataParallel, activation checkpointing, and the opt-in compute modes `bf16` and `fp32_split`.
 """
@@ -40,7 +41,8 @@ class AbstractUNet(nn.Module):
     def __init__(self, in_channels, out_channels, final_sigmoid, basic_module, f_maps=64, layer_order="gcr",
                  num_groups=8, num_levels=4, is_segmentation=True, conv_kernel_size=3, pool_kernel_size=2,
                  conv_padding=1, conv_upscale=2, upsample="default", dropout_prob=0.1, is3d=True, compute_dtype=None,
-                 checkpoint_encoders=None, hip_graph=None, activation_dtype=None, checkpoint_levels=None):
+                 checkpoint_encoders=None, hip_graph=None, activation_dtype=None, checkpoint_levels=None,
+                 native_2d=None):
         super().__init__()
         if isinstance(f_maps, int):
             f_maps = number_of_features_per_level(f_maps, num_levels=num_levels)
@@ -61,9 +63,22 @@ class AbstractUNet(nn.Module):
             self.final_activation = None
 
         # ---- native-path eligibility (everything the gfx950 executor implements today)
+        # `native_2d: true` (model-section key; U3D_NATIVE_2D=1 sets its default): a UNet2D runs on the 2-D kernels of
+        # csrc/u3d_conv2d.hip through the DoubleConv executor with D = 1 (fp32, nearest upsampling); off by default
+        if native_2d is None:
+            native_2d = os.environ.get("U3D_NATIVE_2D", "0") == "1"
+        self.native_2d = bool(native_2d) and not is3d
         reasons = []
-        if not is3d:
+        if not is3d and not self.native_2d:
             reasons.append("2-D model")
+        elif not is3d:
+            if basic_module is not DoubleConv:
+                reasons.append(f"2-D model with {basic_module.__name__} (native_2d covers DoubleConv blocks)")
+            if compute_dtype not in (None, "fp32", "float32") or os.environ.get("U3D_BF16", "0") == "1" or \
+                    os.environ.get("U3D_F32_SPLIT", "0") == "1":
+                reasons.append(f"2-D model with compute_dtype {compute_dtype!r} (native_2d is fp32)")
+            if upsample not in ("default", "nearest"):
+                reasons.append(f"2-D model with upsample '{upsample}' (native_2d: nearest upsampling)")
         if basic_module not in (DoubleConv, ResNetBlock, ResNetBlockSE):
             reasons.append(f"basic_module {basic_module.__name__}")
         if basic_module is ResNetBlockSE and (any(f % 4 for f in f_maps) or max(f_maps) > 1024):
@@ -137,6 +152,9 @@ class AbstractUNet(nn.Module):
         if hip_graph is None:
             hip_graph = os.environ.get("U3D_GRAPH", "0") == "1"
         self.hip_graph = bool(hip_graph)
+        if self.native_2d and self.hip_graph:
+            raise ValueError("u3d: hip_graph is not available with native_2d (the captured training step is 3-D only); "
+                             "drop one of the two keys")
         self._native_blockers = reasons
         self._is3d = bool(is3d)
         self._residual = basic_module in (ResNetBlock, ResNetBlockSE)
@@ -212,7 +230,7 @@ class AbstractUNet(nn.Module):
 
     def _forward_logits(self, x):
         if x.is_cuda:
-            if self.native_supported and x.dtype == torch.float32 and x.dim() == 5:
+            if self.native_supported and x.dtype == torch.float32 and x.dim() == (5 if self._is3d else 4):
                 from ..engine import StaleParameters, run_model
 
                 try:
@@ -224,7 +242,8 @@ class AbstractUNet(nn.Module):
                     object.__setattr__(self, "_engine_stale", True)  # -> full identity walk -> new executor (keeps the grad_sync hook)
                     return run_model(self._get_engine(), x)
             why = ", ".join(self._native_blockers) or (
-                f"input is {x.dim()}-D, the 3-D path takes (N,C,D,H,W)" if x.dim() != 5 else
+                (f"input is {x.dim()}-D, the 3-D path takes (N,C,D,H,W)" if self._is3d else
+                 f"input is {x.dim()}-D, the native 2-D path takes (N,C,H,W)") if x.dim() != (5 if self._is3d else 4) else
                 f"input dtype {x.dtype}: the native path takes float32 tensors (pass x.float(); reduced-precision arithmetic is the "
                 "model key compute_dtype: bf16, not a half-precision input / model.half() / autocast)")
             eng = self.__dict__.get("_engine")
@@ -277,7 +296,7 @@ def _variant(name, basic_module, default_levels, is3d, doc):
                               conv_upscale=conv_upscale, upsample=upsample, dropout_prob=dropout_prob, is3d=is3d,
                               compute_dtype=kwargs.get("compute_dtype"), checkpoint_encoders=kwargs.get("checkpoint_encoders"),
                               hip_graph=kwargs.get("hip_graph"), activation_dtype=kwargs.get("activation_dtype"),
-                              checkpoint_levels=kwargs.get("checkpoint_levels"))
+                              checkpoint_levels=kwargs.get("checkpoint_levels"), native_2d=kwargs.get("native_2d"))
 
     return type(name, (AbstractUNet,), {"__init__": __init__, "__doc__": doc, "__module__": _THIS_MODULE})
 

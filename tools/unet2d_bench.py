@@ -1,0 +1,152 @@
+"""Training-step throughput of the reference's shipped 2-D configurations: forward + BCEDice + backward + FusedAdam, with
+`native_2d: true` (csrc/u3d_conv2d.hip through the DoubleConv executor) and with the default path (the module tree on stock
+PyTorch-ROCm operators, after its one-time warning) in the same process, alternating the two.
+
+  confocal  resources/2DUnet_confocal_boundary/train_config.yml: 32 x 1 x 515 x 512, gcr, f_maps 32, 4 levels
+  dsb2018   resources/2DUnet_dsb2018/train_config.yml: bcr, f_maps [32, 64, 128], batch 32 — DSB2018 images vary in size;
+            32 x 1 x 256 x 256 is an ASSUMPTION of this tool, not a shape the configuration fixes
+
+Prints one JSON line per configuration: images/s of both paths (device time over the steady-state steps only, after --warmup steps
+per path), the conv2d family's ms per native step and its rate on executed FLOPs (18 * Cin * Cout * pixels per direction, from the
+launches that declare them) as a fraction of the fp32 MFMA peak of 157.3 TFLOP/s.
+
+  python tools/unet2d_bench.py [--configs confocal,dsb2018] [--batch 32] [--steps 10] [--warmup 3]"""
+import argparse
+import json
+import os
+import sys
+import warnings
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (os.path.join(ROOT, "pytorch-3dunet_amd"),):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+import torch  # noqa: E402
+
+PEAK_TFLOPS = 157.3
+CONFIGS = {
+    "confocal": (dict(name="UNet2D", in_channels=1, out_channels=1, f_maps=32, num_levels=4, layer_order="gcr", num_groups=8),
+                 (515, 512)),
+    "dsb2018": (dict(name="UNet2D", in_channels=1, out_channels=1, f_maps=[32, 64, 128], layer_order="bcr"), (256, 256)),
+}
+
+
+def conv_flops_per_image(cfg, hw):
+    """18 * Cin * Cout * pixels summed over the 3x3 layers (one direction), counted from the module tree"""
+    from pytorch3dunet_amd.unet3d.model import get_model
+
+    m = get_model(dict(cfg))
+    H, W = hw
+    tot = 0.0
+    for enc in m.encoders:
+        if enc.pooling is not None:
+            H, W = H // 2, W // 2
+        for sc in (enc.basic_module.SingleConv1, enc.basic_module.SingleConv2):
+            tot += 18.0 * sc.conv.in_channels * sc.conv.out_channels * H * W
+    sizes = []
+    H, W = hw
+    for enc in m.encoders:
+        if enc.pooling is not None:
+            H, W = H // 2, W // 2
+        sizes.append((H, W))
+    for dec, (h, w) in zip(m.decoders, sizes[:-1][::-1]):
+        for sc in (dec.basic_module.SingleConv1, dec.basic_module.SingleConv2):
+            tot += 18.0 * sc.conv.in_channels * sc.conv.out_channels * h * w
+    return tot
+
+
+def make(cfg, native, dev):
+    from pytorch3dunet_amd.optim import FusedAdam
+    from pytorch3dunet_amd.unet3d.model import get_model
+
+    torch.manual_seed(0)
+    m = get_model(dict(cfg, native_2d=native)).to(dev).train()
+    return m, FusedAdam(m.parameters(), lr=1e-4, weight_decay=1e-5)
+
+
+def step(model, opt, x, target, loss_fn):
+    opt.zero_grad(set_to_none=True)
+    _, logits = model(x, return_logits=True)
+    loss = loss_fn(logits, target)
+    loss.backward()
+    opt.step()
+
+
+def timed(model, opt, x, target, loss_fn, steps):
+    st, en = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    st.record()
+    for _ in range(steps):
+        step(model, opt, x, target, loss_fn)
+    en.record()
+    torch.cuda.synchronize()
+    return st.elapsed_time(en) / steps
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--configs", default="confocal,dsb2018")
+    ap.add_argument("--batch", type=int, default=32)
+    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--rounds", type=int, default=2, help="alternating native / stock rounds of --steps each")
+    ap.add_argument("--native-only", action="store_true", help="time the native path only (profiler runs)")
+    a = ap.parse_args()
+    assert torch.cuda.is_available(), "unet2d_bench measures on the GPU"
+    from pytorch3dunet_amd import _native as nat
+    from pytorch3dunet_amd.unet3d.losses import BCEDiceLoss
+
+    dev = torch.device("cuda", 0)
+    loss_fn = BCEDiceLoss()  # the package's (fused u3d_bce_dice kernels on a HIP tensor), the same for both paths
+    warnings.simplefilter("ignore")  # (the stock path's one-time "not covered" warning)
+    for name in a.configs.split(","):
+        cfg, hw = CONFIGS[name]
+        g = torch.Generator().manual_seed(1)
+        x = torch.randn((a.batch, 1) + hw, generator=g).to(dev)
+        target = (torch.rand((a.batch, 1) + hw, generator=g) > 0.5).float().to(dev)
+        paths = [True] if a.native_only else [True, False]
+        runs = {p: make(cfg, p, dev) for p in paths}
+        for p in paths:
+            for _ in range(a.warmup):
+                step(*runs[p], x, target, loss_fn)
+        print(f"[unet2d_bench] {name}: warm-up done", file=sys.stderr, flush=True)
+        ms = {p: [] for p in paths}
+        for _ in range(a.rounds):
+            for p in paths:
+                ms[p].append(timed(*runs[p], x, target, loss_fn, a.steps))
+        # conv2d family time in separate (event-bracketed) native steps: brackets cost a little device time each
+        prof = nat.EventProfiler(flops_only=True, prealloc=4096)
+        nat.profiler = prof
+        step(*runs[True], x, target, loss_fn)
+        torch.cuda.synchronize()
+        nat.profiler = None
+        fam = prof.summary()
+        conv = {k: v for k, v in fam.items() if "conv2d" in k}
+        c_ms = sum(v["ms"] for v in conv.values())
+        c_fl = sum(v["flops"] for v in conv.values())
+        fwd = {k: v for k, v in conv.items() if k == "u3d_conv2d_ex_reps"}
+        per_img = conv_flops_per_image(cfg, hw)
+        best = {p: min(v) for p, v in ms.items()}
+        rec = {"config": name, "shape": [a.batch, 1, *hw], "order": cfg["layer_order"], "steps": a.steps, "warmup": a.warmup,
+               "rounds": a.rounds, "native_ms_per_step": [round(v, 3) for v in ms[True]],
+               "native_images_per_s": round(a.batch * 1000.0 / best[True], 2),
+               "conv2d_gflop_fwd_per_image": round(per_img / 1e9, 2),
+               "conv2d_family_ms_per_step": round(c_ms, 3), "conv2d_family_tflops_executed": round(c_fl / c_ms / 1e9, 2) if c_ms else None,
+               "conv2d_family_fraction_of_peak": round(c_fl / c_ms / 1e9 / PEAK_TFLOPS, 3) if c_ms else None,
+               "conv2d_calls": {k: {"calls": v["calls"], "ms": round(v["ms"], 3),
+                                    "fraction_of_peak": round(v["flops"] / v["ms"] / 1e9 / PEAK_TFLOPS, 3) if v["ms"] else None}
+                                for k, v in conv.items()},
+               "conv2d_fwd_fraction_of_peak": round(sum(v["flops"] for v in fwd.values()) / sum(v["ms"] for v in fwd.values()) / 1e9 /
+                                                    PEAK_TFLOPS, 3) if fwd else None,
+               "device": torch.cuda.get_device_name(0)}
+        if not a.native_only:
+            rec.update(stock_ms_per_step=[round(v, 3) for v in ms[False]], stock_images_per_s=round(a.batch * 1000.0 / best[False], 2),
+                       native_speedup=round(best[False] / best[True], 3))
+        print(json.dumps(rec), flush=True)
+        del runs, x, target
+        torch.cuda.empty_cache()
+
+
+if __name__ == "__main__":
+    main()
