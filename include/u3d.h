@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define U3D_VERSION 128 /* 128: u3d_conv3d_wgrad_bf16_job / _b16_job (the GroupNorm-backward reduction rides in the bf16 weight gradient's reduce launch too); 127: u3d_subpixel_conv_dgrad_reps, u3d_gn_bwd_job_t::reps_hi; 126: replica rows also from u3d_chan_stats_reps, u3d_conv3d_small_cin_fwd_reps, u3d_conv1x1_head_bwd_reps + u3d_cvt_f64_f32_sum; 125: replica rows of the statistics tables (u3d_conv3d_ex_reps, u3d_gn_finalize_reps, u3d_gn_bwd_job_t::reps_lo); 124: u3d_bce_dice_scratch_doubles (per-block partials instead of atomics); 123: u3d_conv3d_wgrad_job (the GroupNorm-backward reduction rides in the weight-gradient reduce launch); 122: round 6 — u3d_gn_finalize_split / u3d_gn_bwd_finalize_split (compact half tables of a virtual-concat layer), u3d_adam_step, u3d_chan_stats_children, u3d_pack_weights_batch_cells, tuning key 18; 121: u3d_convtr3d_fwd_t8_b16_ex; 120: flat 5 x 10 x 10 tile of the bf16-storage convolutions (u3d_conv3d_bf16_tile_variant planes = 5), 24 tuning keys; 119: round 5 — ragged volumes on the persistent kernels, u3d_conv3d_variant / u3d_conv3d_wgrad_variant; 112: BatchNorm / conv-bias / dropout entry points (u3d_norm.hip); 113: one-launch bf16 weight packing (u3d_pack_weights_bf16_batch), 16 tuning keys, bf16 activation storage (*_b16); 114: 1x1x1 convolution on the bf16 matrix pipe (u3d_conv1x1_*_mfma_b16); 115: round 4 — u3d_conv3d_bf16_tile_variant, tuning key 12 (free slots in the persistent grids); 116: u3d_conv3d_wgrad_bf16_b16_variant; 117: u3d_convtr3d_dgrad_t8*_ex (split-K); 118: u3d_se_*_b16 */
+#define U3D_VERSION 128 /* 128 (unchanged, additions only): u3d_softmax_ce_* and u3d_dice_* (multi-class losses); 128: u3d_conv3d_wgrad_bf16_job / _b16_job (the GroupNorm-backward reduction rides in the bf16 weight gradient's reduce launch too); 127: u3d_subpixel_conv_dgrad_reps, u3d_gn_bwd_job_t::reps_hi; 126: replica rows also from u3d_chan_stats_reps, u3d_conv3d_small_cin_fwd_reps, u3d_conv1x1_head_bwd_reps + u3d_cvt_f64_f32_sum; 125: replica rows of the statistics tables (u3d_conv3d_ex_reps, u3d_gn_finalize_reps, u3d_gn_bwd_job_t::reps_lo); 124: u3d_bce_dice_scratch_doubles (per-block partials instead of atomics); 123: u3d_conv3d_wgrad_job (the GroupNorm-backward reduction rides in the weight-gradient reduce launch); 122: round 6 — u3d_gn_finalize_split / u3d_gn_bwd_finalize_split (compact half tables of a virtual-concat layer), u3d_adam_step, u3d_chan_stats_children, u3d_pack_weights_batch_cells, tuning key 18; 121: u3d_convtr3d_fwd_t8_b16_ex; 120: flat 5 x 10 x 10 tile of the bf16-storage convolutions (u3d_conv3d_bf16_tile_variant planes = 5), 24 tuning keys; 119: round 5 — ragged volumes on the persistent kernels, u3d_conv3d_variant / u3d_conv3d_wgrad_variant; 112: BatchNorm / conv-bias / dropout entry points (u3d_norm.hip); 113: one-launch bf16 weight packing (u3d_pack_weights_bf16_batch), 16 tuning keys, bf16 activation storage (*_b16); 114: 1x1x1 convolution on the bf16 matrix pipe (u3d_conv1x1_*_mfma_b16); 115: round 4 — u3d_conv3d_bf16_tile_variant, tuning key 12 (free slots in the persistent grids); 116: u3d_conv3d_wgrad_bf16_b16_variant; 117: u3d_convtr3d_dgrad_t8*_ex (split-K); 118: u3d_se_*_b16 */
 
 #define U3D_OK 0
 #define U3D_EINVAL (-1)  /* bad shape / argument */
@@ -521,6 +521,41 @@ int u3d_bce_dice_fwd(int device, u3d_stream_t stream, const float* logits, const
                      float* coef);
 int u3d_bce_dice_bwd(int device, u3d_stream_t stream, const float* logits, const float* target, const float* coef,
                      const float* grad_out, int N, int C, int64_t V, float* dlogits);
+
+/* ---- multi-class losses on the logits: softmax cross entropy and the softmax / generalized Dice family ---------
+ * logits (N, C, V) contiguous fp32 (the reference's NCDHW; 2-D nets run with D = 1), 1 <= C <= 1024, N < 65536.  Every
+ * reduction writes per-block partials in double that a one-block finalize sums in a fixed order: loss and gradient are
+ * bit-reproducible.  Scratch comes from the *_scratch_doubles query (need not be initialised); the library never allocates.
+ * bwd: grad_out is a DEVICE scalar (NULL = 1) — no host synchronisation between forward and backward.
+ *
+ * nn.CrossEntropyLoss(weight, ignore_index) with mean reduction (losses.py:316-319) and WeightedCrossEntropyLoss
+ * (losses.py:204-227):  loss = Σ_i w[t_i] (lse_i − x_i[t_i]) / Σ_i w[t_i] over the voxels with t_i != ignore_index
+ * (every voxel ignored: 0/0 = NaN, as torch).  target int64 (N, V).  A non-ignored label outside [0, C) is never used as
+ * an index: the loss becomes NaN and that voxel's gradient row NaN.
+ * fwd : weight optional device float[C] (NULL = 1); auto_weight = 1 (weight must be NULL) derives the detached
+ *       WeightedCrossEntropyLoss weights w_c = (M − S_c) / S_c, S_c = Σ softmax_c over all M = N·V voxels, ignored ones
+ *       included.  coef float[C + 1] (saved for backward) = the class weights used, then 1 / Σ w.
+ * bwd : dlogits = grad_out · w[t] / Σ w · (softmax − onehot(t)), 0 on ignored voxels. */
+long long u3d_softmax_ce_scratch_doubles(int N, int C, int64_t V);
+int u3d_softmax_ce_fwd(int device, u3d_stream_t stream, const float* logits, const int64_t* target, const float* weight,
+                       int N, int C, int64_t V, int64_t ignore_index, int auto_weight, double* scratch, float* loss,
+                       float* coef);
+int u3d_softmax_ce_bwd(int device, u3d_stream_t stream, const float* logits, const int64_t* target, const float* coef,
+                       const float* grad_out, int N, int C, int64_t V, int64_t ignore_index, float* dlogits);
+
+/* DiceLoss (losses.py:84-145, compute_per_channel_dice :11-37) and GeneralizedDiceLoss (losses.py:148-184) on the
+ * normalised logits p = {sigmoid | softmax over C | identity}(x), norm = 0 | 1 | 2; target fp32 (N, C, V).
+ *   generalized = 0: loss = 1 − mean_c 2 w_c Σpt / clamp(Σp² + Σt², eps), weight optional device float[C] (NULL = 1)
+ *   generalized = 1: w_j = 1 / clamp(T_j², eps) (constant), loss = 1 − 2 Σ_j w_j Σpt / Σ_j clamp(w_j (Σp + Σt), eps);
+ *                    C = 1 is taken as the channel pair (p, 1 − p) / (t, 1 − t); weight must be NULL
+ * (sigmoid DiceLoss / BCEDiceLoss stay on u3d_bce_dice_*.)
+ * fwd : loss float[1], coef float[3C] (saved for backward): dL/dp_c = a_c t + b_c p + k_c as (a_c, b_c, k_c)
+ * bwd : dlogits = grad_out · dL/dp chained through the normalisation (sigmoid p(1 − p), softmax p_c (G_c − Σ_k p_k G_k)). */
+long long u3d_dice_scratch_doubles(int N, int C, int64_t V);
+int u3d_dice_fwd(int device, u3d_stream_t stream, const float* logits, const float* target, const float* weight, int N,
+                 int C, int64_t V, int norm, int generalized, float eps, double* scratch, float* loss, float* coef);
+int u3d_dice_bwd(int device, u3d_stream_t stream, const float* logits, const float* target, const float* coef,
+                 const float* grad_out, int N, int C, int64_t V, int norm, float* dlogits);
 
 /* ---- opt-in bf16-operand convolutions (BASELINE config 4: "bf16 compute", fp32 master weights) --------------
  * The same nn.Conv3d(in,out,3,padding=1,bias=False) (buildingblocks.py:56) and, with mode-1 packed weights on dy, its

@@ -1,4 +1,5 @@
-// u3d_loss.hip — BCEDiceLoss / DiceLoss(sigmoid) / BCEWithLogitsLoss on the logits, fused.
+// u3d_loss.hip — BCEDiceLoss / DiceLoss(sigmoid) / BCEWithLogitsLoss on the logits, fused, and the
+// multi-class losses (softmax cross entropy, weighted CE, softmax / none / generalized Dice) further down.
 //
 // Reference: pytorch3dunet/unet3d/losses.py — BCEDiceLoss :187-201 (= nn.BCEWithLogitsLoss() + alpha * DiceLoss()),
 // DiceLoss / _AbstractDiceLoss :84-127 (sigmoid normalisation, 1 - mean_c dice_c), compute_per_channel_dice :11-37
@@ -194,6 +195,442 @@ extern "C" int u3d_bce_dice_bwd(int device, u3d_stream_t stream, const float* lo
     const int vec = rows_vec_ok(logits, target, dlogits, V) ? 1 : 0;
     hipLaunchKernelGGL(loss_bwd_kernel, loss_grid(N * C, V), dim3(256), 0, (hipStream_t)stream, logits, target, coef,
                        grad_out, C, (long long)V, vec, dlogits);
+    U3D_LAUNCH_CHECK();
+    return 0;
+}
+
+// =====================================================================================================================
+// Multi-class losses on the logits (losses.py:11-37, :84-184, :204-227 and nn.CrossEntropyLoss, built by :316-319).
+// logits (N, C, V) contiguous fp32; a voxel's C values are V apart, so consecutive threads (consecutive voxels) read
+// consecutive addresses for every channel.  Every reduction writes per-block partials in double that a one-block
+// finalize sums in a fixed order: the loss and the gradient are bit-reproducible.  No float atomics anywhere.
+//   softmax CE   pass 1 (Σ w[t]·(lse − x_t), Σ w[t]) per block -> finalize: loss, coef = {w_c}, 1/W
+//                backward: dlogits = g·w[t]/W·(softmax − onehot(t)), zero on ignored voxels
+//   weighted CE  a channel-sums pass (S_c = Σ softmax_c) -> finalize w_c = (M − S_c)/S_c into coef -> softmax CE
+//   Dice family  a channel-sums pass (Σpt, Σp², Σt², Σp, Σt per channel, p normalised) -> finalize: loss and the affine
+//                dL/dp_c = a_c·t + b_c·p + k_c -> backward through the normalisation
+namespace {
+
+constexpr int MC_K = 5;        // per-channel sums: p*t, p*p, t*t, p, t
+constexpr int MC_MAX_C = 1024;  // the head's channel limit
+constexpr int MC_NORM_SIGMOID = 0, MC_NORM_SOFTMAX = 1, MC_NORM_NONE = 2;
+
+// per-row block count: ~4 voxels per thread on large problems, one on small ones (a wide head on a small grid), at most 4096
+// partial rows and 2^18 (block, channel) pairs in all
+inline unsigned mc_blocks_per_row(int N, int C, long long V) {
+    const long long vpt = (long long)N * V >= (1LL << 20) ? 4 : 1;
+    long long gx = (V + 256 * vpt - 1) / (256 * vpt);
+    long long cap = 4096 / N;
+    if (cap < 1) cap = 1;
+    const long long cap2 = (1LL << 18) / ((long long)N * C);
+    if (cap2 < cap) cap = cap2 < 1 ? 1 : cap2;
+    if (gx > cap) gx = cap;
+    if (gx < 1) gx = 1;
+    return (unsigned)gx;
+}
+
+// channel chunks of the passes that are parallel over channels (grid.z): the voxel's softmax terms are recomputed per chunk
+constexpr int MC_CS_CHUNK = 16;  // channel sums: one register accumulator set per channel of the chunk
+constexpr int MC_BWD_CHUNK = 64;  // backward kernels
+inline unsigned mc_chunks(int C, int chunk) { return (unsigned)((C + chunk - 1) / chunk); }
+
+// max-shifted log-sum-exp terms of one voxel: x points at (n, 0, v); on return sum_c exp(x_c - m) = s
+__device__ __forceinline__ void voxel_max_sum(const float* __restrict__ x, long long V, int C, float& m, float& s) {
+    m = x[0];
+    s = 1.f;
+#pragma unroll 4
+    for (int c = 1; c < C; ++c) {
+        const float xv = x[(size_t)c * V];
+        const float mn = fmaxf(m, xv);
+        s = s * expf(m - mn) + expf(xv - mn);
+        m = mn;
+    }
+}
+
+__device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
+
+// sum of (a, b) over a 256-thread block, fixed order; valid in thread 0
+__device__ __forceinline__ void block_sum2_256(double& a, double& b) {
+    __shared__ double red[4][2];
+    for (int m = 32; m >= 1; m >>= 1) {
+        a += __shfl_xor(a, m);
+        b += __shfl_xor(b, m);
+    }
+    const int l = threadIdx.x & 63, w = threadIdx.x >> 6;
+    if (l == 0) red[w][0] = a, red[w][1] = b;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        a = (red[0][0] + red[1][0]) + (red[2][0] + red[3][0]);
+        b = (red[0][1] + red[1][1]) + (red[2][1] + red[3][1]);
+    }
+}
+
+// one 256-thread block: tot[q] = sum_b part[b * CK + q] for q < CK, in a fixed order (G threads per q, then G in sequence)
+__device__ void reduce_partials(const double* __restrict__ part, int nb, int CK, double* tot) {
+    __shared__ double red[256];
+    const int t = threadIdx.x;
+    if (CK >= 256) {
+        for (int q = t; q < CK; q += 256) {
+            double s = 0.0;
+            for (int b = 0; b < nb; ++b) s += part[(size_t)b * CK + q];
+            tot[q] = s;
+        }
+    } else {
+        const int G = 256 / CK, q = t / G, j = t - q * G;
+        double s = 0.0;
+        if (q < CK)
+            for (int b = j; b < nb; b += G) s += part[(size_t)b * CK + q];
+        red[t] = s;
+        __syncthreads();
+        if (q < CK && j == 0) {
+            double a = 0.0;
+            for (int i = 0; i < G; ++i) a += red[t + i];
+            tot[q] = a;
+        }
+    }
+    __syncthreads();
+}
+
+// grid (blocks_per_row, N), 256 threads: per block (Σ w[t]·nll, Σ w[t]) over the non-ignored voxels; a label outside [0, C)
+// is never used as an index and makes the loss sum NaN
+__global__ __launch_bounds__(256) void ce_fwd_kernel(const float* __restrict__ logits, const int64_t* __restrict__ target,
+                                                     const float* weight, int C, long long V, long long ignore,
+                                                     double* __restrict__ part) {
+    const int n = blockIdx.y;
+    const float* x = logits + (size_t)n * C * V;
+    const int64_t* tg = target + (size_t)n * V;
+    double sl = 0.0, sw = 0.0;
+    for (long long v = (long long)blockIdx.x * 256 + threadIdx.x; v < V; v += (long long)gridDim.x * 256) {
+        const long long t = tg[v];
+        if (t == ignore) continue;
+        if (t < 0 || t >= C) {
+            sl = __builtin_nan("");  // the loss only: Σ w stays finite, so the other voxels keep their gradient
+            continue;
+        }
+        float m, s;
+        voxel_max_sum(x + v, V, C, m, s);
+        const float w = weight ? weight[t] : 1.f;
+        sl += (double)(w * (m + logf(s) - x[(size_t)t * V + v]));
+        sw += (double)w;
+    }
+    block_sum2_256(sl, sw);
+    if (threadIdx.x == 0) {
+        double* p = part + ((size_t)n * gridDim.x + blockIdx.x) * 2;
+        p[0] = sl;
+        p[1] = sw;
+    }
+}
+
+// one block: loss = Σ w·nll / Σ w (0/0 = NaN when every voxel is ignored), coef[c] = w_c, coef[C] = 1 / Σ w
+__global__ __launch_bounds__(256) void ce_finalize_kernel(const double* __restrict__ part, int nb, const float* weight, int C,
+                                                          float* loss, float* coef) {
+    __shared__ double tot[2];
+    reduce_partials(part, nb, 2, tot);
+    if (weight != coef)
+        for (int c = threadIdx.x; c < C; c += 256) coef[c] = weight ? weight[c] : 1.f;
+    if (threadIdx.x == 0) {
+        loss[0] = (float)(tot[0] / tot[1]);
+        coef[C] = (float)(1.0 / tot[1]);
+    }
+}
+
+// dlogits = g · coef[t] · coef[C] · (softmax − onehot(t)); 0 on ignored voxels, NaN (in range) for labels outside [0, C);
+// grid (blocks_per_row, N, channel chunks)
+__global__ __launch_bounds__(256) void ce_bwd_kernel(const float* __restrict__ logits, const int64_t* __restrict__ target,
+                                                     const float* __restrict__ coef, const float* __restrict__ grad_out, int C,
+                                                     long long V, long long ignore, float* __restrict__ dlogits) {
+    const int n = blockIdx.y;
+    const float* x = logits + (size_t)n * C * V;
+    const int64_t* tg = target + (size_t)n * V;
+    float* d = dlogits + (size_t)n * C * V;
+    const int c0 = blockIdx.z * MC_BWD_CHUNK, c1 = min(C, c0 + MC_BWD_CHUNK);  // this block's channels
+    const float g = (grad_out ? grad_out[0] : 1.f) * coef[C];
+    for (long long v = (long long)blockIdx.x * 256 + threadIdx.x; v < V; v += (long long)gridDim.x * 256) {
+        const long long t = tg[v];
+        if (t == ignore || t < 0 || t >= C) {
+            const float z = t == ignore ? 0.f : __builtin_nanf("");
+            for (int c = c0; c < c1; ++c) d[(size_t)c * V + v] = z;
+            continue;
+        }
+        float m, s;
+        voxel_max_sum(x + v, V, C, m, s);
+        const float sc = g * coef[t], inv = 1.f / s;
+        for (int c = c0; c < c1; ++c) {
+            const float p = expf(x[(size_t)c * V + v] - m) * inv;
+            d[(size_t)c * V + v] = sc * (c == t ? p - 1.f : p);
+        }
+    }
+}
+
+// channel sums; grid (blocks_per_row, N, channel chunks of CR), 256 threads; accumulators in registers for the chunk's
+// channels [c0, c0 + CR); part[(n*gx + bx)][C][MC_K]
+template <int CR>
+__global__ __launch_bounds__(256) void chan_sums_kernel(const float* __restrict__ logits, const float* __restrict__ target,
+                                                        int C, long long V, int norm, double* __restrict__ part) {
+    const int n = blockIdx.y, c0 = blockIdx.z * CR;
+    const int cn = min(CR, C - c0);  // channels of this chunk
+    const float* x = logits + (size_t)n * C * V;
+    const float* xc = x + (size_t)c0 * V;
+    const float* tg = target ? target + ((size_t)n * C + c0) * V : nullptr;
+    float acc[CR][MC_K];
+#pragma unroll
+    for (int c = 0; c < CR; ++c)
+#pragma unroll
+        for (int k = 0; k < MC_K; ++k) acc[c][k] = 0.f;
+    for (long long v = (long long)blockIdx.x * 256 + threadIdx.x; v < V; v += (long long)gridDim.x * 256) {
+        float p[CR];
+#pragma unroll
+        for (int c = 0; c < CR; ++c) p[c] = c < cn ? xc[(size_t)c * V + v] : 0.f;
+        if (norm == MC_NORM_SOFTMAX) {
+            float m, s;
+            if (cn == C) {  // the whole voxel is in registers
+                m = p[0];
+#pragma unroll
+                for (int c = 1; c < CR; ++c)
+                    if (c < cn) m = fmaxf(m, p[c]);
+                s = 0.f;
+#pragma unroll
+                for (int c = 0; c < CR; ++c)
+                    if (c < cn) s += expf(p[c] - m);
+            } else {
+                voxel_max_sum(x + v, V, C, m, s);
+            }
+            const float inv = 1.f / s;
+#pragma unroll
+            for (int c = 0; c < CR; ++c) p[c] = expf(p[c] - m) * inv;
+        } else if (norm == MC_NORM_SIGMOID) {
+#pragma unroll
+            for (int c = 0; c < CR; ++c) p[c] = sigmoidf_(p[c]);
+        }
+#pragma unroll
+        for (int c = 0; c < CR; ++c)
+            if (c < cn) {
+                const float t = tg ? tg[(size_t)c * V + v] : 0.f;
+                acc[c][0] += p[c] * t;
+                acc[c][1] += p[c] * p[c];
+                acc[c][2] += t * t;
+                acc[c][3] += p[c];
+                acc[c][4] += t;
+            }
+    }
+    __shared__ float red[4][CR * MC_K];
+    const int l = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+    for (int c = 0; c < CR; ++c)
+        if (c < cn)
+#pragma unroll
+            for (int k = 0; k < MC_K; ++k) {
+                float s = acc[c][k];
+#pragma unroll
+                for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m);
+                if (l == 0) red[w][c * MC_K + k] = s;
+            }
+    __syncthreads();
+    double* out = part + ((size_t)n * gridDim.x + blockIdx.x) * C * MC_K + (size_t)c0 * MC_K;
+    for (int q = threadIdx.x; q < cn * MC_K; q += 256)
+        out[q] = ((double)red[0][q] + (double)red[1][q]) + ((double)red[2][q] + (double)red[3][q]);
+}
+
+// one block: w_c = (M − S_c) / S_c (WeightedCrossEntropyLoss._class_weights) into coef[0, C)
+__global__ __launch_bounds__(256) void wce_weights_kernel(const double* __restrict__ part, int nb, int C, double M,
+                                                          float* __restrict__ coef) {
+    __shared__ double tot[MC_MAX_C * MC_K];
+    reduce_partials(part, nb, C * MC_K, tot);
+    for (int c = threadIdx.x; c < C; c += 256) {
+        const double S = tot[c * MC_K + 3];
+        coef[c] = (float)((M - S) / S);
+    }
+}
+
+// one block: the Dice loss and the affine gradient coef[3c..3c+2] = (a_c, b_c, k_c) of dL/dp_c = a_c·t + b_c·p + k_c
+__global__ __launch_bounds__(256) void dice_finalize_kernel(const double* __restrict__ part, int nb, int C,
+                                                            const float* __restrict__ weight, int generalized, float eps_f,
+                                                            double M, float* __restrict__ loss, float* __restrict__ coef) {
+    __shared__ double tot[MC_MAX_C * MC_K];
+    reduce_partials(part, nb, C * MC_K, tot);
+    if (threadIdx.x != 0) return;
+    const double eps = (double)eps_f;
+    if (!generalized) {
+        // compute_per_channel_dice: dice_c = 2 w_c I_c / clamp(P2_c + T2_c, eps); loss = 1 − mean_c dice_c
+        double acc = 0.0;
+        for (int c = 0; c < C; ++c) {
+            const double I = tot[c * MC_K + 0], raw = tot[c * MC_K + 1] + tot[c * MC_K + 2];
+            const double wc = weight ? (double)weight[c] : 1.0;
+            const bool clamped = raw < eps;  // clamp(min=eps): no gradient through the clamped branch
+            const double den = clamped ? eps : raw;
+            acc += 2.0 * wc * I / den;
+            coef[3 * c + 0] = (float)(-2.0 * wc / (C * den));
+            coef[3 * c + 1] = clamped ? 0.f : (float)(4.0 * wc * I / (C * den * den));
+            coef[3 * c + 2] = 0.f;
+        }
+        loss[0] = (float)(1.0 - acc / C);
+        return;
+    }
+    // GeneralizedDiceLoss.dice: w_j = 1 / clamp(T_j², eps) (constant), I = Σ_j w_j I_j, D = Σ_j clamp(w_j (P_j + T_j), eps),
+    // loss = 1 − 2 I / D; a single channel becomes the pair (p, 1 − p) / (t, 1 − t)
+    const int J = C == 1 ? 2 : C;
+    double I = 0.0, D = 0.0;
+    for (int j = 0; j < J; ++j) {
+        const double* s = tot + (C == 1 ? 0 : j * MC_K);
+        const double pt = s[0], P = s[3], T = s[4];
+        const double Ij = j == 1 && C == 1 ? M - P - T + pt : pt;
+        const double Pj = j == 1 && C == 1 ? M - P : P, Tj = j == 1 && C == 1 ? M - T : T;
+        const double w = 1.0 / fmax(Tj * Tj, eps);
+        I += w * Ij;
+        D += fmax(w * (Pj + Tj), eps);
+    }
+    loss[0] = (float)(1.0 - 2.0 * I / D);
+    // dL/dp_j = −2 w_j t_j / D + 2 I w_j [w_j (P_j + T_j) >= eps] / D²
+    double a[2] = {0.0, 0.0}, k[2] = {0.0, 0.0};
+    for (int j = 0; j < J; ++j) {
+        const double* s = tot + (C == 1 ? 0 : j * MC_K);
+        const double P = s[3], T = s[4];
+        const double Pj = j == 1 && C == 1 ? M - P : P, Tj = j == 1 && C == 1 ? M - T : T;
+        const double w = 1.0 / fmax(Tj * Tj, eps);
+        const double aj = -2.0 * w / D, kj = w * (Pj + Tj) < eps ? 0.0 : 2.0 * I * w / (D * D);
+        if (C == 1) {
+            a[j] = aj, k[j] = kj;
+        } else {
+            coef[3 * j + 0] = (float)aj;
+            coef[3 * j + 1] = 0.f;
+            coef[3 * j + 2] = (float)kj;
+        }
+    }
+    if (C == 1) {  // p_1 = 1 − p, t_1 = 1 − t: dL/dp = (a_0 t + k_0) − (a_1 (1 − t) + k_1)
+        coef[0] = (float)(a[0] + a[1]);
+        coef[1] = 0.f;
+        coef[2] = (float)(k[0] - a[1] - k[1]);
+    }
+}
+
+// dlogits = g · dL/dx through the normalisation: sigmoid p(1−p)·G_c, softmax p_c (G_c − Σ_k p_k G_k), none G_c;
+// grid (blocks_per_row, N, channel chunks)
+__global__ __launch_bounds__(256) void dice_bwd_kernel(const float* __restrict__ logits, const float* __restrict__ target,
+                                                       const float* __restrict__ coef, const float* __restrict__ grad_out, int C,
+                                                       long long V, int norm, float* __restrict__ dlogits) {
+    const int n = blockIdx.y;
+    const float* x = logits + (size_t)n * C * V;
+    const float* tg = target + (size_t)n * C * V;
+    float* d = dlogits + (size_t)n * C * V;
+    const int c0 = blockIdx.z * MC_BWD_CHUNK, c1 = min(C, c0 + MC_BWD_CHUNK);  // this block's channels
+    const float g = grad_out ? grad_out[0] : 1.f;
+    for (long long v = (long long)blockIdx.x * 256 + threadIdx.x; v < V; v += (long long)gridDim.x * 256) {
+        if (norm == MC_NORM_SOFTMAX) {
+            float m, s;
+            voxel_max_sum(x + v, V, C, m, s);
+            const float inv = 1.f / s;
+            float dot = 0.f;
+            for (int c = 0; c < C; ++c) {
+                const size_t i = (size_t)c * V + v;
+                const float p = expf(x[i] - m) * inv;
+                dot += p * (coef[3 * c] * tg[i] + coef[3 * c + 1] * p + coef[3 * c + 2]);
+            }
+            for (int c = c0; c < c1; ++c) {
+                const size_t i = (size_t)c * V + v;
+                const float p = expf(x[i] - m) * inv;
+                d[i] = g * p * (coef[3 * c] * tg[i] + coef[3 * c + 1] * p + coef[3 * c + 2] - dot);
+            }
+        } else {
+            for (int c = c0; c < c1; ++c) {
+                const size_t i = (size_t)c * V + v;
+                const float p = norm == MC_NORM_SIGMOID ? sigmoidf_(x[i]) : x[i];
+                const float gc = coef[3 * c] * tg[i] + coef[3 * c + 1] * p + coef[3 * c + 2];
+                d[i] = g * (norm == MC_NORM_SIGMOID ? gc * p * (1.f - p) : gc);
+            }
+        }
+    }
+}
+
+inline long long chan_sums_doubles(int N, int C, long long V) { return (long long)N * mc_blocks_per_row(N, C, V) * C * MC_K; }
+
+// the channel-sums pass; returns the number of partial rows
+inline int launch_chan_sums(hipStream_t st, const float* logits, const float* target, int N, int C, long long V, int norm,
+                            double* part) {
+    const unsigned gx = mc_blocks_per_row(N, C, V);
+    if (C <= 4)
+        hipLaunchKernelGGL(chan_sums_kernel<4>, dim3(gx, (unsigned)N, 1), dim3(256), 0, st, logits, target, C, V, norm, part);
+    else
+        hipLaunchKernelGGL(chan_sums_kernel<MC_CS_CHUNK>, dim3(gx, (unsigned)N, mc_chunks(C, MC_CS_CHUNK)), dim3(256), 0, st,
+                           logits, target, C, V, norm, part);
+    return (int)(gx * N);
+}
+
+}  // namespace
+
+extern "C" long long u3d_softmax_ce_scratch_doubles(int N, int C, int64_t V) {
+    if (N <= 0 || C <= 0 || V <= 0 || C > MC_MAX_C) return 0;
+    const long long ce = (long long)N * mc_blocks_per_row(N, 1, V) * 2;
+    const long long cs = chan_sums_doubles(N, C, V);
+    return ce > cs ? ce : cs;
+}
+
+extern "C" int u3d_softmax_ce_fwd(int device, u3d_stream_t stream, const float* logits, const int64_t* target, const float* weight,
+                                  int N, int C, int64_t V, int64_t ignore_index, int auto_weight, double* scratch, float* loss,
+                                  float* coef) {
+    U3D_ENTER(device);
+    U3D_REQUIRE(logits && target && scratch && loss && coef && N > 0 && C > 0 && V > 0, "u3d_softmax_ce_fwd: bad argument");
+    U3D_REQUIRE(N < 65536 && C <= MC_MAX_C, "u3d_softmax_ce_fwd: needs N < 65536 and C <= 1024");
+    U3D_REQUIRE(!(auto_weight && weight), "u3d_softmax_ce_fwd: auto_weight excludes a weight vector");
+    hipStream_t st = (hipStream_t)stream;
+    if (auto_weight) {
+        const int nb = launch_chan_sums(st, logits, nullptr, N, C, (long long)V, MC_NORM_SOFTMAX, scratch);
+        U3D_LAUNCH_CHECK();
+        hipLaunchKernelGGL(wce_weights_kernel, dim3(1), dim3(256), 0, st, scratch, nb, C, (double)N * (double)V, coef);
+        U3D_LAUNCH_CHECK();
+        weight = coef;
+    }
+    const dim3 grid(mc_blocks_per_row(N, 1, V), (unsigned)N);
+    hipLaunchKernelGGL(ce_fwd_kernel, grid, dim3(256), 0, st, logits, target, weight, C, (long long)V, (long long)ignore_index,
+                       scratch);
+    U3D_LAUNCH_CHECK();
+    hipLaunchKernelGGL(ce_finalize_kernel, dim3(1), dim3(256), 0, st, scratch, (int)(grid.x * grid.y), weight, C, loss, coef);
+    U3D_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int u3d_softmax_ce_bwd(int device, u3d_stream_t stream, const float* logits, const int64_t* target, const float* coef,
+                                  const float* grad_out, int N, int C, int64_t V, int64_t ignore_index, float* dlogits) {
+    U3D_ENTER(device);
+    U3D_REQUIRE(logits && target && coef && dlogits && N > 0 && C > 0 && V > 0, "u3d_softmax_ce_bwd: bad argument");
+    U3D_REQUIRE(N < 65536 && C <= MC_MAX_C, "u3d_softmax_ce_bwd: needs N < 65536 and C <= 1024");
+    const dim3 grid(mc_blocks_per_row(N, 1, V), (unsigned)N, mc_chunks(C, MC_BWD_CHUNK));
+    hipLaunchKernelGGL(ce_bwd_kernel, grid, dim3(256), 0, (hipStream_t)stream, logits, target, coef, grad_out, C, (long long)V,
+                       (long long)ignore_index, dlogits);
+    U3D_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" long long u3d_dice_scratch_doubles(int N, int C, int64_t V) {
+    if (N <= 0 || C <= 0 || V <= 0 || C > MC_MAX_C) return 0;
+    return chan_sums_doubles(N, C, V);
+}
+
+extern "C" int u3d_dice_fwd(int device, u3d_stream_t stream, const float* logits, const float* target, const float* weight,
+                            int N, int C, int64_t V, int norm, int generalized, float eps, double* scratch, float* loss,
+                            float* coef) {
+    U3D_ENTER(device);
+    U3D_REQUIRE(logits && target && scratch && loss && coef && N > 0 && C > 0 && V > 0, "u3d_dice_fwd: bad argument");
+    U3D_REQUIRE(N < 65536 && C <= MC_MAX_C, "u3d_dice_fwd: needs N < 65536 and C <= 1024");
+    U3D_REQUIRE(norm >= MC_NORM_SIGMOID && norm <= MC_NORM_NONE, "u3d_dice_fwd: norm must be 0 (sigmoid), 1 (softmax) or 2 (none)");
+    U3D_REQUIRE(!(generalized && weight), "u3d_dice_fwd: the generalized Dice takes no class weight");
+    hipStream_t st = (hipStream_t)stream;
+    const int nb = launch_chan_sums(st, logits, target, N, C, (long long)V, norm, scratch);
+    U3D_LAUNCH_CHECK();
+    hipLaunchKernelGGL(dice_finalize_kernel, dim3(1), dim3(256), 0, st, scratch, nb, C, weight, generalized ? 1 : 0, eps,
+                       (double)N * (double)V, loss, coef);
+    U3D_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int u3d_dice_bwd(int device, u3d_stream_t stream, const float* logits, const float* target, const float* coef,
+                            const float* grad_out, int N, int C, int64_t V, int norm, float* dlogits) {
+    U3D_ENTER(device);
+    U3D_REQUIRE(logits && target && coef && dlogits && N > 0 && C > 0 && V > 0, "u3d_dice_bwd: bad argument");
+    U3D_REQUIRE(N < 65536 && C <= MC_MAX_C, "u3d_dice_bwd: needs N < 65536 and C <= 1024");
+    U3D_REQUIRE(norm >= MC_NORM_SIGMOID && norm <= MC_NORM_NONE, "u3d_dice_bwd: norm must be 0 (sigmoid), 1 (softmax) or 2 (none)");
+    const dim3 grid(mc_blocks_per_row(N, 1, V), (unsigned)N, mc_chunks(C, MC_BWD_CHUNK));
+    hipLaunchKernelGGL(dice_bwd_kernel, grid, dim3(256), 0, (hipStream_t)stream, logits, target, coef, grad_out, C, (long long)V,
+                       norm, dlogits);
     U3D_LAUNCH_CHECK();
     return 0;
 }

@@ -9,8 +9,13 @@ path is ~15 ATen kernels, a permute+contiguous copy (`flatten`, losses.py:253-27
 temporaries; the fused path is two reads of (logits, target) and one write of dlogits, and the upstream scalar gradient
 is consumed on the device (no host synchronisation on the step's critical path).
 
-CPU tensors, other dtypes, softmax / no normalisation run the same formulas on torch operators (what the reference
-does), so `device: cpu` configs behave identically.
+The multi-class losses are fused too (same file, C-ABI `u3d_softmax_ce_*` / `u3d_dice_*`): `nn.CrossEntropyLoss`
+(mean reduction, no label smoothing, optional `weight` / `ignore_index`; losses.py:316-319), `WeightedCrossEntropyLoss`
+(losses.py:204-227), `DiceLoss` with softmax / no normalisation and `GeneralizedDiceLoss` (losses.py:148-184), for
+C <= 1024 classes.  Loss and gradient are bit-reproducible (per-block partials in double, summed in a fixed order).
+
+CPU tensors, other dtypes and unsupported options run the same formulas on torch operators (what the reference does),
+so `device: cpu` configs behave identically.
 """
 import ctypes
 import functools
@@ -45,6 +50,116 @@ def _native_ok(input, target):
     return (input.is_cuda and input.dtype == torch.float32 and target.dtype == torch.float32
             and input.shape == target.shape and input.dim() >= 3 and input.numel() > 0
             and input.shape[0] * input.shape[1] < 65536)
+
+
+_MAX_CLASSES = 1024  # the head's channel limit, and the multi-class kernels'
+
+
+def _ce_native_ok(input, target):
+    """(N, C, *S) HIP fp32 logits with an int64 (N, *S) target on the same device, C <= 1024"""
+    return (input.is_cuda and input.dtype == torch.float32 and target.dtype == torch.int64 and target.device == input.device
+            and input.dim() >= 2 and tuple(target.shape) == (input.shape[0],) + tuple(input.shape[2:]) and input.numel() > 0
+            and input.shape[1] <= _MAX_CLASSES and input.shape[0] < 65536)
+
+
+def _dice_native_ok(input, target):
+    """(N, C, *S) HIP fp32 logits with an fp32 target of the same shape on the same device, C <= 1024"""
+    return (input.is_cuda and input.dtype == torch.float32 and target.dtype == torch.float32 and target.device == input.device
+            and tuple(target.shape) == tuple(input.shape) and input.dim() >= 2 and input.numel() > 0
+            and input.shape[1] <= _MAX_CLASSES and input.shape[0] < 65536)
+
+
+def _class_vector(weight, c, dev):
+    """an optional per-class weight as a contiguous device float[C] (None stays None)"""
+    if weight is None:
+        return None
+    wt = weight.to(device=dev, dtype=torch.float32).reshape(-1).contiguous()
+    assert wt.numel() == c, "the class weight must have one entry per channel"
+    return wt
+
+
+class _FusedSoftmaxCE(torch.autograd.Function):
+    """mean-reduced softmax cross entropy through u3d_softmax_ce_fwd/_bwd; auto_weight = WeightedCrossEntropyLoss's weights"""
+
+    @staticmethod
+    def forward(ctx, logits, target, weight, ignore_index, auto_weight):
+        from .. import _native as nat
+
+        logits = logits.contiguous()
+        target = target.contiguous()
+        dev = logits.device
+        n, c = logits.shape[0], logits.shape[1]
+        v = logits.numel() // (n * c)
+        scratch = torch.empty(nat.get_lib().u3d_softmax_ce_scratch_doubles(n, c, v), dtype=torch.float64, device=dev)
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        coef = torch.empty(c + 1, dtype=torch.float32, device=dev)
+        wt = _class_vector(weight, c, dev)
+        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        nat.call("u3d_softmax_ce_fwd", dev.index, stream, ctypes.c_void_p(logits.data_ptr()), ctypes.c_void_p(target.data_ptr()),
+                 None if wt is None else ctypes.c_void_p(wt.data_ptr()), n, c, v, int(ignore_index), 1 if auto_weight else 0,
+                 ctypes.c_void_p(scratch.data_ptr()), ctypes.c_void_p(loss.data_ptr()), ctypes.c_void_p(coef.data_ptr()))
+        ctx.save_for_backward(logits, target, coef)
+        ctx.dims = (n, c, v, int(ignore_index))
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        from .. import _native as nat
+
+        logits, target, coef = ctx.saved_tensors
+        n, c, v, ignore_index = ctx.dims
+        dev = logits.device
+        g = grad_out.to(dtype=torch.float32).reshape(1).contiguous()
+        dlogits = torch.empty_like(logits)
+        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        nat.call("u3d_softmax_ce_bwd", dev.index, stream, ctypes.c_void_p(logits.data_ptr()), ctypes.c_void_p(target.data_ptr()),
+                 ctypes.c_void_p(coef.data_ptr()), ctypes.c_void_p(g.data_ptr()), n, c, v, ignore_index,
+                 ctypes.c_void_p(dlogits.data_ptr()))
+        return dlogits, None, None, None, None
+
+
+_NORM_CODE = {"sigmoid": 0, "softmax": 1, "none": 2}
+
+
+class _FusedDice(torch.autograd.Function):
+    """per-channel Dice (generalized = False) or generalized Dice loss through u3d_dice_fwd/_bwd"""
+
+    @staticmethod
+    def forward(ctx, logits, target, weight, normalization, generalized, eps):
+        from .. import _native as nat
+
+        logits = logits.contiguous()
+        target = target.contiguous()
+        dev = logits.device
+        n, c = logits.shape[0], logits.shape[1]
+        v = logits.numel() // (n * c)
+        norm = _NORM_CODE[normalization]
+        scratch = torch.empty(nat.get_lib().u3d_dice_scratch_doubles(n, c, v), dtype=torch.float64, device=dev)
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        coef = torch.empty(3 * c, dtype=torch.float32, device=dev)
+        wt = _class_vector(weight, c, dev)
+        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        nat.call("u3d_dice_fwd", dev.index, stream, ctypes.c_void_p(logits.data_ptr()), ctypes.c_void_p(target.data_ptr()),
+                 None if wt is None else ctypes.c_void_p(wt.data_ptr()), n, c, v, norm, 1 if generalized else 0, float(eps),
+                 ctypes.c_void_p(scratch.data_ptr()), ctypes.c_void_p(loss.data_ptr()), ctypes.c_void_p(coef.data_ptr()))
+        ctx.save_for_backward(logits, target, coef)
+        ctx.dims = (n, c, v, norm)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        from .. import _native as nat
+
+        logits, target, coef = ctx.saved_tensors
+        n, c, v, norm = ctx.dims
+        dev = logits.device
+        g = grad_out.to(dtype=torch.float32).reshape(1).contiguous()
+        dlogits = torch.empty_like(logits)
+        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        nat.call("u3d_dice_bwd", dev.index, stream, ctypes.c_void_p(logits.data_ptr()), ctypes.c_void_p(target.data_ptr()),
+                 ctypes.c_void_p(coef.data_ptr()), ctypes.c_void_p(g.data_ptr()), n, c, v, norm,
+                 ctypes.c_void_p(dlogits.data_ptr()))
+        return dlogits, None, None, None, None, None
 
 
 class _FusedBCEDice(torch.autograd.Function):
@@ -136,8 +251,39 @@ class DiceLoss(_AbstractDiceLoss):
         return compute_per_channel_dice(input, target, weight=self.weight)
 
     def forward(self, input, target):
-        if self.normalization_name == "sigmoid" and _native_ok(input, target):
-            return fused_bce_dice(input, target, 0.0, 1.0, self.weight)
+        if self.normalization_name == "sigmoid":
+            if _native_ok(input, target):
+                return fused_bce_dice(input, target, 0.0, 1.0, self.weight)
+        elif _dice_native_ok(input, target) and (self.weight is None or self.weight.numel() == input.shape[1]):
+            return _FusedDice.apply(input, target, self.weight, self.normalization_name, False, 1e-6)
+        return super().forward(input, target)
+
+
+class GeneralizedDiceLoss(_AbstractDiceLoss):
+    """Generalized Dice loss (losses.py:148-184): w_l = 1 / clamp(T_l^2, eps) per class, loss = 1 - 2 sum_l w_l I_l /
+    sum_l clamp(w_l (P_l + T_l), eps); a single channel is taken as the pair (p, 1 - p).  Fused on an MI355X."""
+
+    def __init__(self, normalization="sigmoid", epsilon=1e-6):
+        super().__init__(weight=None, normalization=normalization)
+        self.epsilon = epsilon
+
+    def dice(self, input, target, weight):
+        assert input.size() == target.size(), "'input' and 'target' must have the same shape"
+        input = flatten(input)
+        target = flatten(target).float()
+        if input.size(0) == 1:
+            input = torch.cat((input, 1 - input), dim=0)
+            target = torch.cat((target, 1 - target), dim=0)
+        w_l = target.sum(-1)
+        w_l = 1 / (w_l * w_l).clamp(min=self.epsilon)
+        w_l.requires_grad = False
+        intersect = (input * target).sum(-1) * w_l
+        denominator = ((input + target).sum(-1) * w_l).clamp(min=self.epsilon)
+        return 2 * (intersect.sum() / denominator.sum())
+
+    def forward(self, input, target):
+        if _dice_native_ok(input, target):
+            return _FusedDice.apply(input, target, None, self.normalization_name, True, self.epsilon)
         return super().forward(input, target)
 
 
@@ -165,27 +311,61 @@ class BCEWithLogitsLoss(nn.BCEWithLogitsLoss):
         return super().forward(input, target)
 
 
+class CrossEntropyLoss(nn.CrossEntropyLoss):
+    """nn.CrossEntropyLoss (losses.py:316-319); mean reduction without label smoothing, optional `weight` / `ignore_index`, on
+    HIP fp32 logits (N, C, *S) with an int64 (N, *S) target and C <= 1024 is fused on an MI355X."""
+
+    def forward(self, input, target):
+        if (self.reduction == "mean" and self.label_smoothing == 0 and _ce_native_ok(input, target)
+                and (self.weight is None or self.weight.numel() == input.shape[1])):
+            return _FusedSoftmaxCE.apply(input, target, self.weight, self.ignore_index, False)
+        return super().forward(input, target)
+
+
+class WeightedCrossEntropyLoss(nn.Module):
+    """Cross entropy with per-batch class weights w_c = sum(1 - p_c) / sum(p_c) of the softmax, detached (losses.py:204-227).
+    Fused on an MI355X."""
+
+    def __init__(self, ignore_index=-1):
+        super().__init__()
+        self.ignore_index = ignore_index
+
+    def forward(self, input, target):
+        if _ce_native_ok(input, target):
+            return _FusedSoftmaxCE.apply(input, target, None, self.ignore_index, True)
+        weight = self._class_weights(input)
+        return F.cross_entropy(input, target, weight=weight, ignore_index=self.ignore_index)
+
+    @staticmethod
+    def _class_weights(input):
+        flattened = flatten(F.softmax(input, dim=1))
+        return ((1.0 - flattened).sum(-1) / flattened.sum(-1)).detach()
+
+
 # ---------------------------------------------------------------------------------------------------------------
 # Everything else of the reference's losses.py (option handling of `get_loss_criterion`, the masking / skip-last-channel
-# wrappers, GeneralizedDice, weighted cross entropy / SmoothL1; losses.py:40-82,148-184,204-345) is host code that this
-# repository does NOT restate: the three fused classes above are patched INTO the caller's own
-# `pytorch3dunet.unet3d.losses` module, whose factory and wrappers keep running unchanged.
-_FUSED = ("BCEDiceLoss", "DiceLoss")
+# wrappers, the regression losses; losses.py:40-82,230-250,273-345) is host code that this repository does NOT restate:
+# the fused classes above are patched INTO the caller's own `pytorch3dunet.unet3d.losses` module, whose factory and
+# wrappers keep running unchanged.
+_FUSED = ("BCEDiceLoss", "DiceLoss", "WeightedCrossEntropyLoss", "GeneralizedDiceLoss")
+_UPGRADES = {nn.BCEWithLogitsLoss: BCEWithLogitsLoss, nn.CrossEntropyLoss: CrossEntropyLoss}
 
 
-def _upgrade_bce(module):
-    """`_create_loss` builds `nn.BCEWithLogitsLoss(pos_weight=...)` from torch.nn directly (losses.py:312-313): give such
-    instances the fused forward by switching their class to the subclass above (same state, no extra attributes)."""
+def _upgrade(module):
+    """`_create_loss` builds `nn.BCEWithLogitsLoss(pos_weight=...)` and `nn.CrossEntropyLoss(weight, ignore_index)` from
+    torch.nn directly (losses.py:312-319): give such instances the fused forward by switching their class to the subclass
+    above (same state and `weight` buffer, no extra attributes)."""
     for m in module.modules():
-        if type(m) is nn.BCEWithLogitsLoss:
-            m.__class__ = BCEWithLogitsLoss
+        cls = _UPGRADES.get(type(m))
+        if cls is not None:
+            m.__class__ = cls
     return module
 
 
 def install_fused(ref_losses):
     """Patch the fused loss family into the caller's `pytorch3dunet.unet3d.losses` module (idempotent): its own `_create_loss`
-    (losses.py:310-345) looks `BCEDiceLoss` / `DiceLoss` up in its module globals at call time, and its `get_loss_criterion`
-    is wrapped once so that plain `nn.BCEWithLogitsLoss` instances come back with the fused forward.  Must run before
+    (losses.py:310-345) looks the fused classes up in its module globals at call time, and its `get_loss_criterion`
+    is wrapped once so that plain `nn.BCEWithLogitsLoss` / `nn.CrossEntropyLoss` instances come back with the fused forward.  Must run before
     `pytorch3dunet.unet3d.trainer` is imported (trainer.py:16 binds `get_loss_criterion` by name)."""
     if ref_losses is sys.modules[__name__]:
         raise RuntimeError("install_fused() takes the REFERENCE's pytorch3dunet.unet3d.losses module, not this one")
@@ -197,7 +377,7 @@ def install_fused(ref_losses):
 
     @functools.wraps(inner)
     def get_loss_criterion(config):
-        return _upgrade_bce(inner(config))
+        return _upgrade(inner(config))
 
     ref_losses.get_loss_criterion = get_loss_criterion
     ref_losses._u3d_fused = True
@@ -213,7 +393,7 @@ def get_loss_criterion(config):
     except ImportError as e:
         raise ImportError("pytorch3dunet_amd.unet3d.losses.get_loss_criterion delegates to the reference's own "
                           "pytorch3dunet.unet3d.losses (wolny/pytorch-3dunet), which is not importable; construct "
-                          "BCEDiceLoss / DiceLoss / BCEWithLogitsLoss of this module directly instead") from e
+                          "the fused loss classes of this module directly instead") from e
     if ref is sys.modules[__name__]:
         raise RuntimeError("pytorch3dunet.unet3d.losses is aliased to pytorch3dunet_amd.unet3d.losses (the pre-round-4 seam); "
                            "use pytorch3dunet_amd.launch.install_seam() / losses.install_fused(reference_module) instead")
