@@ -827,6 +827,13 @@ long long u3d_conv2d_workspace_floats(int N, int H, int W, int Cin, int Cout);
 int u3d_conv2d_ex_reps(int device, u3d_stream_t stream, const u3d_src_t* src, const float* packed_w, float* out, int N, int H, int W,
                        int Cout, int relu, double* out_stats, const u3d_src_t* gx, double* gstats, float* workspace,
                        long long workspace_floats, int stat_reps);
+/* (Added, U3D_VERSION unchanged.)  The same convolution with a residual added before the ReLU — the tail of ResNetBlock in
+ * ResidualUNet2D (buildingblocks.py:277-288, `native_2d_residual: true`): out = [relu](conv2d(src) + residual), residual (N,H,W,Cout)
+ * fp32.  out_stats are the sums of the written values (as u3d_conv3d_ex_reps with a residual); split-K adds the residual in its fixed-order
+ * reduction.  Arguments as u3d_conv2d_ex_reps; gx must be NULL (a residual and the data-gradient statistics exclude each other). */
+int u3d_conv2d_res_reps(int device, u3d_stream_t stream, const u3d_src_t* src, const float* packed_w, float* out, int N, int H, int W,
+                        int Cout, int relu, double* out_stats, const u3d_src_t* gx, double* gstats, float* workspace,
+                        long long workspace_floats, int stat_reps, const float* residual);
 /* Weight gradient of the same convolution (autograd of nn.Conv2d, buildingblocks.py:55-58): dw[cout][cin][ky][kx] =
  * sum_{n,y,x} dz[n,y,x,cout] * g[n, y+ky-1, x+kx-1, cin], g = src with its affine, zero padded.  dw is written (not accumulated) in the
  * reference layout (Cout,Cin,3,3).  Blocks own 32 x 32 channels x 9 taps over a pixel range; their partial sums are added in a fixed
@@ -844,6 +851,28 @@ int u3d_maxpool2d_bwd_merge(int device, u3d_stream_t stream, const float* dg, co
 int u3d_maxpool2d_bwd_merge_gn(int device, u3d_stream_t stream, const float* dg, const float* pooled, const uint8_t* argmax,
                                const float* coef, const float* skip_dg, int Cdg, const float* skip_coef, int Ctot, const float* e, int N,
                                int H, int W, int C, int relu_mask, float* out);
+
+/* ---- (Added, U3D_VERSION unchanged.)  2-D transposed convolution of ResidualUNet2D's decoders: ConvTranspose2d(k=3, stride=2,
+ * padding=1, bias=False) (buildingblocks.py:617-664; csrc/u3d_res.hip).  x (N,H1,W1,Cin) -> t (N,2H1-1,2W1-1,Cout), NHWC fp32; the
+ * weight is the reference's (Cin, Cout, 3, 3).  fp32 gather GEMMs on v_mfma_f32_32x32x2_f32: the forward runs the four output parity
+ * classes (1, 2, 2 and 4 taps: 9 multiply-adds per channel pair and 2x2 output quad, none on the inserted zeros).  Any Cin, Cout >= 1,
+ * any H1, W1 >= 1; N*(2H1-1)*(2W1-1) < 2^31.  The library never allocates and never synchronises.
+ *   u3d_pack_convtr2d            weight image of u3d_convtr2d_packed_floats() floats: mode 0 = [tap][ci][co] (forward),
+ *                                mode 1 = [tap][co][ci] (data gradient)
+ *   u3d_convtr2d_fwd             t = conv_transpose2d(x, w) with the mode-0 image
+ *   u3d_convtr2d_dgrad           dx[i, ci] = sum_{tap, co} dt[2i - 1 + tap, co] * w[ci, co, tap] with the mode-1 image; with x_low
+ *                                non-NULL, dx = 0 where x_low <= 0 (ReLU backward of the block that produced x)
+ *   u3d_convtr2d_wgrad           dw[ci][co][ky][kx] (= sum_i x[i, ci] * dt[2i - 1 + tap, co]) written, or added to dw when accumulate;
+ *                                summed in double in `workspace` (u3d_convtr2d_wgrad_workspace_doubles(), zeroed by the call) */
+size_t u3d_convtr2d_packed_floats(int Cin, int Cout);
+size_t u3d_convtr2d_wgrad_workspace_doubles(int Cin, int Cout);
+int u3d_pack_convtr2d(int device, u3d_stream_t stream, const float* w, int Cin, int Cout, int mode, float* packed);
+int u3d_convtr2d_fwd(int device, u3d_stream_t stream, const float* x, const float* packed, float* t, int N, int H1, int W1, int Cin,
+                     int Cout);
+int u3d_convtr2d_dgrad(int device, u3d_stream_t stream, const float* dt, const float* packed_t, const float* x_low, float* dx, int N,
+                       int H1, int W1, int Cin, int Cout);
+int u3d_convtr2d_wgrad(int device, u3d_stream_t stream, const float* x, const float* dt, float* dw, int N, int H1, int W1, int Cin,
+                       int Cout, int accumulate, double* workspace, size_t workspace_doubles);
 
 /* ---- layout: NCDHW <-> NDHWC for multi-channel model inputs ------------------------------------ */
 int u3d_ncdhw_to_ndhwc(int device, u3d_stream_t stream, const float* src, float* dst, int N, int C, int64_t V);

@@ -118,6 +118,7 @@ struct Conv2dParams {
     u3d_src_t src;
     u3d_src_t gx;
     const float* wp;
+    const float* residual;  // (N,H,W,Cout) added before the ReLU (conv2d_mfma_kernel<.., RES = true>), or null
     float* out;        // ksplit == 1: the output; else the workspace of partial sums [ksplit][N*H*W*Cout]
     double* out_stats;
     double* gstats;
@@ -175,7 +176,7 @@ __device__ __forceinline__ void c2_flush_stats(const Conv2dParams& p, float* red
     }
 }
 
-template <int NT, bool VEC>
+template <int NT, bool VEC, bool RES>
 __global__ __launch_bounds__(256, 2) void conv2d_mfma_kernel(const Conv2dParams p) {
     using namespace c2;
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -322,6 +323,7 @@ __global__ __launch_bounds__(256, 2) void conv2d_mfma_kernel(const Conv2dParams 
                     outp[o] = v;
                     continue;
                 }
+                if (RES) v += p.residual[o];
                 if (p.relu) v = fmaxf(v, 0.f);
                 outp[o] = v;
                 s[nt][0] += v;
@@ -335,12 +337,12 @@ __global__ __launch_bounds__(256, 2) void conv2d_mfma_kernel(const Conv2dParams 
     if (p.ksplit == 1 && (p.out_stats || p.has_gx)) c2_flush_stats<NT>(p, lds + RED, s, n, cb, t);
 }
 
-// split-K: out = [relu](sum over runs in run order), statistics as the main kernel.  Block = 64 pixels of one sample, threads walk the
+// split-K: out = [relu](sum over runs in run order [+ residual]), statistics as the main kernel.  Block = 64 pixels of one sample, threads walk the
 // channels (coalesced), one f64 atomic per (block, channel, quantity).
 __global__ __launch_bounds__(256) void conv2d_splitk_reduce_kernel(const float* __restrict__ part, long long part_stride, int ksplit,
                                                                    float* __restrict__ out, int N, int P, int Cout, int relu,
                                                                    double* out_stats, u3d_src_t gx, int has_gx, double* gstats,
-                                                                   int H, int W) {
+                                                                   int H, int W, const float* __restrict__ residual) {
     const int n = blockIdx.y;
     const int p0 = blockIdx.x * 64, p1 = min(P, p0 + 64);
     for (int co = threadIdx.x; co < Cout; co += blockDim.x) {
@@ -349,6 +351,7 @@ __global__ __launch_bounds__(256) void conv2d_splitk_reduce_kernel(const float* 
             const size_t o = ((size_t)n * P + pp) * Cout + co;
             float v = 0.f;
             for (int k = 0; k < ksplit; ++k) v += part[(size_t)k * part_stride + o];
+            if (residual) v += residual[o];
             if (relu) v = fmaxf(v, 0.f);
             out[o] = v;
             s0 += v;
@@ -402,9 +405,9 @@ extern "C" long long u3d_conv2d_workspace_floats(int N, int H, int W, int Cin, i
     return pl.ksplit > 1 ? (long long)pl.ksplit * N * H * W * Cout : 0;
 }
 
-extern "C" int u3d_conv2d_ex_reps(int device, u3d_stream_t stream, const u3d_src_t* src, const float* packed_w, float* out, int N,
-                                  int H, int W, int Cout, int relu, double* out_stats, const u3d_src_t* gx, double* gstats,
-                                  float* workspace, long long workspace_floats, int stat_reps) {
+static int conv2d_impl(int device, u3d_stream_t stream, const u3d_src_t* src, const float* packed_w, float* out, int N, int H, int W,
+                       int Cout, int relu, double* out_stats, const u3d_src_t* gx, double* gstats, const float* residual,
+                       float* workspace, long long workspace_floats, int stat_reps) {
     U3D_ENTER(device);
     U3D_REQUIRE(src && src->p0 && packed_w && out && N > 0 && H > 0 && W > 0 && Cout > 0 && src->C0 >= 0 && src->C1 >= 0 &&
                     src->C0 + src->C1 > 0 && stat_reps >= 1 && (long long)N * H * W < (1LL << 31),
@@ -421,6 +424,7 @@ extern "C" int u3d_conv2d_ex_reps(int device, u3d_stream_t stream, const u3d_src
     p.src = *src;
     if (gx) p.gx = *gx;
     p.wp = packed_w;
+    p.residual = residual;
     p.out = split ? workspace : out;
     p.out_stats = out_stats;
     p.gstats = gstats;
@@ -437,20 +441,42 @@ extern "C" int u3d_conv2d_ex_reps(int device, u3d_stream_t stream, const u3d_src
     U3D_REQUIRE(blocks < (1LL << 31), "u3d_conv2d_ex_reps: grid too large");
     const size_t lds = c2::LDS_FLOATS * sizeof(float);
     auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, p); };
-    if (pl.nt == 2)
-        vec ? go(conv2d_mfma_kernel<2, true>) : go(conv2d_mfma_kernel<2, false>);
-    else
-        vec ? go(conv2d_mfma_kernel<1, true>) : go(conv2d_mfma_kernel<1, false>);
+    if (residual) {  // (a template flag: the kernel without a residual operand is the one u3d_conv2d_ex_reps always ran)
+        if (pl.nt == 2)
+            vec ? go(conv2d_mfma_kernel<2, true, true>) : go(conv2d_mfma_kernel<2, false, true>);
+        else
+            vec ? go(conv2d_mfma_kernel<1, true, true>) : go(conv2d_mfma_kernel<1, false, true>);
+    } else if (pl.nt == 2) {
+        vec ? go(conv2d_mfma_kernel<2, true, false>) : go(conv2d_mfma_kernel<2, false, false>);
+    } else {
+        vec ? go(conv2d_mfma_kernel<1, true, false>) : go(conv2d_mfma_kernel<1, false, false>);
+    }
     U3D_LAUNCH_CHECK();
     if (split) {
         const int P = H * W;
         u3d_src_t g = {};
         if (gx) g = *gx;
         hipLaunchKernelGGL(conv2d_splitk_reduce_kernel, dim3((unsigned)c2_cdiv(P, 64), N), dim3(256), 0, (hipStream_t)stream, workspace,
-                           p.part_stride, p.ksplit, out, N, P, Cout, p.relu, out_stats, g, p.has_gx, gstats, H, W);
+                           p.part_stride, p.ksplit, out, N, P, Cout, p.relu, out_stats, g, p.has_gx, gstats, H, W, residual);
         U3D_LAUNCH_CHECK();
     }
     return 0;
+}
+
+extern "C" int u3d_conv2d_ex_reps(int device, u3d_stream_t stream, const u3d_src_t* src, const float* packed_w, float* out, int N,
+                                  int H, int W, int Cout, int relu, double* out_stats, const u3d_src_t* gx, double* gstats,
+                                  float* workspace, long long workspace_floats, int stat_reps) {
+    return conv2d_impl(device, stream, src, packed_w, out, N, H, W, Cout, relu, out_stats, gx, gstats, nullptr, workspace,
+                       workspace_floats, stat_reps);
+}
+
+// the tail of ResNetBlock (buildingblocks.py:277-288) in the epilogue: out = [relu](conv + residual); statistics of the written values
+extern "C" int u3d_conv2d_res_reps(int device, u3d_stream_t stream, const u3d_src_t* src, const float* packed_w, float* out, int N,
+                                   int H, int W, int Cout, int relu, double* out_stats, const u3d_src_t* gx, double* gstats,
+                                   float* workspace, long long workspace_floats, int stat_reps, const float* residual) {
+    U3D_REQUIRE(residual && !gx, "u3d_conv2d_res_reps: needs a residual, and a residual excludes gx");
+    return conv2d_impl(device, stream, src, packed_w, out, N, H, W, Cout, relu, out_stats, gx, gstats, residual, workspace,
+                       workspace_floats, stat_reps);
 }
 
 // =================================================================================================

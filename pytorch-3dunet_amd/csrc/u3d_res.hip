@@ -778,15 +778,15 @@ static int parity_taps(int pz, int py, int px, signed char* tz, signed char* ty,
 
 // packed image of the transposed-conv weights for coalesced B-tile loads:
 //   mode 0 (forward):   out[tap][ci][co] = w[ci][co][tap]        mode 1 (data gradient): out[tap][co][ci] = w[ci][co][tap]
-__global__ void pack_convtr_kernel(const float* __restrict__ w, float* __restrict__ out, int Cin, int Cout, int mode) {
-    const long long total = (long long)27 * Cin * Cout;
+__global__ void pack_convtr_kernel(const float* __restrict__ w, float* __restrict__ out, int Cin, int Cout, int mode, int ntaps) {
+    const long long total = (long long)ntaps * Cin * Cout;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
         const int inner = mode == 0 ? Cout : Cin, outer = mode == 0 ? Cin : Cout;
         const int j = (int)(i % inner);
         const long long q = i / inner;
         const int k = (int)(q % outer), tap = (int)(q / outer);
         const int ci = mode == 0 ? k : j, co = mode == 0 ? j : k;
-        out[i] = w[((size_t)ci * Cout + co) * 27 + tap];
+        out[i] = w[((size_t)ci * Cout + co) * ntaps + tap];
     }
 }
 
@@ -797,7 +797,7 @@ extern "C" int u3d_pack_convtr_weights(int device, u3d_stream_t stream, const fl
     const long long total = (long long)27 * Cin * Cout;
     long long blocks = (total + 255) / 256;
     if (blocks > 8192) blocks = 8192;
-    hipLaunchKernelGGL(pack_convtr_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, w, packed, Cin, Cout, mode);
+    hipLaunchKernelGGL(pack_convtr_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, w, packed, Cin, Cout, mode, 27);
     U3D_LAUNCH_CHECK();
     return 0;
 }
@@ -867,6 +867,108 @@ extern "C" int u3d_convtr3d_bwd(int device, u3d_stream_t stream, const float* dt
         g.tz[tp] = (signed char)(tp / 9 - 1), g.ty[tp] = (signed char)((tp / 3) % 3 - 1), g.tx[tp] = (signed char)(tp % 3 - 1);
     g.dst_t = 1, g.dst_a = (long long)Cout * 27, g.dst_b = 27;
     return launch_gwgrad(g, st);
+}
+
+// ---- ConvTranspose2d(k=3, stride=2, padding=1, bias=False) of ResidualUNet2D's decoders (buildingblocks.py:617-664, is3d=False):
+// (N,H1,W1,Cin) -> (N,2H1-1,2W1-1,Cout), NHWC = NDHWC with D = 1.  The same gather GEMMs with 2-D tap tables: four output parity
+// classes of 1, 2, 2 and 4 taps forward (9 multiply-adds per input and output channel per 2x2 output quad, none on the inserted
+// zeros), a stride-2 9-tap convolution of dt for the data gradient and nine tap GEMMs for the weight gradient.  Weight images
+// [tap][ci][co] (mode 0) / [tap][co][ci] (mode 1) of the reference layout (Cin, Cout, 3, 3).
+extern "C" size_t u3d_convtr2d_packed_floats(int Cin, int Cout) {
+    return (Cin > 0 && Cout > 0) ? (size_t)9 * Cin * Cout : 0;
+}
+
+extern "C" size_t u3d_convtr2d_wgrad_workspace_doubles(int Cin, int Cout) {
+    return (Cin > 0 && Cout > 0) ? (size_t)9 * Cin * Cout : 0;
+}
+
+extern "C" int u3d_pack_convtr2d(int device, u3d_stream_t stream, const float* w, int Cin, int Cout, int mode, float* packed) {
+    U3D_ENTER(device);
+    U3D_REQUIRE(w && packed && Cin > 0 && Cout > 0 && (mode == 0 || mode == 1) && (long long)9 * Cin * Cout < (1ll << 31),
+                "u3d_pack_convtr2d: bad argument");
+    const long long total = (long long)9 * Cin * Cout;
+    long long blocks = (total + 255) / 256;
+    if (blocks > 8192) blocks = 8192;
+    hipLaunchKernelGGL(pack_convtr_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, w, packed, Cin, Cout, mode, 9);
+    U3D_LAUNCH_CHECK();
+    return 0;
+}
+
+static bool convtr2d_dims_ok(int N, int H1, int W1, int Cin, int Cout) {
+    return N > 0 && H1 > 0 && W1 > 0 && Cin > 0 && Cout > 0 && (long long)N * (2LL * H1 - 1) * (2LL * W1 - 1) < (1ll << 31) &&
+           (long long)9 * Cin * Cout < (1ll << 31);
+}
+
+extern "C" int u3d_convtr2d_fwd(int device, u3d_stream_t stream, const float* x, const float* packed, float* t, int N, int H1, int W1,
+                                int Cin, int Cout) {
+    U3D_ENTER(device);
+    U3D_REQUIRE(x && packed && t, "u3d_convtr2d_fwd: bad argument");
+    U3D_REQUIRE(convtr2d_dims_ok(N, H1, W1, Cin, Cout), "u3d_convtr2d_fwd: bad sizes (the output pixel count must be < 2^31)");
+    const int Ht = 2 * H1 - 1, Wt = 2 * W1 - 1;
+    hipStream_t st = (hipStream_t)stream;
+    for (int cls = 0; cls < 4; ++cls) {  // one gather GEMM per output parity class (py, px)
+        const int py = cls >> 1, px = cls & 1;
+        GConvParams p{};
+        p.x = x, p.w = packed, p.bias = nullptr, p.mask = nullptr, p.out = t, p.stats = nullptr;
+        p.N = N, p.Di = 1, p.Hi = H1, p.Wi = W1, p.Ci = Cin, p.Do = 1, p.Ho = Ht, p.Wo = Wt, p.Cj = Cout;
+        p.Rz = 1, p.Ry = H1 - py, p.Rx = W1 - px;  // s = 2j + p <= 2n - 2
+        if (p.Ry <= 0 || p.Rx <= 0) continue;
+        p.osz = 1, p.osy = p.osx = 2, p.ooz = 0, p.ooy = py, p.oox = px, p.isz = p.isy = p.isx = 1;
+        int woff[27];
+        p.ntaps = parity_taps(0, py, px, p.tz, p.ty, p.tx, woff);  // (z: tap 1 of the 3-tap axis at input offset 0, i.e. 27-tap index 9 + tap)
+        for (int k = 0; k < p.ntaps; ++k) p.woff[k] = (woff[k] - 9) * Cin * Cout;  // packed[tap][ci][co]
+        p.wsi = Cout, p.wsj = 1;
+        if (int e = launch_gconv(p, st)) return e;
+    }
+    return 0;
+}
+
+extern "C" int u3d_convtr2d_dgrad(int device, u3d_stream_t stream, const float* dt, const float* packed_t, const float* x_low, float* dx,
+                                  int N, int H1, int W1, int Cin, int Cout) {
+    U3D_ENTER(device);
+    U3D_REQUIRE(dt && packed_t && dx, "u3d_convtr2d_dgrad: bad argument");
+    U3D_REQUIRE(convtr2d_dims_ok(N, H1, W1, Cin, Cout), "u3d_convtr2d_dgrad: bad sizes (the output pixel count must be < 2^31)");
+    GConvParams p{};
+    p.x = dt, p.w = packed_t, p.bias = nullptr, p.mask = x_low, p.out = dx, p.stats = nullptr;
+    p.N = N, p.Di = 1, p.Hi = 2 * H1 - 1, p.Wi = 2 * W1 - 1, p.Ci = Cout, p.Do = 1, p.Ho = H1, p.Wo = W1, p.Cj = Cin;
+    p.Rz = 1, p.Ry = H1, p.Rx = W1;
+    p.osz = p.osy = p.osx = 1, p.ooz = p.ooy = p.oox = 0, p.isz = 1, p.isy = p.isx = 2;
+    p.ntaps = 9;
+    for (int tp = 0; tp < 9; ++tp) {
+        p.tz[tp] = 0, p.ty[tp] = (signed char)(tp / 3 - 1), p.tx[tp] = (signed char)(tp % 3 - 1);
+        p.woff[tp] = tp * Cin * Cout;  // packed_t[tap][co][ci]
+    }
+    p.wsi = Cin, p.wsj = 1;
+    return launch_gconv(p, (hipStream_t)stream);
+}
+
+__global__ void convtr2d_wgrad_store_kernel(const double* __restrict__ acc, long long n, int accumulate, float* __restrict__ dw) {
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
+        dw[i] = accumulate ? dw[i] + (float)acc[i] : (float)acc[i];
+}
+
+extern "C" int u3d_convtr2d_wgrad(int device, u3d_stream_t stream, const float* x, const float* dt, float* dw, int N, int H1, int W1,
+                                  int Cin, int Cout, int accumulate, double* workspace, size_t workspace_doubles) {
+    U3D_ENTER(device);
+    U3D_REQUIRE(x && dt && dw && workspace, "u3d_convtr2d_wgrad: bad argument");
+    U3D_REQUIRE(convtr2d_dims_ok(N, H1, W1, Cin, Cout), "u3d_convtr2d_wgrad: bad sizes (the output pixel count must be < 2^31)");
+    const long long n = (long long)9 * Cin * Cout;
+    U3D_REQUIRE(workspace_doubles >= (size_t)n, "u3d_convtr2d_wgrad: workspace too small (%zu < %lld doubles)", workspace_doubles, n);
+    hipStream_t st = (hipStream_t)stream;
+    U3D_HIP(hipMemsetAsync(workspace, 0, (size_t)n * sizeof(double), st));
+    GWgradParams g{};
+    g.X = x, g.Y = dt, g.acc = workspace, g.bias_acc = nullptr;
+    g.N = N, g.Ca = Cin, g.Cb = Cout;
+    g.Rz = 1, g.Ry = H1, g.Rx = W1, g.Dy = 1, g.Hy = 2 * H1 - 1, g.Wy = 2 * W1 - 1, g.ysz = 1, g.ysy = g.ysx = 2;
+    g.ntaps = 9;
+    for (int tp = 0; tp < 9; ++tp) g.tz[tp] = 0, g.ty[tp] = (signed char)(tp / 3 - 1), g.tx[tp] = (signed char)(tp % 3 - 1);
+    g.dst_t = 1, g.dst_a = (long long)Cout * 9, g.dst_b = 9;  // acc[(ci*Cout + co)*9 + tap]: the reference layout
+    if (int e = launch_gwgrad(g, st)) return e;
+    long long blocks = (n + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(convtr2d_wgrad_store_kernel, dim3((unsigned)blocks), dim3(256), 0, st, workspace, n, accumulate ? 1 : 0, dw);
+    U3D_LAUNCH_CHECK();
+    return 0;
 }
 
 // ---- nearest resize to the skip's size + summation joining (buildingblocks.py:650-651 + :493) ---------------------------

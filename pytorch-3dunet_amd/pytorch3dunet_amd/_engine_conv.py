@@ -361,15 +361,21 @@ class ConvLayers:
         return ystats
 
     def _fwd_conv2d(self, c: "_ConvCall"):
-        # fp32 MFMA 3x3 implicit GEMM on the D = 1 tensors (virtual concat, fused affine, ReLU and statistics as the 3-D kernels)
-        assert c.residual is None and c.D == 1
+        # fp32 MFMA 3x3 implicit GEMM on the D = 1 tensors (virtual concat, fused affine, ReLU and statistics as the 3-D kernels);
+        # with a residual (ResidualUNet2D's conv3): out = [relu](conv + residual) in the epilogue (u3d_conv2d_res_reps)
+        assert c.D == 1
         wp = self._packed2d(c.conv.weight, 0, c.dev)
         ystats = c.take_stats(self.stat_reps)
         s = c.src.struct(c.affine)
         need = nat.get_lib().u3d_conv2d_workspace_floats(c.N, c.H, c.W, c.Ctot, c.Cout)  # split-K scratch on small grids
         kws = _empty(need, dtype=_F32, device=c.dev) if need > 0 else None
-        nat.call("u3d_conv2d_ex_reps", c.dev.index, _stream(c.dev), ctypes.byref(s), _p(wp), _p(c.y), c.N, c.H, c.W, c.Cout, c.relu,
-                 _p(ystats), None, None, _p(kws), need, _reps(ystats), flops=18.0 * c.Ctot * c.Cout * c.N * c.H * c.W)
+        if c.residual is not None:
+            nat.call("u3d_conv2d_res_reps", c.dev.index, _stream(c.dev), ctypes.byref(s), _p(wp), _p(c.y), c.N, c.H, c.W, c.Cout, c.relu,
+                     _p(ystats), None, None, _p(kws), need, _reps(ystats), _p(c.residual),
+                     flops=18.0 * c.Ctot * c.Cout * c.N * c.H * c.W)
+        else:
+            nat.call("u3d_conv2d_ex_reps", c.dev.index, _stream(c.dev), ctypes.byref(s), _p(wp), _p(c.y), c.N, c.H, c.W, c.Cout, c.relu,
+                     _p(ystats), None, None, _p(kws), need, _reps(ystats), flops=18.0 * c.Ctot * c.Cout * c.N * c.H * c.W)
         return ystats
 
     def _fwd_fp32(self, c: "_ConvCall"):

@@ -29,7 +29,12 @@ class ResUNetEngine(UNet3DEngine):
     The 3x3x3 convolutions (94 % of the FLOPs at BASELINE config 4) run on the same MFMA kernels as UNet3D, with the
     block's `out += residual; ReLU` fused into conv3's epilogue (u3d_conv3d_residual); GroupNorm statistics of the
     residual come out of the 1x1x1 conv's / the joining kernel's epilogue.  The 1x1x1 convolutions and the transposed
-    convolution run on the FP32 vector units (csrc/u3d_res.hip)."""
+    convolution run on the FP32 vector units (csrc/u3d_res.hip).
+
+    ResidualUNet2D under `native_2d_residual` (unet3d/model.py sets model.native_2d, hence self.is2d): (N,C,H,W) runs as
+    (N,C,1,H,W); the 3x3 convolutions take the `conv2d` family (u3d_conv2d_res_reps fuses `out += residual`), the pools the
+    u3d_maxpool2d_* twins and the decoders ConvTranspose2d (u3d_convtr2d_*) before the same joining kernels at D = 1; the t8,
+    sub-pixel and bf16 branches stay off."""
 
     def __init__(self, model):
         super().__init__(model)
@@ -201,6 +206,9 @@ class ResUNetEngine(UNet3DEngine):
     def forward(self, x: torch.Tensor, save: bool):
         m = self.model
         dev = x.device
+        if self.is2d:
+            assert x.dim() == 4, "the 2-D executor takes (N,C,H,W)"
+            x = x.unsqueeze(2)  # (N,C,1,H,W): NHWC is NDHWC with D = 1
         N, Cin, D, H, W = x.shape
         x = x.contiguous()
         if Cin == 1:
@@ -223,9 +231,11 @@ class ResUNetEngine(UNet3DEngine):
         for i, (has_pool, bm) in enumerate(self.enc):
             if has_pool:
                 Np, Dp, Hp, Wp, Cp = cur.shape
-                pooled = _empty((Np, Dp // 2, Hp // 2, Wp // 2, Cp), dtype=self.adt, device=dev)
+                pooled = _empty((Np, Dp if self.is2d else Dp // 2, Hp // 2, Wp // 2, Cp), dtype=self.adt, device=dev)
                 argmax = _empty(pooled.shape, dtype=torch.uint8, device=dev)
-                if self.act_bf16:
+                if self.is2d:  # (MaxPool2d: D stays 1)
+                    nat.call("u3d_maxpool2d_fwd", dev.index, _stream(dev), _p(cur), Np, Hp, Wp, Cp, _p(pooled), _p(argmax), None)
+                elif self.act_bf16:
                     nat.call("u3d_maxpool2_fwd_b16", dev.index, _stream(dev), _p(cur), Np, Dp, Hp, Wp, Cp, _p(pooled), _p(argmax))
                 else:
                     nat.call("u3d_maxpool2_fwd", dev.index, _stream(dev), _p(cur), Np, Dp, Hp, Wp, Cp, _p(pooled), _p(argmax),
@@ -274,7 +284,10 @@ class ResUNetEngine(UNet3DEngine):
                 cur = self._block_fwd(bm, f"dec{j}", joined, j_st, pool, tape, dev)
                 continue
             t = _empty((Nl, Dt, Ht, Wt, Ct), dtype=_F32, device=dev)
-            if self.subpixel and Cl % 4 == 0 and Ct % 4 == 0:
+            if self.is2d:  # ConvTranspose2d: four parity-class gather GEMMs (D1 = Dt = 1)
+                nat.call("u3d_convtr2d_fwd", dev.index, _stream(dev), _p(cur), _p(self._packed_convtr2d(ct.weight, 0, dev)), _p(t), Nl,
+                         H1, W1, Cl, Ct, flops=4.5 * Cl * Ct * Nl * Ht * Wt)
+            elif self.subpixel and Cl % 4 == 0 and Ct % 4 == 0:
                 # 8 output parity classes accumulated from one staged input halo tile (csrc/u3d_subpix.hip, scheme Deconv3s2)
                 nat.call("u3d_convtr3d_fwd_subpixel", dev.index, _stream(dev), _p(cur), _p(self._packed_convtr(ct.weight, 2, dev)),
                          _p(t), Nl, D1, H1, W1, Cl, Ct, flops=2.0 * 27 * Cl * Ct * Nl * D1 * H1 * W1)
@@ -307,6 +320,9 @@ class ResUNetEngine(UNet3DEngine):
             tape.head_x = cur
             if self.debug is not None:
                 self.debug["tape"] = tape
+        if self.is2d:  # (N,Cout,H,W), the reference's 2-D layout
+            logits = logits.view(N, Co, H, W)
+            probs = probs.view(N, Co, H, W) if probs is not None else None
         return logits, probs, tape
 
     # -- backward -----------------------------------------------------------------------------------
@@ -460,6 +476,15 @@ class ResUNetEngine(UNet3DEngine):
             nat.call("u3d_nearest_sum_bwd", dev.index, _stream(dev), _p(dj), _p(lz), _p(ly), _p(lx), Nl, Ds, Hs, Ws, Dt, Ht, Wt,
                      Cs, _p(dt))
             acc = pool.take(up.weight.numel())
+            if self.is2d:  # ConvTranspose2d: dw (double sums in `acc`, written into the flat gradient), then dx masked by x_low > 0
+                nat.call("u3d_convtr2d_wgrad", dev.index, _stream(dev), _p(xl), _p(dt), _p(gview(self._pindex[id(up.weight)])), Nl, H1,
+                         W1, Cl, Cs, 0, _p(acc), acc.numel(), flops=4.5 * Cl * Cs * Nl * Ht * Wt)
+                dxl = _empty_like(xl)
+                nat.call("u3d_convtr2d_dgrad", dev.index, _stream(dev), _p(dt), _p(self._packed_convtr2d(up.weight, 1, dev)),
+                         _p(xl) if mk else None, _p(dxl), Nl, H1, W1, Cl, Cs, flops=4.5 * Cl * Cs * Nl * Ht * Wt)
+                del dt
+                dz = dxl
+                continue
             dxl = _empty_like(xl)
             nat.call("u3d_convtr3d_bwd", dev.index, _stream(dev), _p(dt), _p(xl), _p(up.weight.detach()), Nl, D1, H1, W1, Cl, Cs,
                      mk, _p(dxl), _p(acc), _p(self._packed_convtr(up.weight, 1, dev)), flops=4.0 * 27 * Cl * Cs * Nl * D1 * H1 * W1)
@@ -510,8 +535,12 @@ class ResUNetEngine(UNet3DEngine):
                     pools[i - 1] = None
                 Ne, De, He, We, Ce = e_in.shape
                 out = _empty_like(e_in)
-                nat.call("u3d_maxpool2_bwd_merge" + ("_b16" if self.act_bf16 else ""), dev.index, _stream(dev), _p(dxin), _p(pooled),
-                         _p(argmax), None, _p(skip_grad.get(i - 1)), _p(e_in), Ne, De, He, We, Ce, mk, _p(out))
+                if self.is2d:
+                    nat.call("u3d_maxpool2d_bwd_merge", dev.index, _stream(dev), _p(dxin), _p(pooled), _p(argmax), None,
+                             _p(skip_grad.get(i - 1)), _p(e_in), Ne, He, We, Ce, mk, _p(out))
+                else:
+                    nat.call("u3d_maxpool2_bwd_merge" + ("_b16" if self.act_bf16 else ""), dev.index, _stream(dev), _p(dxin), _p(pooled),
+                             _p(argmax), None, _p(skip_grad.get(i - 1)), _p(e_in), Ne, De, He, We, Ce, mk, _p(out))
                 skip_grad.pop(i - 1, None)
                 dz = out
             elif need_input_grad:
@@ -530,4 +559,6 @@ class ResUNetEngine(UNet3DEngine):
             else:
                 dx = _empty((N, Cin, D, H, W), dtype=_F32, device=dev)
                 nat.call("u3d_ndhwc_to_ncdhw", dev.index, _stream(dev), _p(dx0), _p(dx), N, Cin, V)
+            if self.is2d:
+                dx = dx.view(N, Cin, H, W)
         return flat, dx

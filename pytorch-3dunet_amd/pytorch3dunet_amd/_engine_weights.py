@@ -105,6 +105,21 @@ class WeightImages:
         self._pack_cache[key] = (ver, out)
         return out
 
+    def _packed_convtr2d(self, w: torch.Tensor, mode: int, dev) -> torch.Tensor:
+        """[tap][Cin][Cout] (mode 0) / [tap][Cout][Cin] (mode 1) image of a ConvTranspose2d weight (Cin, Cout, 3, 3) for
+        u3d_convtr2d_fwd / _dgrad, cached per parameter version"""
+        key = (id(w), 50 + mode)
+        ver = self._ver(w)
+        hit = self._pack_cache.get(key)
+        if hit is not None and hit[0] == ver:
+            return hit[1]
+        Cin, Cout = w.shape[0], w.shape[1]
+        n = nat.get_lib().u3d_convtr2d_packed_floats(Cin, Cout)
+        out = hit[1] if hit is not None and hit[1].numel() == n and hit[1].device == dev else _empty(n, dtype=_F32, device=dev)
+        nat.call("u3d_pack_convtr2d", dev.index, _stream(dev), _p(w.detach()), Cin, Cout, mode, _p(out))
+        self._pack_cache[key] = (ver, out)
+        return out
+
     def _convtr_t8(self, Cl: int, Cs: int) -> bool:
         """the transposed convolution and its gradients run in space-to-depth form on the bf16 MFMA kernels"""
         return self.bf16 and nat.get_lib().u3d_convtr3d_t8_supported(Cl, Cs) == 1

@@ -426,6 +426,15 @@ _PROTOS = {
     "u3d_conv2d_workspace_floats": (c_int64, [c_int, c_int, c_int, c_int, c_int]),
     "u3d_conv2d_ex_reps": (c_int, [c_int, c_void_p, POINTER(U3DSrc), c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p,
                                    POINTER(U3DSrc), c_void_p, c_void_p, c_int64, c_int]),
+    "u3d_conv2d_res_reps": (c_int, [c_int, c_void_p, POINTER(U3DSrc), c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                                    POINTER(U3DSrc), c_void_p, c_void_p, c_int64, c_int, c_void_p]),
+    "u3d_convtr2d_packed_floats": (c_size_t, [c_int, c_int]),
+    "u3d_convtr2d_wgrad_workspace_doubles": (c_size_t, [c_int, c_int]),
+    "u3d_pack_convtr2d": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "u3d_convtr2d_fwd": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int]),
+    "u3d_convtr2d_dgrad": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int]),
+    "u3d_convtr2d_wgrad": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                                   c_size_t]),
     "u3d_wgrad2d_workspace_floats": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "u3d_conv2d_wgrad": (c_int, [c_int, c_void_p, POINTER(U3DSrc), c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t]),
     "u3d_maxpool2d_fwd": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),

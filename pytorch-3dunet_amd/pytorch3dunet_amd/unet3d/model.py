@@ -14,7 +14,8 @@ made of.  ONE backend: a 3-D model variant the executor does not cover (layer or
 conv kernels other than 3/pad 1, `pool_type: avg`) RAISES on a HIP device; U3D_ALLOW_TORCH_FALLBACK=1 opts into running
 the same module tree through stock PyTorch-ROCm operators after a one-time warning (never counted as covered).  2-D
 models are outside the 3-D path and keep that warning path by default (opt-in since round 7: `native_2d: true` / U3D_NATIVE_2D=1 runs a
-fp32 UNet2D with nearest upsampling on the 2-D kernels of csrc/u3d_conv2d.hip); U3D_STRICT=1 makes them an error too.  Covered since round 2: every layer order with at most one
+fp32 UNet2D with nearest upsampling on the 2-D kernels of csrc/u3d_conv2d.hip; `native_2d_residual: true` / U3D_NATIVE_2D_RESIDUAL=1
+does the same for a fp32 ResidualUNet2D); U3D_STRICT=1 makes them an error too.  Covered since round 2: every layer order with at most one
 GroupNorm / BatchNorm, one non-linearity and a trailing dropout, every `upsample` value the reference itself can run
 on a 3-D net, nn.DataParallel, activation checkpointing, and the opt-in compute modes `bf16` and `fp32_split`.
 """
@@ -42,7 +43,7 @@ class AbstractUNet(nn.Module):
                  num_groups=8, num_levels=4, is_segmentation=True, conv_kernel_size=3, pool_kernel_size=2,
                  conv_padding=1, conv_upscale=2, upsample="default", dropout_prob=0.1, is3d=True, compute_dtype=None,
                  checkpoint_encoders=None, hip_graph=None, activation_dtype=None, checkpoint_levels=None,
-                 native_2d=None):
+                 native_2d=None, native_2d_residual=None):
         super().__init__()
         if isinstance(f_maps, int):
             f_maps = number_of_features_per_level(f_maps, num_levels=num_levels)
@@ -67,17 +68,26 @@ class AbstractUNet(nn.Module):
         # csrc/u3d_conv2d.hip through the DoubleConv executor with D = 1 (fp32, nearest upsampling); off by default
         if native_2d is None:
             native_2d = os.environ.get("U3D_NATIVE_2D", "0") == "1"
+        # `native_2d_residual: true` (its own key; U3D_NATIVE_2D_RESIDUAL=1 sets its default): a ResidualUNet2D runs on the same 2-D
+        # kernels through the residual executor (plus the residual conv2d epilogue and ConvTranspose2d of csrc/u3d_res.hip); it implies
+        # native_2d.  Every other class ignores it, and `native_2d: true` alone leaves a ResidualUNet2D on the warning path
+        if native_2d_residual is None:
+            native_2d_residual = os.environ.get("U3D_NATIVE_2D_RESIDUAL", "0") == "1"
+        res2d = bool(native_2d_residual) and not is3d and basic_module is ResNetBlock
+        if res2d:
+            native_2d = True
         self.native_2d = bool(native_2d) and not is3d
         reasons = []
         if not is3d and not self.native_2d:
             reasons.append("2-D model")
         elif not is3d:
-            if basic_module is not DoubleConv:
-                reasons.append(f"2-D model with {basic_module.__name__} (native_2d covers DoubleConv blocks)")
+            if basic_module is not DoubleConv and not res2d:
+                reasons.append(f"2-D model with {basic_module.__name__} (native_2d covers DoubleConv blocks; a ResidualUNet2D needs "
+                               "native_2d_residual: true)")
             if compute_dtype not in (None, "fp32", "float32") or os.environ.get("U3D_BF16", "0") == "1" or \
                     os.environ.get("U3D_F32_SPLIT", "0") == "1":
                 reasons.append(f"2-D model with compute_dtype {compute_dtype!r} (native_2d is fp32)")
-            if upsample not in ("default", "nearest"):
+            if upsample not in ("default", "nearest") and not res2d:  # (residual nets: the residual rule below)
                 reasons.append(f"2-D model with upsample '{upsample}' (native_2d: nearest upsampling)")
         if basic_module not in (DoubleConv, ResNetBlock, ResNetBlockSE):
             reasons.append(f"basic_module {basic_module.__name__}")
@@ -155,6 +165,9 @@ class AbstractUNet(nn.Module):
         if self.native_2d and self.hip_graph:
             raise ValueError("u3d: hip_graph is not available with native_2d (the captured training step is 3-D only); "
                              "drop one of the two keys")
+        if res2d and (self.checkpoint_encoders or self.checkpoint_levels is not None):
+            raise ValueError("u3d: checkpoint_encoders / checkpoint_levels are not available with native_2d_residual (the 2-D residual "
+                             "executor keeps every activation); drop one of the keys")
         self._native_blockers = reasons
         self._is3d = bool(is3d)
         self._residual = basic_module in (ResNetBlock, ResNetBlockSE)
@@ -296,7 +309,8 @@ def _variant(name, basic_module, default_levels, is3d, doc):
                               conv_upscale=conv_upscale, upsample=upsample, dropout_prob=dropout_prob, is3d=is3d,
                               compute_dtype=kwargs.get("compute_dtype"), checkpoint_encoders=kwargs.get("checkpoint_encoders"),
                               hip_graph=kwargs.get("hip_graph"), activation_dtype=kwargs.get("activation_dtype"),
-                              checkpoint_levels=kwargs.get("checkpoint_levels"), native_2d=kwargs.get("native_2d"))
+                              checkpoint_levels=kwargs.get("checkpoint_levels"), native_2d=kwargs.get("native_2d"),
+                              native_2d_residual=kwargs.get("native_2d_residual"))
 
     return type(name, (AbstractUNet,), {"__init__": __init__, "__doc__": doc, "__module__": _THIS_MODULE})
 

@@ -5,12 +5,16 @@ PyTorch-ROCm operators, after its one-time warning) in the same process, alterna
   confocal  resources/2DUnet_confocal_boundary/train_config.yml: 32 x 1 x 515 x 512, gcr, f_maps 32, 4 levels
   dsb2018   resources/2DUnet_dsb2018/train_config.yml: bcr, f_maps [32, 64, 128], batch 32 — DSB2018 images vary in size;
             32 x 1 x 256 x 256 is an ASSUMPTION of this tool, not a shape the configuration fixes
+  resunet2d, resunet2d_515
+            ResidualUNet2D at the reference defaults (f_maps 64, 5 levels, gcr, 8 groups) with `native_2d_residual: true`.  The reference
+            ships no 2-D residual configuration: 16 x 1 x 256 x 256 and 8 x 1 x 515 x 512 are ASSUMPTIONS of this tool.  Their records
+            add the transposed-convolution family (u3d_convtr2d_*: 2 * (9/4) * Cin * Cout FLOPs per output pixel and direction)
 
 Prints one JSON line per configuration: images/s of both paths (device time over the steady-state steps only, after --warmup steps
 per path), the conv2d family's ms per native step and its rate on executed FLOPs (18 * Cin * Cout * pixels per direction, from the
 launches that declare them) as a fraction of the fp32 MFMA peak of 157.3 TFLOP/s.
 
-  python tools/unet2d_bench.py [--configs confocal,dsb2018] [--batch 32] [--steps 10] [--warmup 3]"""
+  python tools/unet2d_bench.py [--configs confocal,dsb2018] [--batch N] [--steps 10] [--warmup 3]   (--batch: every config's own default)"""
 import argparse
 import json
 import os
@@ -29,7 +33,39 @@ CONFIGS = {
     "confocal": (dict(name="UNet2D", in_channels=1, out_channels=1, f_maps=32, num_levels=4, layer_order="gcr", num_groups=8),
                  (515, 512)),
     "dsb2018": (dict(name="UNet2D", in_channels=1, out_channels=1, f_maps=[32, 64, 128], layer_order="bcr"), (256, 256)),
+    "resunet2d": (dict(name="ResidualUNet2D", in_channels=1, out_channels=1, f_maps=64, num_levels=5, layer_order="gcr", num_groups=8),
+                  (256, 256)),
+    "resunet2d_515": (dict(name="ResidualUNet2D", in_channels=1, out_channels=1, f_maps=64, num_levels=5, layer_order="gcr",
+                           num_groups=8), (515, 512)),
 }
+BATCH = {"confocal": 32, "dsb2018": 32, "resunet2d": 16, "resunet2d_515": 8}
+
+
+def _residual(cfg):
+    return cfg["name"] == "ResidualUNet2D"
+
+
+def layer_flops_per_image(cfg, hw):
+    """(3x3 conv FLOPs, transposed-conv FLOPs) of one image and direction, from the layer shapes of a forward on the meta device:
+    18 * Cin * Cout * pixels per 3x3 conv, 2 * (9/4) * Cin * Cout * output pixels per ConvTranspose2d"""
+    from pytorch3dunet_amd.unet3d.model import get_model
+
+    m = get_model(dict(cfg)).to("meta")
+    tot = {"conv": 0.0, "convtr": 0.0}
+
+    def hook(mod, inp, out):
+        px = out.shape[-2] * out.shape[-1]
+        if isinstance(mod, torch.nn.ConvTranspose2d):
+            tot["convtr"] += 4.5 * mod.in_channels * mod.out_channels * px
+        elif mod.kernel_size == (3, 3):
+            tot["conv"] += 18.0 * mod.in_channels * mod.out_channels * px
+
+    for mod in m.modules():
+        if isinstance(mod, (torch.nn.Conv2d, torch.nn.ConvTranspose2d)):
+            mod.register_forward_hook(hook)
+    with torch.no_grad():
+        m._forward_modules(torch.empty((1, 1) + tuple(hw), device="meta"))
+    return tot["conv"], tot["convtr"]
 
 
 def conv_flops_per_image(cfg, hw):
@@ -61,7 +97,8 @@ def make(cfg, native, dev):
     from pytorch3dunet_amd.unet3d.model import get_model
 
     torch.manual_seed(0)
-    m = get_model(dict(cfg, native_2d=native)).to(dev).train()
+    key = "native_2d_residual" if _residual(cfg) else "native_2d"
+    m = get_model(dict(cfg, **{key: native})).to(dev).train()
     return m, FusedAdam(m.parameters(), lr=1e-4, weight_decay=1e-5)
 
 
@@ -87,7 +124,7 @@ def timed(model, opt, x, target, loss_fn, steps):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--configs", default="confocal,dsb2018")
-    ap.add_argument("--batch", type=int, default=32)
+    ap.add_argument("--batch", type=int, default=None, help="images per step (default: the config's own, BATCH)")
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--rounds", type=int, default=2, help="alternating native / stock rounds of --steps each")
@@ -102,9 +139,10 @@ def main():
     warnings.simplefilter("ignore")  # (the stock path's one-time "not covered" warning)
     for name in a.configs.split(","):
         cfg, hw = CONFIGS[name]
+        batch = a.batch if a.batch is not None else BATCH[name]
         g = torch.Generator().manual_seed(1)
-        x = torch.randn((a.batch, 1) + hw, generator=g).to(dev)
-        target = (torch.rand((a.batch, 1) + hw, generator=g) > 0.5).float().to(dev)
+        x = torch.randn((batch, 1) + hw, generator=g).to(dev)
+        target = (torch.rand((batch, 1) + hw, generator=g) > 0.5).float().to(dev)
         paths = [True] if a.native_only else [True, False]
         runs = {p: make(cfg, p, dev) for p in paths}
         for p in paths:
@@ -125,12 +163,12 @@ def main():
         conv = {k: v for k, v in fam.items() if "conv2d" in k}
         c_ms = sum(v["ms"] for v in conv.values())
         c_fl = sum(v["flops"] for v in conv.values())
-        fwd = {k: v for k, v in conv.items() if k == "u3d_conv2d_ex_reps"}
-        per_img = conv_flops_per_image(cfg, hw)
+        fwd = {k: v for k, v in conv.items() if k in ("u3d_conv2d_ex_reps", "u3d_conv2d_res_reps")}
+        per_img, tr_img = layer_flops_per_image(cfg, hw) if _residual(cfg) else (conv_flops_per_image(cfg, hw), 0.0)
         best = {p: min(v) for p, v in ms.items()}
-        rec = {"config": name, "shape": [a.batch, 1, *hw], "order": cfg["layer_order"], "steps": a.steps, "warmup": a.warmup,
+        rec = {"config": name, "shape": [batch, 1, *hw], "order": cfg["layer_order"], "steps": a.steps, "warmup": a.warmup,
                "rounds": a.rounds, "native_ms_per_step": [round(v, 3) for v in ms[True]],
-               "native_images_per_s": round(a.batch * 1000.0 / best[True], 2),
+               "native_images_per_s": round(batch * 1000.0 / best[True], 2),
                "conv2d_gflop_fwd_per_image": round(per_img / 1e9, 2),
                "conv2d_family_ms_per_step": round(c_ms, 3), "conv2d_family_tflops_executed": round(c_fl / c_ms / 1e9, 2) if c_ms else None,
                "conv2d_family_fraction_of_peak": round(c_fl / c_ms / 1e9 / PEAK_TFLOPS, 3) if c_ms else None,
@@ -140,8 +178,20 @@ def main():
                "conv2d_fwd_fraction_of_peak": round(sum(v["flops"] for v in fwd.values()) / sum(v["ms"] for v in fwd.values()) / 1e9 /
                                                     PEAK_TFLOPS, 3) if fwd else None,
                "device": torch.cuda.get_device_name(0)}
+        if _residual(cfg):
+            # the transposed-convolution family: forward, data and weight gradient (FLOPs as declared by the launches, 2 * (9/4) * Cin *
+            # Cout per output pixel and direction) and everything else the native step launches, by entry point
+            tr = {k: v for k, v in fam.items() if "convtr2d" in k}
+            t_ms, t_fl = sum(v["ms"] for v in tr.values()), sum(v["flops"] for v in tr.values())
+            rec.update(shape_is_assumption=True, convtr2d_gflop_fwd_per_image=round(tr_img / 1e9, 3),
+                       convtr2d_family_ms_per_step=round(t_ms, 3),
+                       convtr2d_family_fraction_of_peak=round(t_fl / t_ms / 1e9 / PEAK_TFLOPS, 3) if t_ms else None,
+                       convtr2d_calls={k: {"calls": v["calls"], "ms": round(v["ms"], 3),
+                                           "fraction_of_peak": round(v["flops"] / v["ms"] / 1e9 / PEAK_TFLOPS, 3) if v["ms"] and v["flops"] else None}
+                                       for k, v in tr.items()},
+                       other_declared_flop_ms_per_step=round(sum(v["ms"] for k, v in fam.items() if k not in conv and k not in tr), 3))
         if not a.native_only:
-            rec.update(stock_ms_per_step=[round(v, 3) for v in ms[False]], stock_images_per_s=round(a.batch * 1000.0 / best[False], 2),
+            rec.update(stock_ms_per_step=[round(v, 3) for v in ms[False]], stock_images_per_s=round(batch * 1000.0 / best[False], 2),
                        native_speedup=round(best[False] / best[True], 3))
         print(json.dumps(rec), flush=True)
         del runs, x, target
