@@ -77,6 +77,30 @@ def _inner_act(order: str) -> bool:
     return bool(acts and norms and ci < acts[0] < norms[0])
 
 
+def block_module(mods: Dict[str, nn.Module], block: str) -> str:
+    """`enc{i}` / `dec{j}` (a tape block name) -> `encoders.{i}.basic_module` / `decoders.{j}.basic_module`; raises without one"""
+    side, idx = ("encoders", block[3:]) if block.startswith("enc") else ("decoders", block[3:])
+    assert block[:3] in ("enc", "dec") and idx.isdigit(), block
+    base = f"{side}.{idx}.basic_module"
+    assert base in mods, f"{block}: no module {base}"
+    return base
+
+
+def record_module(mods: Dict[str, nn.Module], name: str):
+    """(basic module, SingleConv module) names of a tape conv record: `enc{i}.c{k}` -> `encoders.{i}.basic_module.SingleConv{k}`
+    (DoubleConv), `.c2` -> `.conv2` and `.c3` -> `.conv3` (ResNetBlock); raises for a record without its module"""
+    blk, _, conv = name.partition(".")
+    base = block_module(mods, blk)
+    if hasattr(mods[base], "conv2"):  # ResNetBlock: c2 = conv2 (the block's order), c3 = conv3 + `out += residual` + non_linearity
+        assert conv in ("c2", "c3"), f"{name}: unknown residual record"
+        sc_name = f"{base}.conv{conv[1]}"
+    else:
+        assert conv in ("c1", "c2"), name
+        sc_name = f"{base}.SingleConv{conv[1]}"
+    assert sc_name in mods, f"{name}: no module {sc_name}"
+    return base, sc_name
+
+
 def decisions_from_tape(model, tape) -> Dict[str, torch.Tensor]:
     """{module name: decision} from a native forward's tape: bool masks (N,C,...) for activations, window indices (uint8) for pools.
     Must be called right after the forward (backward may reuse the tape's buffers)."""
@@ -91,25 +115,13 @@ def decisions_from_tape(model, tape) -> Dict[str, torch.Tensor]:
 
     for rec in tape.convs:
         assert rec.drop is None, f"{rec.name}: dropout records are outside the decided harness"
-        blk, _, conv = rec.name.partition(".")
-        side, idx = ("encoders", blk[3:]) if blk.startswith("enc") else ("decoders", blk[3:])
-        assert blk[:3] in ("enc", "dec") and idx.isdigit(), rec.name
-        base = f"{side}.{idx}.basic_module"
-        bm = mods.get(base)
-        assert bm is not None, f"{rec.name}: no module {base}"
-        if hasattr(bm, "conv2"):  # ResNetBlock: c2 = conv2 (the block's order), c3 = conv3 + `out += residual` + non_linearity
-            if conv == "c2":
-                sc_name = f"{base}.conv2"
-            elif conv == "c3":
-                assert _act_of(bm.conv3) is None, f"{rec.name}: conv3 carries an activation"
-                if isinstance(bm.non_linearity, _DECIDING):
-                    put(f"{base}.non_linearity", _to_nc(rec.y, is2d) > 0)
-                continue
-            else:
-                raise AssertionError(f"{rec.name}: unknown residual record")
-        else:
-            assert conv in ("c1", "c2"), rec.name
-            sc_name = f"{base}.SingleConv{conv[1]}"
+        base, sc_name = record_module(mods, rec.name)
+        if sc_name.endswith(".conv3"):
+            bm = mods[base]
+            assert _act_of(bm.conv3) is None, f"{rec.name}: conv3 carries an activation"
+            if isinstance(bm.non_linearity, _DECIDING):
+                put(f"{base}.non_linearity", _to_nc(rec.y, is2d) > 0)
+            continue
         sc = mods.get(sc_name)
         assert sc is not None, f"{rec.name}: no module {sc_name}"
         act = _act_of(sc)

@@ -533,7 +533,9 @@ def _step(model, x, t):
 
 @pytest.mark.parametrize("net", ["ResidualUNet3D", "ResidualUNetSE3D"])
 def test_model_with_bf16_activation_storage_against_the_storage_emulation(net):
-    """(ResidualUNetSE3D since round 4: the squeeze-and-excitation gates read and write bf16 block outputs, `u3d_se_*_b16`)"""
+    """(ResidualUNetSE3D since round 4: the squeeze-and-excitation gates read and write bf16 block outputs, `u3d_se_*_b16`)
+    Closer to the emulation, layer by layer: tests/test_gpu_bf16_teacher.py forces the native tensors into the storage emulation at
+    every layer and holds each stored tensor to one bf16 ulp and every parameter gradient one by one; the global bar here stays."""
     import unet3d_oracle as orc
 
     model, x, t = _prep(dict(name=net, compute_dtype="bf16", activation_dtype="bf16"))

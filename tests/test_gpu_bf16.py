@@ -350,7 +350,9 @@ def test_model_bf16_against_bf16_operand_oracle_and_fp32_oracle(cfg, shape):
     (bf16 operands, wide accumulation).  The kernels themselves reproduce that arithmetic to 4e-7 (kernel tests above), but a
     NETWORK of them is chaotic in the last bf16 bit: a 1e-6 difference in a layer's input flips a few operand roundings in the
     next (measured layer by layer: 9e-5 -> 2e-3 over ten layers), so the network-level gate is "closer to the emulation than the
-    emulation is to fp32"; (2) within the STATED bf16 tolerance of the plain fp32 oracle = the reference path."""
+    emulation is to fp32"; (2) within the STATED bf16 tolerance of the plain fp32 oracle = the reference path.
+    Closer to the emulation, layer by layer: tests/test_gpu_bf16_teacher.py feeds the emulation the native tensors at every layer and
+    gates each layer's output, dz, dg and every parameter gradient to accumulation order; these global bars stay as they are."""
     import unet3d_oracle as orc
     from conftest import diag
 
