@@ -30,6 +30,7 @@ __all__ = [
     "Optional",
     "ResRec",
     "StaleParameters",
+    "StatTable",
     "slab_boxes",
     "Tape",
     "U3DSrc",
@@ -55,6 +56,7 @@ __all__ = [
     "_p",
     "_resample_tables",
     "_stream",
+    "_tab",
     "_walk",
     "copy",
     "ctypes",
@@ -436,7 +438,34 @@ class Tape:
     cats: dict = field(default_factory=dict)    # DoubleConv executor, bf16 mode: decoder index -> the VIRTUAL source whose concat was materialised
     lean: bool = False      # memory-lean mode (checkpoint_encoders): backward releases every block's tensors as soon as it is done
     consumed: bool = False  # ... so the tape can be walked only once
-    bwd_pool: Optional[object] = None  # DoubleConv executor: the backward pass's zeroed scratch, carved from the forward's pool (one fill launch)
+    bwd_pool: Optional[object] = None  # DoubleConv executor: the backward pass's zeroed scratch, carved from the forward's pool (one fill launch);
+                                       # shared by every copy of the tape, taken once (_StatPool.claim)
+
+
+@dataclass(frozen=True)
+class StatTable:
+    """a per-(sample, channel) float64 sum table `[reps][N][C][2]` (sum, sum of squares — or the GroupNorm-backward pair): `reps`
+    replica rows that the `_reps` entry points add into and sum (u3d_conv3d_ex_reps), `scale` the weight the GroupNorm finalize gives
+    the sums (8.0: an exact-2x upsampled half reuses its producer's sums).  The record, not the tensor, carries the shape: a view or
+    copy of `t` is only ever read through it."""
+
+    t: torch.Tensor
+    N: int
+    C: int
+    reps: int = 1
+    scale: float = 1.0
+
+    def __post_init__(self):
+        assert self.t.numel() == self.reps * self.N * self.C * 2, "u3d: statistics table size does not match reps * N * C * 2"
+
+    def folded(self) -> "StatTable":
+        """the one-row table (consumers without a replica-aware entry point: BatchNorm, stand-alone backward finalize)"""
+        return self if self.reps == 1 else StatTable(self.t.view(self.reps, -1).sum(0), self.N, self.C, 1, self.scale)
+
+
+def _tab(tab: Optional[StatTable]):
+    """(buffer pointer, replica rows) of an optional table, as the `_reps` entry points take them"""
+    return (None, 1) if tab is None else (_p(tab.t), tab.reps)
 
 
 class _StatPool:
@@ -445,6 +474,7 @@ class _StatPool:
     def __init__(self, dev, doubles: int):
         self.buf = torch.zeros(max(doubles, 2), dtype=torch.float64, device=dev)
         self.off = 0
+        self.used = False  # a carved backward scratch: set by the one pass that takes it (claim)
 
     def take(self, n: int) -> torch.Tensor:
         if self.off + n > self.buf.numel():
@@ -456,12 +486,22 @@ class _StatPool:
         self.off += n
         return s
 
+    def table(self, N: int, C: int, reps: int = 1) -> StatTable:
+        return StatTable(self.take(reps * N * C * 2), N, C, reps)
+
     def carve(self, n: int) -> "_StatPool":
         """a pool of its own over the next n zeroed doubles of this one (the backward pass's scratch inside the forward's fill launch)"""
         sub = _StatPool.__new__(_StatPool)
         sub.buf = self.take(n)
         sub.off = 0
+        sub.used = False
         return sub
+
+    def claim(self) -> bool:
+        """True for the first pass that asks, False ever after: a stashed tape keeps this very object in its skeleton, so every tape
+        unstashed from it (a second backward under retain_graph=True) sees the same pool, with the first pass's sums in it"""
+        fresh, self.used = not self.used, True
+        return fresh
 
 
 _SIDE_STREAMS: dict = {}
@@ -493,7 +533,6 @@ class _BwdCtx:
         self.side = None
         self.ws_side = None
         self.side_used = False
-        self.coef_hi = None  # set by ConvLayers._norm_bwd_finalize for a sub-pixel layer: (N,3,C1) table (p, 8q, 8r) of the upsampled channels
 
     def gview(self, idx):
         e = self._e

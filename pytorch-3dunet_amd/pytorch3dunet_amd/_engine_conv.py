@@ -20,27 +20,6 @@ from ._native import U3DSrc
 
 from ._engine_base import *  # noqa: F401,F403  (explicit __all__: helpers, records, activation codes)
 
-_WGRAD_JOB = os.environ.get("U3D_WGRAD_JOB", "1") != "0"  # A/B: 0 = GroupNorm-backward reductions as launches of their own
-
-
-def _reps(t) -> int:
-    """replica rows of a statistics table (u3d_conv3d_ex_reps): the tensor a persistent convolution wrote carries the count as an
-    attribute; every other table is one row"""
-    return getattr(t, "_u3d_reps", 1) if t is not None else 1
-
-
-def _take_reps(pool, n: int, reps: int):
-    t = pool.take(reps * n)
-    if reps > 1:
-        t._u3d_reps = reps
-    return t
-
-
-def _fold_reps(t):
-    """the plain table of a replicated one (consumers without a replica-aware entry point: BatchNorm, stand-alone backward finalize)"""
-    r = _reps(t)
-    return t if r == 1 else t.view(r, -1).sum(0)
-
 
 class _SubLayers(dict):
     """{id(conv weight): (C0, C1)} of the decoder first convs that take the sub-pixel path at one input size; `plus` = the ids whose level
@@ -72,8 +51,8 @@ class _ConvCall:
     affine_lo: Optional[torch.Tensor] = None  # sub-pixel layers: compact rows of `affine` for the skip / upsampled channels
     affine_hi: Optional[torch.Tensor] = None
 
-    def take_stats(self, reps: int = 1):
-        return _take_reps(self.pool, self.N * self.Cout * 2, reps) if self.stats else None
+    def take_stats(self, reps: int = 1) -> Optional[StatTable]:
+        return self.pool.table(self.N, self.Cout, reps) if self.stats else None
 
     @property
     def flops(self):
@@ -95,7 +74,7 @@ class _BwdCall:
     bf16: bool   # both directions of this layer run on the bf16-operand kernels
     b16: bool    # bf16 activation storage
     job: object = None  # U3DGnBwdJob for the weight-gradient reduce launch to carry (the family that takes it sets it back to None)
-    greps: int = 1      # replica rows of the GroupNorm-backward sums the fp32 data-gradient kernel writes (u3d_conv3d_ex_reps)
+    greps: int = 1      # replica rows requested for the GroupNorm-backward sums the fp32 data-gradient kernel writes (u3d_conv3d_ex_reps)
 
     @property
     def flops(self):
@@ -163,41 +142,46 @@ class ConvLayers:
         out.plus = frozenset(plus)  # the layers of this call whose packed set includes the slab images (_repack_all)
         return out
 
-    def _stats_of(self, src: VSrc, st0, st1, pool: _StatPool, dev):
-        """(stats0, C0, scale0, stats1, C1, scale1) describing the per-channel sums of a (virtual) tensor"""
+    def _stats_of(self, src: VSrc, st0: Optional[StatTable], st1: Optional[StatTable], pool: _StatPool, dev):
+        """(lo, hi) tables of the per-channel sums of a (virtual) tensor: `hi` holds the upsampled half's when it has a table of its
+        own, else None (`lo` covers every channel).  st0 / st1: the producers' tables of the two halves, if they wrote any."""
         if src.t1 is None:
             if st0 is None:
-                st0 = _take_reps(pool, src.N * src.C0 * 2, self.stat_reps)
+                st0 = pool.table(src.N, src.C0, self.stat_reps)
                 s = src.struct()
-                nat.call("u3d_chan_stats_reps", dev.index, _stream(dev), ctypes.byref(s), src.N, src.D, src.H, src.W, _p(st0), _reps(st0))
-            return st0, src.C0, 1.0, None, 0, 0.0
+                nat.call("u3d_chan_stats_reps", dev.index, _stream(dev), ctypes.byref(s), src.N, src.D, src.H, src.W, *_tab(st0))
+            return st0, None
         if st0 is not None and st1 is not None and src.exact2x and self.fused_stats:
             # every low-res voxel is replicated exactly 8x: reuse the producer's sums
-            return st0, src.C0, 1.0, st1, src.C1, 8.0
+            return st0, dataclasses.replace(st1, scale=8.0)
         plus = src.plus
         if st0 is not None and plus is not None and any(plus) and self.fused_stats and src.C1 % 4 == 0 and src.t1.dtype == _F32:
             # n -> 2n + 1 along some axes: the first low-res cell of such an axis has three children, every other cell two — the sums of
             # the upsampled half as a weighted pass over the LOW-RES tensor (round 6), the skip half from its producer
-            st1w = pool.take(src.N * src.C1 * 2)
-            nat.call("u3d_chan_stats_children", dev.index, _stream(dev), _p(src.t1), src.N, src.D1, src.H1, src.W1, src.C1, *plus, _p(st1w))
-            return st0, src.C0, 1.0, st1w, src.C1, 1.0
-        st = _take_reps(pool, src.N * src.C * 2, self.stat_reps)
+            st1w = pool.table(src.N, src.C1)
+            nat.call("u3d_chan_stats_children", dev.index, _stream(dev), _p(src.t1), src.N, src.D1, src.H1, src.W1, src.C1, *plus,
+                     _p(st1w.t))
+            return st0, st1w
+        st = pool.table(src.N, src.C, self.stat_reps)
         s = src.struct()
-        nat.call("u3d_chan_stats_reps", dev.index, _stream(dev), ctypes.byref(s), src.N, src.D, src.H, src.W, _p(st), _reps(st))
-        return st, src.C, 1.0, None, 0, 0.0
+        nat.call("u3d_chan_stats_reps", dev.index, _stream(dev), ctypes.byref(s), src.N, src.D, src.H, src.W, *_tab(st))
+        return st, None
 
-    def _norm_finalize(self, kind, mod, st0, C0, sc0, st1, C1, sc1, N, G, count, affine, dev, split=None):
-        """per-(n,c) sums -> the (a, b) table the convolutions / apply passes use; returns what backward needs (mean, rstd).
-        `split` = (Csplit, affine_lo, affine_hi): compact tables of the channel ranges [0, Csplit) / [Csplit, C) written in the same
-        launch (GroupNorm over a virtual concat whose halves are read by different kernels; None entries are skipped)"""
-        r0, r1 = _reps(st0), _reps(st1)
-        if kind == "g" and (r0 > 1 or r1 > 1):
+    def _norm_finalize(self, kind, mod, lo: StatTable, hi: Optional[StatTable], G, count, affine, dev, split=None):
+        """per-(n,c) sums (the `_stats_of` pair) -> the (a, b) table the convolutions / apply passes use; returns what backward needs
+        (mean, rstd).  `split` = (Csplit, affine_lo, affine_hi): compact tables of the channel ranges [0, Csplit) / [Csplit, C) written
+        in the same launch (GroupNorm over a virtual concat whose halves are read by different kernels; None entries are skipped)"""
+        N, C0, sc0 = lo.N, lo.C, lo.scale
+        C1, sc1 = (hi.C, hi.scale) if hi is not None else (0, 0.0)
+        if kind == "g" and (lo.reps > 1 or (hi is not None and hi.reps > 1)):
             mean_rstd = _empty((N, G, 2), dtype=_F32, device=dev)
             sp = split if split is not None else (0, None, None)
-            nat.call("u3d_gn_finalize_reps", dev.index, _stream(dev), _p(st0), C0, sc0, r0, _p(st1), C1, sc1, r1, N, G, count,
+            p1, r1 = _tab(hi)
+            nat.call("u3d_gn_finalize_reps", dev.index, _stream(dev), _p(lo.t), C0, sc0, lo.reps, p1, C1, sc1, r1, N, G, count,
                      _p(mod.weight.detach()), _p(mod.bias.detach()), float(mod.eps), _p(affine), _p(mean_rstd), sp[0], _p(sp[1]), _p(sp[2]))
             return mean_rstd
-        st0, st1 = _fold_reps(st0), _fold_reps(st1)
+        st0 = lo.folded().t
+        st1 = hi.folded().t if hi is not None else None
         if kind == "g":
             mean_rstd = _empty((N, G, 2), dtype=_F32, device=dev)
             if split is not None:
@@ -224,51 +208,54 @@ class ConvLayers:
                  _p(mod.bias.detach()), float(mod.eps), 1 if training else 0, momentum, _p(rm), _p(rv), _p(affine), _p(mean_rstd))
         return mean_rstd
 
-    def _norm_bwd_job(self, cx, rec: ConvRec, gst, N, C, count, coef):
+    def _norm_bwd_job(self, cx, rec: ConvRec, gst, count, coef):
         """The GroupNorm-backward reduction of a layer's input as a job for the launch that reduces the layer's weight gradient
-        (u3d_conv3d_wgrad_job: one launch less per layer); None when it has to run on its own (_norm_bwd_finalize)."""
-        if rec.norm != "g" or not _WGRAD_JOB or nat.get_lib().u3d_conv3d_wgrad_job_supported(N, C, rec.G) != 1:
-            return None
+        (u3d_conv3d_wgrad_job: one launch less per layer).  `gst` = (lo, hi): the data gradient's sums, `hi` those of a sub-pixel
+        layer's upsampled channels (else None).  Returns (job, coef_hi); job None when the reduction has to run on its own
+        (_norm_bwd_finalize); coef_hi: the compact (N,3,C1) table (p, 8q, 8r) of the upsampled channels the job writes, or None."""
+        lo, hi = gst
+        N, C = lo.N, lo.C + (hi.C if hi is not None else 0)
+        if rec.norm != "g" or nat.get_lib().u3d_conv3d_wgrad_job_supported(N, C, rec.G) != 1:
+            return None, None
         dev, gview = cx.dev, cx.gview
-        cx.coef_hi = None
         job = nat.U3DGnBwdJob()
-        if isinstance(gst, tuple):
-            g0, g1 = gst
-            C0 = g0.numel() // (2 * N * _reps(g0))
-            coef_hi = _empty((N, 3, C - C0), dtype=_F32, device=dev) if not any(rec.src.plus) else None
-            job.gstats_lo, job.gstats_hi, job.C0, job.C1, job.hi_scale, job.coef_hi = _p(g0), _p(g1), C0, C - C0, 8.0, _p(coef_hi)
-            cx.coef_hi = coef_hi
+        coef_hi = None
+        job.gstats_lo, job.C0, job.reps_lo = _p(lo.t), lo.C, lo.reps
+        if hi is not None:
+            coef_hi = _empty((N, 3, hi.C), dtype=_F32, device=dev) if not any(rec.src.plus) else None
+            job.gstats_hi, job.C1, job.hi_scale, job.reps_hi, job.coef_hi = _p(hi.t), hi.C, 8.0, hi.reps, _p(coef_hi)
         else:
-            job.gstats_lo, job.gstats_hi, job.C0, job.C1, job.hi_scale, job.coef_hi = _p(gst), None, C, 0, 1.0, None
-        job.reps_lo = _reps(gst[0] if isinstance(gst, tuple) else gst)
-        job.reps_hi = _reps(gst[1]) if isinstance(gst, tuple) else 1
+            job.gstats_hi, job.C1, job.hi_scale, job.reps_hi, job.coef_hi = None, 0, 1.0, 1, None
         job.mean_rstd, job.gamma = _p(rec.mean_rstd), _p(rec.gn_w.detach())
         job.dgamma, job.dbeta, job.coef = _p(gview(rec.idx_gw)), _p(gview(rec.idx_gb)), _p(coef)
         job.count, job.N, job.G = count, N, rec.G
-        return job
+        return job, coef_hi
 
-    def _norm_bwd_finalize(self, cx, rec: ConvRec, gst, N, C, count, coef):
+    def _norm_bwd_finalize(self, cx, rec: ConvRec, gst, count, coef):
+        """the same reduction as launches of its own (`gst` as for _norm_bwd_job); returns coef_hi as _norm_bwd_job does"""
         dev, gview = cx.dev, cx.gview
-        cx.coef_hi = None
-        gst = tuple(_fold_reps(g) for g in gst) if isinstance(gst, tuple) else _fold_reps(gst)
-        if isinstance(gst, tuple):
+        lo, hi = gst
+        lo = lo.folded()
+        N, C = lo.N, lo.C
+        g = lo.t
+        if hi is not None:
             # sub-pixel decoder layer: the sums of the skip / upsampled channels come from two kernels as two tables
-            g0, g1 = gst
-            C0 = g0.numel() // (2 * N)
+            hi = hi.folded()
+            C = lo.C + hi.C
             if rec.norm == "g" and nat.get_lib().u3d_gn_bwd_finalize_split_supported(N, C, rec.G) == 1:
                 # ... and the low-res apply pass of an exact-2x level wants the upper channels' (p, 8q, 8r) as a compact table
-                coef_hi = _empty((N, 3, C - C0), dtype=_F32, device=dev) if not any(rec.src.plus) else None
-                nat.call("u3d_gn_bwd_finalize_split", dev.index, _stream(dev), _p(g0), C0, _p(g1), C - C0, _p(rec.mean_rstd),
+                coef_hi = _empty((N, 3, hi.C), dtype=_F32, device=dev) if not any(rec.src.plus) else None
+                nat.call("u3d_gn_bwd_finalize_split", dev.index, _stream(dev), _p(lo.t), lo.C, _p(hi.t), hi.C, _p(rec.mean_rstd),
                          _p(rec.gn_w.detach()), N, rec.G, count, _p(gview(rec.idx_gw)), _p(gview(rec.idx_gb)), _p(coef), 8.0, _p(coef_hi))
-                cx.coef_hi = coef_hi
-                return
-            gst = torch.cat((g0.view(N, C0, 2), g1.view(N, C - C0, 2)), dim=1)
+                return coef_hi
+            g = torch.cat((lo.t.view(N, lo.C, 2), hi.t.view(N, hi.C, 2)), dim=1)
         if rec.norm == "g":
-            nat.call("u3d_gn_bwd_finalize", dev.index, _stream(dev), _p(gst), _p(rec.mean_rstd), _p(rec.gn_w.detach()), N, C, rec.G,
+            nat.call("u3d_gn_bwd_finalize", dev.index, _stream(dev), _p(g), _p(rec.mean_rstd), _p(rec.gn_w.detach()), N, C, rec.G,
                      count, _p(gview(rec.idx_gw)), _p(gview(rec.idx_gb)), _p(coef))
         else:
-            nat.call("u3d_bn_bwd_finalize", dev.index, _stream(dev), _p(gst), _p(rec.mean_rstd), _p(rec.gn_w.detach()), N, C, count,
+            nat.call("u3d_bn_bwd_finalize", dev.index, _stream(dev), _p(g), _p(rec.mean_rstd), _p(rec.gn_w.detach()), N, C, count,
                      1 if rec.bn_training else 0, _p(gview(rec.idx_gw)), _p(gview(rec.idx_gb)), _p(coef))
+        return None
 
     # ---- forward kernel families (csrc file; what selects it) -------------------------------------------------------------------
     _FWD_KERNELS = {
@@ -297,7 +284,7 @@ class ConvLayers:
         # first layer of the network: K = 27*Cin is too small for the MFMA tiling (csrc/u3d_smallc.hip)
         ystats = c.take_stats(self.stat_reps)
         nat.call("u3d_conv3d_small_cin_fwd_reps", c.dev.index, _stream(c.dev), _p(c.src.t0), _p(c.affine), _p(c.conv.weight.detach()),
-                 _p(c.y), c.N, c.D, c.H, c.W, c.Ctot, c.Cout, c.relu, _p(ystats), _reps(ystats), flops=c.flops)
+                 _p(c.y), c.N, c.D, c.H, c.W, c.Ctot, c.Cout, c.relu, *_tab(ystats), flops=c.flops)
         return ystats
 
     def _fwd_subpixel(self, c: "_ConvCall"):
@@ -329,14 +316,15 @@ class ConvLayers:
                      _p(self._pack_cache[(id(conv.weight), 12)][1]), _p(part), N, D1, H1, W1, C1, Cout, _p(kws), need,
                      flops=128.0 * C1 * Cout * N * D1 * H1 * W1)
         a0 = c.affine_lo if c.affine_lo is not None else c.affine[:, :C0].contiguous()
+        yp, yr = _tab(ystats)
         if self._split_fwd(C0, Cout):
             nat.call("u3d_conv3d_f32s", dev.index, _stream(dev), _p(src.t0), _p(a0), _p(self._packed_f32s(conv.weight, 0, dev, C0, 0)),
-                     _p(c.y), N, D, H, W, C0, Cout, c.relu, _p(ystats), None, None, _p(part), None, 0,
+                     _p(c.y), N, D, H, W, C0, Cout, c.relu, yp, None, None, _p(part), None, 0,
                      flops=54.0 * C0 * Cout * N * D * H * W)
         else:
             s0 = VSrc(src.t0).struct(a0)
             nat.call("u3d_conv3d_ex_reps", dev.index, _stream(dev), ctypes.byref(s0), _p(self._pack_cache[(id(conv.weight), 10)][1]),
-                     _p(c.y), N, D, H, W, Cout, c.relu, _p(ystats), None, None, _p(part), None, 0, _reps(ystats),
+                     _p(c.y), N, D, H, W, Cout, c.relu, yp, None, None, _p(part), None, 0, yr,
                      flops=54.0 * C0 * Cout * N * D * H * W)
         return ystats
 
@@ -346,7 +334,8 @@ class ConvLayers:
         need = nat.get_lib().u3d_conv3d_bf16_workspace_floats(c.N, c.D, c.H, c.W, c.Ctot, c.Cout)
         kws = _empty(need, dtype=_F32, device=c.dev) if need > 0 else None
         nat.call("u3d_conv3d_f32s", c.dev.index, _stream(c.dev), _p(c.src.t0), _p(c.affine), _p(self._packed_f32s(c.conv.weight, 0, c.dev)),
-                 _p(c.y), c.N, c.D, c.H, c.W, c.Ctot, c.Cout, c.relu, _p(ystats), None, None, _p(c.residual), _p(kws), need, flops=c.flops)
+                 _p(c.y), c.N, c.D, c.H, c.W, c.Ctot, c.Cout, c.relu, _tab(ystats)[0], None, None, _p(c.residual), _p(kws), need,
+                 flops=c.flops)
         return ystats
 
     def _fwd_bf16(self, c: "_ConvCall"):
@@ -356,7 +345,7 @@ class ConvLayers:
         need = nat.get_lib().u3d_conv3d_bf16_workspace_floats(c.N, c.D, c.H, c.W, c.Ctot, c.Cout)  # split-K scratch at the bottom of the U
         kws = _empty(need, dtype=_F32, device=c.dev) if need > 0 else None
         nat.call("u3d_conv3d_bf16_ex" + ("_b16" if c.b16 else ""), c.dev.index, _stream(c.dev), _p(c.src.t0), _p(c.affine),
-                 _p(self._packed_bf16(c.conv.weight, 0, c.dev)), _p(c.y), c.N, c.D, c.H, c.W, c.Ctot, c.Cout, c.relu, _p(ystats), None, None,
+                 _p(self._packed_bf16(c.conv.weight, 0, c.dev)), _p(c.y), c.N, c.D, c.H, c.W, c.Ctot, c.Cout, c.relu, _tab(ystats)[0], None, None,
                  _p(c.residual), _p(kws), need, flops=c.flops)
         return ystats
 
@@ -369,13 +358,13 @@ class ConvLayers:
         s = c.src.struct(c.affine)
         need = nat.get_lib().u3d_conv2d_workspace_floats(c.N, c.H, c.W, c.Ctot, c.Cout)  # split-K scratch on small grids
         kws = _empty(need, dtype=_F32, device=c.dev) if need > 0 else None
+        yp, yr = _tab(ystats)
         if c.residual is not None:
             nat.call("u3d_conv2d_res_reps", c.dev.index, _stream(c.dev), ctypes.byref(s), _p(wp), _p(c.y), c.N, c.H, c.W, c.Cout, c.relu,
-                     _p(ystats), None, None, _p(kws), need, _reps(ystats), _p(c.residual),
-                     flops=18.0 * c.Ctot * c.Cout * c.N * c.H * c.W)
+                     yp, None, None, _p(kws), need, yr, _p(c.residual), flops=18.0 * c.Ctot * c.Cout * c.N * c.H * c.W)
         else:
             nat.call("u3d_conv2d_ex_reps", c.dev.index, _stream(c.dev), ctypes.byref(s), _p(wp), _p(c.y), c.N, c.H, c.W, c.Cout, c.relu,
-                     _p(ystats), None, None, _p(kws), need, _reps(ystats), flops=18.0 * c.Ctot * c.Cout * c.N * c.H * c.W)
+                     yp, None, None, _p(kws), need, yr, flops=18.0 * c.Ctot * c.Cout * c.N * c.H * c.W)
         return ystats
 
     def _fwd_fp32(self, c: "_ConvCall"):
@@ -385,8 +374,9 @@ class ConvLayers:
         # bottom-of-the-U shapes split the channel reduction over blocks through a scratch buffer (0 floats otherwise)
         need = nat.get_lib().u3d_conv3d_workspace_floats(c.N, c.D, c.H, c.W, c.Ctot, c.Cout)
         kws = _empty(need, dtype=_F32, device=c.dev) if need > 0 else None
+        yp, yr = _tab(ystats)
         nat.call("u3d_conv3d_ex_reps", c.dev.index, _stream(c.dev), ctypes.byref(s), _p(wp), _p(c.y), c.N, c.D, c.H, c.W, c.Cout, c.relu,
-                 _p(ystats), None, None, _p(c.residual), _p(kws), need, _reps(ystats), flops=c.flops)
+                 yp, None, None, _p(c.residual), _p(kws), need, yr, flops=c.flops)
         return ystats
 
     def _single_conv_fwd(self, sc, name, src: VSrc, st_in, pool: _StatPool, tape: Optional[Tape], want_stats=True,
@@ -421,14 +411,13 @@ class ConvLayers:
         if post:
             affine, mean_rstd = self._identity_affine(N, Ctot, dev), None
         else:
-            st0, C0, sc0, st1, C1, sc1 = st_in
             affine = _empty((N, Ctot, 2), dtype=_F32, device=dev)
             if spec.norm == "g" and src.t1 is not None and residual is None and sub and id(conv.weight) in sub:
                 # sub-pixel layer: its two halves are read by different kernels as plain tensors
                 Cs0, Cs1 = sub[id(conv.weight)]
                 split = (Cs0, _empty((N, Cs0, 2), dtype=_F32, device=dev),
                          _empty((N, Cs1, 2), dtype=_F32, device=dev) if any(src.plus) else None)
-            mean_rstd = self._norm_finalize(spec.norm, gn, st0, C0, sc0, st1, C1, sc1, N, G, float(D * H * W), affine, dev, split)
+            mean_rstd = self._norm_finalize(spec.norm, gn, *st_in, G, float(D * H * W), affine, dev, split)
         # y_out: recomputation under activation checkpointing rewrites the (still alive) block output in place with the
         # bit-identical values instead of allocating a second copy
         b16 = src.t0.dtype == torch.bfloat16  # bf16 activation storage: only the bf16-operand branch below handles it
@@ -473,7 +462,7 @@ class ConvLayers:
             else:
                 if zst is None and (spec.norm == "g" or bn_training):
                     zst = self._stats_of(VSrc(z), None, None, pool, dev)[0]
-                mean_rstd = self._norm_finalize(spec.norm, gn, zst, Cout, 1.0, None, 0, 0.0, N, G, float(D * H * W), aff2, dev)
+                mean_rstd = self._norm_finalize(spec.norm, gn, zst, None, G, float(D * H * W), aff2, dev)
             y = y_out if y_out is not None else _empty_like(z)
             nat.call("u3d_affine_add_act_fwd", dev.index, _stream(dev), _p(z), _p(aff2), _p(residual), N, D * H * W, Cout, act,
                      slope, _p(y))
@@ -629,19 +618,19 @@ class ConvLayers:
         dlow = _empty_like(src.t1)
         split0 = self._split_dgrad(C0, Cout)
         plus = src.plus
-        gst0 = _take_reps(pool, Nn * C0 * 2, 1 if split0 else c.greps)
-        gst1 = _take_reps(pool, Nn * C1 * 2, 1 if any(plus) else c.greps)  # (the windowed form of an n -> 2n + 1 level keeps one row)
+        gst0 = pool.table(Nn, C0, 1 if split0 else c.greps)
+        gst1 = pool.table(Nn, C1, 1 if any(plus) else c.greps)  # (the windowed form of an n -> 2n + 1 level keeps one row)
         if split0:
             need = nat.get_lib().u3d_conv3d_bf16_workspace_floats(Nn, Dd, Hh, Ww, Cout, C0)
             kws = cx.ensure_ws(need) if need > 0 else None
             nat.call("u3d_conv3d_f32s", dev.index, _stream(dev), _p(c.dz), None, _p(self._packed_f32s(rec.conv_w, 1, dev, C0, 0)),
-                     _p(dg0), Nn, Dd, Hh, Ww, Cout, C0, 0, None, _p(src.t0), _p(gst0), None, _p(kws), need,
+                     _p(dg0), Nn, Dd, Hh, Ww, Cout, C0, 0, None, _p(src.t0), _p(gst0.t), None, _p(kws), need,
                      flops=54.0 * C0 * Cout * Nn * Dd * Hh * Ww)
         else:
             s_dz = VSrc(c.dz).struct()
             s_x0 = VSrc(src.t0).struct()
             nat.call("u3d_conv3d_ex_reps", dev.index, _stream(dev), ctypes.byref(s_dz), _p(self._packed_sub(rec, 11, dev)), _p(dg0),
-                     Nn, Dd, Hh, Ww, C0, 0, None, ctypes.byref(s_x0), _p(gst0), None, _p(ws), ws.numel(), _reps(gst0),
+                     Nn, Dd, Hh, Ww, C0, 0, None, ctypes.byref(s_x0), _p(gst0.t), None, _p(ws), ws.numel(), gst0.reps,
                      flops=54.0 * C0 * Cout * Nn * Dd * Hh * Ww)
         plus = src.plus
         if any(plus):
@@ -650,7 +639,7 @@ class ConvLayers:
             # first low-res cells of the shifted axes together with its part of the GroupNorm-backward sums
             win = (ctypes.c_int * 9)(Dd, Hh, Ww, *plus, *plus)
             nat.call("u3d_subpixel_conv_dgrad_win", dev.index, _stream(dev), _p(c.dz), _p(self._packed_sub(rec, 13, dev)), _p(src.t1),
-                     _p(dlow), _p(gst1), Nn, src.D1, src.H1, src.W1, C1, Cout, win,
+                     _p(dlow), _p(gst1.t), Nn, src.D1, src.H1, src.W1, C1, Cout, win,
                      flops=128.0 * C1 * Cout * Nn * src.D1 * src.H1 * src.W1)
             dv = _empty((Nn, Dd, Hh, Ww, C1), dtype=_F32, device=dev)
             s_dz2 = VSrc(c.dz).struct()
@@ -664,35 +653,35 @@ class ConvLayers:
                          (ctypes.c_int * 6)(*box), mask,
                          flops=54.0 * C1 * Cout * Nn * (box[3] - box[0]) * (box[4] - box[1]) * (box[5] - box[2]))
             lz, ly, lx = src.los
-            nat.call("u3d_nearest_childsum_add", dev.index, _stream(dev), _p(dv), _p(src.t1), _p(dlow), _p(gst1), Nn, Dd, Hh, Ww,
+            nat.call("u3d_nearest_childsum_add", dev.index, _stream(dev), _p(dv), _p(src.t1), _p(dlow), _p(gst1.t), Nn, Dd, Hh, Ww,
                      src.D1, src.H1, src.W1, C1, _p(lz), _p(ly), _p(lx), *plus)
             del dv
         else:
             nat.call("u3d_subpixel_conv_dgrad_reps", dev.index, _stream(dev), _p(c.dz), _p(self._packed_sub(rec, 13, dev)), _p(src.t1),
-                     _p(dlow), _p(gst1), Nn, src.D1, src.H1, src.W1, C1, Cout, _reps(gst1),
+                     _p(dlow), _p(gst1.t), Nn, src.D1, src.H1, src.W1, C1, Cout, gst1.reps,
                      flops=128.0 * C1 * Cout * Nn * src.D1 * src.H1 * src.W1)
-        return (dg0, dlow), (gst0, gst1)  # (_norm_bwd_finalize takes the two tables as they are)
+        return (dg0, dlow), (gst0, gst1)
 
     def _dgrad_f32s(self, c: "_BwdCall"):
         cx, dev, src, rec = c.cx, c.cx.dev, c.src, c.rec
         dg = _empty((c.N, c.D, c.H, c.W, src.C), dtype=_F32, device=dev)
-        gst = cx.pool.take(c.N * src.C * 2)
+        gst = cx.pool.table(c.N, src.C)
         need = nat.get_lib().u3d_conv3d_bf16_workspace_floats(c.N, c.D, c.H, c.W, c.Cout, src.C)
         kws = cx.ensure_ws(need) if need > 0 else None
         nat.call("u3d_conv3d_f32s", dev.index, _stream(dev), _p(c.dz), None, _p(self._packed_f32s(rec.conv_w, 1, dev)), _p(dg),
-                 c.N, c.D, c.H, c.W, c.Cout, src.C, 0, None, _p(src.t0), _p(gst), None, _p(kws), need, flops=c.flops)
-        return dg, gst
+                 c.N, c.D, c.H, c.W, c.Cout, src.C, 0, None, _p(src.t0), _p(gst.t), None, _p(kws), need, flops=c.flops)
+        return dg, (gst, None)
 
     def _dgrad_bf16(self, c: "_BwdCall"):
         cx, dev, src, rec = c.cx, c.cx.dev, c.src, c.rec
         dg = _empty((c.N, c.D, c.H, c.W, src.C), dtype=c.dz.dtype if c.b16 else _F32, device=dev)
-        gst = cx.pool.take(c.N * src.C * 2)
+        gst = cx.pool.table(c.N, src.C)
         need = nat.get_lib().u3d_conv3d_bf16_workspace_floats(c.N, c.D, c.H, c.W, c.Cout, src.C)
         kws = cx.ensure_ws(need) if need > 0 else None
         nat.call("u3d_conv3d_bf16_ex" + ("_b16" if c.b16 else ""), dev.index, _stream(dev), _p(c.dz), None,
-                 _p(self._packed_bf16(rec.conv_w, 1, dev)), _p(dg), c.N, c.D, c.H, c.W, c.Cout, src.C, 0, None, _p(src.t0), _p(gst),
+                 _p(self._packed_bf16(rec.conv_w, 1, dev)), _p(dg), c.N, c.D, c.H, c.W, c.Cout, src.C, 0, None, _p(src.t0), _p(gst.t),
                  None, _p(kws), need, flops=c.flops)
-        return dg, gst
+        return dg, (gst, None)
 
     def _wgrad_conv2d(self, c: "_BwdCall"):
         # (takes no GroupNorm-backward job: c.job stays set and _conv_bwd runs the reduction on its own)
@@ -705,27 +694,28 @@ class ConvLayers:
         cx, dev, src, rec, ws = c.cx, c.cx.dev, c.src, c.rec, c.cx.ws
         wpd = self._packed2d(rec.conv_w, 1, dev)
         dg = _empty((c.N, c.D, c.H, c.W, src.C), dtype=_F32, device=dev)
-        gst = _take_reps(cx.pool, c.N * src.C * 2, c.greps)
+        gst = cx.pool.table(c.N, src.C, c.greps)
         s_dz = VSrc(c.dz).struct()
         s_x = src.struct()
         nat.call("u3d_conv2d_ex_reps", dev.index, _stream(dev), ctypes.byref(s_dz), _p(wpd), _p(dg), c.N, c.H, c.W, src.C, 0, None,
-                 ctypes.byref(s_x), _p(gst), _p(ws), ws.numel(), _reps(gst), flops=18.0 * src.C * c.Cout * c.N * c.H * c.W)
-        return dg, gst
+                 ctypes.byref(s_x), _p(gst.t), _p(ws), ws.numel(), gst.reps, flops=18.0 * src.C * c.Cout * c.N * c.H * c.W)
+        return dg, (gst, None)
 
     def _dgrad_fp32(self, c: "_BwdCall"):
         cx, dev, src, rec, ws = c.cx, c.cx.dev, c.src, c.rec, c.cx.ws
         wpd = self._packed(rec.conv_w, 1, dev)
         dg = _empty((c.N, c.D, c.H, c.W, src.C), dtype=_F32, device=dev)
-        gst = _take_reps(cx.pool, c.N * src.C * 2, c.greps)
+        gst = cx.pool.table(c.N, src.C, c.greps)
         s_dz = VSrc(c.dz).struct()
         s_x = src.struct()
         nat.call("u3d_conv3d_ex_reps", dev.index, _stream(dev), ctypes.byref(s_dz), _p(wpd), _p(dg), c.N, c.D, c.H, c.W, src.C, 0, None,
-                 ctypes.byref(s_x), _p(gst), None, _p(ws), ws.numel(), _reps(gst), flops=c.flops)
-        return dg, gst
+                 ctypes.byref(s_x), _p(gst.t), None, _p(ws), ws.numel(), gst.reps, flops=c.flops)
+        return dg, (gst, None)
 
     # -- backward building blocks (shared by the DoubleConv and the residual executors) -----------------------
     def _conv_bwd(self, cx, rec: ConvRec, dz_, need_dg=True):
-        """wgrad + dgrad + GroupNorm-backward reductions of one SingleConv; returns (dg, coef)"""
+        """wgrad + dgrad + GroupNorm-backward reductions of one SingleConv; returns (dg, coef, coef_hi): coef_hi is the compact
+        (p, 8q, 8r) table of a sub-pixel layer's upsampled channels when a finalize wrote one (_norm_bwd_job), else None"""
         dev, pool, ws, gview = cx.dev, cx.pool, cx.ws, cx.gview
         src = rec.src
         Nn, Dd, Hh, Ww = src.N, src.D, src.H, src.W
@@ -744,14 +734,14 @@ class ConvLayers:
             # over the conv output z first — sums (sum dn, sum dn*z), parameter gradients, dz = p*dn + q*z + r
             z, _, inner, islope = rec.post
             Vz = Dd * Hh * Ww
-            gst2 = pool.take(Nn * Cout * 2)
-            nat.call("u3d_pair_stats", dev.index, _stream(dev), _p(dz_), _p(z), Nn, Vz, Cout, _p(gst2))
+            gst2 = pool.table(Nn, Cout)
+            nat.call("u3d_pair_stats", dev.index, _stream(dev), _p(dz_), _p(z), Nn, Vz, Cout, _p(gst2.t))
             if rec.norm is None:
                 # norm-free layer: n = z + bias -> dbias = sum dn, dz = dn
-                nat.call("u3d_bias_grad", dev.index, _stream(dev), _p(gst2), Nn, Cout, _p(gview(rec.idx_gb)))
+                nat.call("u3d_bias_grad", dev.index, _stream(dev), _p(gst2.t), Nn, Cout, _p(gview(rec.idx_gb)))
             else:
                 coef2 = _empty((Nn, 3, Cout), dtype=_F32, device=dev)
-                self._norm_bwd_finalize(cx, rec, gst2, Nn, Cout, float(Vz), coef2)
+                self._norm_bwd_finalize(cx, rec, (gst2, None), float(Vz), coef2)
                 dz_ = self._plain_apply(cx, dz_, coef2, z, 1 if inner == ACT_RELU else 0)  # ('crg': z = relu(conv), mask fused)
                 if inner in (ACT_LEAKY, ACT_ELU):
                     nat.call("u3d_act_bwd", dev.index, _stream(dev), _p(dz_), _p(z), dz_.numel(), inner, islope, _p(dz_))
@@ -759,15 +749,14 @@ class ConvLayers:
             self.debug[rec.name + ".dz"] = dz_.clone()
         if rec.small and not need_dg:
             # one pass gives dw and the GroupNorm-backward sums; no data gradient needed (csrc/u3d_smallc.hip)
-            gst = pool.take(Nn * src.C * 2)
+            gst = pool.table(Nn, src.C)
             nat.call("u3d_conv3d_small_cin_bwd", dev.index, _stream(dev), _p(src.t0), _p(rec.affine), _p(dz_),
-                     _p(rec.conv_w.detach()), _p(gview(rec.idx_w)), _p(gst), Nn, Dd, Hh, Ww, src.C, Cout, _p(ws), ws.numel(),
+                     _p(rec.conv_w.detach()), _p(gview(rec.idx_w)), _p(gst.t), Nn, Dd, Hh, Ww, src.C, Cout, _p(ws), ws.numel(),
                      flops=2 * 54.0 * src.C * Cout * Nn * Dd * Hh * Ww)
             if not rec.pre_norm:
-                return None, self._identity_coef(Nn, src.C, dev)
+                return None, self._identity_coef(Nn, src.C, dev), None
             coef = _empty((Nn, 3, src.C), dtype=_F32, device=dev)
-            self._norm_bwd_finalize(cx, rec, gst, Nn, src.C, float(Dd * Hh * Ww), coef)
-            return None, coef
+            return None, coef, self._norm_bwd_finalize(cx, rec, (gst, None), float(Dd * Hh * Ww), coef)
         bf16 = src.t1 is None and rec.sub is None and not rec.small and self._bf16_layer(src.C, Cout)
         b16 = src.t0.dtype == torch.bfloat16  # bf16 activation storage
         assert not b16 or (bf16 and Cout % 64 == 0 and dz_.dtype == torch.bfloat16)
@@ -775,23 +764,23 @@ class ConvLayers:
         # ---- data gradient (+ the GroupNorm-backward sums of the conv input), then weight gradient: one family decision each.  The
         # one-block reduction of those sums rides in the weight gradient's reduce launch where the family takes a job (round 6)
         # (replica rows for the sums only where the weight-gradient launch will take the reduction as a job: it reads them in that form)
-        if (self.stat_reps > 1 and rec.pre_norm and rec.norm == "g" and _WGRAD_JOB and self._wgrad_family(call) in ("fp32", "subpixel")
+        if (self.stat_reps > 1 and rec.pre_norm and rec.norm == "g" and self._wgrad_family(call) in ("fp32", "subpixel")
                 and nat.get_lib().u3d_conv3d_wgrad_job_supported(Nn, src.C, rec.G) == 1):
             call.greps = self.stat_reps
         dg, gst = getattr(self, self._DGRAD_KERNELS[self._dgrad_family(call)])(call)
         if self.debug is not None and rec.sub is None:
             self.debug[rec.name + ".dg"] = dg.clone()
-        coef = None
+        coef = coef_hi = None
         if rec.pre_norm:
             coef = _empty((Nn, 3, src.C), dtype=_F32, device=dev)
-            call.job = self._norm_bwd_job(cx, rec, gst, Nn, src.C, float(Dd * Hh * Ww), coef)
+            call.job, coef_hi = self._norm_bwd_job(cx, rec, gst, float(Dd * Hh * Ww), coef)
         had_job = call.job is not None
         getattr(self, self._WGRAD_KERNELS[self._wgrad_family(call)])(call)
         if not rec.pre_norm:
-            return dg, self._identity_coef(Nn, src.C, dev)  # no GroupNorm on the conv input: dx = dg
+            return dg, self._identity_coef(Nn, src.C, dev), None  # no GroupNorm on the conv input: dx = dg
         if not had_job or call.job is not None:  # (no job, or a weight-gradient family without a reduce launch to carry it)
-            self._norm_bwd_finalize(cx, rec, gst, Nn, src.C, float(Dd * Hh * Ww), coef)
-        return dg, coef
+            coef_hi = self._norm_bwd_finalize(cx, rec, gst, float(Dd * Hh * Ww), coef)
+        return dg, coef, coef_hi
 
     def _plain_apply(self, cx, dg, coef, x, relu_mask, add=None):
         """GroupNorm backward, elementwise part: (p*dg + q*x + r [+ add]) * (relu_mask ? x > 0 : 1)"""

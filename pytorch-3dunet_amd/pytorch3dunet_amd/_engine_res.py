@@ -97,25 +97,25 @@ class ResUNetEngine(UNet3DEngine):
         if conv1 is None:
             r, r_st = x_in, x_st
             if r_st is None:
-                r_st = pool.take(N * Cout * 2)
+                r_st = pool.table(N, Cout)
                 sx = VSrc(r).struct()
-                nat.call("u3d_chan_stats", dev.index, _stream(dev), ctypes.byref(sx), N, D, H, W, _p(r_st))
+                nat.call("u3d_chan_stats", dev.index, _stream(dev), ctypes.byref(sx), N, D, H, W, _p(r_st.t))
         else:
             r = _empty((N, D, H, W, Cout), dtype=self.adt, device=dev)
-            r_st = pool.take(N * Cout * 2)
+            r_st = pool.table(N, Cout)
             w1 = conv1.weight.detach().view(Cout, Cin)
             if self.act_bf16 and x_in.dtype != _F32 and nat.get_lib().u3d_conv1x1_mfma_b16_supported(Cin, Cout):
                 nat.call("u3d_conv1x1_fwd_mfma_b16", dev.index, _stream(dev), _p(x_in), _p(w1), _p(conv1.bias.detach()), _p(r), N,
-                         D * H * W, Cin, Cout, _p(r_st), flops=2.0 * Cin * Cout * N * D * H * W)
+                         D * H * W, Cin, Cout, _p(r_st.t), flops=2.0 * Cin * Cout * N * D * H * W)
             elif self.act_bf16:  # (the first block reads the fp32 network input)
                 nat.call("u3d_conv1x1_fwd_b16", dev.index, _stream(dev), _p(x_in), 1 if x_in.dtype == _F32 else 0, _p(w1),
-                         _p(conv1.bias.detach()), _p(r), N, D * H * W, Cin, Cout, _p(r_st), flops=2.0 * Cin * Cout * N * D * H * W)
+                         _p(conv1.bias.detach()), _p(r), N, D * H * W, Cin, Cout, _p(r_st.t), flops=2.0 * Cin * Cout * N * D * H * W)
             else:
                 nat.call("u3d_conv1x1_fwd", dev.index, _stream(dev), _p(x_in), _p(w1), _p(conv1.bias.detach()), _p(r), N, D * H * W,
-                         Cin, Cout, _p(r_st), flops=2.0 * Cin * Cout * N * D * H * W)
+                         Cin, Cout, _p(r_st.t), flops=2.0 * Cin * Cout * N * D * H * W)
         n0 = len(tape.convs) if tape is not None else 0
         src2 = VSrc(r)
-        out2, st2 = self._single_conv_fwd(bm.conv2, name + ".c2", src2, (r_st, Cout, 1.0, None, 0, 0.0), pool, tape)
+        out2, st2 = self._single_conv_fwd(bm.conv2, name + ".c2", src2, (r_st, None), pool, tape)
         src3 = VSrc(out2)
         if st2 is None and not self.post_norm:  # conv2's epilogue sums do not describe its (LeakyReLU / ELU) output
             st2 = self._stats_of(src3, None, None, pool, dev)[0]
@@ -124,7 +124,7 @@ class ResUNetEngine(UNet3DEngine):
         # rebuilt; U3D_CKPT_RERUN_LAST=1 re-runs it as rounds 4-5 did (A/B; bit-identical).  An SE block's backward needs conv3's own
         # output, which the forward pass did not keep: re-run.)
         skip3 = (getattr(self, "_in_recompute", False) and se_mod is None and y_out is not None and not _CKPT_RERUN_LAST)
-        y, y_st = self._single_conv_fwd(bm.conv3, name + ".c3", src3, (st2, Cout, 1.0, None, 0, 0.0), pool, tape,
+        y, y_st = self._single_conv_fwd(bm.conv3, name + ".c3", src3, (st2, None), pool, tape,
                                         want_stats=se_mod is not None, residual=r, y_out=y_out if se_mod is None else None,
                                         act=(self.act, self.slope), record_only=skip3)
         se = None
@@ -158,7 +158,7 @@ class ResUNetEngine(UNet3DEngine):
             st["s"] = _empty((N, C), dtype=_F32, device=dev)
             st["h"] = _empty((N, Cr), dtype=_F32, device=dev)
             st["gc"] = _empty((N, C), dtype=_F32, device=dev)
-            nat.call("u3d_se_gate_fwd", dev.index, _stream(dev), _p(y_st), float(V), _p(cse.fc1.weight.detach()),
+            nat.call("u3d_se_gate_fwd", dev.index, _stream(dev), _p(y_st.folded().t), float(V), _p(cse.fc1.weight.detach()),
                      _p(cse.fc1.bias.detach()), _p(cse.fc2.weight.detach()), _p(cse.fc2.bias.detach()), N, C, Cr, _p(st["s"]),
                      _p(st["h"]), _p(st["gc"]))
         ws = bs = None
@@ -262,7 +262,7 @@ class ResUNetEngine(UNet3DEngine):
             t8 = self._convtr_t8(Cl, Cs) and not concat
             (mz, lz), (my, ly), (mx, lx) = _maps(dev, Dt, Ds), _maps(dev, Ht, Hs), _maps(dev, Wt, Ws)
             joined = _empty((Nl, Ds, Hs, Ws, Cs + Ct), dtype=_F32, device=dev) if concat else _empty_like(sk)
-            j_st = None if concat else pool.take(Nl * Cs * 2)
+            j_st = None if concat else pool.table(Nl, Cs)
             if t8:
                 # bf16 mode: 2x2x2 convolution on the low-res grid into the space-to-depth layout T8[i][parity*Cs + c] = t[2i + parity];
                 # the resize + join reads that layout directly
@@ -277,7 +277,7 @@ class ResUNetEngine(UNet3DEngine):
                     nat.call("u3d_convtr3d_fwd_t8" + sfx, dev.index, _stream(dev), _p(cur), _p(self._packed_convtr_t8(ct.weight, 0, dev)),
                              _p(t), Nl, D1, H1, W1, Cl, Cs, flops=2.0 * 27 * Cl * Cs * Nl * D1 * H1 * W1)
                 nat.call("u3d_nearest_add_fwd_t8" + sfx, dev.index, _stream(dev), _p(sk), _p(t), _p(mz), _p(my), _p(mx), Nl, Ds, Hs,
-                         Ws, Dt, Ht, Wt, Cs, _p(joined), _p(j_st))
+                         Ws, Dt, Ht, Wt, Cs, _p(joined), _p(j_st.t))
                 del t
                 if tape is not None:
                     tape.ups.append(UpRec(cur, ct.weight, (lz, ly, lx), (Dt, Ht, Wt), True))
@@ -299,7 +299,7 @@ class ResUNetEngine(UNet3DEngine):
                          Wt, Cs, Ct, _p(joined))
             else:
                 nat.call("u3d_nearest_add_fwd", dev.index, _stream(dev), _p(sk), _p(t), _p(mz), _p(my), _p(mx), Nl, Ds, Hs, Ws, Dt, Ht,
-                         Wt, Cs, _p(joined), _p(j_st))
+                         Wt, Cs, _p(joined), _p(j_st.t))
             del t
             if tape is not None:
                 tape.ups.append(UpRec(cur, ct.weight, (lz, ly, lx), (Dt, Ht, Wt), False, (Cs, Ct) if concat else None))
@@ -333,13 +333,13 @@ class ResUNetEngine(UNet3DEngine):
         if rec.se is not None:
             m_ = self._se_bwd(cx, rec.se, m_)
         self._unact(dev, m_, rec.rec3.y)  # -> gradient of (conv3 branch + residual)
-        dg3, coef3 = self._conv_bwd(cx, rec.rec3, m_)
+        dg3, coef3, _ = self._conv_bwd(cx, rec.rec3, m_)
         o2 = rec.rec3.src.t0
         dz2 = self._plain_apply(cx, dg3, coef3, o2, 1 if self.act2 == ACT_RELU else 0)  # through conv2's non-linearity
         if self.act2 in (ACT_LEAKY, ACT_ELU):
             nat.call("u3d_act_bwd", dev.index, _stream(dev), _p(dz2), _p(o2), dz2.numel(), self.act2, self.slope2, _p(dz2))
         del dg3
-        dg2, coef2 = self._conv_bwd(cx, rec.rec2, dz2)
+        dg2, coef2, _ = self._conv_bwd(cx, rec.rec2, dz2)
         del dz2
         # r feeds conv2's GroupNorm AND the `out += residual` shortcut; r itself is linear (no ReLU mask)
         return self._plain_apply(cx, dg2, coef2, rec.r, 0, add=m_)

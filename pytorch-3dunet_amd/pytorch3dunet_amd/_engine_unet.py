@@ -17,7 +17,7 @@ from . import _native as nat
 from ._native import U3DSrc
 
 from ._engine_base import *  # noqa: F401,F403  (explicit __all__: helpers, records, activation codes)
-from ._engine_conv import ConvLayers, _reps, _take_reps
+from ._engine_conv import ConvLayers
 from ._engine_weights import WeightImages
 
 
@@ -202,15 +202,14 @@ class UNet3DEngine(WeightImages, ConvLayers):
                 Dq = Dp if self.is2d else Dp // 2  # (2-D: MaxPool2d, D stays 1)
                 pooled = _empty((Np, Dq, Hp // 2, Wp // 2, Cp), dtype=_F32, device=dev)
                 argmax = _empty(pooled.shape, dtype=torch.uint8, device=dev)
-                pst = None if self.post_norm else _take_reps(pool, Np * Cp * 2, self.stat_reps)
+                pst = None if self.post_norm else pool.table(Np, Cp, self.stat_reps)
                 if self.is2d:
                     nat.call("u3d_maxpool2d_fwd", dev.index, _stream(dev), _p(cur), Np, Hp, Wp, Cp, _p(pooled), _p(argmax), None)
                 else:
                     nat.call("u3d_maxpool2_fwd", dev.index, _stream(dev), _p(cur), Np, Dp, Hp, Wp, Cp, _p(pooled), _p(argmax), None)
                 if pst is not None:  # (the pooled tensor's statistics: a pass of its own — fused into the pool it was slower — into replica rows)
                     s_p = VSrc(pooled).struct()
-                    nat.call("u3d_chan_stats_reps", dev.index, _stream(dev), ctypes.byref(s_p), Np, Dq, Hp // 2, Wp // 2, _p(pst),
-                             _reps(pst))
+                    nat.call("u3d_chan_stats_reps", dev.index, _stream(dev), ctypes.byref(s_p), Np, Dq, Hp // 2, Wp // 2, *_tab(pst))
                 if tape is not None:
                     tape.pools.append((pooled, argmax, cur))
                 cur, cur_st = pooled, pst
@@ -311,8 +310,10 @@ class UNet3DEngine(WeightImages, ConvLayers):
         tot = self.stat_reps * (Co * Cf + Co) + sum(self.stat_reps * N * r.src.C * 2 for r in tape.convs)
         pool = getattr(tape, "bwd_pool", None)  # zeroed by the forward's fill launch; a second backward over the tape takes a fresh one
         tape.bwd_pool = None
-        # (a backward pass being captured into a hipGraph is replayed without its forward: it zeroes its own scratch inside the graph)
-        if pool is None or pool.buf.numel() < tot or pool.buf.device != dev or torch.cuda.is_current_stream_capturing():
+        # (a backward pass being captured into a hipGraph is replayed without its forward: it zeroes its own scratch inside the graph;
+        # claim() last: only the pass that takes the pool marks it used)
+        if (pool is None or pool.buf.numel() < tot or pool.buf.device != dev or torch.cuda.is_current_stream_capturing()
+                or not pool.claim()):
             pool = _StatPool(dev, tot)
         ws = self._wgrad_workspace(tape, dev)
 
@@ -347,11 +348,11 @@ class UNet3DEngine(WeightImages, ConvLayers):
         # ---- decoders, last to first
         for j in range(n_dec - 1, -1, -1):
             r1, r2 = dec_recs[j]
-            dg2, coef2 = conv_bwd(r2, dz)
+            dg2, coef2, _ = conv_bwd(r2, dz)
             dz1 = plain_apply(dg2, coef2, r2.src.t0, mk)  # r2.src.t0 is r1.y (post-activation)
             self._unact(dev, dz1, r2.src.t0)
             del dg2
-            dg1, coef1 = conv_bwd(r1, dz1)
+            dg1, coef1, coef_hi = conv_bwd(r1, dz1)
             src = tape.cats.get(j, r1.src)  # (bf16 mode: r1 ran on the materialised concat; its two halves are what the gradient splits into)
             C0, C1, Ct = src.C0, src.C1, src.C
             # skip half -> gradient of the encoder feature: its GroupNorm backward (p*dg + q*e + r on the first C0 channels)
@@ -367,7 +368,7 @@ class UNet3DEngine(WeightImages, ConvLayers):
                              src.H1, src.W1, C1, *src.plus, mk, _p(dzl))
                 else:
                     # dlow already holds the children sums: (p*dlow + 8*(q*x + r)) * (x > 0) on the low-res producer
-                    coef_up = cx.coef_hi if cx.coef_hi is not None else coef1[:, :, C0:] * self._up_scale(dev)
+                    coef_up = coef_hi if coef_hi is not None else coef1[:, :, C0:] * self._up_scale(dev)
                     nat.call("u3d_gn_bwd_apply", dev.index, _stream(dev), _p(dlow), C1, 0, _p(src.t1), C1, _p(coef_up), C1,
                              src.D1 * src.H1 * src.W1, src.N, mk, _p(dzl))
                 del dg0, dlow
@@ -422,11 +423,11 @@ class UNet3DEngine(WeightImages, ConvLayers):
         pending_hi = self.n_enc_params  # upper end of the encoder gradients not yet handed to the exchange
         for i in range(n_levels - 1, -1, -1):
             r1, r2 = enc_recs[i]
-            dg2, coef2 = conv_bwd(r2, dz)
+            dg2, coef2, _ = conv_bwd(r2, dz)
             dz1 = plain_apply(dg2, coef2, r2.src.t0, mk)
             self._unact(dev, dz1, r2.src.t0)
             del dg2
-            dg1, coef1 = conv_bwd(r1, dz1, need_dg=(i > 0 or need_input_grad))
+            dg1, coef1, _ = conv_bwd(r1, dz1, need_dg=(i > 0 or need_input_grad))
             if self.grad_sync is not None:
                 pending_hi = self._sync_encoder_level(cx, flat, i, pending_hi)  # this level's parameter gradients are final
             if i > 0:

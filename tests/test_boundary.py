@@ -281,6 +281,48 @@ def test_tape_stash_roundtrip_keeps_structure_and_references_parameters_by_posit
     assert r.src.maps[0] is t.convs[0].src.maps[0] and t2.pools[0][1] is b and t2.dims == (1, 1, 2, 2, 2)
 
 
+def test_tape_stash_backward_scratch_is_taken_once():
+    """the backward's zeroed scratch rides on the tape and the skeleton shares it with every unstashed copy: the first backward takes it,
+    a second one over the same skeleton (retain_graph=True) must not get it as fresh"""
+    import torch
+
+    from pytorch3dunet_amd.engine import Tape, _StatPool, stash_tape, unstash_tape
+    from pytorch3dunet_amd.unet3d.model import UNet3D
+
+    eng = UNet3D(1, 1, f_maps=[8, 16], num_groups=4)._get_engine()
+    t = Tape()
+    t.bwd_pool = _StatPool(torch.device("cpu"), 64).carve(16)
+    skel, bag = stash_tape(t, eng._pindex)
+    first = unstash_tape(skel, bag, eng.params).bwd_pool
+    assert first.claim()
+    first.take(8).fill_(1.0)  # the first backward's sums
+    again = unstash_tape(skel, bag, eng.params).bwd_pool
+    assert not again.claim() and not again.claim()
+
+
+@pytest.mark.parametrize("reps", [1, 3, 8])
+def test_stat_table_checks_its_size_and_folds_replica_rows(reps):
+    import torch
+
+    from pytorch3dunet_amd.engine import StatTable, _StatPool
+
+    N, C = 2, 5
+    t = torch.randn(reps, N, C, 2, dtype=torch.float64)
+    tab = StatTable(t.view(-1), N, C, reps)
+    f = tab.folded()
+    assert (f.N, f.C, f.reps, f.scale) == (N, C, 1, 1.0)
+    assert torch.equal(f.t, t.sum(0).view(-1)) and torch.equal(f.t, t.view(reps, -1).sum(0))
+    assert (f is tab) == (reps == 1)
+    for bad in (t.view(-1)[:-1], torch.zeros(reps * N * C * 2 + 2, dtype=torch.float64)):
+        with pytest.raises(AssertionError):
+            StatTable(bad, N, C, reps)
+    with pytest.raises(AssertionError):
+        StatTable(t.view(-1), N, C + 1, reps)
+    p = _StatPool(torch.device("cpu"), 4 * reps * N * C)
+    g = p.table(N, C, reps)
+    assert g.t.numel() == reps * N * C * 2 and g.reps == reps and not g.t.any()
+
+
 @pytest.mark.parametrize("mode", ["trilinear", "area"])
 @pytest.mark.parametrize("n_in,n_out", [(4, 8), (4, 9), (5, 11), (1, 2), (7, 7), (6, 13)])
 def test_resample_tables_reproduce_f_interpolate(mode, n_in, n_out):
