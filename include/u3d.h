@@ -557,6 +557,56 @@ int u3d_dice_fwd(int device, u3d_stream_t stream, const float* logits, const flo
 int u3d_dice_bwd(int device, u3d_stream_t stream, const float* logits, const float* target, const float* coef,
                  const float* grad_out, int N, int C, int64_t V, int norm, float* dlogits);
 
+/* ---- (Added, U3D_VERSION unchanged.)  The factory's loss options and the regression losses ---------------------
+ * The three families above with the options `get_loss_criterion` (losses.py:274-307) puts in front of a loss, taken inside
+ * the kernels instead of as full-size passes on stock operators.  Scratch sizes are the plain entry points' queries.
+ *   t_batch_stride  elements between the targets of consecutive samples; a sample's target is dense.  C*V (V for the int64
+ *                   cross-entropy target) is a contiguous target; (C+1)*V is `target[:, :-1]` of a contiguous (N, C+1, *S)
+ *                   tensor (SkipLastTargetChannelWrapper, losses.py:66-88) read in place.
+ *   use_mask, ignore_value
+ *                   MaskingLossWrapper (losses.py:40-63): where the fp32 target equals ignore_value the element is computed
+ *                   with x = 0 and t = 0 and its gradient is 0.  It is not skipped: it adds log 2 to the BCE sum, 0.25 to
+ *                   the sigmoid Dice denominator, a zero logit to its voxel's softmax, and counts in every mean.
+ *   pos_weight      one float for the BCE term, -(pw t log p + (1 - t) log(1 - p)) in torch's stable form; 1 = plain.
+ * With t_batch_stride = C*V, use_mask = 0 and pos_weight = 1 they compute the plain entry points' formulas (separately
+ * compiled kernels: equal to a few fp32 roundings, not necessarily to the bit). */
+int u3d_bce_dice_fwd_ex(int device, u3d_stream_t stream, const float* logits, const float* target, const float* weight,
+                        int N, int C, int64_t V, float w_bce, float w_dice, float eps, int64_t t_batch_stride, int use_mask,
+                        float ignore_value, float pos_weight, double* sums, float* loss, float* coef);
+int u3d_bce_dice_bwd_ex(int device, u3d_stream_t stream, const float* logits, const float* target, const float* coef,
+                        const float* grad_out, int N, int C, int64_t V, int64_t t_batch_stride, int use_mask,
+                        float ignore_value, float pos_weight, float* dlogits);
+int u3d_softmax_ce_fwd_ex(int device, u3d_stream_t stream, const float* logits, const int64_t* target, const float* weight,
+                          int N, int C, int64_t V, int64_t ignore_index, int auto_weight, int64_t t_batch_stride,
+                          double* scratch, float* loss, float* coef);
+int u3d_softmax_ce_bwd_ex(int device, u3d_stream_t stream, const float* logits, const int64_t* target, const float* coef,
+                          const float* grad_out, int N, int C, int64_t V, int64_t ignore_index, int64_t t_batch_stride,
+                          float* dlogits);
+int u3d_dice_fwd_ex(int device, u3d_stream_t stream, const float* logits, const float* target, const float* weight, int N,
+                    int C, int64_t V, int norm, int generalized, float eps, int64_t t_batch_stride, int use_mask,
+                    float ignore_value, double* scratch, float* loss, float* coef);
+int u3d_dice_bwd_ex(int device, u3d_stream_t stream, const float* logits, const float* target, const float* coef,
+                    const float* grad_out, int N, int C, int64_t V, int norm, int64_t t_batch_stride, int use_mask,
+                    float ignore_value, float* dlogits);
+
+/* Regression losses with mean reduction on fp32 (N, C, V): loss = mean over all N*C*V elements of w * f(x - t).
+ *   mode 0  nn.MSELoss       f(d) = d^2
+ *   mode 1  nn.L1Loss        f(d) = |d|, gradient sign(d) with sign(0) = 0
+ *   mode 2  nn.SmoothL1Loss  f(d) = 0.5 d^2 / beta where |d| < beta, |d| - 0.5 beta elsewhere (beta > 0)
+ *   mode 3  WeightedSmoothL1Loss (losses.py:230-250): mode 2 times `weight` where t < threshold (apply_below != 0) or
+ *           t >= threshold (apply_below = 0), times 1 elsewhere
+ * (w = 1 and threshold / weight / apply_below unused in modes 0-2.)  t_batch_stride, use_mask and ignore_value as above.
+ * fwd : scratch double[u3d_reg_loss_scratch_doubles(N, C, V)] (per-block partials, summed in a fixed order by one block:
+ *       the loss is bit-reproducible), loss float[1]
+ * bwd : dinput = grad_out[0] * w * f'(x - t) / (N*C*V); grad_out is a DEVICE scalar (NULL = 1) - no host synchronisation. */
+long long u3d_reg_loss_scratch_doubles(int N, int C, int64_t V);
+int u3d_reg_loss_fwd(int device, u3d_stream_t stream, const float* input, const float* target, int N, int C, int64_t V,
+                     int64_t t_batch_stride, int mode, float beta, float threshold, float weight, int apply_below, int use_mask,
+                     float ignore_value, double* scratch, float* loss);
+int u3d_reg_loss_bwd(int device, u3d_stream_t stream, const float* input, const float* target, const float* grad_out, int N,
+                     int C, int64_t V, int64_t t_batch_stride, int mode, float beta, float threshold, float weight,
+                     int apply_below, int use_mask, float ignore_value, float* dinput);
+
 /* ---- opt-in bf16-operand convolutions (BASELINE config 4: "bf16 compute", fp32 master weights) --------------
  * The same nn.Conv3d(in,out,3,padding=1,bias=False) (buildingblocks.py:56) and, with mode-1 packed weights on dy, its
  * data gradient — as u3d_conv3d, but on v_mfma_f32_32x32x16_bf16: operands rounded to bf16 (round-to-nearest-even; the

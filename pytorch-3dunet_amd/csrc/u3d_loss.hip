@@ -23,18 +23,43 @@ __device__ __forceinline__ void sigmoid_softplus(float x, float& p, float& sp_po
     sp_pos = fmaxf(x, 0.f) + log1pf(e);
 }
 
+// The options of the *_ex entry points (the reference's SkipLastTargetChannelWrapper / MaskingLossWrapper / pos_weight, losses.py:40-88,
+// :312).  The kernels below are templates on EX: EX = false is the option-free code of the plain entry points, unchanged.
+struct LossOpt {
+    long long t_stride;  // elements between the targets of consecutive samples (dense inside a sample); N*... contiguous otherwise
+    int use_mask;        // t == ignore: compute with x = 0, t = 0 and write dx = 0 (MaskingLossWrapper's arithmetic)
+    float ignore;
+    float pos_weight;  // BCE term: -(pw t log p + (1 - t) log(1 - p)); 1 = the plain form
+};
+
+// MaskingLossWrapper on one element: true (and x = t = 0) where the fp32 target equals the ignore value
+template <bool EX>
+__device__ __forceinline__ bool mask_elem(const LossOpt& o, float& xv, float& tv) {
+    if (EX && o.use_mask && tv == o.ignore) {
+        xv = 0.f;
+        tv = 0.f;
+        return true;
+    }
+    return false;
+}
+
 // grid (blocks_per_row, N*C), 256 threads; row = one (n, c) plane of V voxels
+template <bool EX>
 __global__ __launch_bounds__(256) void loss_sums_kernel(const float* __restrict__ logits, const float* __restrict__ target,
-                                                        int C, long long V, int vec, double* __restrict__ sums) {
+                                                        int C, long long V, int vec, double* __restrict__ sums, LossOpt o) {
     const int row = blockIdx.y;
     const int c = row % C;
     const float* x = logits + (size_t)row * V;
-    const float* t = target + (size_t)row * V;
+    const float* t = EX ? target + (size_t)(row / C) * o.t_stride + (size_t)c * V : target + (size_t)row * V;
     float s_bce = 0.f, s_pt = 0.f, s_pp = 0.f, s_tt = 0.f;
     auto acc = [&](float xv, float tv) {
         float p, sp;
+        mask_elem<EX>(o, xv, tv);
         sigmoid_softplus(xv, p, sp);
-        s_bce += sp - xv * tv;
+        if (EX && o.pos_weight != 1.f)  // torch's stable form: (1 - t) x + (1 + (pw - 1) t) softplus(-x)
+            s_bce += (1.f - tv) * xv + (1.f + (o.pos_weight - 1.f) * tv) * (sp - xv);
+        else
+            s_bce += sp - xv * tv;
         s_pt += p * tv;
         s_pp += p * p;
         s_tt += tv * tv;
@@ -119,19 +144,23 @@ __global__ __launch_bounds__(256) void loss_finalize_kernel(const double* __rest
 }
 
 // dlogits = g * [ k_bce * (p - t) + (a_c * t + b_c * p) * p * (1 - p) ],  g = *grad_out (device scalar) or 1
+template <bool EX>
 __global__ __launch_bounds__(256) void loss_bwd_kernel(const float* __restrict__ logits, const float* __restrict__ target,
                                                        const float* __restrict__ coef, const float* __restrict__ grad_out,
-                                                       int C, long long V, int vec, float* __restrict__ dlogits) {
+                                                       int C, long long V, int vec, float* __restrict__ dlogits, LossOpt o) {
     const int row = blockIdx.y;
     const int c = row % C;
     const float g = grad_out ? grad_out[0] : 1.f;
     const float a = coef[2 * c] * g, b = coef[2 * c + 1] * g, kb = coef[2 * C] * g;
     const float* x = logits + (size_t)row * V;
-    const float* t = target + (size_t)row * V;
+    const float* t = EX ? target + (size_t)(row / C) * o.t_stride + (size_t)c * V : target + (size_t)row * V;
     float* d = dlogits + (size_t)row * V;
     auto one = [&](float xv, float tv) {
         float p, sp;
+        if (mask_elem<EX>(o, xv, tv)) return 0.f;
         sigmoid_softplus(xv, p, sp);
+        if (EX && o.pos_weight != 1.f)
+            return kb * ((1.f - tv) - (1.f + (o.pos_weight - 1.f) * tv) * (1.f - p)) + (a * tv + b * p) * p * (1.f - p);
         return kb * (p - tv) + (a * tv + b * p) * p * (1.f - p);
     };
     const long long stride = (long long)gridDim.x * 256;
@@ -179,7 +208,7 @@ extern "C" int u3d_bce_dice_fwd(int device, u3d_stream_t stream, const float* lo
     hipStream_t st = (hipStream_t)stream;
     const int vec = rows_vec_ok(logits, target, logits, V) ? 1 : 0;
     const dim3 grid = loss_grid(N * C, V);
-    hipLaunchKernelGGL(loss_sums_kernel, grid, dim3(256), 0, st, logits, target, C, (long long)V, vec, sums);
+    hipLaunchKernelGGL(loss_sums_kernel<false>, grid, dim3(256), 0, st, logits, target, C, (long long)V, vec, sums, LossOpt{});
     U3D_LAUNCH_CHECK();
     hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(256), 0, st, sums, N, (int)grid.x, weight, C, (double)N * C * (double)V,
                        w_bce, w_dice, eps, loss, coef);
@@ -193,8 +222,44 @@ extern "C" int u3d_bce_dice_bwd(int device, u3d_stream_t stream, const float* lo
     U3D_REQUIRE(logits && target && coef && dlogits && N > 0 && C > 0 && V > 0, "u3d_bce_dice_bwd: bad argument");
     U3D_REQUIRE((long long)N * C < 65536, "u3d_bce_dice_bwd: N*C must be < 65536");
     const int vec = rows_vec_ok(logits, target, dlogits, V) ? 1 : 0;
-    hipLaunchKernelGGL(loss_bwd_kernel, loss_grid(N * C, V), dim3(256), 0, (hipStream_t)stream, logits, target, coef,
-                       grad_out, C, (long long)V, vec, dlogits);
+    hipLaunchKernelGGL(loss_bwd_kernel<false>, loss_grid(N * C, V), dim3(256), 0, (hipStream_t)stream, logits, target, coef,
+                       grad_out, C, (long long)V, vec, dlogits, LossOpt{});
+    U3D_LAUNCH_CHECK();
+    return 0;
+}
+
+// the same with the options of LossOpt; the target of sample n starts at target + n * t_batch_stride (>= C*V), dense inside
+extern "C" int u3d_bce_dice_fwd_ex(int device, u3d_stream_t stream, const float* logits, const float* target,
+                                   const float* weight, int N, int C, int64_t V, float w_bce, float w_dice, float eps,
+                                   int64_t t_batch_stride, int use_mask, float ignore_value, float pos_weight, double* sums,
+                                   float* loss, float* coef) {
+    U3D_ENTER(device);
+    U3D_REQUIRE(logits && target && sums && loss && coef && N > 0 && C > 0 && V > 0, "u3d_bce_dice_fwd_ex: bad argument");
+    U3D_REQUIRE((long long)N * C < 65536, "u3d_bce_dice_fwd_ex: N*C must be < 65536");
+    U3D_REQUIRE(t_batch_stride >= (int64_t)C * V, "u3d_bce_dice_fwd_ex: t_batch_stride must be >= C*V");
+    hipStream_t st = (hipStream_t)stream;
+    const int vec = rows_vec_ok(logits, target, logits, V) && t_batch_stride % 4 == 0 ? 1 : 0;
+    const dim3 grid = loss_grid(N * C, V);
+    const LossOpt o{(long long)t_batch_stride, use_mask ? 1 : 0, ignore_value, pos_weight};
+    hipLaunchKernelGGL(loss_sums_kernel<true>, grid, dim3(256), 0, st, logits, target, C, (long long)V, vec, sums, o);
+    U3D_LAUNCH_CHECK();
+    hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(256), 0, st, sums, N, (int)grid.x, weight, C, (double)N * C * (double)V,
+                       w_bce, w_dice, eps, loss, coef);
+    U3D_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int u3d_bce_dice_bwd_ex(int device, u3d_stream_t stream, const float* logits, const float* target,
+                                   const float* coef, const float* grad_out, int N, int C, int64_t V, int64_t t_batch_stride,
+                                   int use_mask, float ignore_value, float pos_weight, float* dlogits) {
+    U3D_ENTER(device);
+    U3D_REQUIRE(logits && target && coef && dlogits && N > 0 && C > 0 && V > 0, "u3d_bce_dice_bwd_ex: bad argument");
+    U3D_REQUIRE((long long)N * C < 65536, "u3d_bce_dice_bwd_ex: N*C must be < 65536");
+    U3D_REQUIRE(t_batch_stride >= (int64_t)C * V, "u3d_bce_dice_bwd_ex: t_batch_stride must be >= C*V");
+    const int vec = rows_vec_ok(logits, target, dlogits, V) && t_batch_stride % 4 == 0 ? 1 : 0;
+    const LossOpt o{(long long)t_batch_stride, use_mask ? 1 : 0, ignore_value, pos_weight};
+    hipLaunchKernelGGL(loss_bwd_kernel<true>, loss_grid(N * C, V), dim3(256), 0, (hipStream_t)stream, logits, target, coef,
+                       grad_out, C, (long long)V, vec, dlogits, o);
     U3D_LAUNCH_CHECK();
     return 0;
 }
@@ -241,6 +306,20 @@ __device__ __forceinline__ void voxel_max_sum(const float* __restrict__ x, long 
 #pragma unroll 4
     for (int c = 1; c < C; ++c) {
         const float xv = x[(size_t)c * V];
+        const float mn = fmaxf(m, xv);
+        s = s * expf(m - mn) + expf(xv - mn);
+        m = mn;
+    }
+}
+
+// the same with MaskingLossWrapper's element mask: x_c counts as 0 where t_c == ignore (t points at the voxel's target)
+__device__ __forceinline__ void voxel_max_sum_masked(const float* __restrict__ x, const float* __restrict__ t, long long V, int C,
+                                                     float ignore, float& m, float& s) {
+    m = t[0] == ignore ? 0.f : x[0];
+    s = 1.f;
+#pragma unroll 4
+    for (int c = 1; c < C; ++c) {
+        const float xv = t[(size_t)c * V] == ignore ? 0.f : x[(size_t)c * V];
         const float mn = fmaxf(m, xv);
         s = s * expf(m - mn) + expf(xv - mn);
         m = mn;
@@ -295,10 +374,10 @@ __device__ void reduce_partials(const double* __restrict__ part, int nb, int CK,
 // is never used as an index and makes the loss sum NaN
 __global__ __launch_bounds__(256) void ce_fwd_kernel(const float* __restrict__ logits, const int64_t* __restrict__ target,
                                                      const float* weight, int C, long long V, long long ignore,
-                                                     double* __restrict__ part) {
+                                                     double* __restrict__ part, long long t_stride) {
     const int n = blockIdx.y;
     const float* x = logits + (size_t)n * C * V;
-    const int64_t* tg = target + (size_t)n * V;
+    const int64_t* tg = target + (size_t)n * t_stride;  // V for a contiguous (N, V) target
     double sl = 0.0, sw = 0.0;
     for (long long v = (long long)blockIdx.x * 256 + threadIdx.x; v < V; v += (long long)gridDim.x * 256) {
         const long long t = tg[v];
@@ -338,10 +417,11 @@ __global__ __launch_bounds__(256) void ce_finalize_kernel(const double* __restri
 // grid (blocks_per_row, N, channel chunks)
 __global__ __launch_bounds__(256) void ce_bwd_kernel(const float* __restrict__ logits, const int64_t* __restrict__ target,
                                                      const float* __restrict__ coef, const float* __restrict__ grad_out, int C,
-                                                     long long V, long long ignore, float* __restrict__ dlogits) {
+                                                     long long V, long long ignore, float* __restrict__ dlogits,
+                                                     long long t_stride) {
     const int n = blockIdx.y;
     const float* x = logits + (size_t)n * C * V;
-    const int64_t* tg = target + (size_t)n * V;
+    const int64_t* tg = target + (size_t)n * t_stride;
     float* d = dlogits + (size_t)n * C * V;
     const int c0 = blockIdx.z * MC_BWD_CHUNK, c1 = min(C, c0 + MC_BWD_CHUNK);  // this block's channels
     const float g = (grad_out ? grad_out[0] : 1.f) * coef[C];
@@ -364,14 +444,14 @@ __global__ __launch_bounds__(256) void ce_bwd_kernel(const float* __restrict__ l
 
 // channel sums; grid (blocks_per_row, N, channel chunks of CR), 256 threads; accumulators in registers for the chunk's
 // channels [c0, c0 + CR); part[(n*gx + bx)][C][MC_K]
-template <int CR>
+template <int CR, bool EX>
 __global__ __launch_bounds__(256) void chan_sums_kernel(const float* __restrict__ logits, const float* __restrict__ target,
-                                                        int C, long long V, int norm, double* __restrict__ part) {
+                                                        int C, long long V, int norm, double* __restrict__ part, LossOpt o) {
     const int n = blockIdx.y, c0 = blockIdx.z * CR;
     const int cn = min(CR, C - c0);  // channels of this chunk
     const float* x = logits + (size_t)n * C * V;
     const float* xc = x + (size_t)c0 * V;
-    const float* tg = target ? target + ((size_t)n * C + c0) * V : nullptr;
+    const float* tg = !target ? nullptr : EX ? target + (size_t)n * o.t_stride + (size_t)c0 * V : target + ((size_t)n * C + c0) * V;
     float acc[CR][MC_K];
 #pragma unroll
     for (int c = 0; c < CR; ++c)
@@ -381,6 +461,14 @@ __global__ __launch_bounds__(256) void chan_sums_kernel(const float* __restrict_
         float p[CR];
 #pragma unroll
         for (int c = 0; c < CR; ++c) p[c] = c < cn ? xc[(size_t)c * V + v] : 0.f;
+        float tt[EX ? CR : 1];  // EX: the chunk's targets, read before the normalisation (the mask zeroes x as well)
+        if constexpr (EX) {
+#pragma unroll
+            for (int c = 0; c < CR; ++c) {
+                tt[c] = c < cn ? tg[(size_t)c * V + v] : 0.f;
+                mask_elem<true>(o, p[c], tt[c]);
+            }
+        }
         if (norm == MC_NORM_SOFTMAX) {
             float m, s;
             if (cn == C) {  // the whole voxel is in registers
@@ -392,6 +480,8 @@ __global__ __launch_bounds__(256) void chan_sums_kernel(const float* __restrict_
 #pragma unroll
                 for (int c = 0; c < CR; ++c)
                     if (c < cn) s += expf(p[c] - m);
+            } else if (EX && o.use_mask) {
+                voxel_max_sum_masked(x + v, target + (size_t)n * o.t_stride + v, V, C, o.ignore, m, s);
             } else {
                 voxel_max_sum(x + v, V, C, m, s);
             }
@@ -405,7 +495,7 @@ __global__ __launch_bounds__(256) void chan_sums_kernel(const float* __restrict_
 #pragma unroll
         for (int c = 0; c < CR; ++c)
             if (c < cn) {
-                const float t = tg ? tg[(size_t)c * V + v] : 0.f;
+                const float t = EX ? tt[EX ? c : 0] : tg ? tg[(size_t)c * V + v] : 0.f;
                 acc[c][0] += p[c] * t;
                 acc[c][1] += p[c] * p[c];
                 acc[c][2] += t * t;
@@ -505,37 +595,49 @@ __global__ __launch_bounds__(256) void dice_finalize_kernel(const double* __rest
 
 // dlogits = g · dL/dx through the normalisation: sigmoid p(1−p)·G_c, softmax p_c (G_c − Σ_k p_k G_k), none G_c;
 // grid (blocks_per_row, N, channel chunks)
+template <bool EX>
 __global__ __launch_bounds__(256) void dice_bwd_kernel(const float* __restrict__ logits, const float* __restrict__ target,
                                                        const float* __restrict__ coef, const float* __restrict__ grad_out, int C,
-                                                       long long V, int norm, float* __restrict__ dlogits) {
+                                                       long long V, int norm, float* __restrict__ dlogits, LossOpt o) {
     const int n = blockIdx.y;
     const float* x = logits + (size_t)n * C * V;
-    const float* tg = target + (size_t)n * C * V;
+    const float* tg = EX ? target + (size_t)n * o.t_stride : target + (size_t)n * C * V;
     float* d = dlogits + (size_t)n * C * V;
     const int c0 = blockIdx.z * MC_BWD_CHUNK, c1 = min(C, c0 + MC_BWD_CHUNK);  // this block's channels
     const float g = grad_out ? grad_out[0] : 1.f;
     for (long long v = (long long)blockIdx.x * 256 + threadIdx.x; v < V; v += (long long)gridDim.x * 256) {
         if (norm == MC_NORM_SOFTMAX) {
             float m, s;
-            voxel_max_sum(x + v, V, C, m, s);
+            if (EX && o.use_mask)
+                voxel_max_sum_masked(x + v, tg + v, V, C, o.ignore, m, s);
+            else
+                voxel_max_sum(x + v, V, C, m, s);
             const float inv = 1.f / s;
             float dot = 0.f;
             for (int c = 0; c < C; ++c) {
                 const size_t i = (size_t)c * V + v;
-                const float p = expf(x[i] - m) * inv;
-                dot += p * (coef[3 * c] * tg[i] + coef[3 * c + 1] * p + coef[3 * c + 2]);
+                float xv = x[i], tv = tg[i];
+                mask_elem<EX>(o, xv, tv);
+                const float p = expf(xv - m) * inv;
+                dot += p * (coef[3 * c] * tv + coef[3 * c + 1] * p + coef[3 * c + 2]);
             }
             for (int c = c0; c < c1; ++c) {
                 const size_t i = (size_t)c * V + v;
-                const float p = expf(x[i] - m) * inv;
-                d[i] = g * p * (coef[3 * c] * tg[i] + coef[3 * c + 1] * p + coef[3 * c + 2] - dot);
+                float xv = x[i], tv = tg[i];
+                const bool off = mask_elem<EX>(o, xv, tv);
+                const float p = expf(xv - m) * inv;
+                const float dv = g * p * (coef[3 * c] * tv + coef[3 * c + 1] * p + coef[3 * c + 2] - dot);
+                d[i] = off ? 0.f : dv;
             }
         } else {
             for (int c = c0; c < c1; ++c) {
                 const size_t i = (size_t)c * V + v;
-                const float p = norm == MC_NORM_SIGMOID ? sigmoidf_(x[i]) : x[i];
-                const float gc = coef[3 * c] * tg[i] + coef[3 * c + 1] * p + coef[3 * c + 2];
-                d[i] = g * (norm == MC_NORM_SIGMOID ? gc * p * (1.f - p) : gc);
+                float xv = x[i], tv = tg[i];
+                const bool off = mask_elem<EX>(o, xv, tv);
+                const float p = norm == MC_NORM_SIGMOID ? sigmoidf_(xv) : xv;
+                const float gc = coef[3 * c] * tv + coef[3 * c + 1] * p + coef[3 * c + 2];
+                const float dv = g * (norm == MC_NORM_SIGMOID ? gc * p * (1.f - p) : gc);
+                d[i] = off ? 0.f : dv;
             }
         }
     }
@@ -544,14 +646,16 @@ __global__ __launch_bounds__(256) void dice_bwd_kernel(const float* __restrict__
 inline long long chan_sums_doubles(int N, int C, long long V) { return (long long)N * mc_blocks_per_row(N, C, V) * C * MC_K; }
 
 // the channel-sums pass; returns the number of partial rows
+template <bool EX = false>
 inline int launch_chan_sums(hipStream_t st, const float* logits, const float* target, int N, int C, long long V, int norm,
-                            double* part) {
+                            double* part, LossOpt o = LossOpt{}) {
     const unsigned gx = mc_blocks_per_row(N, C, V);
     if (C <= 4)
-        hipLaunchKernelGGL(chan_sums_kernel<4>, dim3(gx, (unsigned)N, 1), dim3(256), 0, st, logits, target, C, V, norm, part);
+        hipLaunchKernelGGL((chan_sums_kernel<4, EX>), dim3(gx, (unsigned)N, 1), dim3(256), 0, st, logits, target, C, V, norm, part,
+                           o);
     else
-        hipLaunchKernelGGL(chan_sums_kernel<MC_CS_CHUNK>, dim3(gx, (unsigned)N, mc_chunks(C, MC_CS_CHUNK)), dim3(256), 0, st,
-                           logits, target, C, V, norm, part);
+        hipLaunchKernelGGL((chan_sums_kernel<MC_CS_CHUNK, EX>), dim3(gx, (unsigned)N, mc_chunks(C, MC_CS_CHUNK)), dim3(256), 0, st,
+                           logits, target, C, V, norm, part, o);
     return (int)(gx * N);
 }
 
@@ -564,13 +668,15 @@ extern "C" long long u3d_softmax_ce_scratch_doubles(int N, int C, int64_t V) {
     return ce > cs ? ce : cs;
 }
 
-extern "C" int u3d_softmax_ce_fwd(int device, u3d_stream_t stream, const float* logits, const int64_t* target, const float* weight,
-                                  int N, int C, int64_t V, int64_t ignore_index, int auto_weight, double* scratch, float* loss,
-                                  float* coef) {
+// the target of sample n starts at target + n * t_batch_stride (V for a contiguous (N, V) target)
+extern "C" int u3d_softmax_ce_fwd_ex(int device, u3d_stream_t stream, const float* logits, const int64_t* target,
+                                     const float* weight, int N, int C, int64_t V, int64_t ignore_index, int auto_weight,
+                                     int64_t t_batch_stride, double* scratch, float* loss, float* coef) {
     U3D_ENTER(device);
     U3D_REQUIRE(logits && target && scratch && loss && coef && N > 0 && C > 0 && V > 0, "u3d_softmax_ce_fwd: bad argument");
     U3D_REQUIRE(N < 65536 && C <= MC_MAX_C, "u3d_softmax_ce_fwd: needs N < 65536 and C <= 1024");
     U3D_REQUIRE(!(auto_weight && weight), "u3d_softmax_ce_fwd: auto_weight excludes a weight vector");
+    U3D_REQUIRE(t_batch_stride >= V, "u3d_softmax_ce_fwd: t_batch_stride must be >= V");
     hipStream_t st = (hipStream_t)stream;
     if (auto_weight) {
         const int nb = launch_chan_sums(st, logits, nullptr, N, C, (long long)V, MC_NORM_SOFTMAX, scratch);
@@ -581,23 +687,36 @@ extern "C" int u3d_softmax_ce_fwd(int device, u3d_stream_t stream, const float* 
     }
     const dim3 grid(mc_blocks_per_row(N, 1, V), (unsigned)N);
     hipLaunchKernelGGL(ce_fwd_kernel, grid, dim3(256), 0, st, logits, target, weight, C, (long long)V, (long long)ignore_index,
-                       scratch);
+                       scratch, (long long)t_batch_stride);
     U3D_LAUNCH_CHECK();
     hipLaunchKernelGGL(ce_finalize_kernel, dim3(1), dim3(256), 0, st, scratch, (int)(grid.x * grid.y), weight, C, loss, coef);
     U3D_LAUNCH_CHECK();
     return 0;
 }
 
-extern "C" int u3d_softmax_ce_bwd(int device, u3d_stream_t stream, const float* logits, const int64_t* target, const float* coef,
-                                  const float* grad_out, int N, int C, int64_t V, int64_t ignore_index, float* dlogits) {
+extern "C" int u3d_softmax_ce_fwd(int device, u3d_stream_t stream, const float* logits, const int64_t* target, const float* weight,
+                                  int N, int C, int64_t V, int64_t ignore_index, int auto_weight, double* scratch, float* loss,
+                                  float* coef) {
+    return u3d_softmax_ce_fwd_ex(device, stream, logits, target, weight, N, C, V, ignore_index, auto_weight, V, scratch, loss, coef);
+}
+
+extern "C" int u3d_softmax_ce_bwd_ex(int device, u3d_stream_t stream, const float* logits, const int64_t* target,
+                                     const float* coef, const float* grad_out, int N, int C, int64_t V, int64_t ignore_index,
+                                     int64_t t_batch_stride, float* dlogits) {
     U3D_ENTER(device);
     U3D_REQUIRE(logits && target && coef && dlogits && N > 0 && C > 0 && V > 0, "u3d_softmax_ce_bwd: bad argument");
     U3D_REQUIRE(N < 65536 && C <= MC_MAX_C, "u3d_softmax_ce_bwd: needs N < 65536 and C <= 1024");
+    U3D_REQUIRE(t_batch_stride >= V, "u3d_softmax_ce_bwd: t_batch_stride must be >= V");
     const dim3 grid(mc_blocks_per_row(N, 1, V), (unsigned)N, mc_chunks(C, MC_BWD_CHUNK));
     hipLaunchKernelGGL(ce_bwd_kernel, grid, dim3(256), 0, (hipStream_t)stream, logits, target, coef, grad_out, C, (long long)V,
-                       (long long)ignore_index, dlogits);
+                       (long long)ignore_index, dlogits, (long long)t_batch_stride);
     U3D_LAUNCH_CHECK();
     return 0;
+}
+
+extern "C" int u3d_softmax_ce_bwd(int device, u3d_stream_t stream, const float* logits, const int64_t* target, const float* coef,
+                                  const float* grad_out, int N, int C, int64_t V, int64_t ignore_index, float* dlogits) {
+    return u3d_softmax_ce_bwd_ex(device, stream, logits, target, coef, grad_out, N, C, V, ignore_index, V, dlogits);
 }
 
 extern "C" long long u3d_dice_scratch_doubles(int N, int C, int64_t V) {
@@ -605,16 +724,19 @@ extern "C" long long u3d_dice_scratch_doubles(int N, int C, int64_t V) {
     return chan_sums_doubles(N, C, V);
 }
 
-extern "C" int u3d_dice_fwd(int device, u3d_stream_t stream, const float* logits, const float* target, const float* weight,
-                            int N, int C, int64_t V, int norm, int generalized, float eps, double* scratch, float* loss,
-                            float* coef) {
+namespace {
+
+template <bool EX>
+int dice_fwd_impl(int device, u3d_stream_t stream, const float* logits, const float* target, const float* weight, int N, int C,
+                  int64_t V, int norm, int generalized, float eps, LossOpt o, double* scratch, float* loss, float* coef) {
     U3D_ENTER(device);
     U3D_REQUIRE(logits && target && scratch && loss && coef && N > 0 && C > 0 && V > 0, "u3d_dice_fwd: bad argument");
     U3D_REQUIRE(N < 65536 && C <= MC_MAX_C, "u3d_dice_fwd: needs N < 65536 and C <= 1024");
     U3D_REQUIRE(norm >= MC_NORM_SIGMOID && norm <= MC_NORM_NONE, "u3d_dice_fwd: norm must be 0 (sigmoid), 1 (softmax) or 2 (none)");
     U3D_REQUIRE(!(generalized && weight), "u3d_dice_fwd: the generalized Dice takes no class weight");
+    U3D_REQUIRE(o.t_stride >= (long long)C * V, "u3d_dice_fwd: t_batch_stride must be >= C*V");
     hipStream_t st = (hipStream_t)stream;
-    const int nb = launch_chan_sums(st, logits, target, N, C, (long long)V, norm, scratch);
+    const int nb = launch_chan_sums<EX>(st, logits, target, N, C, (long long)V, norm, scratch, o);
     U3D_LAUNCH_CHECK();
     hipLaunchKernelGGL(dice_finalize_kernel, dim3(1), dim3(256), 0, st, scratch, nb, C, weight, generalized ? 1 : 0, eps,
                        (double)N * (double)V, loss, coef);
@@ -622,15 +744,189 @@ extern "C" int u3d_dice_fwd(int device, u3d_stream_t stream, const float* logits
     return 0;
 }
 
-extern "C" int u3d_dice_bwd(int device, u3d_stream_t stream, const float* logits, const float* target, const float* coef,
-                            const float* grad_out, int N, int C, int64_t V, int norm, float* dlogits) {
+template <bool EX>
+int dice_bwd_impl(int device, u3d_stream_t stream, const float* logits, const float* target, const float* coef,
+                  const float* grad_out, int N, int C, int64_t V, int norm, LossOpt o, float* dlogits) {
     U3D_ENTER(device);
     U3D_REQUIRE(logits && target && coef && dlogits && N > 0 && C > 0 && V > 0, "u3d_dice_bwd: bad argument");
     U3D_REQUIRE(N < 65536 && C <= MC_MAX_C, "u3d_dice_bwd: needs N < 65536 and C <= 1024");
     U3D_REQUIRE(norm >= MC_NORM_SIGMOID && norm <= MC_NORM_NONE, "u3d_dice_bwd: norm must be 0 (sigmoid), 1 (softmax) or 2 (none)");
+    U3D_REQUIRE(o.t_stride >= (long long)C * V, "u3d_dice_bwd: t_batch_stride must be >= C*V");
     const dim3 grid(mc_blocks_per_row(N, 1, V), (unsigned)N, mc_chunks(C, MC_BWD_CHUNK));
-    hipLaunchKernelGGL(dice_bwd_kernel, grid, dim3(256), 0, (hipStream_t)stream, logits, target, coef, grad_out, C, (long long)V,
-                       norm, dlogits);
+    hipLaunchKernelGGL(dice_bwd_kernel<EX>, grid, dim3(256), 0, (hipStream_t)stream, logits, target, coef, grad_out, C, (long long)V,
+                       norm, dlogits, o);
+    U3D_LAUNCH_CHECK();
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int u3d_dice_fwd(int device, u3d_stream_t stream, const float* logits, const float* target, const float* weight,
+                            int N, int C, int64_t V, int norm, int generalized, float eps, double* scratch, float* loss,
+                            float* coef) {
+    return dice_fwd_impl<false>(device, stream, logits, target, weight, N, C, V, norm, generalized, eps,
+                                LossOpt{(long long)C * V, 0, 0.f, 1.f}, scratch, loss, coef);
+}
+
+extern "C" int u3d_dice_bwd(int device, u3d_stream_t stream, const float* logits, const float* target, const float* coef,
+                            const float* grad_out, int N, int C, int64_t V, int norm, float* dlogits) {
+    return dice_bwd_impl<false>(device, stream, logits, target, coef, grad_out, N, C, V, norm, LossOpt{(long long)C * V, 0, 0.f, 1.f},
+                                dlogits);
+}
+
+extern "C" int u3d_dice_fwd_ex(int device, u3d_stream_t stream, const float* logits, const float* target, const float* weight,
+                               int N, int C, int64_t V, int norm, int generalized, float eps, int64_t t_batch_stride, int use_mask,
+                               float ignore_value, double* scratch, float* loss, float* coef) {
+    return dice_fwd_impl<true>(device, stream, logits, target, weight, N, C, V, norm, generalized, eps,
+                               LossOpt{(long long)t_batch_stride, use_mask ? 1 : 0, ignore_value, 1.f}, scratch, loss, coef);
+}
+
+extern "C" int u3d_dice_bwd_ex(int device, u3d_stream_t stream, const float* logits, const float* target, const float* coef,
+                               const float* grad_out, int N, int C, int64_t V, int norm, int64_t t_batch_stride, int use_mask,
+                               float ignore_value, float* dlogits) {
+    return dice_bwd_impl<true>(device, stream, logits, target, coef, grad_out, N, C, V, norm,
+                               LossOpt{(long long)t_batch_stride, use_mask ? 1 : 0, ignore_value, 1.f}, dlogits);
+}
+
+// =====================================================================================================================
+// Regression losses on (N, C, V) fp32: nn.MSELoss / nn.L1Loss / nn.SmoothL1Loss (mean reduction) and WeightedSmoothL1Loss
+// (losses.py:230-250), with the target options of LossOpt.  loss = mean over all N*C*V elements of w * f(x - t):
+//   MSE d^2 | L1 |d| (gradient sign(d), sign(0) = 0) | SmoothL1 0.5 d^2 / beta below beta, |d| - 0.5 beta from beta on
+//   weighted: w = weight where t < threshold (apply_below) or t >= threshold (otherwise), else 1, on the SmoothL1 value
+// forward: one read of (x, t), per-block partials in double, a one-block finalize in a fixed order (bit-reproducible);
+// backward: one read of (x, t), one write of dx = g * w * f'(d) / (N*C*V), g the upstream DEVICE scalar.
+namespace {
+
+constexpr int REG_MSE = 0, REG_L1 = 1, REG_SMOOTH_L1 = 2, REG_WEIGHTED_SMOOTH_L1 = 3;
+
+struct RegOpt {
+    int mode;
+    float beta, threshold, weight;
+    int below;
+};
+
+__device__ __forceinline__ float reg_weight(const RegOpt& r, float tv) {
+    if (r.mode != REG_WEIGHTED_SMOOTH_L1) return 1.f;
+    return (r.below ? tv < r.threshold : tv >= r.threshold) ? r.weight : 1.f;
+}
+
+__device__ __forceinline__ float reg_value(const RegOpt& r, float d) {
+    const float z = fabsf(d);
+    if (r.mode == REG_MSE) return d * d;
+    if (r.mode == REG_L1) return z;
+    return z < r.beta ? 0.5f * z * z / r.beta : z - 0.5f * r.beta;
+}
+
+__device__ __forceinline__ float reg_slope(const RegOpt& r, float d) {
+    const float sgn = d > 0.f ? 1.f : d < 0.f ? -1.f : 0.f;
+    if (r.mode == REG_MSE) return 2.f * d;
+    if (r.mode == REG_L1) return sgn;
+    return fabsf(d) < r.beta ? d / r.beta : sgn;
+}
+
+// grid (blocks_per_row, N), 256 threads; row = one sample of M = C*V elements
+__global__ __launch_bounds__(256) void reg_sums_kernel(const float* __restrict__ input, const float* __restrict__ target,
+                                                       long long M, int vec, RegOpt r, LossOpt o, double* __restrict__ part) {
+    const int n = blockIdx.y;
+    const float* x = input + (size_t)n * M;
+    const float* t = target + (size_t)n * o.t_stride;
+    float s = 0.f;
+    auto acc = [&](float xv, float tv) {
+        mask_elem<true>(o, xv, tv);
+        s += reg_weight(r, tv) * reg_value(r, xv - tv);
+    };
+    const long long stride = (long long)gridDim.x * 256;
+    const long long nq = vec ? M >> 2 : 0;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < nq; i += stride) {
+        const f32x4 xv = reinterpret_cast<const f32x4*>(x)[i];
+        const f32x4 tv = reinterpret_cast<const f32x4*>(t)[i];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc(xv[e], tv[e]);
+    }
+    for (long long i = (nq << 2) + (long long)blockIdx.x * 256 + threadIdx.x; i < M; i += stride) acc(x[i], t[i]);
+    double a = (double)s, b = 0.0;
+    block_sum2_256(a, b);
+    if (threadIdx.x == 0) part[(size_t)n * gridDim.x + blockIdx.x] = a;
+}
+
+// one block: loss = sum of the partials (fixed order) / count
+__global__ __launch_bounds__(256) void reg_finalize_kernel(const double* __restrict__ part, int nb, double count,
+                                                           float* __restrict__ loss) {
+    __shared__ double tot[1];
+    reduce_partials(part, nb, 1, tot);
+    if (threadIdx.x == 0) loss[0] = (float)(tot[0] / count);
+}
+
+__global__ __launch_bounds__(256) void reg_bwd_kernel(const float* __restrict__ input, const float* __restrict__ target,
+                                                      const float* __restrict__ grad_out, long long M, int vec, float inv_count,
+                                                      RegOpt r, LossOpt o, float* __restrict__ dinput) {
+    const int n = blockIdx.y;
+    const float* x = input + (size_t)n * M;
+    const float* t = target + (size_t)n * o.t_stride;
+    float* d = dinput + (size_t)n * M;
+    const float g = (grad_out ? grad_out[0] : 1.f) * inv_count;
+    auto one = [&](float xv, float tv) {
+        if (mask_elem<true>(o, xv, tv)) return 0.f;
+        return g * reg_weight(r, tv) * reg_slope(r, xv - tv);
+    };
+    const long long stride = (long long)gridDim.x * 256;
+    const long long nq = vec ? M >> 2 : 0;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < nq; i += stride) {
+        const f32x4 xv = reinterpret_cast<const f32x4*>(x)[i];
+        const f32x4 tv = reinterpret_cast<const f32x4*>(t)[i];
+        f32x4 ov;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) ov[e] = one(xv[e], tv[e]);
+        reinterpret_cast<f32x4*>(d)[i] = ov;
+    }
+    for (long long i = (nq << 2) + (long long)blockIdx.x * 256 + threadIdx.x; i < M; i += stride) d[i] = one(x[i], t[i]);
+}
+
+inline bool reg_args_ok(int N, int C, int64_t V, int64_t t_batch_stride, int mode, float beta) {
+    return N > 0 && N < 65536 && C > 0 && V > 0 && t_batch_stride >= (int64_t)C * V && mode >= REG_MSE &&
+           mode <= REG_WEIGHTED_SMOOTH_L1 && (mode < REG_SMOOTH_L1 || beta > 0.f);
+}
+
+}  // namespace
+
+extern "C" long long u3d_reg_loss_scratch_doubles(int N, int C, int64_t V) {
+    if (N <= 0 || C <= 0 || V <= 0) return 0;
+    return (long long)N * loss_grid(N, (long long)C * V).x;
+}
+
+extern "C" int u3d_reg_loss_fwd(int device, u3d_stream_t stream, const float* input, const float* target, int N, int C, int64_t V,
+                                int64_t t_batch_stride, int mode, float beta, float threshold, float weight, int apply_below,
+                                int use_mask, float ignore_value, double* scratch, float* loss) {
+    U3D_ENTER(device);
+    U3D_REQUIRE(input && target && scratch && loss, "u3d_reg_loss_fwd: bad argument");
+    U3D_REQUIRE(reg_args_ok(N, C, V, t_batch_stride, mode, beta),
+                "u3d_reg_loss_fwd: needs 0 < N < 65536, C, V > 0, t_batch_stride >= C*V, mode 0..3 and beta > 0 for the SmoothL1 modes");
+    hipStream_t st = (hipStream_t)stream;
+    const long long M = (long long)C * V;
+    const int vec = rows_vec_ok(input, target, input, M) && t_batch_stride % 4 == 0 ? 1 : 0;
+    const dim3 grid = loss_grid(N, M);
+    const RegOpt r{mode, beta, threshold, weight, apply_below ? 1 : 0};
+    const LossOpt o{(long long)t_batch_stride, use_mask ? 1 : 0, ignore_value, 1.f};
+    hipLaunchKernelGGL(reg_sums_kernel, grid, dim3(256), 0, st, input, target, M, vec, r, o, scratch);
+    U3D_LAUNCH_CHECK();
+    hipLaunchKernelGGL(reg_finalize_kernel, dim3(1), dim3(256), 0, st, scratch, (int)(grid.x * grid.y), (double)N * (double)M, loss);
+    U3D_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int u3d_reg_loss_bwd(int device, u3d_stream_t stream, const float* input, const float* target, const float* grad_out,
+                                int N, int C, int64_t V, int64_t t_batch_stride, int mode, float beta, float threshold, float weight,
+                                int apply_below, int use_mask, float ignore_value, float* dinput) {
+    U3D_ENTER(device);
+    U3D_REQUIRE(input && target && dinput, "u3d_reg_loss_bwd: bad argument");
+    U3D_REQUIRE(reg_args_ok(N, C, V, t_batch_stride, mode, beta),
+                "u3d_reg_loss_bwd: needs 0 < N < 65536, C, V > 0, t_batch_stride >= C*V, mode 0..3 and beta > 0 for the SmoothL1 modes");
+    const long long M = (long long)C * V;
+    const int vec = rows_vec_ok(input, target, dinput, M) && t_batch_stride % 4 == 0 ? 1 : 0;
+    const RegOpt r{mode, beta, threshold, weight, apply_below ? 1 : 0};
+    const LossOpt o{(long long)t_batch_stride, use_mask ? 1 : 0, ignore_value, 1.f};
+    hipLaunchKernelGGL(reg_bwd_kernel, loss_grid(N, M), dim3(256), 0, (hipStream_t)stream, input, target, grad_out, M, vec,
+                       (float)(1.0 / ((double)N * (double)M)), r, o, dinput);
     U3D_LAUNCH_CHECK();
     return 0;
 }

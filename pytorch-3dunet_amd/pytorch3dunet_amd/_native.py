@@ -307,6 +307,42 @@ _PROTOS = {
          c_void_p],
     ),
     "u3d_dice_bwd": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_int, c_void_p]),
+    "u3d_bce_dice_fwd_ex": (
+        c_int,
+        [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_float, c_float, c_float, c_int64, c_int, c_float,
+         c_float, c_void_p, c_void_p, c_void_p],
+    ),
+    "u3d_bce_dice_bwd_ex": (
+        c_int,
+        [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_int64, c_int, c_float, c_float, c_void_p],
+    ),
+    "u3d_softmax_ce_fwd_ex": (
+        c_int,
+        [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_int64, c_int, c_int64, c_void_p, c_void_p,
+         c_void_p],
+    ),
+    "u3d_softmax_ce_bwd_ex": (
+        c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_int64, c_int64, c_void_p]),
+    "u3d_dice_fwd_ex": (
+        c_int,
+        [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_int, c_int, c_float, c_int64, c_int, c_float,
+         c_void_p, c_void_p, c_void_p],
+    ),
+    "u3d_dice_bwd_ex": (
+        c_int,
+        [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_int, c_int64, c_int, c_float, c_void_p],
+    ),
+    "u3d_reg_loss_scratch_doubles": (c_int64, [c_int, c_int, c_int64]),
+    "u3d_reg_loss_fwd": (
+        c_int,
+        [c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_int64, c_int, c_float, c_float, c_float, c_int, c_int,
+         c_float, c_void_p, c_void_p],
+    ),
+    "u3d_reg_loss_bwd": (
+        c_int,
+        [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_int64, c_int, c_float, c_float, c_float, c_int,
+         c_int, c_float, c_void_p],
+    ),
     "u3d_conv3d_bf16_supported": (c_int, [c_int, c_int]),
     "u3d_packed_weight_bf16_elems": (c_int64, [c_int, c_int, c_int]),
     "u3d_packed_weight_f32s_elems": (c_int64, [c_int, c_int, c_int]),

@@ -1,21 +1,29 @@
 """The fused loss family of the training path.  `install_fused()` patches it into the reference's own
-`pytorch3dunet.unet3d.losses` module, so the trainer's `get_loss_criterion` (losses.py:273-350) keeps its own option
-handling, wrappers and every other loss — none of that host code is restated here.
+`pytorch3dunet.unet3d.losses` module, so the trainer's `get_loss_criterion` (losses.py:274-343) keeps its own option
+handling; every loss name it accepts, and both of its wrappers, then resolve to the classes of this module.
 
 Natively fused on an MI355X (csrc/u3d_loss.hip, C-ABI `u3d_bce_dice_fwd/_bwd`): `BCEDiceLoss` (losses.py:187-201),
-`DiceLoss` with sigmoid normalisation (losses.py:119-127 on top of :84-116) and `nn.BCEWithLogitsLoss` without
-`pos_weight`.  They are one family: loss = w_bce * mean(BCE-with-logits) + w_dice * (1 - mean_c dice_c).  The stock
-path is ~15 ATen kernels, a permute+contiguous copy (`flatten`, losses.py:253-271) and six full-size autograd
+`DiceLoss` with sigmoid normalisation (losses.py:119-127 on top of :84-116) and `nn.BCEWithLogitsLoss`, without or with a
+one-element `pos_weight`.  They are one family: loss = w_bce * mean(BCE-with-logits) + w_dice * (1 - mean_c dice_c).  The
+stock path is ~15 ATen kernels, a permute+contiguous copy (`flatten`, losses.py:253-271) and six full-size autograd
 temporaries; the fused path is two reads of (logits, target) and one write of dlogits, and the upstream scalar gradient
 is consumed on the device (no host synchronisation on the step's critical path).
 
 The multi-class losses are fused too (same file, C-ABI `u3d_softmax_ce_*` / `u3d_dice_*`): `nn.CrossEntropyLoss`
 (mean reduction, no label smoothing, optional `weight` / `ignore_index`; losses.py:316-319), `WeightedCrossEntropyLoss`
 (losses.py:204-227), `DiceLoss` with softmax / no normalisation and `GeneralizedDiceLoss` (losses.py:148-184), for
-C <= 1024 classes.  Loss and gradient are bit-reproducible (per-block partials in double, summed in a fixed order).
+C <= 1024 classes.  So are the regression losses (C-ABI `u3d_reg_loss_*`): `MSELoss`, `L1Loss`, `SmoothL1Loss` and
+`WeightedSmoothL1Loss` (losses.py:230-250, 330-341) with mean reduction.  Loss and gradient are bit-reproducible (per-block
+partials in double, summed in a fixed order).
 
-CPU tensors, other dtypes and unsupported options run the same formulas on torch operators (what the reference does),
-so `device: cpu` configs behave identically.
+The factory's options run inside the same kernels (the `*_ex` entry points and `u3d_reg_loss_*`), not as passes in front of
+them: `skip_last_target` hands the loss the view `target[:, :-1]`, which the kernels read where it lies (a per-sample stride,
+no `.contiguous()` copy), and `ignore_index` on a non-cross-entropy loss (`MaskingLossWrapper`, losses.py:40-63) becomes a
+compare inside the kernel: a masked element is computed with input = target = 0 and gets a zero gradient, exactly the
+wrapper's arithmetic, without its clone, compare and two full-size multiplies.  Both may be stacked.
+
+CPU tensors, other dtypes and unsupported options (a `pos_weight` vector, `reduction` other than "mean", label smoothing)
+run the same formulas on torch operators (what the reference does), so `device: cpu` configs behave identically.
 """
 import ctypes
 import functools
@@ -69,6 +77,40 @@ def _dice_native_ok(input, target):
             and input.shape[1] <= _MAX_CLASSES and input.shape[0] < 65536)
 
 
+# A/B switch of tools/loss_bench.py.  False: the regression losses, the wrappers' options and `pos_weight` run on stock
+# operators and a strided target is copied before the fused kernels, which is what ran before these paths existed.
+_OPTIONS_NATIVE = True
+
+
+def _reg_native_ok(input, target):
+    """(N, C, *S) HIP fp32 input with an fp32 target of the same shape on the same device"""
+    return (_OPTIONS_NATIVE and input.is_cuda and input.dtype == torch.float32 and target.dtype == torch.float32
+            and target.device == input.device and tuple(target.shape) == tuple(input.shape) and input.dim() >= 2
+            and input.numel() > 0 and input.shape[0] < 65536)
+
+
+def _sample_stride(target):
+    """The number of elements between consecutive samples of a target whose samples are each dense in memory, else None.
+    `target[:, :-1]` of a contiguous (N, C + 1, *S) tensor is such a view: the kernels read it where it lies."""
+    inner = 1
+    for size, stride in zip(reversed(target.shape[1:]), reversed(target.stride()[1:])):
+        if size != 1 and stride != inner:
+            return None
+        inner *= size
+    if target.shape[0] == 1:
+        return inner
+    return target.stride(0) if target.stride(0) >= inner else None
+
+
+def _target_in_place(target):
+    """(target, sample stride in elements): the tensor itself when the kernels can read it in place, a contiguous copy otherwise"""
+    ts = _sample_stride(target) if _OPTIONS_NATIVE else None
+    if ts is None:
+        target = target.contiguous()
+        ts = target.numel() // target.shape[0]
+    return target, ts
+
+
 def _class_vector(weight, c, dev):
     """an optional per-class weight as a contiguous device float[C] (None stays None)"""
     if weight is None:
@@ -86,7 +128,7 @@ class _FusedSoftmaxCE(torch.autograd.Function):
         from .. import _native as nat
 
         logits = logits.contiguous()
-        target = target.contiguous()
+        target, ts = _target_in_place(target)
         dev = logits.device
         n, c = logits.shape[0], logits.shape[1]
         v = logits.numel() // (n * c)
@@ -95,11 +137,15 @@ class _FusedSoftmaxCE(torch.autograd.Function):
         coef = torch.empty(c + 1, dtype=torch.float32, device=dev)
         wt = _class_vector(weight, c, dev)
         stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        nat.call("u3d_softmax_ce_fwd", dev.index, stream, ctypes.c_void_p(logits.data_ptr()), ctypes.c_void_p(target.data_ptr()),
-                 None if wt is None else ctypes.c_void_p(wt.data_ptr()), n, c, v, int(ignore_index), 1 if auto_weight else 0,
-                 ctypes.c_void_p(scratch.data_ptr()), ctypes.c_void_p(loss.data_ptr()), ctypes.c_void_p(coef.data_ptr()))
+        head = (dev.index, stream, ctypes.c_void_p(logits.data_ptr()), ctypes.c_void_p(target.data_ptr()),
+                None if wt is None else ctypes.c_void_p(wt.data_ptr()), n, c, v, int(ignore_index), 1 if auto_weight else 0)
+        out = (ctypes.c_void_p(scratch.data_ptr()), ctypes.c_void_p(loss.data_ptr()), ctypes.c_void_p(coef.data_ptr()))
+        if ts == v:
+            nat.call("u3d_softmax_ce_fwd", *head, *out)
+        else:
+            nat.call("u3d_softmax_ce_fwd_ex", *head, ts, *out)
         ctx.save_for_backward(logits, target, coef)
-        ctx.dims = (n, c, v, int(ignore_index))
+        ctx.dims = (n, c, v, int(ignore_index), ts)
         return loss.reshape(())
 
     @staticmethod
@@ -107,14 +153,17 @@ class _FusedSoftmaxCE(torch.autograd.Function):
         from .. import _native as nat
 
         logits, target, coef = ctx.saved_tensors
-        n, c, v, ignore_index = ctx.dims
+        n, c, v, ignore_index, ts = ctx.dims
         dev = logits.device
         g = grad_out.to(dtype=torch.float32).reshape(1).contiguous()
         dlogits = torch.empty_like(logits)
         stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        nat.call("u3d_softmax_ce_bwd", dev.index, stream, ctypes.c_void_p(logits.data_ptr()), ctypes.c_void_p(target.data_ptr()),
-                 ctypes.c_void_p(coef.data_ptr()), ctypes.c_void_p(g.data_ptr()), n, c, v, ignore_index,
-                 ctypes.c_void_p(dlogits.data_ptr()))
+        head = (dev.index, stream, ctypes.c_void_p(logits.data_ptr()), ctypes.c_void_p(target.data_ptr()),
+                ctypes.c_void_p(coef.data_ptr()), ctypes.c_void_p(g.data_ptr()), n, c, v, ignore_index)
+        if ts == v:
+            nat.call("u3d_softmax_ce_bwd", *head, ctypes.c_void_p(dlogits.data_ptr()))
+        else:
+            nat.call("u3d_softmax_ce_bwd_ex", *head, ts, ctypes.c_void_p(dlogits.data_ptr()))
         return dlogits, None, None, None, None
 
 
@@ -125,11 +174,11 @@ class _FusedDice(torch.autograd.Function):
     """per-channel Dice (generalized = False) or generalized Dice loss through u3d_dice_fwd/_bwd"""
 
     @staticmethod
-    def forward(ctx, logits, target, weight, normalization, generalized, eps):
+    def forward(ctx, logits, target, weight, normalization, generalized, eps, ignore=None):
         from .. import _native as nat
 
         logits = logits.contiguous()
-        target = target.contiguous()
+        target, ts = _target_in_place(target)
         dev = logits.device
         n, c = logits.shape[0], logits.shape[1]
         v = logits.numel() // (n * c)
@@ -139,11 +188,16 @@ class _FusedDice(torch.autograd.Function):
         coef = torch.empty(3 * c, dtype=torch.float32, device=dev)
         wt = _class_vector(weight, c, dev)
         stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        nat.call("u3d_dice_fwd", dev.index, stream, ctypes.c_void_p(logits.data_ptr()), ctypes.c_void_p(target.data_ptr()),
-                 None if wt is None else ctypes.c_void_p(wt.data_ptr()), n, c, v, norm, 1 if generalized else 0, float(eps),
-                 ctypes.c_void_p(scratch.data_ptr()), ctypes.c_void_p(loss.data_ptr()), ctypes.c_void_p(coef.data_ptr()))
+        head = (dev.index, stream, ctypes.c_void_p(logits.data_ptr()), ctypes.c_void_p(target.data_ptr()),
+                None if wt is None else ctypes.c_void_p(wt.data_ptr()), n, c, v, norm, 1 if generalized else 0, float(eps))
+        out = (ctypes.c_void_p(scratch.data_ptr()), ctypes.c_void_p(loss.data_ptr()), ctypes.c_void_p(coef.data_ptr()))
+        opts = None if ts == c * v and ignore is None else (ts, 0 if ignore is None else 1, 0.0 if ignore is None else float(ignore))
+        if opts is None:
+            nat.call("u3d_dice_fwd", *head, *out)
+        else:
+            nat.call("u3d_dice_fwd_ex", *head, *opts, *out)
         ctx.save_for_backward(logits, target, coef)
-        ctx.dims = (n, c, v, norm)
+        ctx.dims = (n, c, v, norm, opts)
         return loss.reshape(())
 
     @staticmethod
@@ -151,26 +205,29 @@ class _FusedDice(torch.autograd.Function):
         from .. import _native as nat
 
         logits, target, coef = ctx.saved_tensors
-        n, c, v, norm = ctx.dims
+        n, c, v, norm, opts = ctx.dims
         dev = logits.device
         g = grad_out.to(dtype=torch.float32).reshape(1).contiguous()
         dlogits = torch.empty_like(logits)
         stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        nat.call("u3d_dice_bwd", dev.index, stream, ctypes.c_void_p(logits.data_ptr()), ctypes.c_void_p(target.data_ptr()),
-                 ctypes.c_void_p(coef.data_ptr()), ctypes.c_void_p(g.data_ptr()), n, c, v, norm,
-                 ctypes.c_void_p(dlogits.data_ptr()))
-        return dlogits, None, None, None, None, None
+        head = (dev.index, stream, ctypes.c_void_p(logits.data_ptr()), ctypes.c_void_p(target.data_ptr()),
+                ctypes.c_void_p(coef.data_ptr()), ctypes.c_void_p(g.data_ptr()), n, c, v, norm)
+        if opts is None:
+            nat.call("u3d_dice_bwd", *head, ctypes.c_void_p(dlogits.data_ptr()))
+        else:
+            nat.call("u3d_dice_bwd_ex", *head, *opts, ctypes.c_void_p(dlogits.data_ptr()))
+        return dlogits, None, None, None, None, None, None
 
 
 class _FusedBCEDice(torch.autograd.Function):
     """loss = w_bce * BCEWithLogits(mean) + w_dice * (1 - mean_c dice_c) through u3d_bce_dice_fwd/_bwd."""
 
     @staticmethod
-    def forward(ctx, logits, target, weight, w_bce, w_dice, eps):
+    def forward(ctx, logits, target, weight, w_bce, w_dice, eps, ignore=None, pos_weight=1.0):
         from .. import _native as nat
 
         logits = logits.contiguous()
-        target = target.contiguous()
+        target, ts = _target_in_place(target)
         dev = logits.device
         n, c = logits.shape[0], logits.shape[1]
         v = logits.numel() // (n * c)
@@ -182,12 +239,18 @@ class _FusedBCEDice(torch.autograd.Function):
             wt = weight.to(device=dev, dtype=torch.float32).reshape(-1).contiguous()
             assert wt.numel() == c, "DiceLoss weight must have one entry per channel"
         stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        nat.call("u3d_bce_dice_fwd", dev.index, stream, ctypes.c_void_p(logits.data_ptr()),
-                 ctypes.c_void_p(target.data_ptr()), None if wt is None else ctypes.c_void_p(wt.data_ptr()), n, c, v,
-                 float(w_bce), float(w_dice), float(eps), ctypes.c_void_p(sums.data_ptr()), ctypes.c_void_p(loss.data_ptr()),
-                 ctypes.c_void_p(coef.data_ptr()))
+        head = (dev.index, stream, ctypes.c_void_p(logits.data_ptr()), ctypes.c_void_p(target.data_ptr()),
+                None if wt is None else ctypes.c_void_p(wt.data_ptr()), n, c, v, float(w_bce), float(w_dice), float(eps))
+        out = (ctypes.c_void_p(sums.data_ptr()), ctypes.c_void_p(loss.data_ptr()), ctypes.c_void_p(coef.data_ptr()))
+        opts = None
+        if ts != c * v or ignore is not None or pos_weight != 1.0:
+            opts = (ts, 0 if ignore is None else 1, 0.0 if ignore is None else float(ignore), float(pos_weight))
+        if opts is None:
+            nat.call("u3d_bce_dice_fwd", *head, *out)
+        else:
+            nat.call("u3d_bce_dice_fwd_ex", *head, *opts, *out)
         ctx.save_for_backward(logits, target, coef)
-        ctx.dims = (n, c, v)
+        ctx.dims = (n, c, v, opts)
         return loss.reshape(())
 
     @staticmethod
@@ -195,14 +258,60 @@ class _FusedBCEDice(torch.autograd.Function):
         from .. import _native as nat
 
         logits, target, coef = ctx.saved_tensors
-        n, c, v = ctx.dims
+        n, c, v, opts = ctx.dims
         dev = logits.device
         g = grad_out.to(dtype=torch.float32).reshape(1).contiguous()
         dlogits = torch.empty_like(logits)
         stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        nat.call("u3d_bce_dice_bwd", dev.index, stream, ctypes.c_void_p(logits.data_ptr()), ctypes.c_void_p(target.data_ptr()),
-                 ctypes.c_void_p(coef.data_ptr()), ctypes.c_void_p(g.data_ptr()), n, c, v, ctypes.c_void_p(dlogits.data_ptr()))
-        return dlogits, None, None, None, None, None
+        head = (dev.index, stream, ctypes.c_void_p(logits.data_ptr()), ctypes.c_void_p(target.data_ptr()),
+                ctypes.c_void_p(coef.data_ptr()), ctypes.c_void_p(g.data_ptr()), n, c, v)
+        if opts is None:
+            nat.call("u3d_bce_dice_bwd", *head, ctypes.c_void_p(dlogits.data_ptr()))
+        else:
+            nat.call("u3d_bce_dice_bwd_ex", *head, *opts, ctypes.c_void_p(dlogits.data_ptr()))
+        return dlogits, None, None, None, None, None, None, None
+
+
+_REG_MODE = {"mse": 0, "l1": 1, "smooth_l1": 2, "weighted_smooth_l1": 3}
+
+
+class _FusedRegression(torch.autograd.Function):
+    """mean over all elements of w * f(input - target) through u3d_reg_loss_fwd/_bwd: MSE, L1, SmoothL1(beta) and the
+    threshold-weighted SmoothL1 (`weighting` = (threshold, weight, apply_below_threshold))"""
+
+    @staticmethod
+    def forward(ctx, input, target, mode, beta=1.0, weighting=None, ignore=None):
+        from .. import _native as nat
+
+        input = input.contiguous()
+        target, ts = _target_in_place(target)
+        dev = input.device
+        n, c = input.shape[0], input.shape[1]
+        v = input.numel() // (n * c)
+        threshold, weight, below = (0.0, 1.0, True) if weighting is None else weighting
+        args = (n, c, v, ts, _REG_MODE[mode], float(beta), float(threshold), float(weight), 1 if below else 0,
+                0 if ignore is None else 1, 0.0 if ignore is None else float(ignore))
+        scratch = torch.empty(nat.get_lib().u3d_reg_loss_scratch_doubles(n, c, v), dtype=torch.float64, device=dev)
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        nat.call("u3d_reg_loss_fwd", dev.index, stream, ctypes.c_void_p(input.data_ptr()), ctypes.c_void_p(target.data_ptr()), *args,
+                 ctypes.c_void_p(scratch.data_ptr()), ctypes.c_void_p(loss.data_ptr()))
+        ctx.save_for_backward(input, target)
+        ctx.args = args
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        from .. import _native as nat
+
+        input, target = ctx.saved_tensors
+        dev = input.device
+        g = grad_out.to(dtype=torch.float32).reshape(1).contiguous()
+        dinput = torch.empty_like(input)
+        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        nat.call("u3d_reg_loss_bwd", dev.index, stream, ctypes.c_void_p(input.data_ptr()), ctypes.c_void_p(target.data_ptr()),
+                 ctypes.c_void_p(g.data_ptr()), *ctx.args, ctypes.c_void_p(dinput.data_ptr()))
+        return dinput, None, None, None, None, None
 
 
 def fused_bce_dice(logits, target, w_bce=1.0, w_dice=1.0, weight=None, eps=1e-6):
@@ -250,13 +359,18 @@ class DiceLoss(_AbstractDiceLoss):
     def dice(self, input, target, weight):
         return compute_per_channel_dice(input, target, weight=self.weight)
 
-    def forward(self, input, target):
+    def _native(self, input, target, ignore):
+        """the fused loss with MaskingLossWrapper's `ignore` value taken inside the kernels, None where it does not apply"""
         if self.normalization_name == "sigmoid":
             if _native_ok(input, target):
-                return fused_bce_dice(input, target, 0.0, 1.0, self.weight)
+                return _FusedBCEDice.apply(input, target, self.weight, 0.0, 1.0, 1e-6, ignore)
         elif _dice_native_ok(input, target) and (self.weight is None or self.weight.numel() == input.shape[1]):
-            return _FusedDice.apply(input, target, self.weight, self.normalization_name, False, 1e-6)
-        return super().forward(input, target)
+            return _FusedDice.apply(input, target, self.weight, self.normalization_name, False, 1e-6, ignore)
+        return None
+
+    def forward(self, input, target):
+        out = self._native(input, target, None)
+        return super().forward(input, target) if out is None else out
 
 
 class GeneralizedDiceLoss(_AbstractDiceLoss):
@@ -281,10 +395,14 @@ class GeneralizedDiceLoss(_AbstractDiceLoss):
         denominator = ((input + target).sum(-1) * w_l).clamp(min=self.epsilon)
         return 2 * (intersect.sum() / denominator.sum())
 
-    def forward(self, input, target):
+    def _native(self, input, target, ignore):
         if _dice_native_ok(input, target):
-            return _FusedDice.apply(input, target, None, self.normalization_name, True, self.epsilon)
-        return super().forward(input, target)
+            return _FusedDice.apply(input, target, None, self.normalization_name, True, self.epsilon, ignore)
+        return None
+
+    def forward(self, input, target):
+        out = self._native(input, target, None)
+        return super().forward(input, target) if out is None else out
 
 
 class BCEDiceLoss(nn.Module):
@@ -296,19 +414,44 @@ class BCEDiceLoss(nn.Module):
         self.bce = nn.BCEWithLogitsLoss()
         self.dice = DiceLoss()
 
-    def forward(self, input, target):
+    def _native(self, input, target, ignore):
         if _native_ok(input, target):
-            return fused_bce_dice(input, target, 1.0, self.alpha)
-        return self.bce(input, target) + self.alpha * self.dice(input, target)
+            return _FusedBCEDice.apply(input, target, None, 1.0, self.alpha, 1e-6, ignore)
+        return None
+
+    def forward(self, input, target):
+        out = self._native(input, target, None)
+        return self.bce(input, target) + self.alpha * self.dice(input, target) if out is None else out
 
 
 class BCEWithLogitsLoss(nn.BCEWithLogitsLoss):
-    """nn.BCEWithLogitsLoss (losses.py:297-298); the plain mean-reduced, unweighted form is fused on an MI355X."""
+    """nn.BCEWithLogitsLoss (losses.py:311-312); the mean-reduced form without `weight`, with no or a one-element `pos_weight`,
+    is fused on an MI355X.  A longer `pos_weight` vector stays on torch's operator."""
+
+    def _pos_weight_value(self):
+        """the one-element `pos_weight` as a host float, read from the device once per value (not once per step); None for a
+        vector"""
+        pw = self.pos_weight
+        if pw is None:
+            return 1.0
+        if pw.numel() != 1 or not _OPTIONS_NATIVE:
+            return None
+        key = (id(pw), pw._version)
+        cached = self.__dict__.get("_u3d_pos_weight")
+        if cached is None or cached[0] != key:
+            cached = self.__dict__["_u3d_pos_weight"] = (key, float(pw))
+        return cached[1]
+
+    def _native(self, input, target, ignore):
+        if self.weight is None and self.reduction == "mean" and _native_ok(input, target):
+            pw = self._pos_weight_value()
+            if pw is not None:
+                return _FusedBCEDice.apply(input, target, None, 1.0, 0.0, 1e-6, ignore, pw)
+        return None
 
     def forward(self, input, target):
-        if self.weight is None and self.pos_weight is None and self.reduction == "mean" and _native_ok(input, target):
-            return fused_bce_dice(input, target, 1.0, 0.0)
-        return super().forward(input, target)
+        out = self._native(input, target, None)
+        return super().forward(input, target) if out is None else out
 
 
 class CrossEntropyLoss(nn.CrossEntropyLoss):
@@ -342,12 +485,115 @@ class WeightedCrossEntropyLoss(nn.Module):
         return ((1.0 - flattened).sum(-1) / flattened.sum(-1)).detach()
 
 
+class MSELoss(nn.MSELoss):
+    """nn.MSELoss (losses.py:330-331); the mean-reduced form on HIP fp32 tensors is fused on an MI355X."""
+
+    def _native(self, input, target, ignore):
+        if self.reduction == "mean" and _reg_native_ok(input, target):
+            return _FusedRegression.apply(input, target, "mse", 1.0, None, ignore)
+        return None
+
+    def forward(self, input, target):
+        out = self._native(input, target, None)
+        return super().forward(input, target) if out is None else out
+
+
+class L1Loss(nn.L1Loss):
+    """nn.L1Loss (losses.py:334-335); the mean-reduced form on HIP fp32 tensors is fused on an MI355X."""
+
+    def _native(self, input, target, ignore):
+        if self.reduction == "mean" and _reg_native_ok(input, target):
+            return _FusedRegression.apply(input, target, "l1", 1.0, None, ignore)
+        return None
+
+    def forward(self, input, target):
+        out = self._native(input, target, None)
+        return super().forward(input, target) if out is None else out
+
+
+class SmoothL1Loss(nn.SmoothL1Loss):
+    """nn.SmoothL1Loss (losses.py:332-333, the loss of the denoising config); the mean-reduced form on HIP fp32 tensors is
+    fused on an MI355X.  beta = 0 is the L1 loss, as in torch."""
+
+    def _native(self, input, target, ignore):
+        if self.reduction == "mean" and self.beta >= 0 and _reg_native_ok(input, target):
+            mode = "smooth_l1" if self.beta > 0 else "l1"
+            return _FusedRegression.apply(input, target, mode, self.beta, None, ignore)
+        return None
+
+    def forward(self, input, target):
+        out = self._native(input, target, None)
+        return super().forward(input, target) if out is None else out
+
+
+def _weighted_smooth_l1_class(base):
+    """`WeightedSmoothL1Loss` of the caller's module (losses.py:230-250: SmoothL1 per element, times `weight` where the target
+    lies below / from `threshold`, then the mean) with the fused forward.  The caller's class stays the base class and the
+    fallback, so its statements are run, not restated; the stock form costs two boolean-mask gather / scatter passes and a
+    host synchronisation for the mask count, the fused one a read of (input, target)."""
+
+    class WeightedSmoothL1Loss(base):
+        def _native(self, input, target, ignore):
+            if _reg_native_ok(input, target) and getattr(self, "beta", 1.0) > 0:
+                weighting = (self.threshold, self.weight, self.apply_below_threshold)
+                return _FusedRegression.apply(input, target, "weighted_smooth_l1", getattr(self, "beta", 1.0), weighting, ignore)
+            return None
+
+        def forward(self, input, target):
+            out = self._native(input, target, None)
+            return super().forward(input, target) if out is None else out
+
+    WeightedSmoothL1Loss.__module__ = __name__
+    WeightedSmoothL1Loss.__qualname__ = "WeightedSmoothL1Loss"
+    return WeightedSmoothL1Loss
+
+
+def _masking_wrapper_class(base):
+    """`MaskingLossWrapper` of the caller's module (losses.py:40-63) for the fused losses: the ignore value goes down to the
+    kernels, which compute the masked elements with input = target = 0 and write a zero gradient, so the wrapper's clone,
+    compare and two full-size multiplies do not run.  Any other wrapped loss gets the caller's own forward."""
+
+    class MaskingLossWrapper(base):
+        def forward(self, input, target):
+            native = getattr(self.loss, "_native", None) if _OPTIONS_NATIVE and _is_fused(self.loss) else None
+            out = None if native is None else native(input, target, float(self.ignore_index))
+            return super().forward(input, target) if out is None else out
+
+    MaskingLossWrapper.__module__ = __name__
+    MaskingLossWrapper.__qualname__ = "MaskingLossWrapper"
+    return MaskingLossWrapper
+
+
+def _skip_last_wrapper_class(base):
+    """`SkipLastTargetChannelWrapper` of the caller's module (losses.py:66-88).  Its forward is the caller's: `target[:, :-1]`
+    (and the optional squeeze) are views, and the fused functions read such a view where it lies (`_sample_stride`) instead
+    of copying it, also through a fused `MaskingLossWrapper` in between."""
+
+    class SkipLastTargetChannelWrapper(base):
+        pass
+
+    SkipLastTargetChannelWrapper.__module__ = __name__
+    SkipLastTargetChannelWrapper.__qualname__ = "SkipLastTargetChannelWrapper"
+    return SkipLastTargetChannelWrapper
+
+
+def _is_fused(loss):
+    """a loss object of this module (the classes defined here and the ones built from the caller's module)"""
+    return type(loss).__module__ == __name__ and hasattr(loss, "_native")
+
+
 # ---------------------------------------------------------------------------------------------------------------
-# Everything else of the reference's losses.py (option handling of `get_loss_criterion`, the masking / skip-last-channel
-# wrappers, the regression losses; losses.py:40-82,230-250,273-345) is host code that this repository does NOT restate:
-# the fused classes above are patched INTO the caller's own `pytorch3dunet.unet3d.losses` module, whose factory and
-# wrappers keep running unchanged.
+# What remains the caller's of the reference's losses.py is the option handling of `get_loss_criterion` / `_create_loss`
+# (losses.py:274-343).  The losses it names, the regression losses and the two wrappers included, are patched INTO the caller's
+# own `pytorch3dunet.unet3d.losses` module, whose factory keeps running unchanged.  Still on stock operators: a `pos_weight`
+# vector, `reduction` other than "mean", tensors that are not fp32 or not on the GPU.
 _FUSED = ("BCEDiceLoss", "DiceLoss", "WeightedCrossEntropyLoss", "GeneralizedDiceLoss")
+# the factory finds these three in its module globals (`from torch.nn import MSELoss, SmoothL1Loss, L1Loss`): patched where the
+# caller's module has the name, so a factory that builds `nn.MSELoss()` itself keeps getting torch's class
+_FUSED_IF_PRESENT = ("MSELoss", "L1Loss", "SmoothL1Loss")
+# subclasses built from the caller's own classes at install time
+_DERIVED = {"WeightedSmoothL1Loss": _weighted_smooth_l1_class, "MaskingLossWrapper": _masking_wrapper_class,
+            "SkipLastTargetChannelWrapper": _skip_last_wrapper_class}
 _UPGRADES = {nn.BCEWithLogitsLoss: BCEWithLogitsLoss, nn.CrossEntropyLoss: CrossEntropyLoss}
 
 
@@ -364,15 +610,23 @@ def _upgrade(module):
 
 def install_fused(ref_losses):
     """Patch the fused loss family into the caller's `pytorch3dunet.unet3d.losses` module (idempotent): its own `_create_loss`
-    (losses.py:310-345) looks the fused classes up in its module globals at call time, and its `get_loss_criterion`
-    is wrapped once so that plain `nn.BCEWithLogitsLoss` / `nn.CrossEntropyLoss` instances come back with the fused forward.  Must run before
-    `pytorch3dunet.unet3d.trainer` is imported (trainer.py:16 binds `get_loss_criterion` by name)."""
+    (losses.py:310-343) and `get_loss_criterion` look the loss and wrapper classes up in the module globals at call time, and
+    `get_loss_criterion` is wrapped once so that plain `nn.BCEWithLogitsLoss` / `nn.CrossEntropyLoss` instances come back with
+    the fused forward.  Must run before `pytorch3dunet.unet3d.trainer` is imported (trainer.py:16 binds `get_loss_criterion`
+    by name)."""
     if ref_losses is sys.modules[__name__]:
         raise RuntimeError("install_fused() takes the REFERENCE's pytorch3dunet.unet3d.losses module, not this one")
     if getattr(ref_losses, "_u3d_fused", False):
         return ref_losses
     for name in _FUSED:
         setattr(ref_losses, name, globals()[name])
+    for name in _FUSED_IF_PRESENT:
+        if hasattr(ref_losses, name):
+            setattr(ref_losses, name, globals()[name])
+    for name, derive in _DERIVED.items():
+        base = getattr(ref_losses, name, None)
+        if isinstance(base, type):
+            setattr(ref_losses, name, derive(base))
     inner = ref_losses.get_loss_criterion
 
     @functools.wraps(inner)
