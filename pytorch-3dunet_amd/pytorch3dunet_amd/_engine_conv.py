@@ -19,6 +19,7 @@ from . import _native as nat
 from ._native import U3DSrc
 
 from ._engine_base import *  # noqa: F401,F403  (explicit __all__: helpers, records, activation codes)
+from ._engine_weights import Kind
 
 
 class _SubLayers(dict):
@@ -138,8 +139,7 @@ class ConvLayers:
                 out[id(c1.conv.weight)] = (C0, C1)
                 if any(ratio):
                     plus.add(id(c1.conv.weight))
-        self._sub_pairs.update(out)
-        out.plus = frozenset(plus)  # the layers of this call whose packed set includes the slab images (_repack_all)
+        out.plus = frozenset(plus)  # the layers of this call whose packed set includes the slab images (WeightImages.repack)
         return out
 
     def _stats_of(self, src: VSrc, st0: Optional[StatTable], st1: Optional[StatTable], pool: _StatPool, dev):
@@ -257,6 +257,22 @@ class ConvLayers:
                      1 if rec.bn_training else 0, _p(gview(rec.idx_gw)), _p(gview(rec.idx_gb)), _p(coef))
         return None
 
+    def _bf16_layer(self, Cin: int, Cout: int) -> bool:
+        """forward AND data gradient of a (Cin -> Cout) 3x3x3 conv can run on the bf16 kernels (both directions need the
+        contraction channels % 16 and the produced channels % 32)"""
+        return self.bf16 and Cin % 32 == 0 and Cout % 32 == 0
+
+    def _split_fwd(self, Cin: int, Cout: int) -> bool:
+        return self.split and Cin % 16 == 0 and Cout % 32 == 0
+
+    def _split_dgrad(self, Cin: int, Cout: int) -> bool:
+        """data gradient of a (Cin -> Cout) conv: contraction over Cout, produces Cin channels"""
+        return self.split and Cout % 16 == 0 and Cin % 32 == 0
+
+    def _convtr_t8(self, Cl: int, Cs: int) -> bool:
+        """the transposed convolution and its gradients run in space-to-depth form on the bf16 MFMA kernels"""
+        return self.bf16 and nat.get_lib().u3d_convtr3d_t8_supported(Cl, Cs) == 1
+
     # ---- forward kernel families (csrc file; what selects it) -------------------------------------------------------------------
     _FWD_KERNELS = {
         "small": "_fwd_small",        # u3d_smallc.hip: first layer, Cin <= 4
@@ -291,7 +307,7 @@ class ConvLayers:
         # cat(skip, nearest2x(low)): the upsampled half as 8 parity-class 2x2x2 convolutions over the low-res tensor
         # (8/27 of the multiply-adds), then the skip half, whose epilogue adds the partial sums before ReLU / statistics
         dev, conv, src, N, D, H, W, Cout = c.dev, c.conv, c.src, c.N, c.D, c.H, c.W, c.Cout
-        C0, C1 = c.sub[id(conv.weight)]
+        pair = C0, C1 = c.sub[id(conv.weight)]
         ystats = c.take_stats(1 if self._split_fwd(C0, Cout) else self.stat_reps)
         part = _empty((N, D, H, W, Cout), dtype=_F32, device=dev)
         D1, H1, W1 = src.D1, src.H1, src.W1
@@ -301,10 +317,10 @@ class ConvLayers:
             # d < 2 of those axes (overwriting the window's first plane, which misses the extra copy of low[0])
             win = (ctypes.c_int * 6)(D, H, W, *plus)
             nat.call("u3d_subpixel_conv_fwd_win", dev.index, _stream(dev), _p(src.t1), _p(c.affine.view(-1)[2 * C0:]), c.Ctot * 2,
-                     _p(self._pack_cache[(id(conv.weight), 12)][1]), _p(part), N, D1, H1, W1, C1, Cout, win,
+                     _p(self.images.get(conv.weight, Kind.UP_FWD, dev, pair)), _p(part), N, D1, H1, W1, C1, Cout, win,
                      flops=128.0 * C1 * Cout * N * D1 * H1 * W1)
             s_up = src.up_only_struct(c.affine_hi if c.affine_hi is not None else c.affine[:, C0:].contiguous())
-            wp1 = self._pack_cache[(id(conv.weight), 14)][1]  # 27-tap forward image of the upsampled channels (slab launches)
+            wp1 = self.images.get(conv.weight, Kind.SLAB_FWD, dev, pair)  # 27-tap forward image of the upsampled channels (slab launches)
             for box in slab_boxes((D, H, W), plus, 2):
                 nat.call("u3d_conv3d_box", dev.index, _stream(dev), ctypes.byref(s_up), _p(wp1), _p(part), N, D, H, W, Cout,
                          (ctypes.c_int * 6)(*box), None,
@@ -313,17 +329,17 @@ class ConvLayers:
             need = nat.get_lib().u3d_subpixel_fwd_workspace_floats(N, D1, H1, W1, C1, Cout)  # split-K scratch, small levels only
             kws = _empty(need, dtype=_F32, device=dev) if need > 0 else None
             nat.call("u3d_subpixel_conv_fwd", dev.index, _stream(dev), _p(src.t1), _p(c.affine.view(-1)[2 * C0:]), c.Ctot * 2,
-                     _p(self._pack_cache[(id(conv.weight), 12)][1]), _p(part), N, D1, H1, W1, C1, Cout, _p(kws), need,
+                     _p(self.images.get(conv.weight, Kind.UP_FWD, dev, pair)), _p(part), N, D1, H1, W1, C1, Cout, _p(kws), need,
                      flops=128.0 * C1 * Cout * N * D1 * H1 * W1)
         a0 = c.affine_lo if c.affine_lo is not None else c.affine[:, :C0].contiguous()
         yp, yr = _tab(ystats)
         if self._split_fwd(C0, Cout):
-            nat.call("u3d_conv3d_f32s", dev.index, _stream(dev), _p(src.t0), _p(a0), _p(self._packed_f32s(conv.weight, 0, dev, C0, 0)),
+            nat.call("u3d_conv3d_f32s", dev.index, _stream(dev), _p(src.t0), _p(a0), _p(self.images.get(conv.weight, Kind.F32S_FWD, dev, pair)),
                      _p(c.y), N, D, H, W, C0, Cout, c.relu, yp, None, None, _p(part), None, 0,
                      flops=54.0 * C0 * Cout * N * D * H * W)
         else:
             s0 = VSrc(src.t0).struct(a0)
-            nat.call("u3d_conv3d_ex_reps", dev.index, _stream(dev), ctypes.byref(s0), _p(self._pack_cache[(id(conv.weight), 10)][1]),
+            nat.call("u3d_conv3d_ex_reps", dev.index, _stream(dev), ctypes.byref(s0), _p(self.images.get(conv.weight, Kind.SKIP_FWD, dev, pair)),
                      _p(c.y), N, D, H, W, Cout, c.relu, yp, None, None, _p(part), None, 0, yr,
                      flops=54.0 * C0 * Cout * N * D * H * W)
         return ystats
@@ -333,7 +349,7 @@ class ConvLayers:
         ystats = c.take_stats()
         need = nat.get_lib().u3d_conv3d_bf16_workspace_floats(c.N, c.D, c.H, c.W, c.Ctot, c.Cout)
         kws = _empty(need, dtype=_F32, device=c.dev) if need > 0 else None
-        nat.call("u3d_conv3d_f32s", c.dev.index, _stream(c.dev), _p(c.src.t0), _p(c.affine), _p(self._packed_f32s(c.conv.weight, 0, c.dev)),
+        nat.call("u3d_conv3d_f32s", c.dev.index, _stream(c.dev), _p(c.src.t0), _p(c.affine), _p(self.images.get(c.conv.weight, Kind.F32S_FWD, c.dev)),
                  _p(c.y), c.N, c.D, c.H, c.W, c.Ctot, c.Cout, c.relu, _tab(ystats)[0], None, None, _p(c.residual), _p(kws), need,
                  flops=c.flops)
         return ystats
@@ -345,7 +361,7 @@ class ConvLayers:
         need = nat.get_lib().u3d_conv3d_bf16_workspace_floats(c.N, c.D, c.H, c.W, c.Ctot, c.Cout)  # split-K scratch at the bottom of the U
         kws = _empty(need, dtype=_F32, device=c.dev) if need > 0 else None
         nat.call("u3d_conv3d_bf16_ex" + ("_b16" if c.b16 else ""), c.dev.index, _stream(c.dev), _p(c.src.t0), _p(c.affine),
-                 _p(self._packed_bf16(c.conv.weight, 0, c.dev)), _p(c.y), c.N, c.D, c.H, c.W, c.Ctot, c.Cout, c.relu, _tab(ystats)[0], None, None,
+                 _p(self.images.get(c.conv.weight, Kind.BF16_FWD, c.dev)), _p(c.y), c.N, c.D, c.H, c.W, c.Ctot, c.Cout, c.relu, _tab(ystats)[0], None, None,
                  _p(c.residual), _p(kws), need, flops=c.flops)
         return ystats
 
@@ -353,7 +369,7 @@ class ConvLayers:
         # fp32 MFMA 3x3 implicit GEMM on the D = 1 tensors (virtual concat, fused affine, ReLU and statistics as the 3-D kernels);
         # with a residual (ResidualUNet2D's conv3): out = [relu](conv + residual) in the epilogue (u3d_conv2d_res_reps)
         assert c.D == 1
-        wp = self._packed2d(c.conv.weight, 0, c.dev)
+        wp = self.images.get(c.conv.weight, Kind.FWD2D, c.dev)
         ystats = c.take_stats(self.stat_reps)
         s = c.src.struct(c.affine)
         need = nat.get_lib().u3d_conv2d_workspace_floats(c.N, c.H, c.W, c.Ctot, c.Cout)  # split-K scratch on small grids
@@ -368,7 +384,7 @@ class ConvLayers:
         return ystats
 
     def _fwd_fp32(self, c: "_ConvCall"):
-        wp = self._packed(c.conv.weight, 0, c.dev)
+        wp = self.images.get(c.conv.weight, Kind.FWD, c.dev)
         ystats = c.take_stats(self.stat_reps)  # (replica rows: the persistent kernel's blocks spread their same-address f64 atomics)
         s = c.src.struct(c.affine)
         # bottom-of-the-U shapes split the channel reduction over blocks through a scratch buffer (0 floats otherwise)
@@ -614,6 +630,7 @@ class ConvLayers:
         cx, dev, src, rec, ws, pool = c.cx, c.cx.dev, c.src, c.rec, c.cx.ws, c.cx.pool
         Nn, Dd, Hh, Ww, Cout = c.N, c.D, c.H, c.W, c.Cout
         C0, C1 = rec.sub
+        w, pair = rec.conv_w, tuple(rec.sub)
         dg0 = _empty((Nn, Dd, Hh, Ww, C0), dtype=_F32, device=dev)
         dlow = _empty_like(src.t1)
         split0 = self._split_dgrad(C0, Cout)
@@ -623,13 +640,13 @@ class ConvLayers:
         if split0:
             need = nat.get_lib().u3d_conv3d_bf16_workspace_floats(Nn, Dd, Hh, Ww, Cout, C0)
             kws = cx.ensure_ws(need) if need > 0 else None
-            nat.call("u3d_conv3d_f32s", dev.index, _stream(dev), _p(c.dz), None, _p(self._packed_f32s(rec.conv_w, 1, dev, C0, 0)),
+            nat.call("u3d_conv3d_f32s", dev.index, _stream(dev), _p(c.dz), None, _p(self.images.get(w, Kind.F32S_DGRAD, dev, pair)),
                      _p(dg0), Nn, Dd, Hh, Ww, Cout, C0, 0, None, _p(src.t0), _p(gst0.t), None, _p(kws), need,
                      flops=54.0 * C0 * Cout * Nn * Dd * Hh * Ww)
         else:
             s_dz = VSrc(c.dz).struct()
             s_x0 = VSrc(src.t0).struct()
-            nat.call("u3d_conv3d_ex_reps", dev.index, _stream(dev), ctypes.byref(s_dz), _p(self._packed_sub(rec, 11, dev)), _p(dg0),
+            nat.call("u3d_conv3d_ex_reps", dev.index, _stream(dev), ctypes.byref(s_dz), _p(self.images.get(w, Kind.SKIP_DGRAD, dev, pair)), _p(dg0),
                      Nn, Dd, Hh, Ww, C0, 0, None, ctypes.byref(s_x0), _p(gst0.t), None, _p(ws), ws.numel(), gst0.reps,
                      flops=54.0 * C0 * Cout * Nn * Dd * Hh * Ww)
         plus = src.plus
@@ -638,12 +655,12 @@ class ConvLayers:
             # gradient of the upsampled channels inside the slab's dilation (general kernel on dz masked to the slab), folded into the
             # first low-res cells of the shifted axes together with its part of the GroupNorm-backward sums
             win = (ctypes.c_int * 9)(Dd, Hh, Ww, *plus, *plus)
-            nat.call("u3d_subpixel_conv_dgrad_win", dev.index, _stream(dev), _p(c.dz), _p(self._packed_sub(rec, 13, dev)), _p(src.t1),
+            nat.call("u3d_subpixel_conv_dgrad_win", dev.index, _stream(dev), _p(c.dz), _p(self.images.get(w, Kind.UP_DGRAD, dev, pair)), _p(src.t1),
                      _p(dlow), _p(gst1.t), Nn, src.D1, src.H1, src.W1, C1, Cout, win,
                      flops=128.0 * C1 * Cout * Nn * src.D1 * src.H1 * src.W1)
             dv = _empty((Nn, Dd, Hh, Ww, C1), dtype=_F32, device=dev)
             s_dz2 = VSrc(c.dz).struct()
-            wpd1 = self._packed_sub(rec, 15, dev)
+            wpd1 = self.images.get(w, Kind.SLAB_DGRAD, dev, pair)
             mask = (ctypes.c_int * 3)(*(2 * e for e in plus))
             # (the two slab launches are one tile-time each on less than half of the chip's block slots — a 2-voxel slab in 4 x 8 x 8
             # tiles — but running them side by side on two streams was measured in round 6: each takes twice as long, 192 + 214 us
@@ -657,7 +674,7 @@ class ConvLayers:
                      src.D1, src.H1, src.W1, C1, _p(lz), _p(ly), _p(lx), *plus)
             del dv
         else:
-            nat.call("u3d_subpixel_conv_dgrad_reps", dev.index, _stream(dev), _p(c.dz), _p(self._packed_sub(rec, 13, dev)), _p(src.t1),
+            nat.call("u3d_subpixel_conv_dgrad_reps", dev.index, _stream(dev), _p(c.dz), _p(self.images.get(w, Kind.UP_DGRAD, dev, pair)), _p(src.t1),
                      _p(dlow), _p(gst1.t), Nn, src.D1, src.H1, src.W1, C1, Cout, gst1.reps,
                      flops=128.0 * C1 * Cout * Nn * src.D1 * src.H1 * src.W1)
         return (dg0, dlow), (gst0, gst1)
@@ -668,7 +685,7 @@ class ConvLayers:
         gst = cx.pool.table(c.N, src.C)
         need = nat.get_lib().u3d_conv3d_bf16_workspace_floats(c.N, c.D, c.H, c.W, c.Cout, src.C)
         kws = cx.ensure_ws(need) if need > 0 else None
-        nat.call("u3d_conv3d_f32s", dev.index, _stream(dev), _p(c.dz), None, _p(self._packed_f32s(rec.conv_w, 1, dev)), _p(dg),
+        nat.call("u3d_conv3d_f32s", dev.index, _stream(dev), _p(c.dz), None, _p(self.images.get(rec.conv_w, Kind.F32S_DGRAD, dev)), _p(dg),
                  c.N, c.D, c.H, c.W, c.Cout, src.C, 0, None, _p(src.t0), _p(gst.t), None, _p(kws), need, flops=c.flops)
         return dg, (gst, None)
 
@@ -679,7 +696,7 @@ class ConvLayers:
         need = nat.get_lib().u3d_conv3d_bf16_workspace_floats(c.N, c.D, c.H, c.W, c.Cout, src.C)
         kws = cx.ensure_ws(need) if need > 0 else None
         nat.call("u3d_conv3d_bf16_ex" + ("_b16" if c.b16 else ""), dev.index, _stream(dev), _p(c.dz), None,
-                 _p(self._packed_bf16(rec.conv_w, 1, dev)), _p(dg), c.N, c.D, c.H, c.W, c.Cout, src.C, 0, None, _p(src.t0), _p(gst.t),
+                 _p(self.images.get(rec.conv_w, Kind.BF16_DGRAD, dev)), _p(dg), c.N, c.D, c.H, c.W, c.Cout, src.C, 0, None, _p(src.t0), _p(gst.t),
                  None, _p(kws), need, flops=c.flops)
         return dg, (gst, None)
 
@@ -692,7 +709,7 @@ class ConvLayers:
 
     def _dgrad_conv2d(self, c: "_BwdCall"):
         cx, dev, src, rec, ws = c.cx, c.cx.dev, c.src, c.rec, c.cx.ws
-        wpd = self._packed2d(rec.conv_w, 1, dev)
+        wpd = self.images.get(rec.conv_w, Kind.DGRAD2D, dev)
         dg = _empty((c.N, c.D, c.H, c.W, src.C), dtype=_F32, device=dev)
         gst = cx.pool.table(c.N, src.C, c.greps)
         s_dz = VSrc(c.dz).struct()
@@ -703,7 +720,7 @@ class ConvLayers:
 
     def _dgrad_fp32(self, c: "_BwdCall"):
         cx, dev, src, rec, ws = c.cx, c.cx.dev, c.src, c.rec, c.cx.ws
-        wpd = self._packed(rec.conv_w, 1, dev)
+        wpd = self.images.get(rec.conv_w, Kind.DGRAD, dev)
         dg = _empty((c.N, c.D, c.H, c.W, src.C), dtype=_F32, device=dev)
         gst = cx.pool.table(c.N, src.C, c.greps)
         s_dz = VSrc(c.dz).struct()

@@ -56,7 +56,7 @@ class GraphStep:
                 # one eager step first: every lazily built constant (index maps, identity tables, the pack descriptor table, the
                 # library's function attributes) must exist before capture — host-to-device copies are illegal inside it
                 self.static_x.copy_(x)
-                engine.begin_forward(True)
+                engine.images.begin_forward(True)
                 logits, probs, tape = engine.forward(self.static_x, True)
                 engine.backward(tape, torch.zeros_like(logits), need_dx)
                 del logits, probs, tape
@@ -67,7 +67,7 @@ class GraphStep:
         self.pool = torch.cuda.graph_pool_handle()
         self.g_fwd = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.g_fwd, pool=self.pool, capture_error_mode="thread_local"):
-            engine.begin_forward(True)
+            engine.images.begin_forward(True)
             self.logits, self.probs, self.tape = engine.forward(self.static_x, True)
         self.static_dl = torch.zeros_like(self.logits)
         # Data parallelism (parallel.GradSync attached): RCCL launches cannot live inside a captured graph that is replayed with
@@ -95,9 +95,9 @@ class GraphStep:
         finally:
             engine.grad_sync = self.sync
         # Strong references to every PRE-CAPTURE device buffer the graphs dereference: the pack descriptor
-        # tables' only other owner is a one-entry dict that the next eager forward with a different stale set clears
-        # (`tab.clear()` in _repack_all / _repack_bf16_all: validation between training steps does exactly that), the packed
-        # images can be replaced in `_pack_cache`, constants can be rebuilt — the caching allocator (or torch.cuda.empty_cache())
+        # tables' only other owner is a one-entry memo that the next eager forward with a different stale set replaces
+        # (WeightImages._plan: validation between training steps does exactly that), the packed
+        # images can be replaced in the cache, constants can be rebuilt — the caching allocator (or torch.cuda.empty_cache())
         # would then hand the blocks to someone else while every later replay still reads / writes them.
         self._pins = engine.graph_pins()
 

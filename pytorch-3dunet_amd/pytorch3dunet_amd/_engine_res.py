@@ -18,6 +18,7 @@ from ._native import U3DSrc
 
 from ._engine_base import *  # noqa: F401,F403  (explicit __all__: helpers, records, activation codes)
 from ._engine_unet import UNet3DEngine
+from ._engine_weights import Kind
 
 _CKPT_RERUN_LAST = os.environ.get("U3D_CKPT_RERUN_LAST", "0") == "1"  # A/B: recomputation re-runs a block's last convolution too (rounds 4-5)
 
@@ -82,6 +83,9 @@ class ResUNetEngine(UNet3DEngine):
 
     def _virtual_weights(self):
         return set()  # summation joining: every 3x3x3 conv reads one real tensor
+
+    def _t8_weights(self):
+        return [ct.weight for (ct, _), concat in zip(self.dec, self.dec_concat) if isinstance(ct, torch.nn.ConvTranspose3d) and not concat]
 
     def _build_layer_table(self, model):
         self.enc = [(e.pooling is not None, e.basic_module) for e in model.encoders]
@@ -222,7 +226,7 @@ class ResUNetEngine(UNet3DEngine):
             tape.dims = (N, Cin, D, H, W)
             tape.blocks = []
             tape.ups = []
-        self._repack_all(dev, (0, 1) if save else (0,))
+        self.images.repack(dev, save)
         widths = [bm.conv2.conv.in_channels for _, bm in self.enc]
         pool = _StatPool(dev, 16 * N * sum(widths) * 2 + 64)
 
@@ -271,10 +275,10 @@ class ResUNetEngine(UNet3DEngine):
                 need = nat.get_lib().u3d_convtr3d_fwd_t8_workspace_floats(Nl, D1, H1, W1, Cl, Cs) if self.act_bf16 else 0
                 if need > 0:  # small grid, many channels: the flat tile with a split channel reduction (csrc/u3d_bf16.hip)
                     kws = _empty(need, dtype=_F32, device=dev)
-                    nat.call("u3d_convtr3d_fwd_t8_b16_ex", dev.index, _stream(dev), _p(cur), _p(self._packed_convtr_t8(ct.weight, 0, dev)),
+                    nat.call("u3d_convtr3d_fwd_t8_b16_ex", dev.index, _stream(dev), _p(cur), _p(self.images.get(ct.weight, Kind.T8_FWD, dev)),
                              _p(t), Nl, D1, H1, W1, Cl, Cs, _p(kws), need, flops=2.0 * 27 * Cl * Cs * Nl * D1 * H1 * W1)
                 else:
-                    nat.call("u3d_convtr3d_fwd_t8" + sfx, dev.index, _stream(dev), _p(cur), _p(self._packed_convtr_t8(ct.weight, 0, dev)),
+                    nat.call("u3d_convtr3d_fwd_t8" + sfx, dev.index, _stream(dev), _p(cur), _p(self.images.get(ct.weight, Kind.T8_FWD, dev)),
                              _p(t), Nl, D1, H1, W1, Cl, Cs, flops=2.0 * 27 * Cl * Cs * Nl * D1 * H1 * W1)
                 nat.call("u3d_nearest_add_fwd_t8" + sfx, dev.index, _stream(dev), _p(sk), _p(t), _p(mz), _p(my), _p(mx), Nl, Ds, Hs,
                          Ws, Dt, Ht, Wt, Cs, _p(joined), _p(j_st.t))
@@ -285,15 +289,15 @@ class ResUNetEngine(UNet3DEngine):
                 continue
             t = _empty((Nl, Dt, Ht, Wt, Ct), dtype=_F32, device=dev)
             if self.is2d:  # ConvTranspose2d: four parity-class gather GEMMs (D1 = Dt = 1)
-                nat.call("u3d_convtr2d_fwd", dev.index, _stream(dev), _p(cur), _p(self._packed_convtr2d(ct.weight, 0, dev)), _p(t), Nl,
+                nat.call("u3d_convtr2d_fwd", dev.index, _stream(dev), _p(cur), _p(self.images.get(ct.weight, Kind.CONVTR2D_FWD, dev)), _p(t), Nl,
                          H1, W1, Cl, Ct, flops=4.5 * Cl * Ct * Nl * Ht * Wt)
             elif self.subpixel and Cl % 4 == 0 and Ct % 4 == 0:
                 # 8 output parity classes accumulated from one staged input halo tile (csrc/u3d_subpix.hip, scheme Deconv3s2)
-                nat.call("u3d_convtr3d_fwd_subpixel", dev.index, _stream(dev), _p(cur), _p(self._packed_convtr(ct.weight, 2, dev)),
+                nat.call("u3d_convtr3d_fwd_subpixel", dev.index, _stream(dev), _p(cur), _p(self.images.get(ct.weight, Kind.CONVTR_SUBPIXEL, dev)),
                          _p(t), Nl, D1, H1, W1, Cl, Ct, flops=2.0 * 27 * Cl * Ct * Nl * D1 * H1 * W1)
             else:
                 nat.call("u3d_convtr3d_fwd", dev.index, _stream(dev), _p(cur), _p(ct.weight.detach()), _p(t), Nl, D1, H1, W1, Cl,
-                         Ct, _p(self._packed_convtr(ct.weight, 0, dev)), flops=2.0 * 27 * Cl * Ct * Nl * D1 * H1 * W1)
+                         Ct, _p(self.images.get(ct.weight, Kind.CONVTR_FWD, dev)), flops=2.0 * 27 * Cl * Ct * Nl * D1 * H1 * W1)
             if concat:
                 nat.call("u3d_nearest_cat_fwd", dev.index, _stream(dev), _p(sk), _p(t), _p(mz), _p(my), _p(mx), Nl, Ds, Hs, Ws, Dt, Ht,
                          Wt, Cs, Ct, _p(joined))
@@ -466,7 +470,7 @@ class ResUNetEngine(UNet3DEngine):
                          _p(gview(self._pindex[id(up.weight)])), Nl, D1, H1, W1, Cl, Cs, _p(wsb), wsb.numel(),
                          flops=2.0 * 27 * Cl * Cs * Nl * D1 * H1 * W1)
                 dxl = _empty_like(xl)
-                nat.call("u3d_convtr3d_dgrad_t8" + sfx + "_ex", dev.index, _stream(dev), _p(dt8), _p(self._packed_convtr_t8(up.weight, 1, dev)),
+                nat.call("u3d_convtr3d_dgrad_t8" + sfx + "_ex", dev.index, _stream(dev), _p(dt8), _p(self.images.get(up.weight, Kind.T8_DGRAD, dev)),
                          _p(xl) if mk else None, _p(dxl), Nl, D1, H1, W1, Cl, Cs, _p(wsb), wsb.numel(),
                          flops=2.0 * 27 * Cl * Cs * Nl * D1 * H1 * W1)
                 del dt8
@@ -480,14 +484,14 @@ class ResUNetEngine(UNet3DEngine):
                 nat.call("u3d_convtr2d_wgrad", dev.index, _stream(dev), _p(xl), _p(dt), _p(gview(self._pindex[id(up.weight)])), Nl, H1,
                          W1, Cl, Cs, 0, _p(acc), acc.numel(), flops=4.5 * Cl * Cs * Nl * Ht * Wt)
                 dxl = _empty_like(xl)
-                nat.call("u3d_convtr2d_dgrad", dev.index, _stream(dev), _p(dt), _p(self._packed_convtr2d(up.weight, 1, dev)),
+                nat.call("u3d_convtr2d_dgrad", dev.index, _stream(dev), _p(dt), _p(self.images.get(up.weight, Kind.CONVTR2D_DGRAD, dev)),
                          _p(xl) if mk else None, _p(dxl), Nl, H1, W1, Cl, Cs, flops=4.5 * Cl * Cs * Nl * Ht * Wt)
                 del dt
                 dz = dxl
                 continue
             dxl = _empty_like(xl)
             nat.call("u3d_convtr3d_bwd", dev.index, _stream(dev), _p(dt), _p(xl), _p(up.weight.detach()), Nl, D1, H1, W1, Cl, Cs,
-                     mk, _p(dxl), _p(acc), _p(self._packed_convtr(up.weight, 1, dev)), flops=4.0 * 27 * Cl * Cs * Nl * D1 * H1 * W1)
+                     mk, _p(dxl), _p(acc), _p(self.images.get(up.weight, Kind.CONVTR_DGRAD, dev)), flops=4.0 * 27 * Cl * Cs * Nl * D1 * H1 * W1)
             nat.call("u3d_cvt_f64_f32", dev.index, _stream(dev), _p(acc), _p(gview(self._pindex[id(up.weight)])),
                      up.weight.numel())
             del dt

@@ -18,18 +18,17 @@ from ._native import U3DSrc
 
 from ._engine_base import *  # noqa: F401,F403  (explicit __all__: helpers, records, activation codes)
 from ._engine_conv import ConvLayers
-from ._engine_weights import WeightImages
+from ._engine_weights import Kind, WeightImages
 
 
 
-class UNet3DEngine(WeightImages, ConvLayers):
+class UNet3DEngine(ConvLayers):
     """Executes the forward / backward of a UNet3D-family model natively.  Built once per model by
     `pytorch3dunet_amd.unet3d.model.AbstractUNet`; holds no tensors between calls except caches keyed on
     parameter versions (packed weights) and index maps."""
 
     def __init__(self, model):
         self.model = model
-        self._pack_cache: dict = {}
         self.grad_sync = None  # set by parallel.GradSync (RCCL all-reduce overlapped with the encoder backward)
         self.debug = None  # dict -> backward stores clones of per-layer dz / dg (tools/gpu_layer_diag.py)
         self.fused_stats = True
@@ -63,10 +62,9 @@ class UNet3DEngine(WeightImages, ConvLayers):
         # bf16 ACTIVATION STORAGE (`activation_dtype: bf16`; ResUNetEngine decides whether the model qualifies): every NDHWC
         # activation / gradient tensor between kernels is bf16, through the `_b16` entry points of include/u3d.h
         self.act_bf16 = False
-        # id(conv weight) -> (C0, C1) of every decoder first conv (static); WHICH of them take the sub-pixel path depends on
-        # the input size and is per-call state (`sub` argument / ConvRec.sub), never stored on the engine: forwards at
-        # different sizes, other threads and nn.DataParallel replicas must not see each other's choice
-        self._sub_pairs: dict = {}
+        # WHICH decoder first convs take the sub-pixel path depends on the input size and is per-call state (`sub` argument /
+        # ConvRec.sub, handed to `images` with every lookup), never stored on the engine: forwards at different sizes, other threads
+        # and nn.DataParallel replicas must not see each other's choice
         self._lock = threading.RLock()  # host-side enqueue of one forward / backward at a time per engine
         # opt-in static-shape step runner (`hip_graph: true` in the YAML's model section or U3D_GRAPH=1): the ~70 forward and ~110
         # backward launches of a TRAINING step are captured once per input shape in two hipGraphs and replayed (GraphStep below)
@@ -74,7 +72,6 @@ class UNet3DEngine(WeightImages, ConvLayers):
         self._graph_steps: dict = {}
         self._graph_off_reason = None
         self._placed = None  # check_placement's memo
-        self._salt = 0  # advanced by every training forward: see _ver
         self._const: dict = {}
         # the model-wide layer order (every SingleConv of a DoubleConv net shares it): non-linearity of the layer outputs
         spec = parse_order(getattr(model, "layer_order", "gcr")) or (False, ACT_RELU, 0.0)
@@ -88,6 +85,7 @@ class UNet3DEngine(WeightImages, ConvLayers):
         self._pindex = _PIndex({id(p): i for i, p in enumerate(self.params)})
         self._build_layer_table(model)
         self._virtual_w = self._virtual_weights()
+        self.images = self._weight_images()  # the packed forms of the conv weights that the kernels read (_engine_weights.py)
         # split point of the flat gradient buffer: encoders first (module order), then decoders + head
         n_enc = sum(p.numel() for p in module_params(model.encoders))
         self.n_enc_params = n_enc
@@ -120,6 +118,28 @@ class UNet3DEngine(WeightImages, ConvLayers):
             cx.join()  # (a side-stream weight gradient of this level may still be writing its slice)
             self.grad_sync.launch(flat[lo:pending_hi])
         return lo
+
+    def _weight_images(self) -> WeightImages:
+        """the image cache, told which weights' images ride in which of a forward's batch pack launches"""
+        ws = [mod.weight for mod in self.model.modules()  # every 3x3x3 (UNet2D under native_2d: 3x3) weight the MFMA kernels read
+              if (isinstance(mod, torch.nn.Conv3d) and mod.kernel_size == (3, 3, 3))
+              or (isinstance(mod, torch.nn.Conv2d) and mod.kernel_size == (3, 3))]
+        if self.is2d:
+            return WeightImages(each=ws)
+        bf16 = {id(w) for w in ws if self._bf16_layer(w.shape[1], w.shape[0])} - self._virtual_w
+        return WeightImages(
+            # (not the first layer: its dedicated kernels read the reference layout)
+            f32=[w for w in ws if id(w) not in bf16 and not (self.small_cin and w.shape[1] <= 4 and w.shape[0] <= 32)],
+            bf16=[w for w in ws if id(w) in bf16], t8=self._t8_weights() if self.bf16 else ())
+
+    def _t8_weights(self) -> list:
+        """ConvTranspose3d weights whose forward / data gradient may run in space-to-depth form (`_convtr_t8`)"""
+        return []
+
+    def graph_pins(self) -> list:
+        """every lazily built device buffer a captured step may dereference (GraphStep keeps this list alive): the weight images with
+        their pack descriptor tables, the constant tables"""
+        return [self.images.pins(), list(self._const.values())]
 
     def _virtual_weights(self):
         """ids of the conv weights whose input is a virtual concat (decoder first convs) and which therefore run on the fp32 /
@@ -172,7 +192,7 @@ class UNet3DEngine(WeightImages, ConvLayers):
             tape.x0 = x0
             tape.dims = (N, Cin, D, H, W)
         sub = self._subpixel_layers((D, H, W))
-        self._repack_all(dev, (0, 1) if save else (0,), sub)
+        self.images.repack(dev, save, sub, sub.plus)
         # stat doubles: every conv output + every GN input computed standalone; generous upper bound
         tot = 0
         R = self.stat_reps
@@ -231,11 +251,11 @@ class UNet3DEngine(WeightImages, ConvLayers):
                 Cs = ct.out_channels
                 t = _empty((Nl, 2 * D1 - 1, 2 * H1 - 1, 2 * W1 - 1, Cs), dtype=_F32, device=dev)
                 if self.subpixel and Cl % 4 == 0 and Cs % 4 == 0:
-                    nat.call("u3d_convtr3d_fwd_subpixel", dev.index, _stream(dev), _p(cur), _p(self._packed_convtr(ct.weight, 2, dev)),
+                    nat.call("u3d_convtr3d_fwd_subpixel", dev.index, _stream(dev), _p(cur), _p(self.images.get(ct.weight, Kind.CONVTR_SUBPIXEL, dev)),
                              _p(t), Nl, D1, H1, W1, Cl, Cs, flops=2.0 * 27 * Cl * Cs * Nl * D1 * H1 * W1)
                 else:
                     nat.call("u3d_convtr3d_fwd", dev.index, _stream(dev), _p(cur), _p(ct.weight.detach()), _p(t), Nl, D1, H1, W1, Cl,
-                             Cs, _p(self._packed_convtr(ct.weight, 0, dev)), flops=2.0 * 27 * Cl * Cs * Nl * D1 * H1 * W1)
+                             Cs, _p(self.images.get(ct.weight, Kind.CONVTR_FWD, dev)), flops=2.0 * 27 * Cl * Cs * Nl * D1 * H1 * W1)
                 if tape is not None:
                     tape.ups.append(UpRec(cur, ct.weight, None, tuple(t.shape[1:4])))
                 cur, cur_st = t, None
@@ -390,7 +410,7 @@ class UNet3DEngine(WeightImages, ConvLayers):
                 acc = pool.take(up.weight.numel())
                 dxl = _empty_like(xl)
                 nat.call("u3d_convtr3d_bwd", dev.index, _stream(dev), _p(dzl), _p(xl), _p(up.weight.detach()), Nl, D1, H1, W1, Cl, Cs,
-                         mk, _p(dxl), _p(acc), _p(self._packed_convtr(up.weight, 1, dev)), flops=4.0 * 27 * Cl * Cs * Nl * D1 * H1 * W1)
+                         mk, _p(dxl), _p(acc), _p(self.images.get(up.weight, Kind.CONVTR_DGRAD, dev)), flops=4.0 * 27 * Cl * Cs * Nl * D1 * H1 * W1)
                 nat.call("u3d_cvt_f64_f32", dev.index, _stream(dev), _p(acc), _p(gview(self._pindex[id(up.weight)])),
                          up.weight.numel())
                 self._unact(dev, dxl, xl)

@@ -53,7 +53,7 @@ class _UNet3DFunction(torch.autograd.Function):
         # backward as None, not as a zero tensor: materialised, the unused `probs` cost a fill + four elementwise launches per step
         ctx.set_materialize_grads(False)
         with engine._lock:
-            engine.begin_forward(save)
+            engine.images.begin_forward(save)
             logits, probs, tape = engine.forward(x, save)
         ctx.engine = engine
         ctx.has_probs = probs is not None

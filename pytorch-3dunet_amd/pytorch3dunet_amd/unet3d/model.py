@@ -232,7 +232,7 @@ class AbstractUNet(nn.Module):
         eng = self.__dict__.get("_engine")
         object.__setattr__(self, "_engine_stale", True)  # also re-walk the parameter identities on the next forward
         if eng is not None:
-            eng._salt += 1
+            eng.images.invalidate()
 
     def forward(self, x, return_logits=False):
         """(N,C,D,H,W) -> probabilities, or (probabilities, logits) when return_logits (model.py:103-121)."""
