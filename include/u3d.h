@@ -924,6 +924,43 @@ int u3d_convtr2d_dgrad(int device, u3d_stream_t stream, const float* dt, const f
 int u3d_convtr2d_wgrad(int device, u3d_stream_t stream, const float* x, const float* dt, float* dw, int N, int H1, int W1, int Cin,
                        int Cout, int accumulate, double* workspace, size_t workspace_doubles);
 
+/* ---- (Added, U3D_VERSION unchanged.)  bf16-operand 3x3 Conv2d of UNet2D (`native_2d_bf16: true`; csrc/u3d_conv2d_bf16.hip) ------
+ * The bf16 twins of u3d_pack_weights2d / u3d_conv2d_ex_reps / u3d_conv2d_wgrad on v_mfma_f32_32x32x16_bf16: operands rounded to bf16
+ * (round-to-nearest-even), products accumulated in FP32; activations, outputs, statistics and dw stay fp32 tensors in HBM (NHWC, the
+ * D = 1 layout).  Rounding points: the weights when the image is packed from the fp32 master copy; the activations ONCE while they are
+ * staged into LDS, after the fp32 affine fmaf(a, x, b) (padding stays exactly 0, it applies after the affine); in the weight gradient
+ * both g = a*x + b (zero padded) and dz.  Single-tensor sources only (no virtual concat), 16-byte aligned pointers.
+ * Envelope (the 3-D rule): the contraction channels % 16 == 0 and the produced channels % 32 == 0 —
+ *   u3d_conv2d_bf16_supported(Cin, Cout)        Cin % 16 == 0 and Cout % 32 == 0 (a data gradient asks with the roles swapped)
+ *   u3d_conv2d_wgrad_bf16_supported(Cin, Cout)  Cin % 32 == 0 and Cout % 32 == 0 (both are produced; the contraction runs over pixels)
+ * Outside it every entry point below returns U3D_EINVAL (u3d_last_error) without launching anything.
+ *   u3d_pack_weights2d_bf16  (Cout, Cin, 3, 3) fp32 -> image [Cin / 16 chunk][9 taps][n-tile][64 lanes][8] bf16 of B[k][n]; mode 0 =
+ *              forward (B[k = ci][n = co] = w[co][ci][tap]), mode 1 = data gradient (B[k = co][n = ci] = w[co][ci][8 - tap]);
+ *              u3d_packed_weight2d_bf16_elems() 2-byte elements (0 outside the envelope of the mode)
+ *   u3d_conv2d_bf16          out (N,H,W,Cout) fp32 = [relu](conv2d(a*x + b)); called with the mode-1 image on dz (Cin = the layer's
+ *              Cout, Cout = its Cin) it is the data gradient.  M = 16 x 16-pixel tile, N = 32 / 64 output channels per block, K = 9 * Cin
+ *              in steps of 16; any H, W >= 1.  affine optional (N,Cin,2); out_stats optional double[stat_reps][N][Cout][2] += (sum, sum
+ *              of squares) of the written values; gx / gstats optional: gx (N,H,W,Cout) fp32 = the layer's forward input, gstats
+ *              double[stat_reps][N][Cout][2] += (sum dg, sum dg * gx).  workspace optional, u3d_conv2d_bf16_workspace_floats() floats
+ *              (0 for shapes that never split): grids with fewer blocks than CUs split the channel reduction and add the partial sums
+ *              in a fixed order (statistics then go to replica row 0).
+ *   u3d_conv2d_wgrad_bf16    dw (Cout,Cin,3,3) fp32 written in the reference layout: dw[co][ci][ky][kx] = sum_{n,y,x} bf16(dz[n,y,x,co])
+ *              * bf16(g[n, y+ky-1, x+kx-1, ci]).  Partial sums over pixel ranges go through the workspace
+ *              (u3d_wgrad2d_bf16_workspace_floats() floats, 0: none needed) and are added in a fixed order: the same inputs give a
+ *              bitwise-identical dw.
+ * Zeroing the statistics tables is the caller's job; the library never allocates and never synchronises. */
+int u3d_conv2d_bf16_supported(int Cin, int Cout);
+int u3d_conv2d_wgrad_bf16_supported(int Cin, int Cout);
+long long u3d_packed_weight2d_bf16_elems(int Cin, int Cout, int mode);
+int u3d_pack_weights2d_bf16(int device, u3d_stream_t stream, const float* w, int Cout, int Cin, int mode, void* packed);
+long long u3d_conv2d_bf16_workspace_floats(int N, int H, int W, int Cin, int Cout);
+int u3d_conv2d_bf16(int device, u3d_stream_t stream, const float* x, const float* affine, const void* packed_w, float* out, int N,
+                    int H, int W, int Cin, int Cout, int relu, double* out_stats, const float* gx, double* gstats, float* workspace,
+                    long long workspace_floats, int stat_reps);
+long long u3d_wgrad2d_bf16_workspace_floats(int N, int H, int W, int Cin, int Cout);
+int u3d_conv2d_wgrad_bf16(int device, u3d_stream_t stream, const float* x, const float* affine, const float* dz, float* dw, int N,
+                          int H, int W, int Cin, int Cout, float* workspace, long long workspace_floats);
+
 /* ---- layout: NCDHW <-> NDHWC for multi-channel model inputs ------------------------------------ */
 int u3d_ncdhw_to_ndhwc(int device, u3d_stream_t stream, const float* src, float* dst, int N, int C, int64_t V);
 int u3d_ndhwc_to_ncdhw(int device, u3d_stream_t stream, const float* src, float* dst, int N, int C, int64_t V);

@@ -280,12 +280,15 @@ class ConvLayers:
         "f32s": "_fwd_f32s",          # u3d_bf16.hip: compute_dtype fp32_split
         "bf16": "_fwd_bf16",          # u3d_bf16.hip: compute_dtype bf16 (fp32 or bf16 activation storage)
         "fp32": "_fwd_fp32",          # u3d_conv.hip: fp32 MFMA (persistent / generic / split-K chosen by the library)
-        "conv2d": "_fwd_conv2d",      # u3d_conv2d.hip: 3x3 convolutions of a 2-D net (native_2d), every layer and only those
+        "conv2d": "_fwd_conv2d",      # u3d_conv2d.hip: 3x3 convolutions of a 2-D net (native_2d), every layer and only those ...
+        "conv2d_bf16": "_fwd_conv2d_bf16",  # u3d_conv2d_bf16.hip: ... except, under native_2d_bf16, the single-source layers that fit
     }
 
     def _fwd_family(self, c: "_ConvCall", residual) -> str:
         if getattr(self, "is2d", False):
-            return "conv2d"
+            # (a decoder's first conv reaches here on its materialised concat when it fits: `_cat_bf16`; forward and data gradient
+            # are covered together by the one channel rule)
+            return "conv2d_bf16" if (c.src.t1 is None and residual is None and self._bf16_layer(c.Ctot, c.Cout)) else "conv2d"
         if self.small_cin and c.src.t1 is None and c.Ctot <= 4 and c.Cout <= 32 and residual is None and not c.b16:
             return "small"
         if c.src.t1 is not None and residual is None and id(c.conv.weight) in c.sub:
@@ -381,6 +384,19 @@ class ConvLayers:
         else:
             nat.call("u3d_conv2d_ex_reps", c.dev.index, _stream(c.dev), ctypes.byref(s), _p(wp), _p(c.y), c.N, c.H, c.W, c.Cout, c.relu,
                      yp, None, None, _p(kws), need, yr, flops=18.0 * c.Ctot * c.Cout * c.N * c.H * c.W)
+        return ystats
+
+    def _fwd_conv2d_bf16(self, c: "_ConvCall"):
+        # bf16 MFMA operands, fp32 accumulation / epilogue on the D = 1 tensors (csrc/u3d_conv2d_bf16.hip): fused affine (rounded once
+        # after it), ReLU and statistics as the fp32 kernel
+        assert c.D == 1 and c.src.t1 is None and c.residual is None
+        wp = self.images.get(c.conv.weight, Kind.BF16_FWD2D, c.dev)
+        ystats = c.take_stats(self.stat_reps)
+        need = nat.get_lib().u3d_conv2d_bf16_workspace_floats(c.N, c.H, c.W, c.Ctot, c.Cout)  # split-K scratch on small grids
+        kws = _empty(need, dtype=_F32, device=c.dev) if need > 0 else None
+        yp, yr = _tab(ystats)
+        nat.call("u3d_conv2d_bf16", c.dev.index, _stream(c.dev), _p(c.src.t0), _p(c.affine), _p(wp), _p(c.y), c.N, c.H, c.W, c.Ctot,
+                 c.Cout, c.relu, yp, None, None, _p(kws), need, yr, flops=18.0 * c.Ctot * c.Cout * c.N * c.H * c.W)
         return ystats
 
     def _fwd_fp32(self, c: "_ConvCall"):
@@ -524,6 +540,7 @@ class ConvLayers:
         "fp32_side": "_wgrad_fp32_side",  # u3d_conv.hip on the side stream (U3D_SIDE_VOXELS, off by default)
         "fp32": "_wgrad_fp32",          # u3d_conv.hip
         "conv2d": "_wgrad_conv2d",      # u3d_conv2d.hip (2-D nets)
+        "conv2d_bf16": "_wgrad_conv2d_bf16",  # u3d_conv2d_bf16.hip (2-D nets in bf16: every layer the bf16 forward covers)
     }
     _DGRAD_KERNELS = {
         "subpixel": "_dgrad_subpixel",  # skip half at full resolution + upsampled half directly at LOW resolution
@@ -531,11 +548,12 @@ class ConvLayers:
         "bf16": "_dgrad_bf16",
         "fp32": "_dgrad_fp32",
         "conv2d": "_dgrad_conv2d",  # u3d_conv2d.hip (2-D nets)
+        "conv2d_bf16": "_dgrad_conv2d_bf16",  # u3d_conv2d_bf16.hip
     }
 
     def _wgrad_family(self, c: "_BwdCall") -> str:
         if getattr(self, "is2d", False):
-            return "conv2d"
+            return "conv2d_bf16" if c.bf16 else "conv2d"
         if c.bf16 and c.Cout % 32 == 0:  # (Cout % 64 == 32 since round 4: 64-column blocks with a zero upper half)
             return "bf16"
         if c.rec.sub is not None:
@@ -546,7 +564,7 @@ class ConvLayers:
 
     def _dgrad_family(self, c: "_BwdCall") -> str:
         if getattr(self, "is2d", False):
-            return "conv2d"
+            return "conv2d_bf16" if c.bf16 else "conv2d"
         if c.rec.sub is not None:
             return "subpixel"
         if c.src.t1 is None and not c.rec.small and self._split_dgrad(c.src.C, c.Cout):
@@ -718,6 +736,26 @@ class ConvLayers:
                  ctypes.byref(s_x), _p(gst.t), _p(ws), ws.numel(), gst.reps, flops=18.0 * src.C * c.Cout * c.N * c.H * c.W)
         return dg, (gst, None)
 
+    def _wgrad_conv2d_bf16(self, c: "_BwdCall"):
+        # both operands rounded to bf16 while staged (g = a*x + b and dz), fp32 sums added in a fixed order; takes no GroupNorm-backward
+        # job, like the fp32 2-D kernel
+        cx, dev, src, rec = c.cx, c.cx.dev, c.src, c.rec
+        need = nat.get_lib().u3d_wgrad2d_bf16_workspace_floats(c.N, c.H, c.W, src.C, c.Cout)
+        ws = cx.ensure_ws(need)
+        nat.call("u3d_conv2d_wgrad_bf16", dev.index, _stream(dev), _p(src.t0), _p(rec.affine), _p(c.dz), _p(cx.gview(rec.idx_w)), c.N,
+                 c.H, c.W, src.C, c.Cout, _p(ws), ws.numel(), flops=18.0 * src.C * c.Cout * c.N * c.H * c.W)
+
+    def _dgrad_conv2d_bf16(self, c: "_BwdCall"):
+        cx, dev, src, rec = c.cx, c.cx.dev, c.src, c.rec
+        wpd = self.images.get(rec.conv_w, Kind.BF16_DGRAD2D, dev)
+        dg = _empty((c.N, c.D, c.H, c.W, src.C), dtype=_F32, device=dev)
+        gst = cx.pool.table(c.N, src.C, c.greps)
+        need = nat.get_lib().u3d_conv2d_bf16_workspace_floats(c.N, c.H, c.W, c.Cout, src.C)  # roles swapped
+        kws = cx.ensure_ws(need) if need > 0 else None
+        nat.call("u3d_conv2d_bf16", dev.index, _stream(dev), _p(c.dz), None, _p(wpd), _p(dg), c.N, c.H, c.W, c.Cout, src.C, 0, None,
+                 _p(src.t0), _p(gst.t), _p(kws), need, gst.reps, flops=18.0 * src.C * c.Cout * c.N * c.H * c.W)
+        return dg, (gst, None)
+
     def _dgrad_fp32(self, c: "_BwdCall"):
         cx, dev, src, rec, ws = c.cx, c.cx.dev, c.src, c.rec, c.cx.ws
         wpd = self.images.get(rec.conv_w, Kind.DGRAD, dev)
@@ -824,6 +862,8 @@ class ConvLayers:
         """scratch floats one 3x3x3 layer's backward needs from the shared buffer, for the kernels it will actually run"""
         lib = nat.get_lib()
         if getattr(self, "is2d", False):  # weight gradient + the data gradient's split-K scratch (roles swapped)
+            if not virtual and self._bf16_layer(Cin, Cout):  # (the bf16 kernels' plans, csrc/u3d_conv2d_bf16.hip)
+                return max(lib.u3d_wgrad2d_bf16_workspace_floats(N, H, W, Cin, Cout), lib.u3d_conv2d_bf16_workspace_floats(N, H, W, Cout, Cin))
             return max(lib.u3d_wgrad2d_workspace_floats(N, H, W, Cin, Cout), lib.u3d_conv2d_workspace_floats(N, H, W, Cout, Cin))
         if small:
             return lib.u3d_small_cin_bwd_workspace_floats(N, D, H, W, Cin, Cout)

@@ -473,6 +473,17 @@ _PROTOS = {
                                    c_size_t]),
     "u3d_wgrad2d_workspace_floats": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "u3d_conv2d_wgrad": (c_int, [c_int, c_void_p, POINTER(U3DSrc), c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t]),
+    # bf16-operand 2-D convolutions (csrc/u3d_conv2d_bf16.hip)
+    "u3d_conv2d_bf16_supported": (c_int, [c_int, c_int]),
+    "u3d_conv2d_wgrad_bf16_supported": (c_int, [c_int, c_int]),
+    "u3d_packed_weight2d_bf16_elems": (c_int64, [c_int, c_int, c_int]),
+    "u3d_pack_weights2d_bf16": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "u3d_conv2d_bf16_workspace_floats": (c_int64, [c_int, c_int, c_int, c_int, c_int]),
+    "u3d_conv2d_bf16": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
+                                c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int]),
+    "u3d_wgrad2d_bf16_workspace_floats": (c_int64, [c_int, c_int, c_int, c_int, c_int]),
+    "u3d_conv2d_wgrad_bf16": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                      c_void_p, c_int64]),
     "u3d_maxpool2d_fwd": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "u3d_maxpool2d_bwd_merge": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                                         c_int, c_int, c_void_p]),

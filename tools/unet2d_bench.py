@@ -1,6 +1,7 @@
 """Training-step throughput of the reference's shipped 2-D configurations: forward + BCEDice + backward + FusedAdam, with
 `native_2d: true` (csrc/u3d_conv2d.hip through the DoubleConv executor) and with the default path (the module tree on stock
-PyTorch-ROCm operators, after its one-time warning) in the same process, alternating the two.
+PyTorch-ROCm operators, after its one-time warning) in the same process, alternating the two.  --bf16 adds the same step with
+`native_2d_bf16: true` (csrc/u3d_conv2d_bf16.hip for the layers that fit) as a third path in the same alternation (UNet2D configs).
 
   confocal  resources/2DUnet_confocal_boundary/train_config.yml: 32 x 1 x 515 x 512, gcr, f_maps 32, 4 levels
   dsb2018   resources/2DUnet_dsb2018/train_config.yml: bcr, f_maps [32, 64, 128], batch 32 — DSB2018 images vary in size;
@@ -14,7 +15,11 @@ Prints one JSON line per configuration: images/s of both paths (device time over
 per path), the conv2d family's ms per native step and its rate on executed FLOPs (18 * Cin * Cout * pixels per direction, from the
 launches that declare them) as a fraction of the fp32 MFMA peak of 157.3 TFLOP/s.
 
-  python tools/unet2d_bench.py [--configs confocal,dsb2018] [--batch N] [--steps 10] [--warmup 3]   (--batch: every config's own default)"""
+With --bf16 the record adds the bf16 path's ms per step, images/s, its speed-up over the native fp32 step of the same process, and its
+own conv2d family by entry point (the bf16 entry points' rate as TFLOP/s on executed FLOPs; the bf16 MFMA peak to hold it against is
+measured with tools/mfma_bf16_peak.hip).
+
+  python tools/unet2d_bench.py [--configs confocal,dsb2018] [--batch N] [--steps 10] [--warmup 3] [--bf16]   (--batch: every config's own default)"""
 import argparse
 import json
 import os
@@ -97,7 +102,10 @@ def make(cfg, native, dev):
     from pytorch3dunet_amd.unet3d.model import get_model
 
     torch.manual_seed(0)
-    key = "native_2d_residual" if _residual(cfg) else "native_2d"
+    if native == "bf16":
+        key, native = "native_2d_bf16", True
+    else:
+        key = "native_2d_residual" if _residual(cfg) else "native_2d"
     m = get_model(dict(cfg, **{key: native})).to(dev).train()
     return m, FusedAdam(m.parameters(), lr=1e-4, weight_decay=1e-5)
 
@@ -129,6 +137,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--rounds", type=int, default=2, help="alternating native / stock rounds of --steps each")
     ap.add_argument("--native-only", action="store_true", help="time the native path only (profiler runs)")
+    ap.add_argument("--bf16", action="store_true", help="also time the step with native_2d_bf16 (UNet2D configs), alternated with the others")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "unet2d_bench measures on the GPU"
     from pytorch3dunet_amd import _native as nat
@@ -144,6 +153,8 @@ def main():
         x = torch.randn((batch, 1) + hw, generator=g).to(dev)
         target = (torch.rand((batch, 1) + hw, generator=g) > 0.5).float().to(dev)
         paths = [True] if a.native_only else [True, False]
+        if a.bf16 and not _residual(cfg):
+            paths.insert(1, "bf16")
         runs = {p: make(cfg, p, dev) for p in paths}
         for p in paths:
             for _ in range(a.warmup):
@@ -190,6 +201,19 @@ def main():
                                            "fraction_of_peak": round(v["flops"] / v["ms"] / 1e9 / PEAK_TFLOPS, 3) if v["ms"] and v["flops"] else None}
                                        for k, v in tr.items()},
                        other_declared_flop_ms_per_step=round(sum(v["ms"] for k, v in fam.items() if k not in conv and k not in tr), 3))
+        if "bf16" in ms:
+            prof = nat.EventProfiler(flops_only=True, prealloc=4096)
+            nat.profiler = prof
+            step(*runs["bf16"], x, target, loss_fn)
+            torch.cuda.synchronize()
+            nat.profiler = None
+            bconv = {k: v for k, v in prof.summary().items() if "conv2d" in k}
+            rec.update(bf16_ms_per_step=[round(v, 3) for v in ms["bf16"]], bf16_images_per_s=round(batch * 1000.0 / best["bf16"], 2),
+                       bf16_speedup_over_native_fp32=round(best[True] / best["bf16"], 3),
+                       bf16_conv2d_family_ms_per_step=round(sum(v["ms"] for v in bconv.values()), 3),
+                       bf16_conv2d_calls={k: {"calls": v["calls"], "ms": round(v["ms"], 3),
+                                              "tflops_executed": round(v["flops"] / v["ms"] / 1e9, 2) if v["ms"] else None}
+                                          for k, v in bconv.items()})
         if not a.native_only:
             rec.update(stock_ms_per_step=[round(v, 3) for v in ms[False]], stock_images_per_s=round(batch * 1000.0 / best[False], 2),
                        native_speedup=round(best[False] / best[True], 3))
