@@ -948,16 +948,28 @@ int u3d_convtr2d_wgrad(int device, u3d_stream_t stream, const float* x, const fl
  *              * bf16(g[n, y+ky-1, x+kx-1, ci]).  Partial sums over pixel ranges go through the workspace
  *              (u3d_wgrad2d_bf16_workspace_floats() floats, 0: none needed) and are added in a fixed order: the same inputs give a
  *              bitwise-identical dw.
+ * Host-only: which launch plan a shape takes on the current device (the plan follows its CU count), from the same plan functions the
+ * launches call; -1 outside the envelope (or N, H, W < 1).
+ *   u3d_conv2d_bf16_variant        (ksplit << 8) | (32-channel n-tiles per block: 1 or 2).  ksplit = 1: one launch with the fused
+ *              epilogue (ReLU, statistics, gx / gstats, replica rows); > 1: the split-K launch and the reduction kernel that owns the
+ *              epilogue.  has_workspace = 0 asks for a call without the scratch, which never splits.  Asked with the roles swapped for a
+ *              data gradient, as the launch is.
+ *   u3d_conv2d_wgrad_bf16_variant  (tiles per block << 16) | nsplit (tiles per block saturates at 32767, nsplit at 65535): more than
+ *              one tile per block restages both LDS images under live accumulators; nsplit > 1 goes through the workspace.
+ * No reference counterpart (ATen picks its algorithm behind buildingblocks.py:56); the kernel tests assert with them that a pinned
+ * shape runs the variant a full-resolution UNet2D level runs.
  * Zeroing the statistics tables is the caller's job; the library never allocates and never synchronises. */
 int u3d_conv2d_bf16_supported(int Cin, int Cout);
 int u3d_conv2d_wgrad_bf16_supported(int Cin, int Cout);
 long long u3d_packed_weight2d_bf16_elems(int Cin, int Cout, int mode);
 int u3d_pack_weights2d_bf16(int device, u3d_stream_t stream, const float* w, int Cout, int Cin, int mode, void* packed);
 long long u3d_conv2d_bf16_workspace_floats(int N, int H, int W, int Cin, int Cout);
+int u3d_conv2d_bf16_variant(int N, int H, int W, int Cin, int Cout, int has_workspace);
 int u3d_conv2d_bf16(int device, u3d_stream_t stream, const float* x, const float* affine, const void* packed_w, float* out, int N,
                     int H, int W, int Cin, int Cout, int relu, double* out_stats, const float* gx, double* gstats, float* workspace,
                     long long workspace_floats, int stat_reps);
 long long u3d_wgrad2d_bf16_workspace_floats(int N, int H, int W, int Cin, int Cout);
+int u3d_conv2d_wgrad_bf16_variant(int N, int H, int W, int Cin, int Cout);
 int u3d_conv2d_wgrad_bf16(int device, u3d_stream_t stream, const float* x, const float* affine, const float* dz, float* dw, int N,
                           int H, int W, int Cin, int Cout, float* workspace, long long workspace_floats);
 

@@ -377,6 +377,10 @@ C2bPlan c2b_plan(int device, int N, int H, int W, int Cin, int Cout) {
     return pl;
 }
 
+// the split a launch really uses: the plan's, when the caller brought the scratch for it; else the unsplit kernel with its fused epilogue
+// (ONE statement for the launcher and the host-only query u3d_conv2d_bf16_variant)
+inline int c2b_launch_ksplit(const C2bPlan& pl, bool has_workspace) { return (pl.ksplit > 1 && has_workspace) ? pl.ksplit : 1; }
+
 // =================================================================================================
 // weight gradient: dw[co][ci][tap] = sum_{n,y,x} dz[n,y,x,co] * g[n, y + dy - 1, x + dx - 1, ci], g = affine(x), zero padded.
 // MFMA: M = 32 output channels (A = dz), N = 32 input channels (B = g), K = 16 pixels of one tile row; the same A fragment feeds 9 taps.
@@ -596,6 +600,13 @@ extern "C" long long u3d_conv2d_bf16_workspace_floats(int N, int H, int W, int C
     return pl.ksplit > 1 ? (long long)pl.ksplit * N * H * W * Cout : 0;
 }
 
+// host-only query of that plan (tests assert that the shapes they pin really run the variants a full-resolution level runs)
+extern "C" int u3d_conv2d_bf16_variant(int N, int H, int W, int Cin, int Cout, int has_workspace) {
+    if (N <= 0 || H <= 0 || W <= 0 || !c2b_fwd_ok(Cin, Cout)) return -1;
+    const C2bPlan pl = c2b_plan(c2b_current_device(), N, H, W, Cin, Cout);
+    return (c2b_launch_ksplit(pl, has_workspace != 0) << 8) | pl.nt;
+}
+
 extern "C" int u3d_conv2d_bf16(int device, u3d_stream_t stream, const float* x, const float* affine, const void* packed_w, float* out,
                                int N, int H, int W, int Cin, int Cout, int relu, double* out_stats, const float* gx, double* gstats,
                                float* workspace, long long workspace_floats, int stat_reps) {
@@ -609,7 +620,8 @@ extern "C" int u3d_conv2d_bf16(int device, u3d_stream_t stream, const float* x, 
                 "u3d_conv2d_bf16: pointers must be 16-byte aligned");
     const C2bPlan pl = c2b_plan(device, N, H, W, Cin, Cout);
     const long long need = pl.ksplit > 1 ? (long long)pl.ksplit * N * H * W * Cout : 0;
-    const bool split = need > 0 && workspace != nullptr;
+    const int ksplit = c2b_launch_ksplit(pl, workspace != nullptr);
+    const bool split = ksplit > 1;
     U3D_REQUIRE(!split || workspace_floats >= need, "u3d_conv2d_bf16: workspace too small (%lld < %lld floats)", workspace_floats, need);
     Conv2dBf16Params p = {};
     p.x = x;
@@ -623,7 +635,7 @@ extern "C" int u3d_conv2d_bf16(int device, u3d_stream_t stream, const float* x, 
     p.nchunks = pl.nchunks, p.ntg = pl.ntg, p.ncb = pl.ncb, p.ty = pl.ty, p.tx = pl.tx;
     p.relu = relu ? 1 : 0;
     p.stat_reps = stat_reps;
-    p.ksplit = split ? pl.ksplit : 1;
+    p.ksplit = ksplit;
     p.cps = split ? pl.cps : pl.nchunks;
     p.part_stride = (long long)N * H * W * Cout;
     const long long blocks = (long long)N * pl.ty * pl.tx * pl.ncb * p.ksplit;
@@ -646,6 +658,12 @@ extern "C" long long u3d_wgrad2d_bf16_workspace_floats(int N, int H, int W, int 
     if (N <= 0 || H <= 0 || W <= 0 || !c2b_wgrad_ok(Cin, Cout)) return 0;
     const W2bPlan pl = w2b_plan(c2b_current_device(), N, H, W, Cin, Cout);
     return pl.nsplit > 1 ? (long long)pl.nsplit * Cout * Cin * 9 : 0;
+}
+
+extern "C" int u3d_conv2d_wgrad_bf16_variant(int N, int H, int W, int Cin, int Cout) {
+    if (N <= 0 || H <= 0 || W <= 0 || !c2b_wgrad_ok(Cin, Cout)) return -1;
+    const W2bPlan pl = w2b_plan(c2b_current_device(), N, H, W, Cin, Cout);
+    return (std::min(pl.tps, 0x7fff) << 16) | std::min(pl.nsplit, 0xffff);
 }
 
 extern "C" int u3d_conv2d_wgrad_bf16(int device, u3d_stream_t stream, const float* x, const float* affine, const float* dz, float* dw,

@@ -479,9 +479,11 @@ _PROTOS = {
     "u3d_packed_weight2d_bf16_elems": (c_int64, [c_int, c_int, c_int]),
     "u3d_pack_weights2d_bf16": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "u3d_conv2d_bf16_workspace_floats": (c_int64, [c_int, c_int, c_int, c_int, c_int]),
+    "u3d_conv2d_bf16_variant": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int]),
     "u3d_conv2d_bf16": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
                                 c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int]),
     "u3d_wgrad2d_bf16_workspace_floats": (c_int64, [c_int, c_int, c_int, c_int, c_int]),
+    "u3d_conv2d_wgrad_bf16_variant": (c_int, [c_int, c_int, c_int, c_int, c_int]),
     "u3d_conv2d_wgrad_bf16": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
                                       c_void_p, c_int64]),
     "u3d_maxpool2d_fwd": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),

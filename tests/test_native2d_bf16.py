@@ -121,6 +121,35 @@ def test_host_sizes_of_bf16_2d_images_and_workspaces():
     assert lib.u3d_wgrad2d_bf16_workspace_floats(0, 8, 8, 32, 32) == 0
 
 
+def test_plan_queries_of_the_bf16_2d_launches():
+    """u3d_conv2d_bf16_variant / u3d_conv2d_wgrad_bf16_variant report the plans the workspace sizes come from (properties that hold for
+    every CU count; the GPU tests assert the variants of their pinned shapes)"""
+    from pytorch3dunet_amd import _native as nat
+
+    lib = nat.get_lib()
+    for bad in [(1, 8, 8, 20, 32), (1, 8, 8, 32, 8), (0, 8, 8, 32, 32), (1, 0, 8, 32, 32), (1, 8, 0, 32, 32)]:
+        assert lib.u3d_conv2d_bf16_variant(*bad, 1) == -1 and lib.u3d_conv2d_wgrad_bf16_variant(*bad) == -1
+    assert lib.u3d_conv2d_bf16_variant(1, 8, 8, 16, 32, 1) > 0 and lib.u3d_conv2d_wgrad_bf16_variant(1, 8, 8, 16, 32) == -1
+    shapes = [(1, 4, 5, 32, 32), (2, 17, 19, 32, 64), (1, 8, 8, 256, 128), (1, 8, 8, 16, 128), (2, 250, 245, 16, 64), (1, 250, 245, 32, 96),
+              (32, 515, 512, 32, 64), (1, 139, 141, 128, 128), (1, 70, 75, 256, 256)]
+    for N, H, W, Cin, Cout in shapes:
+        v = lib.u3d_conv2d_bf16_variant(N, H, W, Cin, Cout, 1)
+        nt, ksplit = v & 255, v >> 8
+        assert nt in (1, 2) and 1 <= ksplit <= Cin // 16, (N, H, W, Cin, Cout, v)
+        need = lib.u3d_conv2d_bf16_workspace_floats(N, H, W, Cin, Cout)
+        assert need == (ksplit * N * H * W * Cout if ksplit > 1 else 0)
+        assert lib.u3d_conv2d_bf16_variant(N, H, W, Cin, Cout, 0) == (1 << 8) | nt  # no scratch: the same block, never split
+        if Cin % 32 == 0:
+            v = lib.u3d_conv2d_wgrad_bf16_variant(N, H, W, Cin, Cout)
+            tps, nsplit = v >> 16, v & 0xFFFF
+            ntiles = N * ((H + 15) // 16) * ((W + 15) // 16)
+            assert tps >= 1 and (nsplit - 1) * tps < ntiles <= nsplit * tps, (N, H, W, Cin, Cout, v)
+            assert lib.u3d_wgrad2d_bf16_workspace_floats(N, H, W, Cin, Cout) == (nsplit * Cout * Cin * 9 if nsplit > 1 else 0)
+    assert lib.u3d_conv2d_bf16_variant(1, 8, 8, 16, 128, 1) >> 8 == 1  # one input chunk: nothing to split
+    assert lib.u3d_conv2d_bf16_variant(32, 515, 512, 32, 64, 1) == (1 << 8) | 2  # a full-resolution level: the 64-channel block, unsplit
+    assert lib.u3d_conv2d_bf16_variant(32, 515, 512, 32, 32, 1) == (1 << 8) | 1  # one n-tile in all
+
+
 # ---- the emulation helper of the GPU model tests ----------------------------------------------------------------------------------
 @pytest.mark.parametrize("cfg,n_bf16", [
     (dict(name="UNet2D", in_channels=1, out_channels=1, f_maps=[32, 64, 128], layer_order="gcr", num_groups=8), 8),  # all but 1->16, 16->32
