@@ -968,6 +968,17 @@ int u3d_conv2d_bf16_variant(int N, int H, int W, int Cin, int Cout, int has_work
 int u3d_conv2d_bf16(int device, u3d_stream_t stream, const float* x, const float* affine, const void* packed_w, float* out, int N,
                     int H, int W, int Cin, int Cout, int relu, double* out_stats, const float* gx, double* gstats, float* workspace,
                     long long workspace_floats, int stat_reps);
+/* (Added, U3D_VERSION unchanged.)  The same convolution with a residual added before the ReLU — conv3 of a ResNetBlock in ResidualUNet2D
+ * (buildingblocks.py:277-288, `native_2d_residual_bf16: true`), the bf16 twin of u3d_conv2d_res_reps:
+ *   out = [relu](conv2d(bf16(a*x + b), bf16(w)) + residual),   residual (N,H,W,Cout) fp32, 16-byte aligned.
+ * The residual is added in fp32 to the fp32 accumulator and is never rounded; out_stats are the sums of the written values, replica rows
+ * as u3d_conv2d_bf16.  The unsplit launch adds it in the fused epilogue; a split-K launch adds it in the reduction kernel, after the
+ * partial sums (which carry none) in run order.  The launch plan does not depend on the residual: u3d_conv2d_bf16_variant and
+ * u3d_conv2d_bf16_workspace_floats describe this entry point unchanged.  Arguments as u3d_conv2d_bf16; residual must not be NULL and
+ * gx / gstats must be NULL (a residual and the data-gradient statistics exclude each other), else U3D_EINVAL without a launch. */
+int u3d_conv2d_bf16_res(int device, u3d_stream_t stream, const float* x, const float* affine, const void* packed_w, float* out, int N,
+                        int H, int W, int Cin, int Cout, int relu, double* out_stats, const float* gx, double* gstats, float* workspace,
+                        long long workspace_floats, int stat_reps, const float* residual);
 long long u3d_wgrad2d_bf16_workspace_floats(int N, int H, int W, int Cin, int Cout);
 int u3d_conv2d_wgrad_bf16_variant(int N, int H, int W, int Cin, int Cout);
 int u3d_conv2d_wgrad_bf16(int device, u3d_stream_t stream, const float* x, const float* affine, const float* dz, float* dw, int N,

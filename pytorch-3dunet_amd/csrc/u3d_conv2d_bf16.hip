@@ -16,7 +16,9 @@
 // Double-buffered like the fp32 kernel: the next chunk's halo is in flight (registers) during the current chunk's 9 * 2 * NT MFMAs and
 // stored to the other buffer after them, one barrier per chunk.  B fragments (16 bytes per lane) stream from the pre-swizzled packed
 // image one tap ahead.  Small grids split the channel reduction over blocks and add the partial sums in a fixed order
-// (conv2d_bf16_splitk_reduce_kernel).
+// (conv2d_bf16_splitk_reduce_kernel).  With a residual (u3d_conv2d_bf16_res: conv3 of a ResNetBlock, `native_2d_residual_bf16: true` on a
+// ResidualUNet2D) the epilogue that owns ReLU and statistics — the fused one, or the split-K reduction — adds the fp32 residual to the fp32
+// sum first: out = [relu](conv + residual); it is read where the output is stored (lane = channel: 128 contiguous bytes per half-wave).
 //
 // Weight gradient (conv2d_wgrad_bf16_kernel): the contraction runs over PIXELS while both tensors are channel-innermost, so both operand
 // fragments (8 pixels of one channel per lane) are transposed reads: the g halo and the dz tile sit in LDS as [pixel][32 channels] bf16
@@ -120,6 +122,7 @@ struct Conv2dBf16Params {
     const float* affine;  // (N,Cin,2) or null
     const c2b_bf16x8* wp;
     const float* gx;      // (N,H,W,Cout) fp32 or null
+    const float* residual;  // (N,H,W,Cout) fp32 or null: added to the fp32 sum before the ReLU (never with gx)
     float* out;           // ksplit == 1: the output; else the workspace of partial sums [ksplit][N*H*W*Cout]
     double* out_stats;
     double* gstats;
@@ -306,6 +309,7 @@ __global__ __launch_bounds__(256, 2) void conv2d_bf16_kernel(const Conv2dBf16Par
                     outp[o] = v;
                     continue;
                 }
+                if (p.residual) v += p.residual[o];  // (uniform over the grid; the split-K partial sums above carry none)
                 if (p.relu) v = fmaxf(v, 0.f);
                 outp[o] = v;
                 s[nt][0] += v;
@@ -319,11 +323,12 @@ __global__ __launch_bounds__(256, 2) void conv2d_bf16_kernel(const Conv2dBf16Par
     if (p.ksplit == 1 && (p.out_stats || p.gx)) c2b_flush_stats<NT>(p, reinterpret_cast<float*>(lds + RED), s, n, cb, t);
 }
 
-// split-K: out = [relu](sum over runs in run order), statistics as the main kernel (replica row 0).  Block = 64 pixels of one sample,
+// split-K: out = [relu](sum over runs in run order [+ residual]), statistics as the main kernel (replica row 0).  Block = 64 pixels of one sample,
 // threads walk the channels (coalesced), one f64 atomic per (block, channel, quantity).
 __global__ __launch_bounds__(256) void conv2d_bf16_splitk_reduce_kernel(const float* __restrict__ part, long long part_stride, int ksplit,
                                                                         float* __restrict__ out, int P, int Cout, int relu,
-                                                                        double* out_stats, const float* __restrict__ gx, double* gstats) {
+                                                                        double* out_stats, const float* __restrict__ gx, double* gstats,
+                                                                        const float* __restrict__ residual) {
     const int n = blockIdx.y;
     const int p0 = blockIdx.x * 64, p1 = min(P, p0 + 64);
     for (int co = threadIdx.x; co < Cout; co += blockDim.x) {
@@ -332,6 +337,7 @@ __global__ __launch_bounds__(256) void conv2d_bf16_splitk_reduce_kernel(const fl
             const size_t o = ((size_t)n * P + pp) * Cout + co;
             float v = 0.f;
             for (int k = 0; k < ksplit; ++k) v += part[(size_t)k * part_stride + o];
+            if (residual) v += residual[o];
             if (relu) v = fmaxf(v, 0.f);
             out[o] = v;
             s0 += v;
@@ -607,27 +613,33 @@ extern "C" int u3d_conv2d_bf16_variant(int N, int H, int W, int Cin, int Cout, i
     return (c2b_launch_ksplit(pl, has_workspace != 0) << 8) | pl.nt;
 }
 
-extern "C" int u3d_conv2d_bf16(int device, u3d_stream_t stream, const float* x, const float* affine, const void* packed_w, float* out,
-                               int N, int H, int W, int Cin, int Cout, int relu, double* out_stats, const float* gx, double* gstats,
-                               float* workspace, long long workspace_floats, int stat_reps) {
+namespace {
+
+// the one launcher behind u3d_conv2d_bf16 (residual == nullptr) and u3d_conv2d_bf16_res: same plan, same kernels
+int c2b_conv2d_launch(const char* who, int device, u3d_stream_t stream, const float* x, const float* affine, const void* packed_w,
+                      float* out, int N, int H, int W, int Cin, int Cout, int relu, double* out_stats, const float* gx, double* gstats,
+                      float* workspace, long long workspace_floats, int stat_reps, const float* residual) {
     U3D_ENTER(device);
-    U3D_REQUIRE(c2b_fwd_ok(Cin, Cout), "u3d_conv2d_bf16: (%d -> %d) channels are outside the bf16 envelope (Cin %% 16, Cout %% 32)", Cin,
+    U3D_REQUIRE(c2b_fwd_ok(Cin, Cout), "%s: (%d -> %d) channels are outside the bf16 envelope (Cin %% 16, Cout %% 32)", who, Cin,
                 Cout);
     U3D_REQUIRE(x && packed_w && out && N > 0 && H > 0 && W > 0 && stat_reps >= 1 && (long long)N * H * W < (1LL << 31),
-                "u3d_conv2d_bf16: bad argument");
-    U3D_REQUIRE(!gx || gstats, "u3d_conv2d_bf16: gx needs gstats");
-    U3D_REQUIRE(c2b_aligned(x) && c2b_aligned(affine) && c2b_aligned(packed_w) && c2b_aligned(out) && c2b_aligned(workspace),
-                "u3d_conv2d_bf16: pointers must be 16-byte aligned");
+                "%s: bad argument", who);
+    U3D_REQUIRE(!gx || gstats, "%s: gx needs gstats", who);
+    U3D_REQUIRE(c2b_aligned(x) && c2b_aligned(affine) && c2b_aligned(packed_w) && c2b_aligned(out) && c2b_aligned(workspace) &&
+                    c2b_aligned(residual),
+                "%s: pointers must be 16-byte aligned", who);
     const C2bPlan pl = c2b_plan(device, N, H, W, Cin, Cout);
     const long long need = pl.ksplit > 1 ? (long long)pl.ksplit * N * H * W * Cout : 0;
     const int ksplit = c2b_launch_ksplit(pl, workspace != nullptr);
     const bool split = ksplit > 1;
-    U3D_REQUIRE(!split || workspace_floats >= need, "u3d_conv2d_bf16: workspace too small (%lld < %lld floats)", workspace_floats, need);
+    U3D_REQUIRE(!split || workspace_floats >= need, "%s: workspace too small (%lld < %lld floats)", who, workspace_floats,
+                need);
     Conv2dBf16Params p = {};
     p.x = x;
     p.affine = affine;
     p.wp = reinterpret_cast<const c2b_bf16x8*>(packed_w);
     p.gx = gx;
+    p.residual = residual;
     p.out = split ? workspace : out;
     p.out_stats = out_stats;
     p.gstats = gstats;
@@ -639,7 +651,7 @@ extern "C" int u3d_conv2d_bf16(int device, u3d_stream_t stream, const float* x, 
     p.cps = split ? pl.cps : pl.nchunks;
     p.part_stride = (long long)N * H * W * Cout;
     const long long blocks = (long long)N * pl.ty * pl.tx * pl.ncb * p.ksplit;
-    U3D_REQUIRE(blocks < (1LL << 31), "u3d_conv2d_bf16: grid too large");
+    U3D_REQUIRE(blocks < (1LL << 31), "%s: grid too large", who);
     if (pl.nt == 2)
         hipLaunchKernelGGL(conv2d_bf16_kernel<2>, dim3((unsigned)blocks), dim3(256), c2b::LDS_BYTES, (hipStream_t)stream, p);
     else
@@ -648,10 +660,29 @@ extern "C" int u3d_conv2d_bf16(int device, u3d_stream_t stream, const float* x, 
     if (split) {
         const int P = H * W;
         hipLaunchKernelGGL(conv2d_bf16_splitk_reduce_kernel, dim3((unsigned)c2b_cdiv(P, 64), N), dim3(256), 0, (hipStream_t)stream, workspace,
-                           p.part_stride, p.ksplit, out, P, Cout, p.relu, out_stats, gx, gstats);
+                           p.part_stride, p.ksplit, out, P, Cout, p.relu, out_stats, gx, gstats, residual);
         U3D_LAUNCH_CHECK();
     }
     return 0;
+}
+
+}  // namespace
+
+extern "C" int u3d_conv2d_bf16(int device, u3d_stream_t stream, const float* x, const float* affine, const void* packed_w, float* out,
+                               int N, int H, int W, int Cin, int Cout, int relu, double* out_stats, const float* gx, double* gstats,
+                               float* workspace, long long workspace_floats, int stat_reps) {
+    return c2b_conv2d_launch("u3d_conv2d_bf16", device, stream, x, affine, packed_w, out, N, H, W, Cin, Cout, relu, out_stats, gx, gstats,
+                             workspace, workspace_floats, stat_reps, nullptr);
+}
+
+// out = [relu](conv2d(bf16(a*x + b), bf16(w)) + residual): the bf16 twin of u3d_conv2d_res_reps.  The plan (u3d_conv2d_bf16_variant,
+// u3d_conv2d_bf16_workspace_floats) does not depend on the residual.
+extern "C" int u3d_conv2d_bf16_res(int device, u3d_stream_t stream, const float* x, const float* affine, const void* packed_w, float* out,
+                                   int N, int H, int W, int Cin, int Cout, int relu, double* out_stats, const float* gx, double* gstats,
+                                   float* workspace, long long workspace_floats, int stat_reps, const float* residual) {
+    U3D_REQUIRE(residual && !gx && !gstats, "u3d_conv2d_bf16_res: needs a residual, and a residual excludes gx / gstats");
+    return c2b_conv2d_launch("u3d_conv2d_bf16_res", device, stream, x, affine, packed_w, out, N, H, W, Cin, Cout, relu, out_stats, nullptr,
+                             nullptr, workspace, workspace_floats, stat_reps, residual);
 }
 
 extern "C" long long u3d_wgrad2d_bf16_workspace_floats(int N, int H, int W, int Cin, int Cout) {

@@ -262,6 +262,18 @@ class ConvLayers:
         contraction channels % 16 and the produced channels % 32)"""
         return self.bf16 and Cin % 32 == 0 and Cout % 32 == 0
 
+    def _bf16_routed_weight(self, Cin: int, Cout: int, virtual: bool) -> bool:
+        """THE rule for a 2-D net in bf16 (`native_2d_bf16`, `native_2d_residual_bf16`), stated once: a 3x3 layer runs forward, data
+        gradient and weight gradient on the `conv2d_bf16` family when it reads ONE real tensor (`virtual`: its input is a virtual concat)
+        and `_bf16_layer` holds — with or without a residual in its epilogue (u3d_conv2d_bf16_res).  Asked in this form by
+        `_weight_images` (which weights get BF16_FWD2D / BF16_DGRAD2D images) and `_layer_ws_floats` (scratch), and through
+        `_bf16_routed` by `_fwd_family` and `_conv_bwd`."""
+        return not virtual and self._bf16_layer(Cin, Cout)
+
+    def _bf16_routed(self, src: VSrc, Cout: int) -> bool:
+        """`_bf16_routed_weight` for a layer about to run on `src`"""
+        return self._bf16_routed_weight(src.C, Cout, src.t1 is not None)
+
     def _split_fwd(self, Cin: int, Cout: int) -> bool:
         return self.split and Cin % 16 == 0 and Cout % 32 == 0
 
@@ -271,7 +283,7 @@ class ConvLayers:
 
     def _convtr_t8(self, Cl: int, Cs: int) -> bool:
         """the transposed convolution and its gradients run in space-to-depth form on the bf16 MFMA kernels"""
-        return self.bf16 and nat.get_lib().u3d_convtr3d_t8_supported(Cl, Cs) == 1
+        return self.bf16 and not getattr(self, "is2d", False) and nat.get_lib().u3d_convtr3d_t8_supported(Cl, Cs) == 1
 
     # ---- forward kernel families (csrc file; what selects it) -------------------------------------------------------------------
     _FWD_KERNELS = {
@@ -281,14 +293,14 @@ class ConvLayers:
         "bf16": "_fwd_bf16",          # u3d_bf16.hip: compute_dtype bf16 (fp32 or bf16 activation storage)
         "fp32": "_fwd_fp32",          # u3d_conv.hip: fp32 MFMA (persistent / generic / split-K chosen by the library)
         "conv2d": "_fwd_conv2d",      # u3d_conv2d.hip: 3x3 convolutions of a 2-D net (native_2d), every layer and only those ...
-        "conv2d_bf16": "_fwd_conv2d_bf16",  # u3d_conv2d_bf16.hip: ... except, under native_2d_bf16, the single-source layers that fit
+        "conv2d_bf16": "_fwd_conv2d_bf16",  # u3d_conv2d_bf16.hip: ... except, in bf16, the single-source layers that fit (`_bf16_routed`)
     }
 
     def _fwd_family(self, c: "_ConvCall", residual) -> str:
         if getattr(self, "is2d", False):
             # (a decoder's first conv reaches here on its materialised concat when it fits: `_cat_bf16`; forward and data gradient
-            # are covered together by the one channel rule)
-            return "conv2d_bf16" if (c.src.t1 is None and residual is None and self._bf16_layer(c.Ctot, c.Cout)) else "conv2d"
+            # are covered together by the one channel rule; a residual rides in either family's epilogue)
+            return "conv2d_bf16" if self._bf16_routed(c.src, c.Cout) else "conv2d"
         if self.small_cin and c.src.t1 is None and c.Ctot <= 4 and c.Cout <= 32 and residual is None and not c.b16:
             return "small"
         if c.src.t1 is not None and residual is None and id(c.conv.weight) in c.sub:
@@ -388,15 +400,20 @@ class ConvLayers:
 
     def _fwd_conv2d_bf16(self, c: "_ConvCall"):
         # bf16 MFMA operands, fp32 accumulation / epilogue on the D = 1 tensors (csrc/u3d_conv2d_bf16.hip): fused affine (rounded once
-        # after it), ReLU and statistics as the fp32 kernel
-        assert c.D == 1 and c.src.t1 is None and c.residual is None
+        # after it), ReLU and statistics as the fp32 kernel; with a residual (ResidualUNet2D's conv3 in a pre-norm order): out =
+        # [relu](conv + residual), the fp32 residual added to the fp32 sum in the epilogue (u3d_conv2d_bf16_res)
+        assert c.D == 1 and c.src.t1 is None
         wp = self.images.get(c.conv.weight, Kind.BF16_FWD2D, c.dev)
         ystats = c.take_stats(self.stat_reps)
         need = nat.get_lib().u3d_conv2d_bf16_workspace_floats(c.N, c.H, c.W, c.Ctot, c.Cout)  # split-K scratch on small grids
         kws = _empty(need, dtype=_F32, device=c.dev) if need > 0 else None
         yp, yr = _tab(ystats)
-        nat.call("u3d_conv2d_bf16", c.dev.index, _stream(c.dev), _p(c.src.t0), _p(c.affine), _p(wp), _p(c.y), c.N, c.H, c.W, c.Ctot,
-                 c.Cout, c.relu, yp, None, None, _p(kws), need, yr, flops=18.0 * c.Ctot * c.Cout * c.N * c.H * c.W)
+        args = [c.dev.index, _stream(c.dev), _p(c.src.t0), _p(c.affine), _p(wp), _p(c.y), c.N, c.H, c.W, c.Ctot, c.Cout, c.relu, yp, None,
+                None, _p(kws), need, yr]
+        if c.residual is not None:  # (the `_res` entry point: the same arguments plus the residual)
+            args.append(_p(c.residual))
+        nat.call("u3d_conv2d_bf16_res" if c.residual is not None else "u3d_conv2d_bf16", *args,
+                 flops=18.0 * c.Ctot * c.Cout * c.N * c.H * c.W)
         return ystats
 
     def _fwd_fp32(self, c: "_ConvCall"):
@@ -812,7 +829,7 @@ class ConvLayers:
                 return None, self._identity_coef(Nn, src.C, dev), None
             coef = _empty((Nn, 3, src.C), dtype=_F32, device=dev)
             return None, coef, self._norm_bwd_finalize(cx, rec, (gst, None), float(Dd * Hh * Ww), coef)
-        bf16 = src.t1 is None and rec.sub is None and not rec.small and self._bf16_layer(src.C, Cout)
+        bf16 = rec.sub is None and not rec.small and self._bf16_routed(src, Cout)  # (the forward's decision, `_fwd_family`)
         b16 = src.t0.dtype == torch.bfloat16  # bf16 activation storage
         assert not b16 or (bf16 and Cout % 64 == 0 and dz_.dtype == torch.bfloat16)
         call = _BwdCall(cx, rec, dz_, src, Nn, Dd, Hh, Ww, Cout, bf16, b16)
@@ -862,7 +879,7 @@ class ConvLayers:
         """scratch floats one 3x3x3 layer's backward needs from the shared buffer, for the kernels it will actually run"""
         lib = nat.get_lib()
         if getattr(self, "is2d", False):  # weight gradient + the data gradient's split-K scratch (roles swapped)
-            if not virtual and self._bf16_layer(Cin, Cout):  # (the bf16 kernels' plans, csrc/u3d_conv2d_bf16.hip)
+            if self._bf16_routed_weight(Cin, Cout, virtual):  # (the bf16 kernels' plans, csrc/u3d_conv2d_bf16.hip)
                 return max(lib.u3d_wgrad2d_bf16_workspace_floats(N, H, W, Cin, Cout), lib.u3d_conv2d_bf16_workspace_floats(N, H, W, Cout, Cin))
             return max(lib.u3d_wgrad2d_workspace_floats(N, H, W, Cin, Cout), lib.u3d_conv2d_workspace_floats(N, H, W, Cout, Cin))
         if small:

@@ -34,8 +34,10 @@ class ResUNetEngine(UNet3DEngine):
 
     ResidualUNet2D under `native_2d_residual` (unet3d/model.py sets model.native_2d, hence self.is2d): (N,C,H,W) runs as
     (N,C,1,H,W); the 3x3 convolutions take the `conv2d` family (u3d_conv2d_res_reps fuses `out += residual`), the pools the
-    u3d_maxpool2d_* twins and the decoders ConvTranspose2d (u3d_convtr2d_*) before the same joining kernels at D = 1; the t8,
-    sub-pixel and bf16 branches stay off."""
+    u3d_maxpool2d_* twins and the decoders ConvTranspose2d (u3d_convtr2d_*) before the same joining kernels at D = 1; the t8 and
+    sub-pixel branches stay off.  Under `native_2d_residual_bf16` conv2 / conv3 of the blocks whose width is a multiple of 32 take the
+    `conv2d_bf16` family in all three directions (`_bf16_routed`; u3d_conv2d_bf16_res fuses `out += residual`); the 1x1 convolutions,
+    ConvTranspose2d and every activation tensor stay fp32."""
 
     def __init__(self, model):
         super().__init__(model)
@@ -64,6 +66,8 @@ class ResUNetEngine(UNet3DEngine):
         lib = nat.get_lib()
         if not self.bf16:
             return "compute_dtype is not bf16"
+        if self.is2d:
+            return "the 2-D kernels have no bf16-storage (`_b16`) forms"
         if order != "gcr":
             return f"layer_order '{order}' (only 'gcr')"
         if any(self.dec_concat):

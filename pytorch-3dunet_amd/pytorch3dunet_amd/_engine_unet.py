@@ -124,9 +124,10 @@ class UNet3DEngine(ConvLayers):
         ws = [mod.weight for mod in self.model.modules()  # every 3x3x3 (UNet2D under native_2d: 3x3) weight the MFMA kernels read
               if (isinstance(mod, torch.nn.Conv3d) and mod.kernel_size == (3, 3, 3))
               or (isinstance(mod, torch.nn.Conv2d) and mod.kernel_size == (3, 3))]
-        bf16 = {id(w) for w in ws if self._bf16_layer(w.shape[1], w.shape[0])} - self._virtual_w
-        if self.is2d:  # (`native_2d_bf16`: the single-source layers with both channel counts % 32 read bf16 images, `_fwd_family`)
+        if self.is2d:  # (2-D nets in bf16: the single-source layers with both channel counts % 32 read bf16 images, `_bf16_routed`)
+            bf16 = {id(w) for w in ws if self._bf16_routed_weight(w.shape[1], w.shape[0], id(w) in self._virtual_w)}
             return WeightImages(each=[w for w in ws if id(w) not in bf16], each_bf16=[w for w in ws if id(w) in bf16])
+        bf16 = {id(w) for w in ws if self._bf16_layer(w.shape[1], w.shape[0])} - self._virtual_w
         return WeightImages(
             # (not the first layer: its dedicated kernels read the reference layout)
             f32=[w for w in ws if id(w) not in bf16 and not (self.small_cin and w.shape[1] <= 4 and w.shape[0] <= 32)],

@@ -44,7 +44,7 @@ class Kind(enum.IntEnum):
     DGRAD2D = enum.auto()
     CONVTR2D_FWD = enum.auto()
     CONVTR2D_DGRAD = enum.auto()
-    BF16_FWD2D = enum.auto()    # ... of a 2-D net in bf16 (`native_2d_bf16`): the layers the bf16 kernels cover
+    BF16_FWD2D = enum.auto()    # ... of a 2-D net in bf16 (`native_2d_bf16`, `native_2d_residual_bf16`): the layers the bf16 kernels cover
     BF16_DGRAD2D = enum.auto()
 
 

@@ -482,6 +482,8 @@ _PROTOS = {
     "u3d_conv2d_bf16_variant": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int]),
     "u3d_conv2d_bf16": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
                                 c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int]),
+    "u3d_conv2d_bf16_res": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
+                                    c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p]),
     "u3d_wgrad2d_bf16_workspace_floats": (c_int64, [c_int, c_int, c_int, c_int, c_int]),
     "u3d_conv2d_wgrad_bf16_variant": (c_int, [c_int, c_int, c_int, c_int, c_int]),
     "u3d_conv2d_wgrad_bf16": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,

@@ -16,7 +16,7 @@ the same module tree through stock PyTorch-ROCm operators after a one-time warni
 models are outside the 3-D path and keep that warning path by default (opt-in since round 7: `native_2d: true` / U3D_NATIVE_2D=1 runs a
 fp32 UNet2D with nearest upsampling on the 2-D kernels of csrc/u3d_conv2d.hip; `native_2d_residual: true` / U3D_NATIVE_2D_RESIDUAL=1
 does the same for a fp32 ResidualUNet2D; `native_2d_bf16: true` / U3D_NATIVE_2D_BF16=1 runs a UNet2D with bf16 MFMA operands on the kernels
-of csrc/u3d_conv2d_bf16.hip); U3D_STRICT=1 makes them an error too.  Covered since round 2: every layer order with at most one
+of csrc/u3d_conv2d_bf16.hip, `native_2d_residual_bf16: true` / U3D_NATIVE_2D_RESIDUAL_BF16=1 a ResidualUNet2D); U3D_STRICT=1 makes them an error too.  Covered since round 2: every layer order with at most one
 GroupNorm / BatchNorm, one non-linearity and a trailing dropout, every `upsample` value the reference itself can run
 on a 3-D net, nn.DataParallel, activation checkpointing, and the opt-in compute modes `bf16` and `fp32_split`.
 """
@@ -44,7 +44,7 @@ class AbstractUNet(nn.Module):
                  num_groups=8, num_levels=4, is_segmentation=True, conv_kernel_size=3, pool_kernel_size=2,
                  conv_padding=1, conv_upscale=2, upsample="default", dropout_prob=0.1, is3d=True, compute_dtype=None,
                  checkpoint_encoders=None, hip_graph=None, activation_dtype=None, checkpoint_levels=None,
-                 native_2d=None, native_2d_residual=None, native_2d_bf16=None):
+                 native_2d=None, native_2d_residual=None, native_2d_bf16=None, native_2d_residual_bf16=None):
         super().__init__()
         if isinstance(f_maps, int):
             f_maps = number_of_features_per_level(f_maps, num_levels=num_levels)
@@ -74,6 +74,21 @@ class AbstractUNet(nn.Module):
         # native_2d.  Every other class ignores it, and `native_2d: true` alone leaves a ResidualUNet2D on the warning path
         if native_2d_residual is None:
             native_2d_residual = os.environ.get("U3D_NATIVE_2D_RESIDUAL", "0") == "1"
+        # `native_2d_residual_bf16: true` (its own key; U3D_NATIVE_2D_RESIDUAL_BF16=1 sets its default): a ResidualUNet2D runs natively with
+        # bf16 MFMA operands on csrc/u3d_conv2d_bf16.hip for every 3x3 layer whose channel counts are both multiples of 32 (conv2 and conv3
+        # of a ResNetBlock map C -> C: at the reference's f_maps every one of them; conv3's `out += residual` is the fp32 epilogue of
+        # u3d_conv2d_bf16_res).  The 1x1 convolutions, ConvTranspose2d, pooling, joining, the head and the activations in HBM stay fp32.  It
+        # implies native_2d_residual (hence native_2d) and compute_dtype bf16; an explicit fp32 / fp32_split compute_dtype next to it is a
+        # contradiction.  Every other class ignores it, and `native_2d_residual: true` + `compute_dtype: bf16` without it stays on the
+        # warning path
+        if native_2d_residual_bf16 is None:
+            native_2d_residual_bf16 = os.environ.get("U3D_NATIVE_2D_RESIDUAL_BF16", "0") == "1"
+        res2d_bf16 = bool(native_2d_residual_bf16) and not is3d and basic_module is ResNetBlock
+        if res2d_bf16:
+            if compute_dtype is not None and str(compute_dtype).lower() not in ("bf16", "bfloat16"):
+                raise ValueError(f"u3d: native_2d_residual_bf16 runs bf16 operands; compute_dtype {compute_dtype!r} contradicts it — drop "
+                                 "one of the two keys (native_2d_residual: true is the fp32 2-D path)")
+            native_2d_residual, compute_dtype = True, "bf16"
         res2d = bool(native_2d_residual) and not is3d and basic_module is ResNetBlock
         if res2d:
             native_2d = True
@@ -92,6 +107,7 @@ class AbstractUNet(nn.Module):
             native_2d, compute_dtype = True, "bf16"
         self.native_2d = bool(native_2d) and not is3d
         self.native_2d_bf16 = bf16_2d
+        self.native_2d_residual_bf16 = res2d_bf16
         reasons = []
         if not is3d and not self.native_2d:
             reasons.append("2-D model")
@@ -99,10 +115,10 @@ class AbstractUNet(nn.Module):
             if basic_module is not DoubleConv and not res2d:
                 reasons.append(f"2-D model with {basic_module.__name__} (native_2d covers DoubleConv blocks; a ResidualUNet2D needs "
                                "native_2d_residual: true)")
-            if not bf16_2d and (compute_dtype not in (None, "fp32", "float32") or os.environ.get("U3D_BF16", "0") == "1" or
-                                os.environ.get("U3D_F32_SPLIT", "0") == "1"):
+            if not (bf16_2d or res2d_bf16) and (compute_dtype not in (None, "fp32", "float32") or os.environ.get("U3D_BF16", "0") == "1" or
+                                                os.environ.get("U3D_F32_SPLIT", "0") == "1"):
                 reasons.append(f"2-D model with compute_dtype {compute_dtype!r} (native_2d is fp32; a UNet2D in bf16 needs "
-                               "native_2d_bf16: true)")
+                               "native_2d_bf16: true, a ResidualUNet2D native_2d_residual_bf16: true)")
             if upsample not in ("default", "nearest") and not res2d:  # (residual nets: the residual rule below)
                 reasons.append(f"2-D model with upsample '{upsample}' (native_2d: nearest upsampling)")
         if basic_module not in (DoubleConv, ResNetBlock, ResNetBlockSE):
@@ -326,7 +342,8 @@ def _variant(name, basic_module, default_levels, is3d, doc):
                               compute_dtype=kwargs.get("compute_dtype"), checkpoint_encoders=kwargs.get("checkpoint_encoders"),
                               hip_graph=kwargs.get("hip_graph"), activation_dtype=kwargs.get("activation_dtype"),
                               checkpoint_levels=kwargs.get("checkpoint_levels"), native_2d=kwargs.get("native_2d"),
-                              native_2d_residual=kwargs.get("native_2d_residual"), native_2d_bf16=kwargs.get("native_2d_bf16"))
+                              native_2d_residual=kwargs.get("native_2d_residual"), native_2d_bf16=kwargs.get("native_2d_bf16"),
+                              native_2d_residual_bf16=kwargs.get("native_2d_residual_bf16"))
 
     return type(name, (AbstractUNet,), {"__init__": __init__, "__doc__": doc, "__module__": _THIS_MODULE})
 

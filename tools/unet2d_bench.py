@@ -1,7 +1,8 @@
 """Training-step throughput of the reference's shipped 2-D configurations: forward + BCEDice + backward + FusedAdam, with
 `native_2d: true` (csrc/u3d_conv2d.hip through the DoubleConv executor) and with the default path (the module tree on stock
 PyTorch-ROCm operators, after its one-time warning) in the same process, alternating the two.  --bf16 adds the same step with
-`native_2d_bf16: true` (csrc/u3d_conv2d_bf16.hip for the layers that fit) as a third path in the same alternation (UNet2D configs).
+`native_2d_bf16: true` — on the ResidualUNet2D configurations `native_2d_residual_bf16: true` — (csrc/u3d_conv2d_bf16.hip for the layers
+that fit) as a third path in the same alternation.
 
   confocal  resources/2DUnet_confocal_boundary/train_config.yml: 32 x 1 x 515 x 512, gcr, f_maps 32, 4 levels
   dsb2018   resources/2DUnet_dsb2018/train_config.yml: bcr, f_maps [32, 64, 128], batch 32 — DSB2018 images vary in size;
@@ -103,7 +104,7 @@ def make(cfg, native, dev):
 
     torch.manual_seed(0)
     if native == "bf16":
-        key, native = "native_2d_bf16", True
+        key, native = ("native_2d_residual_bf16" if _residual(cfg) else "native_2d_bf16"), True
     else:
         key = "native_2d_residual" if _residual(cfg) else "native_2d"
     m = get_model(dict(cfg, **{key: native})).to(dev).train()
@@ -137,7 +138,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--rounds", type=int, default=2, help="alternating native / stock rounds of --steps each")
     ap.add_argument("--native-only", action="store_true", help="time the native path only (profiler runs)")
-    ap.add_argument("--bf16", action="store_true", help="also time the step with native_2d_bf16 (UNet2D configs), alternated with the others")
+    ap.add_argument("--bf16", action="store_true", help="also time the step with native_2d_bf16 / native_2d_residual_bf16, alternated with the others")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "unet2d_bench measures on the GPU"
     from pytorch3dunet_amd import _native as nat
@@ -153,7 +154,7 @@ def main():
         x = torch.randn((batch, 1) + hw, generator=g).to(dev)
         target = (torch.rand((batch, 1) + hw, generator=g) > 0.5).float().to(dev)
         paths = [True] if a.native_only else [True, False]
-        if a.bf16 and not _residual(cfg):
+        if a.bf16:
             paths.insert(1, "bf16")
         runs = {p: make(cfg, p, dev) for p in paths}
         for p in paths:
