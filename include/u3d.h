@@ -984,6 +984,51 @@ int u3d_conv2d_wgrad_bf16_variant(int N, int H, int W, int Cin, int Cout);
 int u3d_conv2d_wgrad_bf16(int device, u3d_stream_t stream, const float* x, const float* affine, const float* dz, float* dw, int N,
                           int H, int W, int Cin, int Cout, float* workspace, long long workspace_floats);
 
+/* ---- (Added, U3D_VERSION unchanged.)  bf16-operand ConvTranspose2d of ResidualUNet2D's decoders (`native_2d_residual_bf16_deconv:
+ * true`; csrc/u3d_conv2d_bf16.hip) ------
+ * The bf16 twins of u3d_pack_convtr2d / u3d_convtr2d_fwd / _dgrad / _wgrad on v_mfma_f32_32x32x16_bf16: ConvTranspose2d(k=3, stride=2,
+ * padding=1, bias=False), x (N,H1,W1,Cin) -> t (N,2H1-1,2W1-1,Cout), NHWC fp32 in HBM, master weight (Cin,Cout,3,3) fp32.  Operands
+ * rounded to bf16 (round-to-nearest-even) where the 3x3 family rounds them — the weights when the image is packed, x / dt ONCE while
+ * they are staged into LDS, both x and dt in the weight gradient — products accumulated in FP32; padding and the inserted zeros stay
+ * exactly 0 and are never multiplied.  16-byte aligned pointers.
+ * Envelope: Cin % 32 == 0 and Cout % 32 == 0 (u3d_convtr2d_bf16_supported), any N, H1, W1 >= 1, N*(2H1-1)*(2W1-1) < 2^31 and
+ * 9*Cin*Cout < 2^31 (the limits of u3d_convtr2d_*).  Outside it every entry point below returns U3D_EINVAL (u3d_last_error) without
+ * launching anything.
+ *   u3d_pack_convtr2d_bf16   (Cin,Cout,3,3) fp32 -> image [K / 16 chunk][9 taps][n-tile][64 lanes][8] bf16 of B[k][n], the fragment
+ *              layout of u3d_pack_weights2d_bf16, taps not flipped: mode 0 = forward (B[k = ci][n = co] = w[ci][co][tap]), mode 1 =
+ *              data gradient (B[k = co][n = ci] = w[ci][co][tap]); u3d_packed_convtr2d_bf16_elems() 2-byte elements (0 outside the
+ *              envelope)
+ *   u3d_convtr2d_fwd_bf16    t = conv_transpose2d(bf16(x), bf16(w)) with the mode-0 image, ONE launch in the sub-pixel form: a block
+ *              stages its 16 x 16 input tile plus the right / bottom halo pixel once per 16-channel chunk and produces the four output
+ *              parity classes (1, 2, 2 and 4 taps: 9 multiply-adds per input pixel and channel pair) for 32 output channels; every
+ *              element of t is written exactly once.  One launch plan.
+ *   u3d_convtr2d_dgrad_bf16  dx[i, ci] = sum_{tap, co} bf16(dt[2i - 1 + tap, co]) * bf16(w[ci, co, tap]) with the mode-1 image (dt is
+ *              zero outside [0, 2H1-2] x [0, 2W1-2]); with x_low non-NULL, dx = 0 where x_low <= 0.  16 x 16 dx pixels x 32 or 64
+ *              input channels per block over the 33 x 33 dt halo.
+ *   u3d_convtr2d_wgrad_bf16  dw[ci][co][ky][kx] = sum_i bf16(x[i, ci]) * bf16(dt[2i - 1 + tap, co]) written in the reference layout, or
+ *              added to dw when accumulate.  Blocks own 32 x 32 channels x 9 taps over a range of 8 x 16-pixel tiles; their partial sums
+ *              go through `workspace` and are added in split order: the same inputs (and workspace size) give a bitwise-identical dw.  No
+ *              atomics, no fp64.  workspace: u3d_convtr2d_wgrad_bf16_workspace_floats() floats hold the plan that fills the chip; a
+ *              shorter one, of at least one split (9*Cin*Cout floats), runs as many splits as it holds; less is U3D_EINVAL.
+ * Host-only: which launch plan a shape takes, from the same functions the launches call; -1 outside the envelope.
+ *   u3d_convtr2d_dgrad_bf16_variant  32-channel n-tiles per block: 2 when Cin % 64 == 0, else 1 (shape-only)
+ *   u3d_convtr2d_wgrad_bf16_variant  (tiles per block << 16) | nsplit on the current device (the plan follows its CU count) for a
+ *              workspace of workspace_floats floats (< 0: the full workspace); saturates as u3d_conv2d_wgrad_bf16_variant
+ * No reference counterpart (ATen picks its algorithm behind buildingblocks.py:617-664).  The library never allocates and never
+ * synchronises. */
+int u3d_convtr2d_bf16_supported(int Cin, int Cout);
+long long u3d_packed_convtr2d_bf16_elems(int Cin, int Cout, int mode);
+int u3d_pack_convtr2d_bf16(int device, u3d_stream_t stream, const float* w, int Cin, int Cout, int mode, void* packed);
+int u3d_convtr2d_fwd_bf16(int device, u3d_stream_t stream, const float* x, const void* packed, float* t, int N, int H1, int W1, int Cin,
+                          int Cout);
+int u3d_convtr2d_dgrad_bf16_variant(int N, int H1, int W1, int Cin, int Cout);
+int u3d_convtr2d_dgrad_bf16(int device, u3d_stream_t stream, const float* dt, const void* packed_t, const float* x_low, float* dx, int N,
+                            int H1, int W1, int Cin, int Cout);
+long long u3d_convtr2d_wgrad_bf16_workspace_floats(int N, int H1, int W1, int Cin, int Cout);
+int u3d_convtr2d_wgrad_bf16_variant(int N, int H1, int W1, int Cin, int Cout, long long workspace_floats);
+int u3d_convtr2d_wgrad_bf16(int device, u3d_stream_t stream, const float* x, const float* dt, float* dw, int N, int H1, int W1, int Cin,
+                            int Cout, int accumulate, float* workspace, long long workspace_floats);
+
 /* ---- layout: NCDHW <-> NDHWC for multi-channel model inputs ------------------------------------ */
 int u3d_ncdhw_to_ndhwc(int device, u3d_stream_t stream, const float* src, float* dst, int N, int C, int64_t V);
 int u3d_ndhwc_to_ncdhw(int device, u3d_stream_t stream, const float* src, float* dst, int N, int C, int64_t V);

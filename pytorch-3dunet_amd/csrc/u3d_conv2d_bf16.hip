@@ -729,3 +729,605 @@ extern "C" int u3d_conv2d_wgrad_bf16(int device, u3d_stream_t stream, const floa
     }
     return 0;
 }
+
+// =================================================================================================
+// ConvTranspose2d(k = 3, stride = 2, padding = 1, bias = False) of ResidualUNet2D's decoders on the same MFMA (`native_2d_residual_bf16_deconv:
+// true`): the bf16 twins of u3d_convtr2d_fwd / _dgrad / _wgrad of csrc/u3d_res.hip.  (N,H1,W1,Cin) -> (N,2H1-1,2W1-1,Cout), NHWC fp32 in HBM,
+// master weight (Cin,Cout,3,3); output coordinate s = 2i - 1 + tap per axis, so an even s = 2j takes (input j, tap 1) and an odd s = 2j + 1
+// takes (input j + 1, tap 0) and (input j, tap 2).  Operands are rounded where the 3x3 family rounds them: the weights when the image is
+// packed, x / dt once while they are staged into LDS; fp32 accumulation; padding and the inserted zeros are never multiplied.
+//
+// Forward (convtr2d_fwd_bf16_kernel, sub-pixel form): a block stages its 16 x 16 INPUT tile plus the right / bottom halo pixel (17 x 17,
+// [hy][hx][16 bf16], 35 slots of 16 bytes per row: the odd row stride of the 3x3 kernel, same conflict-free ds_read_b128) once per 16-channel
+// chunk and feeds all four output parity classes from it — 1 + 2 + 2 + 4 = 9 MFMAs per M-tile and chunk, the four distinct A fragments
+// (input offsets (0|1, 0|1)) read once per chunk.  8 accumulators (2 M-tiles x 4 classes) = 128 registers, so a block owns 32 output channels.
+// Every element of t is written exactly once: class (py, px) of input pixel (i, j) is t[2i + py][2j + px], dropped past 2H1 - 2 / 2W1 - 2.
+//
+// Data gradient (convtr2d_dgrad_bf16_kernel<NT>): dx[i] = sum_tap dt[2i - 1 + tap] * w[tap], a stride-2 3x3 convolution of dt.  The
+// 33 x 33 dt halo of a 16 x 16 dx tile is staged DE-INTERLEAVED: halo row / column h sits in slot (h & 1) * 17 + (h >> 1), so the 16 pixels
+// a tap reads at stride 2 are 16 neighbouring slots and neighbouring tile rows are neighbouring LDS rows — the 3x3 kernel's read pattern
+// again (67 slots per row).  One 35 KB buffer (two would not leave two blocks per CU their registers' worth of LDS): the next chunk's halo
+// is in flight in registers during the MFMAs and stored between two barriers.  NT = 2 (64 produced channels per block) when Cin % 64 == 0.
+//
+// Weight gradient (convtr2d_wgrad_bf16_kernel): dw[ci][co][tap] = sum_i x[i, ci] * dt[2i - 1 + tap, co], contraction over INPUT pixels;
+// A = x (8 x 16-pixel tile, [pixel][32 ci]), B = dt (17 x 33 halo, columns de-interleaved as above, [pixel][32 co]), both fetched with
+// the transposed read of the 3x3 weight gradient; 9 accumulators, one x fragment feeds 9 taps.  Partial sums over tile ranges go to the
+// workspace and convtr2d_wgrad_bf16_reduce_kernel adds them in split order (bitwise-reproducible; no atomics, no fp64).
+namespace {
+
+namespace ct2b {
+constexpr int T = 16;                      // tile edge (input pixels forward, dx pixels in the data gradient)
+constexpr int PS = 32;                     // bytes per staged pixel (16 bf16)
+// forward
+constexpr int FH = T + 1;                  // tile + right / bottom halo
+constexpr int FRS = FH * PS + 16;          // 560 bytes per row: 35 slots
+constexpr int FBUF = FH * FRS;             // 9520
+constexpr int FITEMS = FH * FH * 2;        // 578 (pixel, channel octet) items per chunk
+constexpr int FNIT = (FITEMS + 255) / 256; // 3
+constexpr int F_LDS_BYTES = 2 * FBUF;      // 19040 (double-buffered)
+// data gradient
+constexpr int DH = 2 * T + 1;              // 33: dt rows 2 y0 - 1 .. 2 y0 + 31
+constexpr int DODD = T + 1;                // first slot of the odd rows / columns (17 even ones in front)
+constexpr int DRS = DH * PS + 16;          // 1072 bytes per row: 67 slots
+constexpr int DBUF = DH * DRS;             // 35376
+constexpr int DITEMS = DH * DH * 2;        // 2178
+constexpr int DNIT = (DITEMS + 255) / 256; // 9
+constexpr int D_LDS_BYTES = DBUF;
+// weight gradient
+constexpr int WTY = 8;                     // tile rows (x 16 columns)
+constexpr int WHY = 2 * WTY + 1;           // 17 dt rows
+constexpr int WHX = 2 * T + 1;             // 33 dt columns (slots)
+constexpr int WPP = 64;                    // bytes per staged pixel (32 bf16)
+constexpr int W_DT = 0;                    // [17][33][32] bf16
+constexpr int W_X = WHY * WHX * WPP;       // 35904: [8 * 16][32] bf16
+constexpr int W_LDS_BYTES = W_X + WTY * T * WPP;  // 44096 (the final [4][32][32] float reduction reuses the first 16384)
+constexpr int W_DIT = (WHY * WHX * 4 + 255) / 256;  // 9 dt items (pixel, octet) per thread
+constexpr int W_XIT = WTY * T * 4 / 256;            // 2 x items per thread
+constexpr int W_DB = 3, W_XB = 2;                   // items staged per batch
+}  // namespace ct2b
+
+inline bool ct2b_ok(int Cin, int Cout) { return Cin > 0 && Cout > 0 && Cin % 32 == 0 && Cout % 32 == 0; }
+
+// (the limits of convtr2d_dims_ok, csrc/u3d_res.hip)
+inline bool ct2b_dims_ok(int N, int H1, int W1, int Cin, int Cout) {
+    return N > 0 && H1 > 0 && W1 > 0 && Cin > 0 && Cout > 0 && (long long)N * (2LL * H1 - 1) * (2LL * W1 - 1) < (1ll << 31) &&
+           (long long)9 * Cin * Cout < (1ll << 31);
+}
+
+// image [K / 16 chunk][tap][n-tile][lane][8] of B[k][n], the fragment layout of pack_weights2d_bf16_kernel; taps are NOT flipped:
+//   mode 0 (forward): B[k = ci][n = co] = w[ci][co][tap]           mode 1 (data gradient): B[k = co][n = ci] = w[ci][co][tap]
+__global__ void pack_convtr2d_bf16_kernel(const float* __restrict__ w, int Cout, int mode, int ntg, long long total,
+                                          __bf16* __restrict__ packed) {
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const int j = (int)(i & 7);
+        const int lane = (int)((i >> 3) & 63);
+        long long r = i >> 9;
+        const int nt = (int)(r % ntg);
+        r /= ntg;
+        const int tap = (int)(r % 9);
+        const int chunk = (int)(r / 9);
+        const int k = chunk * 16 + 8 * (lane >> 5) + j;
+        const int nn = nt * 32 + (lane & 31);
+        packed[i] = (__bf16)(mode == 0 ? w[((size_t)k * Cout + nn) * 9 + tap] : w[((size_t)nn * Cout + k) * 9 + tap]);
+    }
+}
+
+struct ConvTr2dBf16Params {
+    const float* src;     // forward: x (N,H1,W1,Cin); data gradient: dt (N,Ht,Wt,Cout)
+    const c2b_bf16x8* wp;
+    const float* x_low;   // data gradient: optional ReLU mask (N,H1,W1,Cin)
+    float* out;           // forward: t; data gradient: dx
+    int N, H1, W1, Ht, Wt, Cin, Cout;
+    int nchunks, ntg, ncb, ty, tx;
+};
+
+__global__ __launch_bounds__(256, 2) void convtr2d_fwd_bf16_kernel(const ConvTr2dBf16Params p) {
+    using namespace ct2b;
+    extern __shared__ __attribute__((aligned(16))) char lds_ct2f[];
+    char* const lds = lds_ct2f;
+    const int t = threadIdx.x;
+    const int l = t & 63, w = t >> 6, h = l >> 5, i32 = l & 31;
+    int tile = blockIdx.x;
+    const int cb = tile % p.ntg;
+    tile /= p.ntg;
+    const int txi = tile % p.tx;
+    tile /= p.tx;
+    const int tyi = tile % p.ty;
+    const int n = tile / p.ty;
+    const int y0 = tyi * T, x0 = txi * T;
+    const int H1 = p.H1, W1 = p.W1, Cin = p.Cin;
+
+    int ldsoff[FNIT], gpix[FNIT];  // gpix < 0: outside the image (stays exactly 0)
+#pragma unroll
+    for (int it = 0; it < FNIT; ++it) {
+        const int item = t + 256 * it;
+        const bool in = item < FITEMS;
+        const int pix = item >> 1, q = item & 1;
+        const int hy = pix / FH, hx = pix - (pix / FH) * FH;
+        const int gy = y0 + hy, gxx = x0 + hx;
+        const bool ok = in && gy < H1 && gxx < W1;
+        ldsoff[it] = in ? hy * FRS + hx * PS + 16 * q : -1;
+        gpix[it] = ok ? (n * H1 + gy) * W1 + gxx : -1;
+    }
+    f32x4 raw[FNIT][2];
+    auto load_chunk = [&](int c) {
+#pragma unroll
+        for (int it = 0; it < FNIT; ++it) {
+            raw[it][0] = raw[it][1] = f32x4{0.f, 0.f, 0.f, 0.f};
+            if (gpix[it] >= 0) {
+                const float* src = p.src + (size_t)gpix[it] * Cin + c * 16 + 8 * ((t + 256 * it) & 1);
+                raw[it][0] = u3d_ldq(src);
+                raw[it][1] = u3d_ldq(src + 4);
+            }
+        }
+    };
+    auto store_chunk = [&](char* buf) {
+#pragma unroll
+        for (int it = 0; it < FNIT; ++it)
+            if (ldsoff[it] >= 0)
+                *reinterpret_cast<c2b_bf16x8*>(buf + ldsoff[it]) = c2b_stage8(raw[it][0], raw[it][1], nullptr, gpix[it] >= 0);
+    };
+
+    f32x16 acc[2][4];  // [M-tile][parity class 2 py + px]
+#pragma unroll
+    for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+        for (int cls = 0; cls < 4; ++cls)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[mt][cls][r] = 0.f;
+
+    // A-fragment base: lane (i32, h) of M-tile mt reads input pixel (4w + 2mt + (i32 >> 4), i32 & 15), channels 8h .. 8h + 7
+    const int abase = (4 * w + (i32 >> 4)) * FRS + (i32 & 15) * PS + 16 * h;
+    auto bidx = [&](int c, int tap) -> long long { return ((long long)(c * 9 + tap) * p.ntg + cb) * 64 + l; };
+
+    load_chunk(0);
+    store_chunk(lds);
+    __syncthreads();
+    for (int c = 0; c < p.nchunks; ++c) {
+        const char* cur = lds + (c & 1) * FBUF;
+        if (c + 1 < p.nchunks) load_chunk(c + 1);  // in flight during the MFMAs
+        c2b_bf16x8 a[2][2][2];                     // [input dy][input dx][M-tile]
+#pragma unroll
+        for (int dy = 0; dy < 2; ++dy)
+#pragma unroll
+            for (int dx = 0; dx < 2; ++dx)
+#pragma unroll
+                for (int mt = 0; mt < 2; ++mt)
+                    a[dy][dx][mt] = *reinterpret_cast<const c2b_bf16x8*>(cur + abase + (2 * mt + dy) * FRS + dx * PS);
+        c2b_bf16x8 bq = p.wp[bidx(c, 0)], bn = bq;
+#pragma unroll
+        for (int tap = 0; tap < 9; ++tap) {
+            const int ky = tap / 3, kx = tap - (tap / 3) * 3;
+            if (tap + 1 < 9) bn = p.wp[bidx(c, tap + 1)];
+            // tap 1 serves the even outputs from input +0; taps 0 / 2 serve the odd outputs from inputs +1 / +0
+            const int cls = 2 * (ky != 1) + (kx != 1), dy = ky == 0, dx = kx == 0;
+#pragma unroll
+            for (int mt = 0; mt < 2; ++mt) acc[mt][cls] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[dy][dx][mt], bq, acc[mt][cls], 0, 0, 0);
+            bq = bn;
+        }
+        if (c + 1 < p.nchunks) store_chunk(lds + ((c + 1) & 1) * FBUF);  // (that buffer was last read in chunk c - 1)
+        __syncthreads();
+    }
+
+    // ---- lane column = output channel, register r = M row (r & 3) + 8 (r >> 2) + 4h; class (py, px) of input (i, j) is t[2i + py][2j + px]
+    const int co = cb * 32 + i32;
+#pragma unroll
+    for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+        for (int cls = 0; cls < 4; ++cls)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int row = (r & 3) + 8 * (r >> 2) + 4 * h;
+                const int i = y0 + 4 * w + 2 * mt + (row >> 4), j = x0 + (row & 15);
+                const int oy = 2 * i + (cls >> 1), ox = 2 * j + (cls & 1);
+                if (i >= H1 || j >= W1 || oy >= p.Ht || ox >= p.Wt) continue;
+                p.out[((size_t)(n * p.Ht + oy) * p.Wt + ox) * p.Cout + co] = acc[mt][cls][r];
+            }
+}
+
+template <int NT>
+__global__ __launch_bounds__(256, 2) void convtr2d_dgrad_bf16_kernel(const ConvTr2dBf16Params p) {
+    using namespace ct2b;
+    extern __shared__ __attribute__((aligned(16))) char lds_ct2d[];
+    char* const lds = lds_ct2d;
+    const int t = threadIdx.x;
+    const int l = t & 63, w = t >> 6, h = l >> 5, i32 = l & 31;
+    int tile = blockIdx.x;
+    const int cb = tile % p.ncb;
+    tile /= p.ncb;
+    const int txi = tile % p.tx;
+    tile /= p.tx;
+    const int tyi = tile % p.ty;
+    const int n = tile / p.ty;
+    const int y0 = tyi * T, x0 = txi * T;
+    const int H1 = p.H1, W1 = p.W1, Ht = p.Ht, Wt = p.Wt, K = p.Cout;  // the contraction runs over the layer's Cout
+
+    int ldsoff[DNIT], gpix[DNIT];  // gpix < 0: outside dt (zero)
+#pragma unroll
+    for (int it = 0; it < DNIT; ++it) {
+        const int item = t + 256 * it;
+        const bool in = item < DITEMS;
+        const int pix = item >> 1, q = item & 1;
+        const int hy = pix / DH, hx = pix - (pix / DH) * DH;
+        const int gy = 2 * y0 - 1 + hy, gxx = 2 * x0 - 1 + hx;
+        const bool ok = in && gy >= 0 && gy < Ht && gxx >= 0 && gxx < Wt;
+        ldsoff[it] = in ? ((hy & 1) * DODD + (hy >> 1)) * DRS + ((hx & 1) * DODD + (hx >> 1)) * PS + 16 * q : -1;
+        gpix[it] = ok ? (n * Ht + gy) * Wt + gxx : -1;
+    }
+    f32x4 raw[DNIT][2];
+    auto load_chunk = [&](int c) {
+#pragma unroll
+        for (int it = 0; it < DNIT; ++it) {
+            raw[it][0] = raw[it][1] = f32x4{0.f, 0.f, 0.f, 0.f};
+            if (gpix[it] >= 0) {
+                const float* src = p.src + (size_t)gpix[it] * K + c * 16 + 8 * ((t + 256 * it) & 1);
+                raw[it][0] = u3d_ldq(src);
+                raw[it][1] = u3d_ldq(src + 4);
+            }
+        }
+    };
+    auto store_chunk = [&]() {
+#pragma unroll
+        for (int it = 0; it < DNIT; ++it)
+            if (ldsoff[it] >= 0)
+                *reinterpret_cast<c2b_bf16x8*>(lds + ldsoff[it]) = c2b_stage8(raw[it][0], raw[it][1], nullptr, gpix[it] >= 0);
+    };
+
+    f32x16 acc[2][NT];
+#pragma unroll
+    for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[mt][nt][r] = 0.f;
+
+    // lane (i32, h) of M-tile mt owns dx pixel (ii, jj) = (4w + 2mt + (i32 >> 4), i32 & 15); tap (ty, tx) reads halo (2 ii + ty, 2 jj + tx),
+    // i.e. slot row (ty & 1) * 17 + (ty >> 1) + ii and slot column (tx & 1) * 17 + (tx >> 1) + jj
+    const int abase = (4 * w + (i32 >> 4)) * DRS + (i32 & 15) * PS + 16 * h;
+    auto bidx = [&](int c, int tap, int nt) -> long long { return ((long long)(c * 9 + tap) * p.ntg + (cb * NT + nt)) * 64 + l; };
+
+    load_chunk(0);
+    store_chunk();
+    __syncthreads();
+    for (int c = 0; c < p.nchunks; ++c) {
+        if (c + 1 < p.nchunks) load_chunk(c + 1);  // in flight during the MFMAs
+        c2b_bf16x8 bq[NT], bn[NT];
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) bq[nt] = p.wp[bidx(c, 0, nt)];
+#pragma unroll
+        for (int tap = 0; tap < 9; ++tap) {
+            const int ty = tap / 3, tx = tap - (tap / 3) * 3;
+            if (tap + 1 < 9) {
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt) bn[nt] = p.wp[bidx(c, tap + 1, nt)];
+            }
+            const int toff = ((ty & 1) * DODD + (ty >> 1)) * DRS + ((tx & 1) * DODD + (tx >> 1)) * PS;
+            c2b_bf16x8 a[2];
+#pragma unroll
+            for (int mt = 0; mt < 2; ++mt) a[mt] = *reinterpret_cast<const c2b_bf16x8*>(lds + abase + toff + 2 * mt * DRS);
+#pragma unroll
+            for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt)
+                    acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[mt], bq[nt], acc[mt][nt], 0, 0, 0);
+            if (tap + 1 < 9) {
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt) bq[nt] = bn[nt];
+            }
+        }
+        __syncthreads();  // every wave is done reading the one buffer
+        if (c + 1 < p.nchunks) {
+            store_chunk();
+            __syncthreads();
+        }
+    }
+
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) {
+        const int ci = (cb * NT + nt) * 32 + i32;
+#pragma unroll
+        for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int row = (r & 3) + 8 * (r >> 2) + 4 * h;
+                const int y = y0 + 4 * w + 2 * mt + (row >> 4), x = x0 + (row & 15);
+                if (y >= H1 || x >= W1) continue;
+                const size_t o = ((size_t)(n * H1 + y) * W1 + x) * p.Cin + ci;
+                float v = acc[mt][nt][r];
+                if (p.x_low != nullptr && !(p.x_low[o] > 0.f)) v = 0.f;  // ReLU backward of the block that produced x
+                p.out[o] = v;
+            }
+    }
+}
+
+struct ConvTr2dWgradBf16Params {
+    const float* x;   // (N,H1,W1,Cin)
+    const float* dt;  // (N,Ht,Wt,Cout)
+    float* ws;        // [nsplit][Cin][Cout][9]
+    int N, H1, W1, Ht, Wt, Cin, Cout;
+    int ty, tx, ncob, ncib, ntiles, tps;
+};
+
+__global__ __launch_bounds__(256, 2) void convtr2d_wgrad_bf16_kernel(const ConvTr2dWgradBf16Params p) {
+    using namespace ct2b;
+    extern __shared__ __attribute__((aligned(16))) char lds_ct2w[];
+    char* const lds = lds_ct2w;
+    const int t = threadIdx.x, l = t & 63, w = t >> 6, h = l >> 5, i32 = l & 31;
+    int b = blockIdx.x;
+    const int cob = b % p.ncob;
+    b /= p.ncob;
+    const int cib = b % p.ncib;
+    const int split = b / p.ncib;
+    const int ci0 = cib * 32, co0 = cob * 32;
+    const int tile0 = split * p.tps, tile1 = min(p.ntiles, tile0 + p.tps);
+    const int H1 = p.H1, W1 = p.W1, Ht = p.Ht, Wt = p.Wt, Cin = p.Cin, Cout = p.Cout;
+    char* const dtl = lds + W_DT;
+    char* const xl = lds + W_X;
+
+    f32x16 acc[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[k][r] = 0.f;
+
+    // transposed-read lane offset, as conv2d_wgrad_bf16_kernel: lane l receives channel (l & 31) of the 8 pixels 8 * (l >> 5) .. + 7
+    const int g4 = l >> 4, sidx = l & 15;
+    const int lane_off = (8 * (g4 >> 1) + (sidx >> 2)) * WPP + (16 * (g4 & 1) + 4 * (sidx & 3)) * 2;
+
+    for (int tile = tile0; tile < tile1; ++tile) {
+        int tt = tile;
+        const int txi = tt % p.tx;
+        tt /= p.tx;
+        const int tyi = tt % p.ty;
+        const int n = tt / p.ty;
+        const int y0 = tyi * WTY, x0 = txi * T;
+        // stage dt (17 x 33 halo from (2 y0 - 1, 2 x0 - 1), 32 channels from co0, columns de-interleaved, zero outside) and x (8 x 16, 32
+        // channels from ci0), a few items at a time: the 9 accumulators leave ~100 registers for the staging
+        auto stage_dt = [&](int it0) {
+            f32x4 rg[W_DB][2];
+            bool okg[W_DB];
+#pragma unroll
+            for (int k = 0; k < W_DB; ++k) {
+                const int item = t + 256 * (it0 + k);
+                const int pix = item >> 2, q = item & 3;
+                const int hy = pix / WHX, hx = pix - (pix / WHX) * WHX;
+                const int gy = 2 * y0 - 1 + hy, gxx = 2 * x0 - 1 + hx;
+                okg[k] = item < WHY * WHX * 4 && gy >= 0 && gy < Ht && gxx >= 0 && gxx < Wt;
+                rg[k][0] = rg[k][1] = f32x4{0.f, 0.f, 0.f, 0.f};
+                if (okg[k]) {
+                    const float* src = p.dt + ((size_t)(n * Ht + gy) * Wt + gxx) * Cout + co0 + 8 * q;
+                    rg[k][0] = u3d_ldq(src);
+                    rg[k][1] = u3d_ldq(src + 4);
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < W_DB; ++k) {
+                const int item = t + 256 * (it0 + k);
+                if (item >= WHY * WHX * 4) continue;
+                const int pix = item >> 2, q = item & 3;
+                const int hy = pix / WHX, hx = pix - (pix / WHX) * WHX;
+                *reinterpret_cast<c2b_bf16x8*>(dtl + (hy * WHX + (hx & 1) * DODD + (hx >> 1)) * WPP + 16 * q) =
+                    c2b_stage8(rg[k][0], rg[k][1], nullptr, okg[k]);
+            }
+        };
+        auto stage_x = [&](int it0) {
+            f32x4 rd[W_XB][2];
+            bool okd[W_XB];
+#pragma unroll
+            for (int k = 0; k < W_XB; ++k) {
+                const int item = t + 256 * (it0 + k);
+                const int pix = item >> 2, q = item & 3;
+                const int y = y0 + (pix >> 4), x = x0 + (pix & 15);
+                okd[k] = y < H1 && x < W1;
+                rd[k][0] = rd[k][1] = f32x4{0.f, 0.f, 0.f, 0.f};
+                if (okd[k]) {
+                    const float* src = p.x + ((size_t)(n * H1 + y) * W1 + x) * Cin + ci0 + 8 * q;
+                    rd[k][0] = u3d_ldq(src);
+                    rd[k][1] = u3d_ldq(src + 4);
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < W_XB; ++k) {
+                const int item = t + 256 * (it0 + k);
+                *reinterpret_cast<c2b_bf16x8*>(xl + (item >> 2) * WPP + 16 * (item & 3)) = c2b_stage8(rd[k][0], rd[k][1], nullptr, okd[k]);
+            }
+        };
+        for (int it0 = 0; it0 < W_DIT; it0 += W_DB) stage_dt(it0);
+        for (int it0 = 0; it0 < W_XIT; it0 += W_XB) stage_x(it0);
+        __syncthreads();
+        // wave w: rows 2w, 2w + 1 of the tile, one 16-pixel row per k-step; tap (ty, tx) pairs input (py, jj) with dt halo (2 py + ty, 2 jj + tx)
+#pragma unroll 1
+        for (int r = 0; r < 2; ++r) {
+            const int py = 2 * w + r;
+            const c2b_bf16x8 a = c2b_tr_frag(xl + py * T * WPP + lane_off);
+#pragma unroll
+            for (int ty = 0; ty < 3; ++ty)
+#pragma unroll
+                for (int tx = 0; tx < 3; ++tx) {
+                    const c2b_bf16x8 g = c2b_tr_frag(dtl + ((2 * py + ty) * WHX + (tx & 1) * DODD + (tx >> 1)) * WPP + lane_off);
+                    acc[ty * 3 + tx] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, g, acc[ty * 3 + tx], 0, 0, 0);
+                }
+        }
+        __syncthreads();
+    }
+
+    // ---- add the 4 waves' partial sums in a fixed order, one tap at a time, through LDS; write [ci][co][tap] of this split
+    float* red = reinterpret_cast<float*>(lds);  // [4][32][32]
+    float* const dst = p.ws + (size_t)split * Cin * Cout * 9;
+#pragma unroll
+    for (int tap = 0; tap < 9; ++tap) {  // (unrolled: acc[tap] must stay a register index)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int row = (r & 3) + 8 * (r >> 2) + 4 * h;  // input channel within the block
+            red[(w * 32 + row) * 32 + i32] = acc[tap][r];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int idx = t + 256 * e;  // (row, col) of the 32 x 32 tile
+            const int row = idx >> 5, col = idx & 31;
+            const float v = ((red[(0 * 32 + row) * 32 + col] + red[(1 * 32 + row) * 32 + col]) + red[(2 * 32 + row) * 32 + col]) +
+                            red[(3 * 32 + row) * 32 + col];
+            dst[((size_t)(ci0 + row) * Cout + co0 + col) * 9 + tap] = v;
+        }
+        __syncthreads();
+    }
+}
+
+// dw[i] = [dw[i] +] sum over splits in split order (bitwise-reproducible)
+__global__ void convtr2d_wgrad_bf16_reduce_kernel(const float* __restrict__ ws, int nsplit, long long total, int accumulate,
+                                                  float* __restrict__ dw) {
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        float v = 0.f;
+        for (int s = 0; s < nsplit; ++s) v += ws[(size_t)s * total + i];
+        dw[i] = accumulate ? dw[i] + v : v;
+    }
+}
+
+// data gradient: 64 produced channels per block whenever they divide evenly (shape-only: no device in this plan)
+inline int ct2b_dgrad_nt(int Cin) { return Cin % 64 == 0 ? 2 : 1; }
+
+struct Ct2bWPlan {
+    int ty, tx, ncob, ncib, ntiles, tps, nsplit;
+};
+
+// the plan fills the chip (~4 blocks per CU); a launch takes as many of its splits as the caller's workspace holds (at least one).
+// ONE function for the launcher, the workspace size and the host-only query.  max_splits <= 0: no cap.
+Ct2bWPlan ct2b_wplan(int device, int N, int H1, int W1, int Cin, int Cout, long long max_splits) {
+    Ct2bWPlan pl;
+    pl.ty = (int)c2b_cdiv(H1, ct2b::WTY);
+    pl.tx = (int)c2b_cdiv(W1, ct2b::T);
+    pl.ncob = Cout / 32;
+    pl.ncib = Cin / 32;
+    pl.ntiles = N * pl.ty * pl.tx;
+    const long long cells = (long long)pl.ncob * pl.ncib;
+    const long long target = 4LL * c2b_cu_count(device);
+    long long ns = std::max<long long>(1, std::min<long long>(pl.ntiles, c2b_cdiv(target, cells)));
+    if (max_splits > 0) ns = std::min(ns, max_splits);
+    pl.tps = (int)c2b_cdiv(pl.ntiles, ns);
+    pl.nsplit = (int)c2b_cdiv(pl.ntiles, pl.tps);
+    return pl;
+}
+
+inline long long ct2b_splits_in(long long workspace_floats, int Cin, int Cout) { return workspace_floats / ((long long)9 * Cin * Cout); }
+
+}  // namespace
+
+extern "C" int u3d_convtr2d_bf16_supported(int Cin, int Cout) { return ct2b_ok(Cin, Cout) ? 1 : 0; }
+
+extern "C" long long u3d_packed_convtr2d_bf16_elems(int Cin, int Cout, int mode) {
+    if ((mode != 0 && mode != 1) || !ct2b_ok(Cin, Cout) || (long long)9 * Cin * Cout >= (1ll << 31)) return 0;
+    return (long long)9 * Cin * Cout;  // [K / 16][9][Nn / 32][64][8]
+}
+
+extern "C" int u3d_pack_convtr2d_bf16(int device, u3d_stream_t stream, const float* w, int Cin, int Cout, int mode, void* packed) {
+    U3D_ENTER(device);
+    U3D_REQUIRE(w && packed && (mode == 0 || mode == 1), "u3d_pack_convtr2d_bf16: bad argument");
+    U3D_REQUIRE(ct2b_ok(Cin, Cout) && (long long)9 * Cin * Cout < (1ll << 31),
+                "u3d_pack_convtr2d_bf16: (%d -> %d) channels are outside the bf16 envelope (both %% 32)", Cin, Cout);
+    U3D_REQUIRE(c2b_aligned(packed), "u3d_pack_convtr2d_bf16: the image must be 16-byte aligned");
+    const long long total = (long long)9 * Cin * Cout;
+    long long blocks = c2b_cdiv(total, 256);
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(pack_convtr2d_bf16_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, w, Cout, mode,
+                       (mode == 0 ? Cout : Cin) / 32, total, reinterpret_cast<__bf16*>(packed));
+    U3D_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int u3d_convtr2d_fwd_bf16(int device, u3d_stream_t stream, const float* x, const void* packed, float* t, int N, int H1, int W1,
+                                     int Cin, int Cout) {
+    U3D_ENTER(device);
+    U3D_REQUIRE(ct2b_ok(Cin, Cout), "u3d_convtr2d_fwd_bf16: (%d -> %d) channels are outside the bf16 envelope (both %% 32)", Cin, Cout);
+    U3D_REQUIRE(x && packed && t, "u3d_convtr2d_fwd_bf16: bad argument");
+    U3D_REQUIRE(ct2b_dims_ok(N, H1, W1, Cin, Cout), "u3d_convtr2d_fwd_bf16: bad sizes (the output pixel count must be < 2^31)");
+    U3D_REQUIRE(c2b_aligned(x) && c2b_aligned(packed) && c2b_aligned(t), "u3d_convtr2d_fwd_bf16: pointers must be 16-byte aligned");
+    ConvTr2dBf16Params p = {};
+    p.src = x;
+    p.wp = reinterpret_cast<const c2b_bf16x8*>(packed);
+    p.out = t;
+    p.N = N, p.H1 = H1, p.W1 = W1, p.Ht = 2 * H1 - 1, p.Wt = 2 * W1 - 1, p.Cin = Cin, p.Cout = Cout;
+    p.nchunks = Cin / 16, p.ntg = Cout / 32, p.ncb = p.ntg;
+    p.ty = (int)c2b_cdiv(H1, ct2b::T), p.tx = (int)c2b_cdiv(W1, ct2b::T);
+    const long long blocks = (long long)N * p.ty * p.tx * p.ncb;
+    U3D_REQUIRE(blocks < (1LL << 31), "u3d_convtr2d_fwd_bf16: grid too large");
+    hipLaunchKernelGGL(convtr2d_fwd_bf16_kernel, dim3((unsigned)blocks), dim3(256), ct2b::F_LDS_BYTES, (hipStream_t)stream, p);
+    U3D_LAUNCH_CHECK();
+    return 0;
+}
+
+// host-only: 32-channel n-tiles per data-gradient block (1 or 2), from the function the launch calls; -1 outside the envelope
+extern "C" int u3d_convtr2d_dgrad_bf16_variant(int N, int H1, int W1, int Cin, int Cout) {
+    if (!ct2b_ok(Cin, Cout) || !ct2b_dims_ok(N, H1, W1, Cin, Cout)) return -1;
+    return ct2b_dgrad_nt(Cin);
+}
+
+extern "C" int u3d_convtr2d_dgrad_bf16(int device, u3d_stream_t stream, const float* dt, const void* packed_t, const float* x_low,
+                                       float* dx, int N, int H1, int W1, int Cin, int Cout) {
+    U3D_ENTER(device);
+    U3D_REQUIRE(ct2b_ok(Cin, Cout), "u3d_convtr2d_dgrad_bf16: (%d -> %d) channels are outside the bf16 envelope (both %% 32)", Cin, Cout);
+    U3D_REQUIRE(dt && packed_t && dx, "u3d_convtr2d_dgrad_bf16: bad argument");
+    U3D_REQUIRE(ct2b_dims_ok(N, H1, W1, Cin, Cout), "u3d_convtr2d_dgrad_bf16: bad sizes (the output pixel count must be < 2^31)");
+    U3D_REQUIRE(c2b_aligned(dt) && c2b_aligned(packed_t) && c2b_aligned(dx), "u3d_convtr2d_dgrad_bf16: pointers must be 16-byte aligned");
+    const int nt = ct2b_dgrad_nt(Cin);
+    ConvTr2dBf16Params p = {};
+    p.src = dt;
+    p.wp = reinterpret_cast<const c2b_bf16x8*>(packed_t);
+    p.x_low = x_low;
+    p.out = dx;
+    p.N = N, p.H1 = H1, p.W1 = W1, p.Ht = 2 * H1 - 1, p.Wt = 2 * W1 - 1, p.Cin = Cin, p.Cout = Cout;
+    p.nchunks = Cout / 16, p.ntg = Cin / 32, p.ncb = p.ntg / nt;
+    p.ty = (int)c2b_cdiv(H1, ct2b::T), p.tx = (int)c2b_cdiv(W1, ct2b::T);
+    const long long blocks = (long long)N * p.ty * p.tx * p.ncb;
+    U3D_REQUIRE(blocks < (1LL << 31), "u3d_convtr2d_dgrad_bf16: grid too large");
+    if (nt == 2)
+        hipLaunchKernelGGL(convtr2d_dgrad_bf16_kernel<2>, dim3((unsigned)blocks), dim3(256), ct2b::D_LDS_BYTES, (hipStream_t)stream, p);
+    else
+        hipLaunchKernelGGL(convtr2d_dgrad_bf16_kernel<1>, dim3((unsigned)blocks), dim3(256), ct2b::D_LDS_BYTES, (hipStream_t)stream, p);
+    U3D_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" long long u3d_convtr2d_wgrad_bf16_workspace_floats(int N, int H1, int W1, int Cin, int Cout) {
+    if (!ct2b_ok(Cin, Cout) || !ct2b_dims_ok(N, H1, W1, Cin, Cout)) return 0;
+    return (long long)ct2b_wplan(c2b_current_device(), N, H1, W1, Cin, Cout, 0).nsplit * 9 * Cin * Cout;
+}
+
+// host-only: (tiles per block << 16) | nsplit of the launch a workspace of that many floats gets (< 0: the full workspace); -1 outside
+// the envelope or for a workspace shorter than one split
+extern "C" int u3d_convtr2d_wgrad_bf16_variant(int N, int H1, int W1, int Cin, int Cout, long long workspace_floats) {
+    if (!ct2b_ok(Cin, Cout) || !ct2b_dims_ok(N, H1, W1, Cin, Cout)) return -1;
+    const long long cap = workspace_floats < 0 ? 0 : ct2b_splits_in(workspace_floats, Cin, Cout);
+    if (workspace_floats >= 0 && cap < 1) return -1;
+    const Ct2bWPlan pl = ct2b_wplan(c2b_current_device(), N, H1, W1, Cin, Cout, cap);
+    return (std::min(pl.tps, 0x7fff) << 16) | std::min(pl.nsplit, 0xffff);
+}
+
+extern "C" int u3d_convtr2d_wgrad_bf16(int device, u3d_stream_t stream, const float* x, const float* dt, float* dw, int N, int H1, int W1,
+                                       int Cin, int Cout, int accumulate, float* workspace, long long workspace_floats) {
+    U3D_ENTER(device);
+    U3D_REQUIRE(ct2b_ok(Cin, Cout), "u3d_convtr2d_wgrad_bf16: (%d -> %d) channels are outside the bf16 envelope (both %% 32)", Cin, Cout);
+    U3D_REQUIRE(x && dt && dw && workspace, "u3d_convtr2d_wgrad_bf16: bad argument");
+    U3D_REQUIRE(ct2b_dims_ok(N, H1, W1, Cin, Cout), "u3d_convtr2d_wgrad_bf16: bad sizes (the output pixel count must be < 2^31)");
+    U3D_REQUIRE(c2b_aligned(x) && c2b_aligned(dt), "u3d_convtr2d_wgrad_bf16: pointers must be 16-byte aligned");
+    const long long total = (long long)9 * Cin * Cout;
+    const long long cap = ct2b_splits_in(workspace_floats, Cin, Cout);
+    U3D_REQUIRE(cap >= 1, "u3d_convtr2d_wgrad_bf16: workspace too small (%lld < %lld floats, one split)", workspace_floats, total);
+    const Ct2bWPlan pl = ct2b_wplan(device, N, H1, W1, Cin, Cout, cap);
+    ConvTr2dWgradBf16Params p = {};
+    p.x = x;
+    p.dt = dt;
+    p.ws = workspace;
+    p.N = N, p.H1 = H1, p.W1 = W1, p.Ht = 2 * H1 - 1, p.Wt = 2 * W1 - 1, p.Cin = Cin, p.Cout = Cout;
+    p.ty = pl.ty, p.tx = pl.tx, p.ncob = pl.ncob, p.ncib = pl.ncib, p.ntiles = pl.ntiles, p.tps = pl.tps;
+    const long long blocks = (long long)pl.nsplit * pl.ncob * pl.ncib;
+    U3D_REQUIRE(blocks < (1LL << 31), "u3d_convtr2d_wgrad_bf16: grid too large");
+    hipLaunchKernelGGL(convtr2d_wgrad_bf16_kernel, dim3((unsigned)blocks), dim3(256), ct2b::W_LDS_BYTES, (hipStream_t)stream, p);
+    U3D_LAUNCH_CHECK();
+    long long rb = c2b_cdiv(total, 256);
+    if (rb > 4096) rb = 4096;
+    hipLaunchKernelGGL(convtr2d_wgrad_bf16_reduce_kernel, dim3((unsigned)rb), dim3(256), 0, (hipStream_t)stream, workspace, pl.nsplit, total,
+                       accumulate ? 1 : 0, dw);
+    U3D_LAUNCH_CHECK();
+    return 0;
+}

@@ -274,6 +274,12 @@ class ConvLayers:
         """`_bf16_routed_weight` for a layer about to run on `src`"""
         return self._bf16_routed_weight(src.C, Cout, src.t1 is not None)
 
+    def _bf16_convtr2d(self, Cin: int, Cout: int) -> bool:
+        """THE rule for a decoder's ConvTranspose2d under `native_2d_residual_bf16_deconv`, stated once: forward, data gradient and weight
+        gradient run on the bf16 u3d_convtr2d_*_bf16 kernels when both channel counts are multiples of 32 (their envelope).  Asked by the
+        residual executor's forward (which image kind, which entry point) and backward (entry points, scratch size)."""
+        return self.bf16_deconv and Cin % 32 == 0 and Cout % 32 == 0
+
     def _split_fwd(self, Cin: int, Cout: int) -> bool:
         return self.split and Cin % 16 == 0 and Cout % 32 == 0
 

@@ -37,7 +37,8 @@ class ResUNetEngine(UNet3DEngine):
     u3d_maxpool2d_* twins and the decoders ConvTranspose2d (u3d_convtr2d_*) before the same joining kernels at D = 1; the t8 and
     sub-pixel branches stay off.  Under `native_2d_residual_bf16` conv2 / conv3 of the blocks whose width is a multiple of 32 take the
     `conv2d_bf16` family in all three directions (`_bf16_routed`; u3d_conv2d_bf16_res fuses `out += residual`); the 1x1 convolutions,
-    ConvTranspose2d and every activation tensor stay fp32."""
+    ConvTranspose2d and every activation tensor stay fp32.  `native_2d_residual_bf16_deconv` adds the decoders' ConvTranspose2d whose
+    channel counts are both multiples of 32 (`_bf16_convtr2d`; u3d_convtr2d_*_bf16): t, the resize + join and the tape are unchanged."""
 
     def __init__(self, model):
         super().__init__(model)
@@ -292,7 +293,10 @@ class ResUNetEngine(UNet3DEngine):
                 cur = self._block_fwd(bm, f"dec{j}", joined, j_st, pool, tape, dev)
                 continue
             t = _empty((Nl, Dt, Ht, Wt, Ct), dtype=_F32, device=dev)
-            if self.is2d:  # ConvTranspose2d: four parity-class gather GEMMs (D1 = Dt = 1)
+            if self.is2d and self._bf16_convtr2d(Cl, Ct):  # ... on the bf16 matrix pipe: one sub-pixel launch
+                nat.call("u3d_convtr2d_fwd_bf16", dev.index, _stream(dev), _p(cur), _p(self.images.get(ct.weight, Kind.CONVTR2D_BF16_FWD, dev)),
+                         _p(t), Nl, H1, W1, Cl, Ct, flops=4.5 * Cl * Ct * Nl * Ht * Wt)
+            elif self.is2d:  # ConvTranspose2d: four parity-class gather GEMMs (D1 = Dt = 1)
                 nat.call("u3d_convtr2d_fwd", dev.index, _stream(dev), _p(cur), _p(self.images.get(ct.weight, Kind.CONVTR2D_FWD, dev)), _p(t), Nl,
                          H1, W1, Cl, Ct, flops=4.5 * Cl * Ct * Nl * Ht * Wt)
             elif self.subpixel and Cl % 4 == 0 and Ct % 4 == 0:
@@ -483,6 +487,16 @@ class ResUNetEngine(UNet3DEngine):
             dt = _empty((Nl, Dt, Ht, Wt, Cs), dtype=_F32, device=dev)
             nat.call("u3d_nearest_sum_bwd", dev.index, _stream(dev), _p(dj), _p(lz), _p(ly), _p(lx), Nl, Ds, Hs, Ws, Dt, Ht, Wt,
                      Cs, _p(dt))
+            if self.is2d and self._bf16_convtr2d(Cl, Cs):  # bf16 operands: dw through the fp32 scratch in a fixed order, then dx
+                wsb = cx.ensure_ws(nat.get_lib().u3d_convtr2d_wgrad_bf16_workspace_floats(Nl, H1, W1, Cl, Cs))
+                nat.call("u3d_convtr2d_wgrad_bf16", dev.index, _stream(dev), _p(xl), _p(dt), _p(gview(self._pindex[id(up.weight)])), Nl, H1,
+                         W1, Cl, Cs, 0, _p(wsb), wsb.numel(), flops=4.5 * Cl * Cs * Nl * Ht * Wt)
+                dxl = _empty_like(xl)
+                nat.call("u3d_convtr2d_dgrad_bf16", dev.index, _stream(dev), _p(dt), _p(self.images.get(up.weight, Kind.CONVTR2D_BF16_DGRAD, dev)),
+                         _p(xl) if mk else None, _p(dxl), Nl, H1, W1, Cl, Cs, flops=4.5 * Cl * Cs * Nl * Ht * Wt)
+                del dt
+                dz = dxl
+                continue
             acc = pool.take(up.weight.numel())
             if self.is2d:  # ConvTranspose2d: dw (double sums in `acc`, written into the flat gradient), then dx masked by x_low > 0
                 nat.call("u3d_convtr2d_wgrad", dev.index, _stream(dev), _p(xl), _p(dt), _p(gview(self._pindex[id(up.weight)])), Nl, H1,

@@ -50,6 +50,9 @@ class UNet3DEngine(ConvLayers):
         # encoder blocks in backward instead of keeping their intermediates.  Set through the model
         # (`compute_dtype: bf16`, `checkpoint_encoders: true` in the YAML's model section, or U3D_BF16=1 / U3D_CHECKPOINT=1).
         self.bf16 = bool(getattr(model, "compute_bf16", False))
+        # opt-in `native_2d_residual_bf16_deconv` (a ResidualUNet2D in bf16): the decoders' ConvTranspose2d on the bf16 matrix pipe too
+        # (`_bf16_convtr2d`)
+        self.bf16_deconv = self.is2d and self.bf16 and bool(getattr(model, "native_2d_residual_bf16_deconv", False))
         # opt-in `compute_dtype: fp32_split`: FP32-grade convolutions on the bf16 matrix pipe — every fp32 operand split exactly
         # into three bf16 values, six partial products per multiply accumulated in fp32 (csrc/u3d_bf16.hip, u3d_conv3d_f32s);
         # forward and data gradients only, weight gradients stay on the fp32 MFMA kernels

@@ -46,6 +46,8 @@ class Kind(enum.IntEnum):
     CONVTR2D_DGRAD = enum.auto()
     BF16_FWD2D = enum.auto()    # ... of a 2-D net in bf16 (`native_2d_bf16`, `native_2d_residual_bf16`): the layers the bf16 kernels cover
     BF16_DGRAD2D = enum.auto()
+    CONVTR2D_BF16_FWD = enum.auto()    # ConvTranspose2d on the bf16 kernels (`native_2d_residual_bf16_deconv`): B[ci][co] per tap ...
+    CONVTR2D_BF16_DGRAD = enum.auto()  # ... B[co][ci] per tap
 
 
 @dataclass(frozen=True)
@@ -67,6 +69,7 @@ _taps = lambda lib, ci, co, m: 27 * ci * co  # noqa: E731
 _2d = lambda lib, ci, co, m: lib.u3d_packed_weight2d_floats(ci, co, m)  # noqa: E731
 _tr2d = lambda lib, ci, co, m: lib.u3d_convtr2d_packed_floats(ci, co)  # noqa: E731
 _2db = lambda lib, ci, co, m: lib.u3d_packed_weight2d_bf16_elems(ci, co, m)  # noqa: E731
+_tr2db = lambda lib, ci, co, m: lib.u3d_packed_convtr2d_bf16_elems(ci, co, m)  # noqa: E731
 
 # the C-ABI mode numbers of include/u3d.h live in this table (and `_BF16_BOTH`) and nowhere else in the package
 _KINDS = {
@@ -94,6 +97,8 @@ _KINDS = {
     Kind.CONVTR2D_DGRAD: _Spec(_tr2d, _F32, "u3d_pack_convtr2d", 1, transposed=True),
     Kind.BF16_FWD2D: _Spec(_2db, _BF16, "u3d_pack_weights2d_bf16", 0),
     Kind.BF16_DGRAD2D: _Spec(_2db, _BF16, "u3d_pack_weights2d_bf16", 1),
+    Kind.CONVTR2D_BF16_FWD: _Spec(_tr2db, _BF16, "u3d_pack_convtr2d_bf16", 0, transposed=True),
+    Kind.CONVTR2D_BF16_DGRAD: _Spec(_tr2db, _BF16, "u3d_pack_convtr2d_bf16", 1, transposed=True),
 }
 _BF16_BOTH = 6  # batch row that writes BF16_FWD and, right behind it in one buffer, BF16_DGRAD from one read of the weight
 

@@ -488,6 +488,17 @@ _PROTOS = {
     "u3d_conv2d_wgrad_bf16_variant": (c_int, [c_int, c_int, c_int, c_int, c_int]),
     "u3d_conv2d_wgrad_bf16": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
                                       c_void_p, c_int64]),
+    # bf16-operand ConvTranspose2d (csrc/u3d_conv2d_bf16.hip)
+    "u3d_convtr2d_bf16_supported": (c_int, [c_int, c_int]),
+    "u3d_packed_convtr2d_bf16_elems": (c_int64, [c_int, c_int, c_int]),
+    "u3d_pack_convtr2d_bf16": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "u3d_convtr2d_fwd_bf16": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int]),
+    "u3d_convtr2d_dgrad_bf16_variant": (c_int, [c_int, c_int, c_int, c_int, c_int]),
+    "u3d_convtr2d_dgrad_bf16": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int]),
+    "u3d_convtr2d_wgrad_bf16_workspace_floats": (c_int64, [c_int, c_int, c_int, c_int, c_int]),
+    "u3d_convtr2d_wgrad_bf16_variant": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int64]),
+    "u3d_convtr2d_wgrad_bf16": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                                        c_int64]),
     "u3d_maxpool2d_fwd": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "u3d_maxpool2d_bwd_merge": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                                         c_int, c_int, c_void_p]),

@@ -44,7 +44,8 @@ class AbstractUNet(nn.Module):
                  num_groups=8, num_levels=4, is_segmentation=True, conv_kernel_size=3, pool_kernel_size=2,
                  conv_padding=1, conv_upscale=2, upsample="default", dropout_prob=0.1, is3d=True, compute_dtype=None,
                  checkpoint_encoders=None, hip_graph=None, activation_dtype=None, checkpoint_levels=None,
-                 native_2d=None, native_2d_residual=None, native_2d_bf16=None, native_2d_residual_bf16=None):
+                 native_2d=None, native_2d_residual=None, native_2d_bf16=None, native_2d_residual_bf16=None,
+                 native_2d_residual_bf16_deconv=None):
         super().__init__()
         if isinstance(f_maps, int):
             f_maps = number_of_features_per_level(f_maps, num_levels=num_levels)
@@ -83,10 +84,18 @@ class AbstractUNet(nn.Module):
         # warning path
         if native_2d_residual_bf16 is None:
             native_2d_residual_bf16 = os.environ.get("U3D_NATIVE_2D_RESIDUAL_BF16", "0") == "1"
-        res2d_bf16 = bool(native_2d_residual_bf16) and not is3d and basic_module is ResNetBlock
+        # `native_2d_residual_bf16_deconv: true` (a separate key, so that native_2d_residual_bf16 alone stays bit-identical;
+        # U3D_NATIVE_2D_RESIDUAL_BF16_DECONV=1 sets its default): in addition the decoders' ConvTranspose2d whose channel counts are both
+        # multiples of 32 run forward, data gradient and weight gradient with bf16 operands (u3d_convtr2d_*_bf16).  It implies
+        # native_2d_residual_bf16 and everything that key implies; every other class ignores it
+        if native_2d_residual_bf16_deconv is None:
+            native_2d_residual_bf16_deconv = os.environ.get("U3D_NATIVE_2D_RESIDUAL_BF16_DECONV", "0") == "1"
+        res2d_bf16_deconv = bool(native_2d_residual_bf16_deconv) and not is3d and basic_module is ResNetBlock
+        res2d_bf16 = (bool(native_2d_residual_bf16) or res2d_bf16_deconv) and not is3d and basic_module is ResNetBlock
         if res2d_bf16:
+            key = "native_2d_residual_bf16_deconv" if res2d_bf16_deconv else "native_2d_residual_bf16"
             if compute_dtype is not None and str(compute_dtype).lower() not in ("bf16", "bfloat16"):
-                raise ValueError(f"u3d: native_2d_residual_bf16 runs bf16 operands; compute_dtype {compute_dtype!r} contradicts it — drop "
+                raise ValueError(f"u3d: {key} runs bf16 operands; compute_dtype {compute_dtype!r} contradicts it — drop "
                                  "one of the two keys (native_2d_residual: true is the fp32 2-D path)")
             native_2d_residual, compute_dtype = True, "bf16"
         res2d = bool(native_2d_residual) and not is3d and basic_module is ResNetBlock
@@ -108,6 +117,7 @@ class AbstractUNet(nn.Module):
         self.native_2d = bool(native_2d) and not is3d
         self.native_2d_bf16 = bf16_2d
         self.native_2d_residual_bf16 = res2d_bf16
+        self.native_2d_residual_bf16_deconv = res2d_bf16_deconv
         reasons = []
         if not is3d and not self.native_2d:
             reasons.append("2-D model")
@@ -343,7 +353,8 @@ def _variant(name, basic_module, default_levels, is3d, doc):
                               hip_graph=kwargs.get("hip_graph"), activation_dtype=kwargs.get("activation_dtype"),
                               checkpoint_levels=kwargs.get("checkpoint_levels"), native_2d=kwargs.get("native_2d"),
                               native_2d_residual=kwargs.get("native_2d_residual"), native_2d_bf16=kwargs.get("native_2d_bf16"),
-                              native_2d_residual_bf16=kwargs.get("native_2d_residual_bf16"))
+                              native_2d_residual_bf16=kwargs.get("native_2d_residual_bf16"),
+                              native_2d_residual_bf16_deconv=kwargs.get("native_2d_residual_bf16_deconv"))
 
     return type(name, (AbstractUNet,), {"__init__": __init__, "__doc__": doc, "__module__": _THIS_MODULE})
 

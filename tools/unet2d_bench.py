@@ -2,7 +2,8 @@
 `native_2d: true` (csrc/u3d_conv2d.hip through the DoubleConv executor) and with the default path (the module tree on stock
 PyTorch-ROCm operators, after its one-time warning) in the same process, alternating the two.  --bf16 adds the same step with
 `native_2d_bf16: true` — on the ResidualUNet2D configurations `native_2d_residual_bf16: true` — (csrc/u3d_conv2d_bf16.hip for the layers
-that fit) as a third path in the same alternation.
+that fit) as a third path in the same alternation, and on the ResidualUNet2D configurations `native_2d_residual_bf16_deconv: true` (the
+decoders' ConvTranspose2d on u3d_convtr2d_*_bf16 as well) as a fourth.
 
   confocal  resources/2DUnet_confocal_boundary/train_config.yml: 32 x 1 x 515 x 512, gcr, f_maps 32, 4 levels
   dsb2018   resources/2DUnet_dsb2018/train_config.yml: bcr, f_maps [32, 64, 128], batch 32 — DSB2018 images vary in size;
@@ -18,7 +19,9 @@ launches that declare them) as a fraction of the fp32 MFMA peak of 157.3 TFLOP/s
 
 With --bf16 the record adds the bf16 path's ms per step, images/s, its speed-up over the native fp32 step of the same process, and its
 own conv2d family by entry point (the bf16 entry points' rate as TFLOP/s on executed FLOPs; the bf16 MFMA peak to hold it against is
-measured with tools/mfma_bf16_peak.hip).
+measured with tools/mfma_bf16_peak.hip).  The ResidualUNet2D records add the deconv arm's ms per step, its speed-up over the
+native_2d_residual_bf16 arm of the same run, and the transposed-convolution family of both arms by entry point (fp32 u3d_convtr2d_* in
+the bf16 arm, u3d_convtr2d_*_bf16 in the deconv arm: ms per step and TFLOP/s on executed FLOPs).
 
   python tools/unet2d_bench.py [--configs confocal,dsb2018] [--batch N] [--steps 10] [--warmup 3] [--bf16]   (--batch: every config's own default)"""
 import argparse
@@ -103,7 +106,9 @@ def make(cfg, native, dev):
     from pytorch3dunet_amd.unet3d.model import get_model
 
     torch.manual_seed(0)
-    if native == "bf16":
+    if native == "bf16_deconv":
+        key, native = "native_2d_residual_bf16_deconv", True
+    elif native == "bf16":
         key, native = ("native_2d_residual_bf16" if _residual(cfg) else "native_2d_bf16"), True
     else:
         key = "native_2d_residual" if _residual(cfg) else "native_2d"
@@ -156,6 +161,8 @@ def main():
         paths = [True] if a.native_only else [True, False]
         if a.bf16:
             paths.insert(1, "bf16")
+            if _residual(cfg):
+                paths.insert(2, "bf16_deconv")
         runs = {p: make(cfg, p, dev) for p in paths}
         for p in paths:
             for _ in range(a.warmup):
@@ -202,19 +209,43 @@ def main():
                                            "fraction_of_peak": round(v["flops"] / v["ms"] / 1e9 / PEAK_TFLOPS, 3) if v["ms"] and v["flops"] else None}
                                        for k, v in tr.items()},
                        other_declared_flop_ms_per_step=round(sum(v["ms"] for k, v in fam.items() if k not in conv and k not in tr), 3))
-        if "bf16" in ms:
+        def family_step(path):
+            """entry-point summary of one event-bracketed step of `path`"""
             prof = nat.EventProfiler(flops_only=True, prealloc=4096)
             nat.profiler = prof
-            step(*runs["bf16"], x, target, loss_fn)
+            step(*runs[path], x, target, loss_fn)
             torch.cuda.synchronize()
             nat.profiler = None
-            bconv = {k: v for k, v in prof.summary().items() if "conv2d" in k}
+            return prof.summary()
+
+        def calls(d):
+            return {k: {"calls": v["calls"], "ms": round(v["ms"], 3), "tflops_executed": round(v["flops"] / v["ms"] / 1e9, 2) if v["ms"] else None}
+                    for k, v in d.items()}
+
+        if "bf16" in ms:
+            bfam = family_step("bf16")
+            bconv = {k: v for k, v in bfam.items() if "conv2d" in k}
             rec.update(bf16_ms_per_step=[round(v, 3) for v in ms["bf16"]], bf16_images_per_s=round(batch * 1000.0 / best["bf16"], 2),
                        bf16_speedup_over_native_fp32=round(best[True] / best["bf16"], 3),
                        bf16_conv2d_family_ms_per_step=round(sum(v["ms"] for v in bconv.values()), 3),
                        bf16_conv2d_calls={k: {"calls": v["calls"], "ms": round(v["ms"], 3),
                                               "tflops_executed": round(v["flops"] / v["ms"] / 1e9, 2) if v["ms"] else None}
                                           for k, v in bconv.items()})
+        if "bf16_deconv" in ms:
+            # the transposed family of both bf16 arms in the same run: fp32 kernels in the bf16 arm, the bf16 twins in the deconv arm
+            dfam = family_step("bf16_deconv")
+            tr32 = {k: v for k, v in bfam.items() if "convtr2d" in k}
+            tr16 = {k: v for k, v in dfam.items() if "convtr2d" in k}
+            dconv = {k: v for k, v in dfam.items() if "conv2d" in k}
+            rec.update(bf16_deconv_ms_per_step=[round(v, 3) for v in ms["bf16_deconv"]],
+                       bf16_deconv_images_per_s=round(batch * 1000.0 / best["bf16_deconv"], 2),
+                       bf16_deconv_speedup_over_bf16=round(best["bf16"] / best["bf16_deconv"], 3),
+                       bf16_deconv_speedup_over_native_fp32=round(best[True] / best["bf16_deconv"], 3),
+                       bf16_arm_convtr2d_family_ms_per_step=round(sum(v["ms"] for v in tr32.values()), 3),
+                       bf16_arm_convtr2d_calls=calls(tr32),
+                       bf16_deconv_convtr2d_family_ms_per_step=round(sum(v["ms"] for v in tr16.values()), 3),
+                       bf16_deconv_convtr2d_calls=calls(tr16),
+                       bf16_deconv_conv2d_calls=calls(dconv))
         if not a.native_only:
             rec.update(stock_ms_per_step=[round(v, 3) for v in ms[False]], stock_images_per_s=round(batch * 1000.0 / best[False], 2),
                        native_speedup=round(best[False] / best[True], 3))
