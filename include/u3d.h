@@ -891,6 +891,26 @@ int u3d_conv2d_res_reps(int device, u3d_stream_t stream, const u3d_src_t* src, c
 size_t u3d_wgrad2d_workspace_floats(int N, int H, int W, int Cin, int Cout);
 int u3d_conv2d_wgrad(int device, u3d_stream_t stream, const u3d_src_t* src, const float* dz, float* dw, int N, int H, int W, int Cout,
                      float* workspace, size_t workspace_floats);
+/* (Added, U3D_VERSION unchanged.)  The first convolution of a 2-D net (`native_2d_stem: true`): the 2-D twins of
+ * u3d_conv3d_small_cin_fwd_reps / u3d_conv3d_small_cin_bwd for Cin <= 4, Cout <= 32, exact fp32 (csrc/u3d_conv2d.hip).  x is a plain
+ * (N,H,W,Cin) tensor, w the reference (Cout,Cin,3,3) layout — no packed image.  N <= 65535, N*H*W < 2^31.
+ *   u3d_conv2d_small_cin_fwd_reps   out = [relu](conv2d(a*x + b zero padded, w)); affine optional (N,Cin,2), padding stays exactly 0;
+ *                                   out_stats optional double[reps][N][Cout][2] += (sum, sum of squares) of the written values
+ *   u3d_conv2d_small_cin_bwd        ONE pass over (dz, x): dw (written, reference layout) and gstats[N][Cin][2] += (sum dg, sum dg * x)
+ *                                   (gstats optional), where dg is the data gradient — which is never formed.  Partial sums go through
+ *                                   `workspace` (u3d_small_cin2d_bwd_workspace_floats() floats, need not be zeroed) and are added in a
+ *                                   fixed order: the same inputs give a bitwise-identical dw
+ *   u3d_conv2d_small_cin_fwd_variant / _bwd_variant   host-only: the plan a launch takes, -1 outside the envelope.  Forward: bit 0 =
+ *                                   matrix-pipe kernel (Cout % 4 == 0 and a 16-byte aligned out; else the direct kernel), bit 1 = a block
+ *                                   walks several tiles.  Backward: bit 0 = two row tiles of 16 channels (Cout > 16), bit 1 = a block
+ *                                   walks several tiles, bit 2 = more than one partial per sample in the reduction */
+int u3d_conv2d_small_cin_fwd_variant(int N, int H, int W, int Cin, int Cout);
+int u3d_conv2d_small_cin_fwd_reps(int device, u3d_stream_t stream, const float* x, const float* affine, const float* w, float* out, int N,
+                                  int H, int W, int Cin, int Cout, int relu, double* out_stats, int reps);
+size_t u3d_small_cin2d_bwd_workspace_floats(int N, int H, int W, int Cin, int Cout);
+int u3d_conv2d_small_cin_bwd_variant(int N, int H, int W, int Cin, int Cout);
+int u3d_conv2d_small_cin_bwd(int device, u3d_stream_t stream, const float* x, const float* affine, const float* dz, const float* w,
+                             float* dw, double* gstats, int N, int H, int W, int Cin, int Cout, float* workspace, size_t workspace_floats);
 /* MaxPool2d(kernel_size=2) (buildingblocks.py:358): stride 2, floor.  The 2-D twins of u3d_maxpool2_fwd / _bwd_merge / _bwd_merge_gn
  * (same arguments without D): argmax byte = 2 * dy + dx of the first maximum in (y, x) scan order (ATen); H, W >= 2. */
 int u3d_maxpool2d_fwd(int device, u3d_stream_t stream, const float* x, int N, int H, int W, int C, float* out, uint8_t* argmax,
@@ -983,6 +1003,27 @@ long long u3d_wgrad2d_bf16_workspace_floats(int N, int H, int W, int Cin, int Co
 int u3d_conv2d_wgrad_bf16_variant(int N, int H, int W, int Cin, int Cout);
 int u3d_conv2d_wgrad_bf16(int device, u3d_stream_t stream, const float* x, const float* affine, const float* dz, float* dw, int N,
                           int H, int W, int Cin, int Cout, float* workspace, long long workspace_floats);
+/* (Added, U3D_VERSION unchanged.)  The `_c16` twins of the entry points above for the 16-channel layers of a UNet2D stem (`native_2d_stem:
+ * true` next to `native_2d_bf16: true`): the envelope is BOTH channel counts % 16 == 0, in every role (forward, data gradient on the
+ * mode-1 image, weight gradient) — (16,32), (32,16), (16,16), (48,80) fit, (20,32) and (32,8) do not.  Same kernels, same rounding points,
+ * same arguments, same plans (the `_c16` queries report them): 16 produced channels are half a 32-column n-tile — the image stores the
+ * tile whole with zeros in its upper columns (u3d_packed_weight2d_bf16_c16_elems counts it so) and the epilogue masks stores and
+ * statistics at co >= Cout; a 16-channel cell of the weight gradient stages zeros for its two missing channel octets and masks its dw
+ * stores.  For a layer inside the envelope of the entry points above the `_c16` ones write the same images, outputs, statistics and dw bit
+ * for bit.  The entry points above keep their envelopes and refusals. */
+int u3d_conv2d_bf16_c16_supported(int Cin, int Cout);
+int u3d_conv2d_wgrad_bf16_c16_supported(int Cin, int Cout);
+long long u3d_packed_weight2d_bf16_c16_elems(int Cin, int Cout, int mode);
+int u3d_pack_weights2d_bf16_c16(int device, u3d_stream_t stream, const float* w, int Cout, int Cin, int mode, void* packed);
+long long u3d_conv2d_bf16_c16_workspace_floats(int N, int H, int W, int Cin, int Cout);
+int u3d_conv2d_bf16_c16_variant(int N, int H, int W, int Cin, int Cout, int has_workspace);
+int u3d_conv2d_bf16_c16(int device, u3d_stream_t stream, const float* x, const float* affine, const void* packed_w, float* out, int N,
+                        int H, int W, int Cin, int Cout, int relu, double* out_stats, const float* gx, double* gstats, float* workspace,
+                        long long workspace_floats, int stat_reps);
+long long u3d_wgrad2d_bf16_c16_workspace_floats(int N, int H, int W, int Cin, int Cout);
+int u3d_conv2d_wgrad_bf16_c16_variant(int N, int H, int W, int Cin, int Cout);
+int u3d_conv2d_wgrad_bf16_c16(int device, u3d_stream_t stream, const float* x, const float* affine, const float* dz, float* dw, int N,
+                              int H, int W, int Cin, int Cout, float* workspace, long long workspace_floats);
 
 /* ---- (Added, U3D_VERSION unchanged.)  bf16-operand ConvTranspose2d of ResidualUNet2D's decoders (`native_2d_residual_bf16_deconv:
  * true`; csrc/u3d_conv2d_bf16.hip) ------

@@ -678,6 +678,621 @@ extern "C" int u3d_conv2d_wgrad(int device, u3d_stream_t stream, const u3d_src_t
 }
 
 // =================================================================================================
+// Small-Cin family (`native_2d_stem`): the net's first convolution, Cin <= 4 and Cout <= 32, exact fp32 — the 2-D twins of
+// csrc/u3d_smallc.hip.  K = 9 * Cin is far too small for the tiling above (Cin would be padded to a 16-channel chunk, 16 produced
+// channels to a 32-column n-tile, and the weight gradient owns 32 x 32 channels), so the layer gets bandwidth-shaped kernels on the
+// reference (Cout,Cin,3,3) weight layout, no packed image:
+//   forward : a block walks 16 x 16-pixel tiles b, b + B, ... of one sample; the 18 x 18 halo goes through LDS with the affine applied
+//             (padding stays exactly 0).  Cout % 4 == 0: GEMM on v_mfma_f32_16x16x4_f32 with the WEIGHTS as the A operand (rows = output
+//             channels, K = 9 * Cin padded to 4: registers, loaded once per block) and 16 pixels of a row as the B columns — a lane's
+//             accumulator is four consecutive channels of one pixel, stored as one 16-byte store (a row of 16 pixels x 16 channels =
+//             1 KB contiguous).  Otherwise a direct kernel, one pixel per thread.  Statistics are carried in registers over a block's
+//             tiles and leave it as one f64 atomic pair per channel.
+//   backward: no data gradient.  With X[n,k,c,t] = sum_u dz[n,u,k] * x[n,u+t-1,c] and T[n,k,t] = sum_{u : u+t-1 in bounds} dz[n,u,k]
+//             (9 taps t, T = the 9 border-class sums), dw and the GroupNorm-backward sums are linear in (X, T) — the identity at the
+//             top of csrc/u3d_smallc.hip.  One pass over (dz, x) forms per-block partials of the GEMM P[k][(t,c)] (x with an in-bounds
+//             indicator as channel Cin); the finalize kernel adds them in a fixed order: the same inputs give a bitwise-identical dw.
+typedef float f32x4s __attribute__((ext_vector_type(4)));
+
+namespace c2s {
+constexpr int TY = 16, TX = 16;
+constexpr int HY = TY + 2, HX = TX + 2;
+constexpr int HV = HY * HX;  // 324 halo pixels
+constexpr int MAXC = 4;
+constexpr int FWD_BLOCKS = 512;   // blocks per launch over all samples (2 per CU: one f64 atomic pair per channel and block)
+constexpr int BWD_BLOCKS = 1024;  // ~4 per CU; the finalize kernel's work is proportional to it
+}  // namespace c2s
+
+struct Small2dFwdParams {
+    const float* x;       // (N,H,W,Cin)
+    const float* affine;  // [N][Cin][2] or null
+    const float* w;       // (Cout,Cin,9) reference layout
+    float* out;           // (N,H,W,Cout)
+    double* out_stats;    // optional [reps][N][Cout][2] += (sum, sum of squares) of the written values; block b adds to row b % reps
+    int N, H, W, Cin, Cout, relu;
+    int ty, tx, B, reps;
+};
+
+// direct form: any Cout <= COUTP, scalar stores (Cout % 4 != 0, or an `out` that is not 16-byte aligned)
+template <int COUTP>
+__global__ __launch_bounds__(256) void conv2d_small_fwd_kernel(const Small2dFwdParams p) {
+    using namespace c2s;
+    __shared__ __attribute__((aligned(16))) float xs[HV * MAXC];
+    __shared__ __attribute__((aligned(16))) float ws[9 * MAXC * COUTP];
+    __shared__ double sred[COUTP][2];
+    const int t = threadIdx.x;
+    const int n = blockIdx.y;
+    const int Cin = p.Cin, H = p.H, W = p.W;
+    // weights -> LDS as [tap][c][k] (k padded to COUTP with zeros)
+    for (int i = t; i < 9 * Cin * COUTP; i += 256) {
+        const int k = i % COUTP;
+        const int r = i / COUTP;
+        const int c = r % Cin, tap = r / Cin;
+        ws[i] = k < p.Cout ? p.w[((size_t)k * Cin + c) * 9 + tap] : 0.f;
+    }
+    if (t < COUTP) sred[t][0] = sred[t][1] = 0.0;
+    float s1[COUTP], s2[COUTP];
+#pragma unroll
+    for (int k = 0; k < COUTP; ++k) s1[k] = s2[k] = 0.f;
+    const int yl = t >> 4, xl = t & 15;
+    const int ntiles = p.ty * p.tx;
+    for (int tile = blockIdx.x; tile < ntiles; tile += p.B) {
+        const int y0 = (tile / p.tx) * TY, x0 = (tile % p.tx) * TX;
+        __syncthreads();  // the previous tile's reads of xs are done (and ws / sred are initialised)
+        for (int i = t; i < HV * Cin; i += 256) {
+            const int c = i % Cin;
+            const int hv = i / Cin;
+            const int hy = hv / HX, hx = hv - hy * HX;
+            const int gy = y0 - 1 + hy, gx = x0 - 1 + hx;
+            float v = 0.f;
+            if (gy >= 0 && gy < H && gx >= 0 && gx < W) {
+                v = p.x[((size_t)(n * H + gy) * W + gx) * Cin + c];
+                if (p.affine) v = v * p.affine[((size_t)n * Cin + c) * 2] + p.affine[((size_t)n * Cin + c) * 2 + 1];
+            }
+            xs[i] = v;
+        }
+        __syncthreads();
+        float acc[COUTP];
+#pragma unroll
+        for (int k = 0; k < COUTP; ++k) acc[k] = 0.f;
+        for (int tap = 0; tap < 9; ++tap) {
+            const int hv = (yl + tap / 3) * HX + xl + tap % 3;
+            for (int c = 0; c < Cin; ++c) {
+                const float xv = xs[hv * Cin + c];
+                const f32x4* wr = reinterpret_cast<const f32x4*>(&ws[(tap * Cin + c) * COUTP]);
+#pragma unroll
+                for (int k4 = 0; k4 < COUTP / 4; ++k4) {
+                    const f32x4 wv = wr[k4];  // broadcast read
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) acc[4 * k4 + e] = fmaf(xv, wv[e], acc[4 * k4 + e]);
+                }
+            }
+        }
+        const int y = y0 + yl, x = x0 + xl;
+        if (y < H && x < W) {
+            float* o = p.out + ((size_t)(n * H + y) * W + x) * p.Cout;
+#pragma unroll
+            for (int k = 0; k < COUTP; ++k) {
+                if (p.relu) acc[k] = fmaxf(acc[k], 0.f);
+                s1[k] += acc[k];  // padded channels (k >= Cout) are exactly 0
+                s2[k] += acc[k] * acc[k];
+                if (k < p.Cout) o[k] = acc[k];
+            }
+        }
+    }
+    if (p.out_stats) {
+#pragma unroll
+        for (int k = 0; k < COUTP; ++k) {
+            float a = s1[k], b2 = s2[k];
+#pragma unroll
+            for (int m = 32; m > 0; m >>= 1) {
+                a += __shfl_xor(a, m);
+                b2 += __shfl_xor(b2, m);
+            }
+            if ((t & 63) == 0) {
+                __hip_atomic_fetch_add(&sred[k][0], (double)a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                __hip_atomic_fetch_add(&sred[k][1], (double)b2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            }
+        }
+        __syncthreads();
+        if (t < p.Cout) {
+            double* dst = p.out_stats + ((size_t)(blockIdx.x % (unsigned)p.reps) * p.N * p.Cout + (size_t)n * p.Cout + t) * 2;
+            u3d_atomic_add_f64(dst, sred[t][0]);
+            u3d_atomic_add_f64(dst + 1, sred[t][1]);
+        }
+    }
+}
+
+// matrix-pipe form: Cout % 4 == 0, `out` 16-byte aligned.  RT = row tiles of 16 output channels.  Wave w owns rows 4w .. 4w + 3 of the
+// tile = 4 M-tiles of 16 pixels; the halo is double-buffered (the next tile's loads run under the current tile's MFMAs and stores).
+template <int CIN, int RT>
+__global__ __launch_bounds__(256) void conv2d_small_fwd_mfma_kernel(const Small2dFwdParams p) {
+    using namespace c2s;
+    constexpr int K = 9 * CIN;
+    constexpr int KS = (K + 3) / 4;             // k-steps of 4
+    constexpr int NH = (HV * CIN + 255) / 256;  // halo elements per thread
+    __shared__ __attribute__((aligned(16))) float xsb[2][HV * CIN];
+    __shared__ double sred[16 * RT][2];
+    const int t = threadIdx.x, l = t & 63, w = t >> 6;
+    const int j = l & 15, kq = l >> 4;  // B column (pixel of the M-tile) / A row (output channel); k index within a step
+    const int n = blockIdx.y;
+    const int H = p.H, W = p.W;
+    // A fragments: W[k = 16 * rt + j][kk = 4 * s + kq], kk = tap * CIN + c
+    float wa[RT][KS];
+    int boff[KS];  // LDS offset of this lane's B element of step s, relative to the pixel's halo origin
+#pragma unroll
+    for (int s_ = 0; s_ < KS; ++s_) {
+        const int kk = 4 * s_ + kq;
+        const int tap = kk / CIN, c = kk - tap * CIN;
+        const bool ok = kk < K;
+#pragma unroll
+        for (int rt = 0; rt < RT; ++rt) wa[rt][s_] = (ok && 16 * rt + j < p.Cout) ? p.w[((size_t)(16 * rt + j) * CIN + c) * 9 + tap] : 0.f;
+        boff[s_] = ok ? ((tap / 3) * HX + tap % 3) * CIN + c : 0;  // dead k: any valid slot (A is 0)
+    }
+    if (t < 16 * RT) sred[t][0] = sred[t][1] = 0.0;
+    f32x4s s1[RT], s2[RT];  // this lane's channels 16 * rt + 4 * kq .. +3 over its pixels
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt) s1[rt] = s2[rt] = f32x4s{0.f, 0.f, 0.f, 0.f};
+    const int vbase = 4 * w * HX + j;  // pixel of column j in M-tile mt: y = 4 * w + mt, x = j
+    const int ntiles = p.ty * p.tx;
+    // this thread's halo elements (element i = hv * CIN + c): constant coordinates inside the tile, and the affine of its channel
+    int hrel[NH];  // hy * W + hx relative to the halo origin, in pixels; -1: beyond the 324 halo pixels
+    int hco[NH];   // hy | hx << 8 | c << 24
+    float ha[NH], hb[NH];
+#pragma unroll
+    for (int it = 0; it < NH; ++it) {
+        const int i = t + 256 * it;
+        const int c = i % CIN, hv = i / CIN;
+        const int hy = hv / HX, hx = hv - hy * HX;
+        hrel[it] = i < HV * CIN ? hy * W + hx : -1;
+        hco[it] = hy | (hx << 8) | (c << 24);
+        ha[it] = p.affine ? p.affine[((size_t)n * CIN + c) * 2] : 1.f;
+        hb[it] = p.affine ? p.affine[((size_t)n * CIN + c) * 2 + 1] : 0.f;
+    }
+    auto halo_load = [&](int tile, float (&hv)[NH], unsigned& inside) {
+        const int y0 = (tile / p.tx) * TY, x0 = (tile % p.tx) * TX;
+        const long long base = ((long long)n * H + y0 - 1) * W + x0 - 1;
+        inside = 0;
+#pragma unroll
+        for (int it = 0; it < NH; ++it) {
+            const int gy = y0 - 1 + (hco[it] & 255), gx = x0 - 1 + ((hco[it] >> 8) & 255);
+            const bool in = hrel[it] >= 0 && gy >= 0 && gy < H && gx >= 0 && gx < W;
+            inside |= (in ? 1u : 0u) << it;
+            hv[it] = in ? p.x[(size_t)(base + hrel[it]) * CIN + (hco[it] >> 24)] : 0.f;
+        }
+    };
+    auto halo_store = [&](float* xs, const float (&hv)[NH], unsigned inside) {
+#pragma unroll
+        for (int it = 0; it < NH; ++it)
+            if (t + 256 * it < HV * CIN) xs[t + 256 * it] = ((inside >> it) & 1u) ? fmaf(hv[it], ha[it], hb[it]) : 0.f;  // padding stays 0
+    };
+    float hv[NH];
+    unsigned hin = 0;
+    int cur = 0;
+    if ((int)blockIdx.x < ntiles) {
+        halo_load(blockIdx.x, hv, hin);
+        halo_store(xsb[0], hv, hin);
+    }
+    __syncthreads();  // (also: sred initialised)
+    for (int tile = blockIdx.x; tile < ntiles; tile += p.B) {
+        const int y0 = (tile / p.tx) * TY, x0 = (tile % p.tx) * TX;
+        const float* xs = xsb[cur];
+        const bool has_next = tile + p.B < ntiles;
+        if (has_next) halo_load(tile + p.B, hv, hin);
+        f32x4s acc[RT][4];
+#pragma unroll
+        for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+            for (int mt = 0; mt < 4; ++mt) acc[rt][mt] = f32x4s{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int s_ = 0; s_ < KS; ++s_) {
+#pragma unroll
+            for (int mt = 0; mt < 4; ++mt) {
+                const float b = xs[(vbase + mt * HX) * CIN + boff[s_]];
+#pragma unroll
+                for (int rt = 0; rt < RT; ++rt) acc[rt][mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[rt][s_], b, acc[rt][mt], 0, 0, 0);
+            }
+        }
+        const int x = x0 + j;
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt) {
+            const int y = y0 + 4 * w + mt;
+#pragma unroll
+            for (int rt = 0; rt < RT; ++rt) {
+                f32x4s v = acc[rt][mt];
+                if (p.relu) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
+                }
+                if (16 * rt + 4 * kq < p.Cout && y < H && x < W) {  // (Cout % 4 == 0 on this path)
+                    *reinterpret_cast<f32x4s*>(p.out + ((size_t)(n * H + y) * W + x) * p.Cout + 16 * rt + 4 * kq) = v;
+                    s1[rt] += v;
+                    s2[rt] += v * v;
+                }
+            }
+        }
+        if (has_next) halo_store(xsb[cur ^ 1], hv, hin);
+        __syncthreads();  // the next tile's halo is complete; nobody reads the current buffer any more
+        cur ^= 1;
+    }
+    if (p.out_stats) {
+        // the 16 lanes j of a k-group hold 16 pixels of the same four channels: butterfly over j, then the four waves through LDS (f64),
+        // one global f64 atomic pair per channel and block
+#pragma unroll
+        for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                float a = s1[rt][e], b2 = s2[rt][e];
+#pragma unroll
+                for (int m = 8; m > 0; m >>= 1) {
+                    a += __shfl_xor(a, m);
+                    b2 += __shfl_xor(b2, m);
+                }
+                const int k = 16 * rt + 4 * kq + e;
+                if (j == 0 && k < p.Cout) {
+                    __hip_atomic_fetch_add(&sred[k][0], (double)a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    __hip_atomic_fetch_add(&sred[k][1], (double)b2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                }
+            }
+        __syncthreads();
+        if (t < p.Cout) {
+            double* dst = p.out_stats + ((size_t)(blockIdx.x % (unsigned)p.reps) * p.N * p.Cout + (size_t)n * p.Cout + t) * 2;
+            u3d_atomic_add_f64(dst, sred[t][0]);
+            u3d_atomic_add_f64(dst + 1, sred[t][1]);
+        }
+    }
+}
+
+static bool c2s_envelope(int N, int H, int W, int Cin, int Cout) {
+    return N > 0 && N <= 65535 && H > 0 && W > 0 && (long long)N * H * W < (1LL << 31) && Cin >= 1 && Cin <= c2s::MAXC && Cout >= 1 &&
+           Cout <= 32;
+}
+
+static int c2s_blocks(int total, int N, int H, int W) {
+    const long long ntiles = c2_cdiv(H, c2s::TY) * c2_cdiv(W, c2s::TX);
+    long long B = total / N;
+    if (B < 1) B = 1;
+    if (B > ntiles) B = ntiles;
+    return (int)B;
+}
+
+// which forward plan a launch with a 16-byte aligned `out` takes: bit 0 = matrix-pipe kernel (Cout % 4 == 0; else the direct one),
+// bit 1 = a block walks more than one tile; -1 outside the envelope.  Host-only.
+extern "C" int u3d_conv2d_small_cin_fwd_variant(int N, int H, int W, int Cin, int Cout) {
+    if (!c2s_envelope(N, H, W, Cin, Cout)) return -1;
+    const long long ntiles = c2_cdiv(H, c2s::TY) * c2_cdiv(W, c2s::TX);
+    return (Cout % 4 == 0 ? 1 : 0) | (ntiles > c2s_blocks(c2s::FWD_BLOCKS, N, H, W) ? 2 : 0);
+}
+
+extern "C" int u3d_conv2d_small_cin_fwd_reps(int device, u3d_stream_t stream, const float* x, const float* affine, const float* w,
+                                             float* out, int N, int H, int W, int Cin, int Cout, int relu, double* out_stats, int reps) {
+    U3D_ENTER(device);
+    U3D_REQUIRE(x && w && out, "u3d_conv2d_small_cin_fwd_reps: bad argument");
+    U3D_REQUIRE(c2s_envelope(N, H, W, Cin, Cout), "u3d_conv2d_small_cin_fwd_reps: needs Cin<=4, Cout<=32, N*H*W < 2^31 (got %d,%d)", Cin,
+                Cout);
+    U3D_REQUIRE(reps >= 1 && reps <= 64, "u3d_conv2d_small_cin_fwd_reps: reps must be 1 .. 64");
+    Small2dFwdParams p;
+    p.x = x, p.affine = affine, p.w = w, p.out = out, p.out_stats = out_stats;
+    p.N = N, p.H = H, p.W = W, p.Cin = Cin, p.Cout = Cout, p.relu = relu;
+    p.ty = (int)c2_cdiv(H, c2s::TY), p.tx = (int)c2_cdiv(W, c2s::TX);
+    p.B = c2s_blocks(c2s::FWD_BLOCKS, N, H, W);
+    p.reps = reps;
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((unsigned)p.B, (unsigned)N);
+    const bool mfma = Cout % 4 == 0 && ((uintptr_t)out & 15) == 0;
+#define U3D_SMALL2D_FWD(CIN_)                                                                             \
+    do {                                                                                                  \
+        if (Cout <= 16)                                                                                   \
+            hipLaunchKernelGGL((conv2d_small_fwd_mfma_kernel<CIN_, 1>), grid, dim3(256), 0, st, p);       \
+        else                                                                                              \
+            hipLaunchKernelGGL((conv2d_small_fwd_mfma_kernel<CIN_, 2>), grid, dim3(256), 0, st, p);       \
+    } while (0)
+    if (mfma && Cin == 1)
+        U3D_SMALL2D_FWD(1);
+    else if (mfma && Cin == 2)
+        U3D_SMALL2D_FWD(2);
+    else if (mfma && Cin == 3)
+        U3D_SMALL2D_FWD(3);
+    else if (mfma)
+        U3D_SMALL2D_FWD(4);
+    else if (Cout <= 8)
+        hipLaunchKernelGGL(conv2d_small_fwd_kernel<8>, grid, dim3(256), 0, st, p);
+    else if (Cout <= 16)
+        hipLaunchKernelGGL(conv2d_small_fwd_kernel<16>, grid, dim3(256), 0, st, p);
+    else
+        hipLaunchKernelGGL(conv2d_small_fwd_kernel<32>, grid, dim3(256), 0, st, p);
+#undef U3D_SMALL2D_FWD
+    U3D_LAUNCH_CHECK();
+    return 0;
+}
+
+// backward: partial[n][b][(k * 9 + tap) * (Cin + 1) + c]  (c == Cin is the T slot).  grid (B, N).  The contraction
+// P[k][(tap,c)] = sum_u dz[u,k] * xs[u + tap][c] (xs = raw x with an in-bounds indicator as channel Cin, zero outside the image) is a
+// GEMM with M = Cout, N = 9 * (Cin + 1), K = pixels on v_mfma_f32_16x16x4_f32: A[i = k][kk = pixel] straight from global dz,
+// B[kk = pixel][j = column] from the LDS halo tile.  Wave w owns rows 4w .. 4w + 3 of the tile = 16 k-steps of 4 consecutive x; the four
+// waves' sums are folded in a fixed order at the end of the block.
+struct Small2dBwdParams {
+    const float* x;   // raw input (N,H,W,Cin)
+    const float* dz;  // (N,H,W,Cout)
+    float* partial;
+    int N, H, W, Cin, Cout;
+    int ty, tx, B;
+};
+
+template <int CIN, int RT>  // RT = row tiles of 16 output channels (Cout <= 16 * RT)
+__global__ __launch_bounds__(256) void conv2d_small_bwd_kernel(const Small2dBwdParams p) {
+    using namespace c2s;
+    constexpr int C1 = CIN + 1;
+    constexpr int NCOL = 9 * C1;
+    constexpr int NCT = (NCOL + 15) / 16;
+    constexpr int NH = (HV + 255) / 256;  // halo pixels per thread (2)
+    __shared__ float xsb[2][HV * C1];     // [hv][CIN + 1]: raw x, then the in-bounds indicator; two buffers
+    __shared__ float red[RT * NCT * 4 * 64];
+    const int t = threadIdx.x, l = t & 63, w = t >> 6;
+    const int n = blockIdx.y;
+    const int j = l & 15, kk = l >> 4;
+    const int Cout = p.Cout, H = p.H, W = p.W;
+    int boff[NCT];
+#pragma unroll
+    for (int ct = 0; ct < NCT; ++ct) {
+        const int col = ct * 16 + j;
+        const int tap = col / C1, c = col - tap * C1;
+        boff[ct] = col < NCOL ? ((tap / 3) * HX + tap % 3) * C1 + c : 0;  // dead columns read column 0; never written out
+    }
+    const int bbase = (4 * w * HX + kk) * C1;
+    f32x4s acc[RT][NCT];
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+        for (int ct = 0; ct < NCT; ++ct) acc[rt][ct] = f32x4s{0.f, 0.f, 0.f, 0.f};
+    const int ntiles = p.ty * p.tx;
+    // A operands of a whole tile: dz[pixel(step, kk)][k = j + 16 * rt], zero outside the image / beyond Cout
+    auto a_load = [&](int tile, float (&a)[RT][16]) {
+        const int y0 = (tile / p.tx) * TY, x0 = (tile % p.tx) * TX;
+#pragma unroll
+        for (int s_ = 0; s_ < 16; ++s_) {
+            const int y = y0 + 4 * w + (s_ >> 2), x = x0 + (s_ & 3) * 4 + kk;
+            const bool vin = y < H && x < W;
+            const size_t pix = (size_t)(n * H + (vin ? y : 0)) * W + (vin ? x : 0);
+#pragma unroll
+            for (int rt = 0; rt < RT; ++rt) {
+                const int k = j + 16 * rt;
+                const float v = p.dz[pix * Cout + (k < Cout ? k : 0)];
+                a[rt][s_] = (vin && k < Cout) ? v : 0.f;
+            }
+        }
+    };
+    auto halo_load = [&](int tile, float (&hx)[NH][CIN], unsigned& inside) {
+        const int y0 = (tile / p.tx) * TY, x0 = (tile % p.tx) * TX;
+        inside = 0;
+#pragma unroll
+        for (int it = 0; it < NH; ++it) {
+            const int i = t + 256 * it;
+            const int hy = i / HX, hxx = i - hy * HX;
+            const int gy = y0 - 1 + hy, gx = x0 - 1 + hxx;
+            const bool in = i < HV && gy >= 0 && gy < H && gx >= 0 && gx < W;
+            inside |= (in ? 1u : 0u) << it;
+            const float* src = p.x + (in ? ((size_t)(n * H + gy) * W + gx) * CIN : 0);
+#pragma unroll
+            for (int c = 0; c < CIN; ++c) hx[it][c] = in ? src[c] : 0.f;
+        }
+    };
+    auto halo_store = [&](float* xs, const float (&hx)[NH][CIN], unsigned inside) {
+#pragma unroll
+        for (int it = 0; it < NH; ++it) {
+            const int i = t + 256 * it;
+            if (i < HV) {
+#pragma unroll
+                for (int c = 0; c < CIN; ++c) xs[i * C1 + c] = hx[it][c];
+                xs[i * C1 + CIN] = ((inside >> it) & 1u) ? 1.f : 0.f;
+            }
+        }
+    };
+    float a[RT][16], hx[NH][CIN];
+    unsigned hin = 0;
+    int cur = 0;
+    if ((int)blockIdx.x < ntiles) {
+        a_load(blockIdx.x, a);
+        halo_load(blockIdx.x, hx, hin);
+        halo_store(xsb[0], hx, hin);
+    }
+    __syncthreads();
+    for (int tile = blockIdx.x; tile < ntiles; tile += p.B) {
+        const float* xs = xsb[cur];
+        const bool has_next = tile + p.B < ntiles;
+        float an[RT][16];
+        if (has_next) {
+            a_load(tile + p.B, an);
+            halo_load(tile + p.B, hx, hin);
+        }
+#pragma unroll
+        for (int s_ = 0; s_ < 16; ++s_) {
+            const int so = ((s_ >> 2) * HX + (s_ & 3) * 4) * C1;
+            float b[NCT];
+#pragma unroll
+            for (int ct = 0; ct < NCT; ++ct) b[ct] = xs[bbase + so + boff[ct]];
+#pragma unroll
+            for (int ct = 0; ct < NCT; ++ct)
+#pragma unroll
+                for (int rt = 0; rt < RT; ++rt)
+                    acc[rt][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[rt][s_], b[ct], acc[rt][ct], 0, 0, 0);
+        }
+        if (has_next) {
+            halo_store(xsb[cur ^ 1], hx, hin);
+#pragma unroll
+            for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+                for (int s_ = 0; s_ < 16; ++s_) a[rt][s_] = an[rt][s_];
+        }
+        __syncthreads();  // the next tile's halo is complete; nobody reads the current buffer any more
+        cur ^= 1;
+    }
+    // fold the four waves' partials (fixed order 0+1+2+3) through LDS, then write the block's partial.
+    // D layout of 16x16x4: col = lane & 15, row = 4 * (lane >> 4) + reg
+    for (int src = 1; src < 4; ++src) {
+        __syncthreads();
+        if (w == src) {
+#pragma unroll
+            for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+                for (int ct = 0; ct < NCT; ++ct)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) red[((rt * NCT + ct) * 4 + r) * 64 + l] = acc[rt][ct][r];
+        }
+        __syncthreads();
+        if (w == 0) {
+#pragma unroll
+            for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+                for (int ct = 0; ct < NCT; ++ct)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) acc[rt][ct][r] += red[((rt * NCT + ct) * 4 + r) * 64 + l];
+        }
+    }
+    if (w != 0) return;
+    float* dst = p.partial + ((size_t)n * p.B + blockIdx.x) * ((size_t)Cout * NCOL);
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+        for (int ct = 0; ct < NCT; ++ct) {
+            const int col = ct * 16 + j;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int k = rt * 16 + 4 * kk + r;
+                if (k < Cout && col < NCOL) dst[(size_t)k * NCOL + col] = acc[rt][ct][r];
+            }
+        }
+}
+
+// finalize: grid = ceil(Cout * 9 / 64) blocks of 1024 threads = 64 (k,tap) lanes x 16 partial-groups.  Fixed summation order; forms dw
+// (summed over n in-thread) and adds the GroupNorm-backward sums (S1, S2) per (n, c).
+constexpr int C2S_FIN_GROUPS = 16, C2S_FIN_UNROLL = 4;
+__global__ __launch_bounds__(64 * C2S_FIN_GROUPS) void conv2d_small_bwd_finalize_kernel(const float* __restrict__ partial,
+                                                                                       const float* __restrict__ affine,
+                                                                                       const float* __restrict__ w, int N, int B, int Cin,
+                                                                                       int Cout, float* __restrict__ dw,
+                                                                                       double* __restrict__ gstats) {
+    __shared__ float red[C2S_FIN_GROUPS][64][c2s::MAXC + 1];
+    const int C1 = Cin + 1;
+    const int nkt = Cout * 9;
+    const int lane = threadIdx.x & 63, grp = threadIdx.x >> 6;
+    const int kt = blockIdx.x * 64 + lane;
+    const bool valid = kt < nkt;
+    const int k = valid ? kt / 9 : 0, tap = valid ? kt % 9 : 0;
+    double dwacc[c2s::MAXC];
+    for (int c = 0; c < c2s::MAXC; ++c) dwacc[c] = 0.0;
+    for (int n = 0; n < N; ++n) {
+        float acc[c2s::MAXC + 1];
+#pragma unroll
+        for (int c = 0; c <= c2s::MAXC; ++c) acc[c] = 0.f;
+        if (valid) {
+            const float* base = partial + (size_t)n * B * ((size_t)nkt * C1) + (size_t)kt * C1;
+            for (int b = grp; b < B; b += C2S_FIN_GROUPS * C2S_FIN_UNROLL) {
+                float tmp[C2S_FIN_UNROLL][c2s::MAXC + 1];
+#pragma unroll
+                for (int u = 0; u < C2S_FIN_UNROLL; ++u) {
+                    const int bb = b + u * C2S_FIN_GROUPS;
+                    const float* src = base + (size_t)(bb < B ? bb : b) * ((size_t)nkt * C1);
+#pragma unroll
+                    for (int c = 0; c <= c2s::MAXC; ++c) tmp[u][c] = (c < C1 && bb < B) ? src[c] : 0.f;
+                }
+#pragma unroll
+                for (int u = 0; u < C2S_FIN_UNROLL; ++u)
+#pragma unroll
+                    for (int c = 0; c <= c2s::MAXC; ++c) acc[c] += tmp[u][c];
+            }
+        }
+#pragma unroll
+        for (int c = 0; c <= c2s::MAXC; ++c)
+            if (c < C1) red[grp][lane][c] = acc[c];
+        __syncthreads();
+        if (grp == 0) {  // wave 0: lanes = 64 (k,tap) pairs
+            double X[c2s::MAXC + 1];
+            for (int c = 0; c < C1; ++c) {
+                double sum = 0.0;
+                for (int g = 0; g < C2S_FIN_GROUPS; ++g) sum += (double)red[g][lane][c];
+                X[c] = sum;
+            }
+            const double T = X[Cin];
+            for (int c = 0; c < Cin; ++c) {
+                double s1 = 0.0, s2 = 0.0;
+                if (valid) {
+                    const double a = affine ? (double)affine[((size_t)n * Cin + c) * 2] : 1.0;
+                    const double bb = affine ? (double)affine[((size_t)n * Cin + c) * 2 + 1] : 0.0;
+                    dwacc[c] += a * X[c] + bb * T;
+                    const double wv = (double)w[((size_t)k * Cin + c) * 9 + tap];
+                    s1 = wv * T;
+                    s2 = wv * X[c];
+                }
+                for (int m = 32; m > 0; m >>= 1) {
+                    s1 += __shfl_xor(s1, m);
+                    s2 += __shfl_xor(s2, m);
+                }
+                if (lane == 0 && gstats) {
+                    u3d_atomic_add_f64(&gstats[((size_t)n * Cin + c) * 2], s1);
+                    u3d_atomic_add_f64(&gstats[((size_t)n * Cin + c) * 2 + 1], s2);
+                }
+            }
+        }
+        __syncthreads();
+    }
+    if (grp == 0 && valid)
+        for (int c = 0; c < Cin; ++c) dw[((size_t)k * Cin + c) * 9 + tap] = (float)dwacc[c];
+}
+
+extern "C" size_t u3d_small_cin2d_bwd_workspace_floats(int N, int H, int W, int Cin, int Cout) {
+    if (!c2s_envelope(N, H, W, Cin, Cout)) return 0;
+    return (size_t)N * c2s_blocks(c2s::BWD_BLOCKS, N, H, W) * Cout * 9 * (Cin + 1);
+}
+
+// which backward plan a launch takes: bit 0 = two row tiles of 16 output channels (Cout > 16), bit 1 = a block walks more than one
+// tile, bit 2 = the finalize kernel adds more than one partial per sample; -1 outside the envelope.  Host-only.
+extern "C" int u3d_conv2d_small_cin_bwd_variant(int N, int H, int W, int Cin, int Cout) {
+    if (!c2s_envelope(N, H, W, Cin, Cout)) return -1;
+    const long long ntiles = c2_cdiv(H, c2s::TY) * c2_cdiv(W, c2s::TX);
+    const int B = c2s_blocks(c2s::BWD_BLOCKS, N, H, W);
+    return (Cout > 16 ? 1 : 0) | (ntiles > B ? 2 : 0) | (B > 1 ? 4 : 0);
+}
+
+extern "C" int u3d_conv2d_small_cin_bwd(int device, u3d_stream_t stream, const float* x, const float* affine, const float* dz,
+                                        const float* w, float* dw, double* gstats, int N, int H, int W, int Cin, int Cout,
+                                        float* workspace, size_t workspace_floats) {
+    U3D_ENTER(device);
+    U3D_REQUIRE(x && dz && w && dw && workspace, "u3d_conv2d_small_cin_bwd: bad argument");
+    U3D_REQUIRE(c2s_envelope(N, H, W, Cin, Cout), "u3d_conv2d_small_cin_bwd: needs Cin<=4, Cout<=32, N*H*W < 2^31 (got %d,%d)", Cin, Cout);
+    Small2dBwdParams p;
+    p.x = x, p.dz = dz, p.partial = workspace;
+    p.N = N, p.H = H, p.W = W, p.Cin = Cin, p.Cout = Cout;
+    p.ty = (int)c2_cdiv(H, c2s::TY), p.tx = (int)c2_cdiv(W, c2s::TX);
+    p.B = c2s_blocks(c2s::BWD_BLOCKS, N, H, W);
+    const size_t need = (size_t)N * p.B * Cout * 9 * (Cin + 1);
+    U3D_REQUIRE(workspace_floats >= need, "u3d_conv2d_small_cin_bwd: workspace too small (%zu < %zu floats)", workspace_floats, need);
+    const dim3 grid((unsigned)p.B, (unsigned)N), block(256);
+    hipStream_t st = (hipStream_t)stream;
+#define U3D_SMALL2D_BWD(CIN_)                                                                \
+    do {                                                                                     \
+        if (Cout <= 16)                                                                      \
+            hipLaunchKernelGGL((conv2d_small_bwd_kernel<CIN_, 1>), grid, block, 0, st, p);   \
+        else                                                                                 \
+            hipLaunchKernelGGL((conv2d_small_bwd_kernel<CIN_, 2>), grid, block, 0, st, p);   \
+    } while (0)
+    if (Cin == 1)
+        U3D_SMALL2D_BWD(1);
+    else if (Cin == 2)
+        U3D_SMALL2D_BWD(2);
+    else if (Cin == 3)
+        U3D_SMALL2D_BWD(3);
+    else
+        U3D_SMALL2D_BWD(4);
+#undef U3D_SMALL2D_BWD
+    U3D_LAUNCH_CHECK();
+    hipLaunchKernelGGL(conv2d_small_bwd_finalize_kernel, dim3((Cout * 9 + 63) / 64), dim3(64 * C2S_FIN_GROUPS), 0, st, workspace, affine, w,
+                       N, p.B, Cin, Cout, dw, gstats);
+    U3D_LAUNCH_CHECK();
+    return 0;
+}
+
+// =================================================================================================
 // MaxPool2d(2): stride 2, floor.  argmax byte k = 2 * dy + dx of the first maximum in (y, x) scan order (ATen); NaN propagates.
 __global__ void maxpool2d_fwd_kernel(const float* __restrict__ x, int N, int H, int W, int C, float* __restrict__ out,
                                      uint8_t* __restrict__ argmax) {

@@ -72,6 +72,9 @@ int c2b_cu_count(int device) {
 
 inline bool c2b_fwd_ok(int Cin, int Cout) { return Cin > 0 && Cout > 0 && Cin % 16 == 0 && Cout % 32 == 0; }
 inline bool c2b_wgrad_ok(int Cin, int Cout) { return Cin > 0 && Cout > 0 && Cin % 32 == 0 && Cout % 32 == 0; }
+// the `_c16` entry points (`native_2d_stem` next to `native_2d_bf16`): both channel counts % 16.  16 produced channels are half an n-tile:
+// the image holds zeros there and the epilogue masks co >= Cout; the weight gradient stages zeros for the two missing channel octets
+inline bool c2b_c16_ok(int Cin, int Cout) { return Cin > 0 && Cout > 0 && Cin % 16 == 0 && Cout % 16 == 0; }
 inline bool c2b_aligned(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 void c2b_dims(int Cin, int Cout, int mode, int& K, int& Nn) {
@@ -455,7 +458,8 @@ __global__ __launch_bounds__(256, 2) void conv2d_wgrad_bf16_kernel(const Wgrad2d
                 const int pix = item >> 2, q = item & 3;
                 const int hy = pix / HX, hx = pix - (pix / HX) * HX;
                 const int gy = y0 - 1 + hy, gxx = x0 - 1 + hx;
-                okg[k] = item < HY * HX * 4 && gy >= 0 && gy < H && gxx >= 0 && gxx < W;
+                // (ci0 + 8q >= Cin: the missing channel octets of a 16-channel cell are staged as zeros, `_c16`)
+                okg[k] = item < HY * HX * 4 && gy >= 0 && gy < H && gxx >= 0 && gxx < W && ci0 + 8 * q < Cin;
                 rg[k][0] = rg[k][1] = f32x4{0.f, 0.f, 0.f, 0.f};
                 if (okg[k]) {
                     const float* src = p.x + ((size_t)(n * H + gy) * W + gxx) * Cin + ci0 + 8 * q;
@@ -480,7 +484,7 @@ __global__ __launch_bounds__(256, 2) void conv2d_wgrad_bf16_kernel(const Wgrad2d
                 const int item = t + 256 * (it0 + k);
                 const int pix = item >> 2, q = item & 3;
                 const int y = y0 + (pix >> 4), x = x0 + (pix & 15);
-                okd[k] = y < H && x < W;
+                okd[k] = y < H && x < W && co0 + 8 * q < Cout;
                 rd[k][0] = rd[k][1] = f32x4{0.f, 0.f, 0.f, 0.f};
                 if (okd[k]) {
                     const float* src = p.dz + ((size_t)(n * H + y) * W + x) * Cout + co0 + 8 * q;
@@ -575,42 +579,87 @@ extern "C" int u3d_conv2d_bf16_supported(int Cin, int Cout) { return c2b_fwd_ok(
 
 extern "C" int u3d_conv2d_wgrad_bf16_supported(int Cin, int Cout) { return c2b_wgrad_ok(Cin, Cout) ? 1 : 0; }
 
-extern "C" long long u3d_packed_weight2d_bf16_elems(int Cin, int Cout, int mode) {
+extern "C" int u3d_conv2d_bf16_c16_supported(int Cin, int Cout) { return c2b_c16_ok(Cin, Cout) ? 1 : 0; }
+
+extern "C" int u3d_conv2d_wgrad_bf16_c16_supported(int Cin, int Cout) { return c2b_c16_ok(Cin, Cout) ? 1 : 0; }
+
+namespace {
+
+// envelope of an entry point: today's (forward: contraction % 16, produced % 32; weight gradient: both % 32) or the `_c16` one
+inline bool c2b_env_fwd(int Cin, int Cout, bool c16) { return c16 ? c2b_c16_ok(Cin, Cout) : c2b_fwd_ok(Cin, Cout); }
+inline bool c2b_env_wgrad(int Cin, int Cout, bool c16) { return c16 ? c2b_c16_ok(Cin, Cout) : c2b_wgrad_ok(Cin, Cout); }
+
+long long c2b_packed_elems(int Cin, int Cout, int mode, bool c16) {
     if (mode != 0 && mode != 1) return 0;
     int K, Nn;
     c2b_dims(Cin, Cout, mode, K, Nn);
-    if (!c2b_fwd_ok(K, Nn)) return 0;
-    return (long long)(K / c2b::CC) * 9 * (Nn / 32) * 64 * 8;
+    if (!c2b_env_fwd(K, Nn, c16)) return 0;
+    return (long long)(K / c2b::CC) * 9 * c2b_cdiv(Nn, 32) * 64 * 8;  // (a half n-tile is stored whole, its upper columns zero)
 }
 
-extern "C" int u3d_pack_weights2d_bf16(int device, u3d_stream_t stream, const float* w, int Cout, int Cin, int mode, void* packed) {
+int c2b_pack_launch(const char* who, int device, u3d_stream_t stream, const float* w, int Cout, int Cin, int mode, void* packed, bool c16) {
     U3D_ENTER(device);
-    U3D_REQUIRE(w && packed && Cout > 0 && Cin > 0 && (mode == 0 || mode == 1), "u3d_pack_weights2d_bf16: bad argument");
+    U3D_REQUIRE(w && packed && Cout > 0 && Cin > 0 && (mode == 0 || mode == 1), "%s: bad argument", who);
     int K, Nn;
     c2b_dims(Cin, Cout, mode, K, Nn);
-    U3D_REQUIRE(c2b_fwd_ok(K, Nn), "u3d_pack_weights2d_bf16: mode %d of a (%d -> %d) weight is outside the bf16 envelope (contraction %% 16, "
-                "produced %% 32)", mode, Cin, Cout);
-    U3D_REQUIRE(c2b_aligned(packed), "u3d_pack_weights2d_bf16: the image must be 16-byte aligned");
-    const long long total = u3d_packed_weight2d_bf16_elems(Cin, Cout, mode);
+    U3D_REQUIRE(c2b_env_fwd(K, Nn, c16), "%s: mode %d of a (%d -> %d) weight is outside the bf16 envelope (contraction %% 16, "
+                "produced %% %d)", who, mode, Cin, Cout, c16 ? 16 : 32);
+    U3D_REQUIRE(c2b_aligned(packed), "%s: the image must be 16-byte aligned", who);
+    const long long total = c2b_packed_elems(Cin, Cout, mode, c16);
     long long blocks = c2b_cdiv(total, 256);
     if (blocks > 4096) blocks = 4096;
     hipLaunchKernelGGL(pack_weights2d_bf16_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, w, Cout, Cin, mode, K, Nn,
-                       Nn / 32, total, reinterpret_cast<__bf16*>(packed));
+                       (int)c2b_cdiv(Nn, 32), total, reinterpret_cast<__bf16*>(packed));
     U3D_LAUNCH_CHECK();
     return 0;
 }
 
-extern "C" long long u3d_conv2d_bf16_workspace_floats(int N, int H, int W, int Cin, int Cout) {
-    if (N <= 0 || H <= 0 || W <= 0 || !c2b_fwd_ok(Cin, Cout)) return 0;
+}  // namespace
+
+extern "C" long long u3d_packed_weight2d_bf16_elems(int Cin, int Cout, int mode) { return c2b_packed_elems(Cin, Cout, mode, false); }
+
+extern "C" long long u3d_packed_weight2d_bf16_c16_elems(int Cin, int Cout, int mode) { return c2b_packed_elems(Cin, Cout, mode, true); }
+
+extern "C" int u3d_pack_weights2d_bf16(int device, u3d_stream_t stream, const float* w, int Cout, int Cin, int mode, void* packed) {
+    return c2b_pack_launch("u3d_pack_weights2d_bf16", device, stream, w, Cout, Cin, mode, packed, false);
+}
+
+// ... of a layer with both channel counts % 16: the same fragment layout (for produced channels % 32 the same image bit for bit)
+extern "C" int u3d_pack_weights2d_bf16_c16(int device, u3d_stream_t stream, const float* w, int Cout, int Cin, int mode, void* packed) {
+    return c2b_pack_launch("u3d_pack_weights2d_bf16_c16", device, stream, w, Cout, Cin, mode, packed, true);
+}
+
+namespace {
+
+long long c2b_fwd_workspace(int N, int H, int W, int Cin, int Cout, bool c16) {
+    if (N <= 0 || H <= 0 || W <= 0 || !c2b_env_fwd(Cin, Cout, c16)) return 0;
     const C2bPlan pl = c2b_plan(c2b_current_device(), N, H, W, Cin, Cout);
     return pl.ksplit > 1 ? (long long)pl.ksplit * N * H * W * Cout : 0;
 }
 
-// host-only query of that plan (tests assert that the shapes they pin really run the variants a full-resolution level runs)
-extern "C" int u3d_conv2d_bf16_variant(int N, int H, int W, int Cin, int Cout, int has_workspace) {
-    if (N <= 0 || H <= 0 || W <= 0 || !c2b_fwd_ok(Cin, Cout)) return -1;
+int c2b_fwd_variant(int N, int H, int W, int Cin, int Cout, int has_workspace, bool c16) {
+    if (N <= 0 || H <= 0 || W <= 0 || !c2b_env_fwd(Cin, Cout, c16)) return -1;
     const C2bPlan pl = c2b_plan(c2b_current_device(), N, H, W, Cin, Cout);
     return (c2b_launch_ksplit(pl, has_workspace != 0) << 8) | pl.nt;
+}
+
+}  // namespace
+
+extern "C" long long u3d_conv2d_bf16_workspace_floats(int N, int H, int W, int Cin, int Cout) {
+    return c2b_fwd_workspace(N, H, W, Cin, Cout, false);
+}
+
+extern "C" long long u3d_conv2d_bf16_c16_workspace_floats(int N, int H, int W, int Cin, int Cout) {
+    return c2b_fwd_workspace(N, H, W, Cin, Cout, true);
+}
+
+// host-only query of that plan (tests assert that the shapes they pin really run the variants a full-resolution level runs)
+extern "C" int u3d_conv2d_bf16_variant(int N, int H, int W, int Cin, int Cout, int has_workspace) {
+    return c2b_fwd_variant(N, H, W, Cin, Cout, has_workspace, false);
+}
+
+extern "C" int u3d_conv2d_bf16_c16_variant(int N, int H, int W, int Cin, int Cout, int has_workspace) {
+    return c2b_fwd_variant(N, H, W, Cin, Cout, has_workspace, true);
 }
 
 namespace {
@@ -618,10 +667,10 @@ namespace {
 // the one launcher behind u3d_conv2d_bf16 (residual == nullptr) and u3d_conv2d_bf16_res: same plan, same kernels
 int c2b_conv2d_launch(const char* who, int device, u3d_stream_t stream, const float* x, const float* affine, const void* packed_w,
                       float* out, int N, int H, int W, int Cin, int Cout, int relu, double* out_stats, const float* gx, double* gstats,
-                      float* workspace, long long workspace_floats, int stat_reps, const float* residual) {
+                      float* workspace, long long workspace_floats, int stat_reps, const float* residual, bool c16 = false) {
     U3D_ENTER(device);
-    U3D_REQUIRE(c2b_fwd_ok(Cin, Cout), "%s: (%d -> %d) channels are outside the bf16 envelope (Cin %% 16, Cout %% 32)", who, Cin,
-                Cout);
+    U3D_REQUIRE(c2b_env_fwd(Cin, Cout, c16), "%s: (%d -> %d) channels are outside the bf16 envelope (Cin %% 16, Cout %% %d)", who, Cin,
+                Cout, c16 ? 16 : 32);
     U3D_REQUIRE(x && packed_w && out && N > 0 && H > 0 && W > 0 && stat_reps >= 1 && (long long)N * H * W < (1LL << 31),
                 "%s: bad argument", who);
     U3D_REQUIRE(!gx || gstats, "%s: gx needs gstats", who);
@@ -675,6 +724,14 @@ extern "C" int u3d_conv2d_bf16(int device, u3d_stream_t stream, const float* x, 
                              workspace, workspace_floats, stat_reps, nullptr);
 }
 
+// the same launch for a layer with both channel counts % 16 (image of u3d_pack_weights2d_bf16_c16): the kernels mask co >= Cout
+extern "C" int u3d_conv2d_bf16_c16(int device, u3d_stream_t stream, const float* x, const float* affine, const void* packed_w, float* out,
+                                   int N, int H, int W, int Cin, int Cout, int relu, double* out_stats, const float* gx, double* gstats,
+                                   float* workspace, long long workspace_floats, int stat_reps) {
+    return c2b_conv2d_launch("u3d_conv2d_bf16_c16", device, stream, x, affine, packed_w, out, N, H, W, Cin, Cout, relu, out_stats, gx, gstats,
+                             workspace, workspace_floats, stat_reps, nullptr, true);
+}
+
 // out = [relu](conv2d(bf16(a*x + b), bf16(w)) + residual): the bf16 twin of u3d_conv2d_res_reps.  The plan (u3d_conv2d_bf16_variant,
 // u3d_conv2d_bf16_workspace_floats) does not depend on the residual.
 extern "C" int u3d_conv2d_bf16_res(int device, u3d_stream_t stream, const float* x, const float* affine, const void* packed_w, float* out,
@@ -685,28 +742,30 @@ extern "C" int u3d_conv2d_bf16_res(int device, u3d_stream_t stream, const float*
                              nullptr, workspace, workspace_floats, stat_reps, residual);
 }
 
-extern "C" long long u3d_wgrad2d_bf16_workspace_floats(int N, int H, int W, int Cin, int Cout) {
-    if (N <= 0 || H <= 0 || W <= 0 || !c2b_wgrad_ok(Cin, Cout)) return 0;
+namespace {
+
+long long c2b_wgrad_workspace(int N, int H, int W, int Cin, int Cout, bool c16) {
+    if (N <= 0 || H <= 0 || W <= 0 || !c2b_env_wgrad(Cin, Cout, c16)) return 0;
     const W2bPlan pl = w2b_plan(c2b_current_device(), N, H, W, Cin, Cout);
     return pl.nsplit > 1 ? (long long)pl.nsplit * Cout * Cin * 9 : 0;
 }
 
-extern "C" int u3d_conv2d_wgrad_bf16_variant(int N, int H, int W, int Cin, int Cout) {
-    if (N <= 0 || H <= 0 || W <= 0 || !c2b_wgrad_ok(Cin, Cout)) return -1;
+int c2b_wgrad_variant(int N, int H, int W, int Cin, int Cout, bool c16) {
+    if (N <= 0 || H <= 0 || W <= 0 || !c2b_env_wgrad(Cin, Cout, c16)) return -1;
     const W2bPlan pl = w2b_plan(c2b_current_device(), N, H, W, Cin, Cout);
     return (std::min(pl.tps, 0x7fff) << 16) | std::min(pl.nsplit, 0xffff);
 }
 
-extern "C" int u3d_conv2d_wgrad_bf16(int device, u3d_stream_t stream, const float* x, const float* affine, const float* dz, float* dw,
-                                     int N, int H, int W, int Cin, int Cout, float* workspace, long long workspace_floats) {
+int c2b_wgrad_launch(const char* who, int device, u3d_stream_t stream, const float* x, const float* affine, const float* dz, float* dw,
+                     int N, int H, int W, int Cin, int Cout, float* workspace, long long workspace_floats, bool c16) {
     U3D_ENTER(device);
-    U3D_REQUIRE(c2b_wgrad_ok(Cin, Cout), "u3d_conv2d_wgrad_bf16: (%d -> %d) channels are outside the bf16 envelope (both %% 32)", Cin,
-                Cout);
-    U3D_REQUIRE(x && dz && dw && N > 0 && H > 0 && W > 0 && (long long)N * H * W < (1LL << 31), "u3d_conv2d_wgrad_bf16: bad argument");
-    U3D_REQUIRE(c2b_aligned(x) && c2b_aligned(affine) && c2b_aligned(dz), "u3d_conv2d_wgrad_bf16: pointers must be 16-byte aligned");
+    U3D_REQUIRE(c2b_env_wgrad(Cin, Cout, c16), "%s: (%d -> %d) channels are outside the bf16 envelope (both %% %d)", who, Cin, Cout,
+                c16 ? 16 : 32);
+    U3D_REQUIRE(x && dz && dw && N > 0 && H > 0 && W > 0 && (long long)N * H * W < (1LL << 31), "%s: bad argument", who);
+    U3D_REQUIRE(c2b_aligned(x) && c2b_aligned(affine) && c2b_aligned(dz), "%s: pointers must be 16-byte aligned", who);
     const W2bPlan pl = w2b_plan(device, N, H, W, Cin, Cout);
     const long long need = pl.nsplit > 1 ? (long long)pl.nsplit * Cout * Cin * 9 : 0;
-    U3D_REQUIRE(need == 0 || (workspace && workspace_floats >= need), "u3d_conv2d_wgrad_bf16: workspace too small (%lld < %lld floats)",
+    U3D_REQUIRE(need == 0 || (workspace && workspace_floats >= need), "%s: workspace too small (%lld < %lld floats)", who,
                 workspace_floats, need);
     Wgrad2dBf16Params p = {};
     p.x = x;
@@ -716,7 +775,7 @@ extern "C" int u3d_conv2d_wgrad_bf16(int device, u3d_stream_t stream, const floa
     p.N = N, p.H = H, p.W = W, p.Cin = Cin, p.Cout = Cout;
     p.ty = pl.ty, p.tx = pl.tx, p.ncob = pl.ncob, p.ncib = pl.ncib, p.ntiles = pl.ntiles, p.tps = pl.tps;
     const long long blocks = (long long)pl.nsplit * pl.ncob * pl.ncib;
-    U3D_REQUIRE(blocks < (1LL << 31), "u3d_conv2d_wgrad_bf16: grid too large");
+    U3D_REQUIRE(blocks < (1LL << 31), "%s: grid too large", who);
     hipLaunchKernelGGL(conv2d_wgrad_bf16_kernel, dim3((unsigned)blocks), dim3(256), c2b::WG_LDS_BYTES, (hipStream_t)stream, p);
     U3D_LAUNCH_CHECK();
     if (need) {
@@ -728,6 +787,34 @@ extern "C" int u3d_conv2d_wgrad_bf16(int device, u3d_stream_t stream, const floa
         U3D_LAUNCH_CHECK();
     }
     return 0;
+}
+
+}  // namespace
+
+extern "C" long long u3d_wgrad2d_bf16_workspace_floats(int N, int H, int W, int Cin, int Cout) {
+    return c2b_wgrad_workspace(N, H, W, Cin, Cout, false);
+}
+
+extern "C" long long u3d_wgrad2d_bf16_c16_workspace_floats(int N, int H, int W, int Cin, int Cout) {
+    return c2b_wgrad_workspace(N, H, W, Cin, Cout, true);
+}
+
+extern "C" int u3d_conv2d_wgrad_bf16_variant(int N, int H, int W, int Cin, int Cout) { return c2b_wgrad_variant(N, H, W, Cin, Cout, false); }
+
+extern "C" int u3d_conv2d_wgrad_bf16_c16_variant(int N, int H, int W, int Cin, int Cout) {
+    return c2b_wgrad_variant(N, H, W, Cin, Cout, true);
+}
+
+extern "C" int u3d_conv2d_wgrad_bf16(int device, u3d_stream_t stream, const float* x, const float* affine, const float* dz, float* dw,
+                                     int N, int H, int W, int Cin, int Cout, float* workspace, long long workspace_floats) {
+    return c2b_wgrad_launch("u3d_conv2d_wgrad_bf16", device, stream, x, affine, dz, dw, N, H, W, Cin, Cout, workspace, workspace_floats, false);
+}
+
+// ... of a layer with both channel counts % 16: a 16-channel cell stages zeros for its two missing channel octets, dw stores are masked
+extern "C" int u3d_conv2d_wgrad_bf16_c16(int device, u3d_stream_t stream, const float* x, const float* affine, const float* dz, float* dw,
+                                         int N, int H, int W, int Cin, int Cout, float* workspace, long long workspace_floats) {
+    return c2b_wgrad_launch("u3d_conv2d_wgrad_bf16_c16", device, stream, x, affine, dz, dw, N, H, W, Cin, Cout, workspace, workspace_floats,
+                            true);
 }
 
 // =================================================================================================

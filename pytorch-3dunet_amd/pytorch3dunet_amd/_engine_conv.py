@@ -267,8 +267,16 @@ class ConvLayers:
         gradient and weight gradient on the `conv2d_bf16` family when it reads ONE real tensor (`virtual`: its input is a virtual concat)
         and `_bf16_layer` holds — with or without a residual in its epilogue (u3d_conv2d_bf16_res).  Asked in this form by
         `_weight_images` (which weights get BF16_FWD2D / BF16_DGRAD2D images) and `_layer_ws_floats` (scratch), and through
-        `_bf16_routed` by `_fwd_family` and `_conv_bwd`."""
-        return not virtual and self._bf16_layer(Cin, Cout)
+        `_bf16_routed` by `_fwd_family` and `_conv_bwd`, and by `_cat_bf16` for a decoder's written-out concat.  Under `native_2d_stem`
+        the rule widens to both channel counts % 16 (the net's 16-channel stem layers); a layer only inside the wider rule runs on the
+        `_c16` entry points with the `*_C16` images (`_c16`), a layer inside the old one keeps today's."""
+        if virtual:
+            return False
+        return self._bf16_layer(Cin, Cout) or bool(self.bf16 and getattr(self, "stem", False) and Cin % 16 == 0 and Cout % 16 == 0)
+
+    def _c16(self, Cin: int, Cout: int) -> bool:
+        """a layer `_bf16_routed_weight` accepts lies outside today's envelope: the `_c16` entry points and `*_C16` images are its"""
+        return not self._bf16_layer(Cin, Cout)
 
     def _bf16_routed(self, src: VSrc, Cout: int) -> bool:
         """`_bf16_routed_weight` for a layer about to run on `src`"""
@@ -300,10 +308,13 @@ class ConvLayers:
         "fp32": "_fwd_fp32",          # u3d_conv.hip: fp32 MFMA (persistent / generic / split-K chosen by the library)
         "conv2d": "_fwd_conv2d",      # u3d_conv2d.hip: 3x3 convolutions of a 2-D net (native_2d), every layer and only those ...
         "conv2d_bf16": "_fwd_conv2d_bf16",  # u3d_conv2d_bf16.hip: ... except, in bf16, the single-source layers that fit (`_bf16_routed`)
+        "small2d": "_fwd_small2d",    # u3d_conv2d.hip: ... and, under `native_2d_stem`, the first layer, Cin <= 4 (the 3-D `small` rule)
     }
 
     def _fwd_family(self, c: "_ConvCall", residual) -> str:
         if getattr(self, "is2d", False):
+            if self._small2d(c.Ctot, c.Cout, c.src.t1 is not None) and residual is None:
+                return "small2d"
             # (a decoder's first conv reaches here on its materialised concat when it fits: `_cat_bf16`; forward and data gradient
             # are covered together by the one channel rule; a residual rides in either family's epilogue)
             return "conv2d_bf16" if self._bf16_routed(c.src, c.Cout) else "conv2d"
@@ -322,6 +333,20 @@ class ConvLayers:
         ystats = c.take_stats(self.stat_reps)
         nat.call("u3d_conv3d_small_cin_fwd_reps", c.dev.index, _stream(c.dev), _p(c.src.t0), _p(c.affine), _p(c.conv.weight.detach()),
                  _p(c.y), c.N, c.D, c.H, c.W, c.Ctot, c.Cout, c.relu, *_tab(ystats), flops=c.flops)
+        return ystats
+
+    def _small2d(self, Cin: int, Cout: int, virtual: bool) -> bool:
+        """THE rule for the small-Cin family of a 2-D net under `native_2d_stem`, the 3-D `small` rule: a single real source with
+        Cin <= 4 and Cout <= 32 (no residual: DoubleConv nets have none).  Asked by `_fwd_family`, `_weight_images` (such a layer gets no
+        packed image up front) and `_layer_ws_floats`."""
+        return bool(getattr(self, "stem", False)) and self.small_cin and not virtual and Cin <= 4 and Cout <= 32
+
+    def _fwd_small2d(self, c: "_ConvCall"):
+        # first layer of a 2-D net under `native_2d_stem`: direct / 16x16x4-MFMA kernels on the reference weight layout (csrc/u3d_conv2d.hip)
+        assert c.D == 1 and c.src.t1 is None
+        ystats = c.take_stats(self.stat_reps)
+        nat.call("u3d_conv2d_small_cin_fwd_reps", c.dev.index, _stream(c.dev), _p(c.src.t0), _p(c.affine), _p(c.conv.weight.detach()),
+                 _p(c.y), c.N, c.H, c.W, c.Ctot, c.Cout, c.relu, *_tab(ystats), flops=18.0 * c.Ctot * c.Cout * c.N * c.H * c.W)
         return ystats
 
     def _fwd_subpixel(self, c: "_ConvCall"):
@@ -409,16 +434,20 @@ class ConvLayers:
         # after it), ReLU and statistics as the fp32 kernel; with a residual (ResidualUNet2D's conv3 in a pre-norm order): out =
         # [relu](conv + residual), the fp32 residual added to the fp32 sum in the epilogue (u3d_conv2d_bf16_res)
         assert c.D == 1 and c.src.t1 is None
-        wp = self.images.get(c.conv.weight, Kind.BF16_FWD2D, c.dev)
+        c16 = self._c16(c.Ctot, c.Cout)  # (a 16-channel stem layer under `native_2d_stem`: same kernels, `_c16` envelope)
+        assert not (c16 and c.residual is not None)
+        wp = self.images.get(c.conv.weight, Kind.BF16_FWD2D_C16 if c16 else Kind.BF16_FWD2D, c.dev)
         ystats = c.take_stats(self.stat_reps)
-        need = nat.get_lib().u3d_conv2d_bf16_workspace_floats(c.N, c.H, c.W, c.Ctot, c.Cout)  # split-K scratch on small grids
+        lib = nat.get_lib()
+        need = (lib.u3d_conv2d_bf16_c16_workspace_floats if c16 else lib.u3d_conv2d_bf16_workspace_floats)(
+            c.N, c.H, c.W, c.Ctot, c.Cout)  # split-K scratch on small grids
         kws = _empty(need, dtype=_F32, device=c.dev) if need > 0 else None
         yp, yr = _tab(ystats)
         args = [c.dev.index, _stream(c.dev), _p(c.src.t0), _p(c.affine), _p(wp), _p(c.y), c.N, c.H, c.W, c.Ctot, c.Cout, c.relu, yp, None,
                 None, _p(kws), need, yr]
         if c.residual is not None:  # (the `_res` entry point: the same arguments plus the residual)
             args.append(_p(c.residual))
-        nat.call("u3d_conv2d_bf16_res" if c.residual is not None else "u3d_conv2d_bf16", *args,
+        nat.call("u3d_conv2d_bf16_res" if c.residual is not None else ("u3d_conv2d_bf16_c16" if c16 else "u3d_conv2d_bf16"), *args,
                  flops=18.0 * c.Ctot * c.Cout * c.N * c.H * c.W)
         return ystats
 
@@ -484,7 +513,7 @@ class ConvLayers:
         call = _ConvCall(dev, conv, src, affine, y, N, D, H, W, Ctot, Cout, relu, bool(want_stats and self.fused_stats), pool, conv_res,
                          sub, b16, *(split[1:] if split is not None else (None, None)))
         family = self._fwd_family(call, residual)
-        small = family == "small"
+        small = family in ("small", "small2d")
         dmod = getattr(sc, "dropout", None) if spec.drop == "d" else (getattr(sc, "dropout2d", None) if spec.drop == "D" else None)
         # record_only (recomputation under activation checkpointing, the block's LAST convolution): y_out still holds this layer's final
         # output — the block output the forward pass kept — so only what backward needs beside it is rebuilt (the GroupNorm tables of
@@ -763,19 +792,22 @@ class ConvLayers:
         # both operands rounded to bf16 while staged (g = a*x + b and dz), fp32 sums added in a fixed order; takes no GroupNorm-backward
         # job, like the fp32 2-D kernel
         cx, dev, src, rec = c.cx, c.cx.dev, c.src, c.rec
-        need = nat.get_lib().u3d_wgrad2d_bf16_workspace_floats(c.N, c.H, c.W, src.C, c.Cout)
+        sfx = "_c16" if self._c16(src.C, c.Cout) else ""
+        need = getattr(nat.get_lib(), f"u3d_wgrad2d_bf16{sfx}_workspace_floats")(c.N, c.H, c.W, src.C, c.Cout)
         ws = cx.ensure_ws(need)
-        nat.call("u3d_conv2d_wgrad_bf16", dev.index, _stream(dev), _p(src.t0), _p(rec.affine), _p(c.dz), _p(cx.gview(rec.idx_w)), c.N,
+        nat.call("u3d_conv2d_wgrad_bf16" + sfx, dev.index, _stream(dev), _p(src.t0), _p(rec.affine), _p(c.dz), _p(cx.gview(rec.idx_w)), c.N,
                  c.H, c.W, src.C, c.Cout, _p(ws), ws.numel(), flops=18.0 * src.C * c.Cout * c.N * c.H * c.W)
 
     def _dgrad_conv2d_bf16(self, c: "_BwdCall"):
         cx, dev, src, rec = c.cx, c.cx.dev, c.src, c.rec
-        wpd = self.images.get(rec.conv_w, Kind.BF16_DGRAD2D, dev)
+        c16 = self._c16(src.C, c.Cout)
+        sfx = "_c16" if c16 else ""
+        wpd = self.images.get(rec.conv_w, Kind.BF16_DGRAD2D_C16 if c16 else Kind.BF16_DGRAD2D, dev)
         dg = _empty((c.N, c.D, c.H, c.W, src.C), dtype=_F32, device=dev)
         gst = cx.pool.table(c.N, src.C, c.greps)
-        need = nat.get_lib().u3d_conv2d_bf16_workspace_floats(c.N, c.H, c.W, c.Cout, src.C)  # roles swapped
+        need = getattr(nat.get_lib(), f"u3d_conv2d_bf16{sfx}_workspace_floats")(c.N, c.H, c.W, c.Cout, src.C)  # roles swapped
         kws = cx.ensure_ws(need) if need > 0 else None
-        nat.call("u3d_conv2d_bf16", dev.index, _stream(dev), _p(c.dz), None, _p(wpd), _p(dg), c.N, c.H, c.W, c.Cout, src.C, 0, None,
+        nat.call("u3d_conv2d_bf16" + sfx, dev.index, _stream(dev), _p(c.dz), None, _p(wpd), _p(dg), c.N, c.H, c.W, c.Cout, src.C, 0, None,
                  _p(src.t0), _p(gst.t), _p(kws), need, gst.reps, flops=18.0 * src.C * c.Cout * c.N * c.H * c.W)
         return dg, (gst, None)
 
@@ -828,9 +860,14 @@ class ConvLayers:
         if rec.small and not need_dg:
             # one pass gives dw and the GroupNorm-backward sums; no data gradient needed (csrc/u3d_smallc.hip)
             gst = pool.table(Nn, src.C)
-            nat.call("u3d_conv3d_small_cin_bwd", dev.index, _stream(dev), _p(src.t0), _p(rec.affine), _p(dz_),
-                     _p(rec.conv_w.detach()), _p(gview(rec.idx_w)), _p(gst.t), Nn, Dd, Hh, Ww, src.C, Cout, _p(ws), ws.numel(),
-                     flops=2 * 54.0 * src.C * Cout * Nn * Dd * Hh * Ww)
+            if getattr(self, "is2d", False):  # (D = 1: the 2-D twin, csrc/u3d_conv2d.hip)
+                nat.call("u3d_conv2d_small_cin_bwd", dev.index, _stream(dev), _p(src.t0), _p(rec.affine), _p(dz_),
+                         _p(rec.conv_w.detach()), _p(gview(rec.idx_w)), _p(gst.t), Nn, Hh, Ww, src.C, Cout, _p(ws), ws.numel(),
+                         flops=2 * 18.0 * src.C * Cout * Nn * Hh * Ww)
+            else:
+                nat.call("u3d_conv3d_small_cin_bwd", dev.index, _stream(dev), _p(src.t0), _p(rec.affine), _p(dz_),
+                         _p(rec.conv_w.detach()), _p(gview(rec.idx_w)), _p(gst.t), Nn, Dd, Hh, Ww, src.C, Cout, _p(ws), ws.numel(),
+                         flops=2 * 54.0 * src.C * Cout * Nn * Dd * Hh * Ww)
             if not rec.pre_norm:
                 return None, self._identity_coef(Nn, src.C, dev), None
             coef = _empty((Nn, 3, src.C), dtype=_F32, device=dev)
@@ -885,8 +922,13 @@ class ConvLayers:
         """scratch floats one 3x3x3 layer's backward needs from the shared buffer, for the kernels it will actually run"""
         lib = nat.get_lib()
         if getattr(self, "is2d", False):  # weight gradient + the data gradient's split-K scratch (roles swapped)
+            if small:  # (the one-pass backward, or — when a data gradient is needed — the fall-through to the fp32 family)
+                return max(lib.u3d_small_cin2d_bwd_workspace_floats(N, H, W, Cin, Cout), lib.u3d_wgrad2d_workspace_floats(N, H, W, Cin, Cout),
+                           lib.u3d_conv2d_workspace_floats(N, H, W, Cout, Cin))
             if self._bf16_routed_weight(Cin, Cout, virtual):  # (the bf16 kernels' plans, csrc/u3d_conv2d_bf16.hip)
-                return max(lib.u3d_wgrad2d_bf16_workspace_floats(N, H, W, Cin, Cout), lib.u3d_conv2d_bf16_workspace_floats(N, H, W, Cout, Cin))
+                sfx = "_c16" if self._c16(Cin, Cout) else ""
+                return max(getattr(lib, f"u3d_wgrad2d_bf16{sfx}_workspace_floats")(N, H, W, Cin, Cout),
+                           getattr(lib, f"u3d_conv2d_bf16{sfx}_workspace_floats")(N, H, W, Cout, Cin))
             return max(lib.u3d_wgrad2d_workspace_floats(N, H, W, Cin, Cout), lib.u3d_conv2d_workspace_floats(N, H, W, Cout, Cin))
         if small:
             return lib.u3d_small_cin_bwd_workspace_floats(N, D, H, W, Cin, Cout)

@@ -46,6 +46,8 @@ class Kind(enum.IntEnum):
     CONVTR2D_DGRAD = enum.auto()
     BF16_FWD2D = enum.auto()    # ... of a 2-D net in bf16 (`native_2d_bf16`, `native_2d_residual_bf16`): the layers the bf16 kernels cover
     BF16_DGRAD2D = enum.auto()
+    BF16_FWD2D_C16 = enum.auto()    # ... the 16-channel stem layers among them (`native_2d_stem`): half n-tiles stored whole, zero upper columns
+    BF16_DGRAD2D_C16 = enum.auto()
     CONVTR2D_BF16_FWD = enum.auto()    # ConvTranspose2d on the bf16 kernels (`native_2d_residual_bf16_deconv`): B[ci][co] per tap ...
     CONVTR2D_BF16_DGRAD = enum.auto()  # ... B[co][ci] per tap
 
@@ -69,6 +71,7 @@ _taps = lambda lib, ci, co, m: 27 * ci * co  # noqa: E731
 _2d = lambda lib, ci, co, m: lib.u3d_packed_weight2d_floats(ci, co, m)  # noqa: E731
 _tr2d = lambda lib, ci, co, m: lib.u3d_convtr2d_packed_floats(ci, co)  # noqa: E731
 _2db = lambda lib, ci, co, m: lib.u3d_packed_weight2d_bf16_elems(ci, co, m)  # noqa: E731
+_2db16 = lambda lib, ci, co, m: lib.u3d_packed_weight2d_bf16_c16_elems(ci, co, m)  # noqa: E731
 _tr2db = lambda lib, ci, co, m: lib.u3d_packed_convtr2d_bf16_elems(ci, co, m)  # noqa: E731
 
 # the C-ABI mode numbers of include/u3d.h live in this table (and `_BF16_BOTH`) and nowhere else in the package
@@ -97,6 +100,8 @@ _KINDS = {
     Kind.CONVTR2D_DGRAD: _Spec(_tr2d, _F32, "u3d_pack_convtr2d", 1, transposed=True),
     Kind.BF16_FWD2D: _Spec(_2db, _BF16, "u3d_pack_weights2d_bf16", 0),
     Kind.BF16_DGRAD2D: _Spec(_2db, _BF16, "u3d_pack_weights2d_bf16", 1),
+    Kind.BF16_FWD2D_C16: _Spec(_2db16, _BF16, "u3d_pack_weights2d_bf16_c16", 0),
+    Kind.BF16_DGRAD2D_C16: _Spec(_2db16, _BF16, "u3d_pack_weights2d_bf16_c16", 1),
     Kind.CONVTR2D_BF16_FWD: _Spec(_tr2db, _BF16, "u3d_pack_convtr2d_bf16", 0, transposed=True),
     Kind.CONVTR2D_BF16_DGRAD: _Spec(_tr2db, _BF16, "u3d_pack_convtr2d_bf16", 1, transposed=True),
 }
@@ -104,14 +109,14 @@ _BF16_BOTH = 6  # batch row that writes BF16_FWD and, right behind it in one buf
 
 
 class WeightImages:
-    """The image cache of one executor.  `f32` / `bf16` / `t8` / `each` / `each_bf16`: the weights whose images ride in the fp32 batch
+    """The image cache of one executor.  `f32` / `bf16` / `t8` / `each` / `each_bf16` / `each_bf16_c16`: the weights whose images ride in the fp32 batch
     launch, in the bf16 batch launch (3x3x3 layers, space-to-depth transposed convolutions) or are packed one launch each (2-D nets: fp32
     images, bf16 images of the layers on the bf16 kernels) at the start of a forward (`repack`); every other image is packed when `get`
     first misses it.  Constructing it does not touch the native library."""
 
-    def __init__(self, f32=(), bf16=(), t8=(), each=(), each_bf16=()):
+    def __init__(self, f32=(), bf16=(), t8=(), each=(), each_bf16=(), each_bf16_c16=()):
         self._f32, self._bf16, self._t8, self._each = list(f32), list(bf16), list(t8), list(each)
-        self._each_bf16 = list(each_bf16)
+        self._each_bf16, self._each_bf16_c16 = list(each_bf16), list(each_bf16_c16)
         self._images: dict = {}  # (id(weight), kind, sub-pixel pair or None) -> (version key, device buffer)
         self._tables: dict = {}  # batch launch -> (its stale set, descriptor tables + the buffers they point at): one live plan each
         self._salt = 0           # advanced by begin_forward / invalidate: see _ver
@@ -223,6 +228,9 @@ class WeightImages:
                 self.get(w, kind, dev)
         for w in self._each_bf16:  # ... and of the 2-D layers on the bf16 kernels (u3d_pack_weights2d_bf16)
             for kind in (Kind.BF16_FWD2D, Kind.BF16_DGRAD2D)[:nd]:
+                self.get(w, kind, dev)
+        for w in self._each_bf16_c16:  # ... and of its 16-channel stem layers (u3d_pack_weights2d_bf16_c16)
+            for kind in (Kind.BF16_FWD2D_C16, Kind.BF16_DGRAD2D_C16)[:nd]:
                 self.get(w, kind, dev)
         if self._bf16 or self._t8:
             self._repack_bf16(dev, nd)

@@ -473,6 +473,14 @@ _PROTOS = {
                                    c_size_t]),
     "u3d_wgrad2d_workspace_floats": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "u3d_conv2d_wgrad": (c_int, [c_int, c_void_p, POINTER(U3DSrc), c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t]),
+    # small-Cin first layer of a 2-D net (`native_2d_stem`; csrc/u3d_conv2d.hip)
+    "u3d_conv2d_small_cin_fwd_variant": (c_int, [c_int, c_int, c_int, c_int, c_int]),
+    "u3d_conv2d_small_cin_fwd_reps": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                              c_int, c_void_p, c_int]),
+    "u3d_small_cin2d_bwd_workspace_floats": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "u3d_conv2d_small_cin_bwd_variant": (c_int, [c_int, c_int, c_int, c_int, c_int]),
+    "u3d_conv2d_small_cin_bwd": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                         c_int, c_int, c_void_p, c_size_t]),
     # bf16-operand 2-D convolutions (csrc/u3d_conv2d_bf16.hip)
     "u3d_conv2d_bf16_supported": (c_int, [c_int, c_int]),
     "u3d_conv2d_wgrad_bf16_supported": (c_int, [c_int, c_int]),
@@ -488,6 +496,19 @@ _PROTOS = {
     "u3d_conv2d_wgrad_bf16_variant": (c_int, [c_int, c_int, c_int, c_int, c_int]),
     "u3d_conv2d_wgrad_bf16": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
                                       c_void_p, c_int64]),
+    # ... their `_c16` twins: both channel counts % 16 (`native_2d_stem` next to `native_2d_bf16`)
+    "u3d_conv2d_bf16_c16_supported": (c_int, [c_int, c_int]),
+    "u3d_conv2d_wgrad_bf16_c16_supported": (c_int, [c_int, c_int]),
+    "u3d_packed_weight2d_bf16_c16_elems": (c_int64, [c_int, c_int, c_int]),
+    "u3d_pack_weights2d_bf16_c16": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "u3d_conv2d_bf16_c16_workspace_floats": (c_int64, [c_int, c_int, c_int, c_int, c_int]),
+    "u3d_conv2d_bf16_c16_variant": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int]),
+    "u3d_conv2d_bf16_c16": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
+                                    c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int]),
+    "u3d_wgrad2d_bf16_c16_workspace_floats": (c_int64, [c_int, c_int, c_int, c_int, c_int]),
+    "u3d_conv2d_wgrad_bf16_c16_variant": (c_int, [c_int, c_int, c_int, c_int, c_int]),
+    "u3d_conv2d_wgrad_bf16_c16": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                          c_void_p, c_int64]),
     # bf16-operand ConvTranspose2d (csrc/u3d_conv2d_bf16.hip)
     "u3d_convtr2d_bf16_supported": (c_int, [c_int, c_int]),
     "u3d_packed_convtr2d_bf16_elems": (c_int64, [c_int, c_int, c_int]),

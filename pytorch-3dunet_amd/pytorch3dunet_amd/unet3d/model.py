@@ -16,7 +16,8 @@ the same module tree through stock PyTorch-ROCm operators after a one-time warni
 models are outside the 3-D path and keep that warning path by default (opt-in since round 7: `native_2d: true` / U3D_NATIVE_2D=1 runs a
 fp32 UNet2D with nearest upsampling on the 2-D kernels of csrc/u3d_conv2d.hip; `native_2d_residual: true` / U3D_NATIVE_2D_RESIDUAL=1
 does the same for a fp32 ResidualUNet2D; `native_2d_bf16: true` / U3D_NATIVE_2D_BF16=1 runs a UNet2D with bf16 MFMA operands on the kernels
-of csrc/u3d_conv2d_bf16.hip, `native_2d_residual_bf16: true` / U3D_NATIVE_2D_RESIDUAL_BF16=1 a ResidualUNet2D); U3D_STRICT=1 makes them an error too.  Covered since round 2: every layer order with at most one
+of csrc/u3d_conv2d_bf16.hip, `native_2d_residual_bf16: true` / U3D_NATIVE_2D_RESIDUAL_BF16=1 a ResidualUNet2D; `native_2d_stem: true` /
+U3D_NATIVE_2D_STEM=1 adds the small-Cin first-layer kernels to a native UNet2D); U3D_STRICT=1 makes them an error too.  Covered since round 2: every layer order with at most one
 GroupNorm / BatchNorm, one non-linearity and a trailing dropout, every `upsample` value the reference itself can run
 on a 3-D net, nn.DataParallel, activation checkpointing, and the opt-in compute modes `bf16` and `fp32_split`.
 """
@@ -45,7 +46,7 @@ class AbstractUNet(nn.Module):
                  conv_padding=1, conv_upscale=2, upsample="default", dropout_prob=0.1, is3d=True, compute_dtype=None,
                  checkpoint_encoders=None, hip_graph=None, activation_dtype=None, checkpoint_levels=None,
                  native_2d=None, native_2d_residual=None, native_2d_bf16=None, native_2d_residual_bf16=None,
-                 native_2d_residual_bf16_deconv=None):
+                 native_2d_residual_bf16_deconv=None, native_2d_stem=None):
         super().__init__()
         if isinstance(f_maps, int):
             f_maps = number_of_features_per_level(f_maps, num_levels=num_levels)
@@ -114,7 +115,17 @@ class AbstractUNet(nn.Module):
                 raise ValueError(f"u3d: native_2d_bf16 runs bf16 operands; compute_dtype {compute_dtype!r} contradicts it — drop one of "
                                  "the two keys (native_2d: true is the fp32 2-D path)")
             native_2d, compute_dtype = True, "bf16"
+        # `native_2d_stem: true` (its own key, so that native_2d / native_2d_bf16 alone stay bit-identical; U3D_NATIVE_2D_STEM=1 sets its
+        # default): the first layer of a UNet2D (DoubleConv blocks; a single real source with Cin <= 4 and Cout <= 32, the 3-D path's
+        # rule) runs on the small-Cin kernels of csrc/u3d_conv2d.hip — exact fp32 in either precision mode.  It implies native_2d and no
+        # precision: next to native_2d_bf16 every other layer keeps that mode's routing.  Every other class ignores it
+        if native_2d_stem is None:
+            native_2d_stem = os.environ.get("U3D_NATIVE_2D_STEM", "0") == "1"
+        stem_2d = bool(native_2d_stem) and not is3d and basic_module is DoubleConv
+        if stem_2d:
+            native_2d = True
         self.native_2d = bool(native_2d) and not is3d
+        self.native_2d_stem = stem_2d
         self.native_2d_bf16 = bf16_2d
         self.native_2d_residual_bf16 = res2d_bf16
         self.native_2d_residual_bf16_deconv = res2d_bf16_deconv
@@ -354,7 +365,8 @@ def _variant(name, basic_module, default_levels, is3d, doc):
                               checkpoint_levels=kwargs.get("checkpoint_levels"), native_2d=kwargs.get("native_2d"),
                               native_2d_residual=kwargs.get("native_2d_residual"), native_2d_bf16=kwargs.get("native_2d_bf16"),
                               native_2d_residual_bf16=kwargs.get("native_2d_residual_bf16"),
-                              native_2d_residual_bf16_deconv=kwargs.get("native_2d_residual_bf16_deconv"))
+                              native_2d_residual_bf16_deconv=kwargs.get("native_2d_residual_bf16_deconv"),
+                              native_2d_stem=kwargs.get("native_2d_stem"))
 
     return type(name, (AbstractUNet,), {"__init__": __init__, "__doc__": doc, "__module__": _THIS_MODULE})
 

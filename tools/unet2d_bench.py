@@ -3,7 +3,9 @@
 PyTorch-ROCm operators, after its one-time warning) in the same process, alternating the two.  --bf16 adds the same step with
 `native_2d_bf16: true` — on the ResidualUNet2D configurations `native_2d_residual_bf16: true` — (csrc/u3d_conv2d_bf16.hip for the layers
 that fit) as a third path in the same alternation, and on the ResidualUNet2D configurations `native_2d_residual_bf16_deconv: true` (the
-decoders' ConvTranspose2d on u3d_convtr2d_*_bf16 as well) as a fourth.
+decoders' ConvTranspose2d on u3d_convtr2d_*_bf16 as well) as a fourth.  --stem adds, on the UNet2D configurations, `native_2d` +
+`native_2d_stem: true` (the first layer on the small-Cin kernels of csrc/u3d_conv2d.hip) and, with --bf16, `native_2d_bf16` +
+`native_2d_stem: true` (also the 16-channel layers on the `_c16` entry points) to the same alternation.
 
   confocal  resources/2DUnet_confocal_boundary/train_config.yml: 32 x 1 x 515 x 512, gcr, f_maps 32, 4 levels
   dsb2018   resources/2DUnet_dsb2018/train_config.yml: bcr, f_maps [32, 64, 128], batch 32 — DSB2018 images vary in size;
@@ -23,7 +25,12 @@ measured with tools/mfma_bf16_peak.hip).  The ResidualUNet2D records add the dec
 native_2d_residual_bf16 arm of the same run, and the transposed-convolution family of both arms by entry point (fp32 u3d_convtr2d_* in
 the bf16 arm, u3d_convtr2d_*_bf16 in the deconv arm: ms per step and TFLOP/s on executed FLOPs).
 
-  python tools/unet2d_bench.py [--configs confocal,dsb2018] [--batch N] [--steps 10] [--warmup 3] [--bf16]   (--batch: every config's own default)"""
+With --stem the record adds each stem arm's ms per step and its speed-up over the arm it sits on in the same run, the per-call ms of
+the new entry points next to the fp32 launches of the first two layers they replace (u3d_conv2d_ex_reps / u3d_conv2d_wgrad of the arm
+without the key: the difference of the two arms' totals), and the new entry points' GB/s on the bytes each launch must move (inputs read
+once, outputs written once) to hold against the chip's ~6.3 TB/s copy rate.
+
+  python tools/unet2d_bench.py [--configs confocal,dsb2018] [--batch N] [--steps 10] [--warmup 3] [--bf16] [--stem]   (--batch: every config's own default)"""
 import argparse
 import json
 import os
@@ -106,13 +113,16 @@ def make(cfg, native, dev):
     from pytorch3dunet_amd.unet3d.model import get_model
 
     torch.manual_seed(0)
+    extra = {}
+    if native in ("stem", "bf16_stem"):
+        extra, native = dict(native_2d_stem=True), ("bf16" if native == "bf16_stem" else True)
     if native == "bf16_deconv":
         key, native = "native_2d_residual_bf16_deconv", True
     elif native == "bf16":
         key, native = ("native_2d_residual_bf16" if _residual(cfg) else "native_2d_bf16"), True
     else:
         key = "native_2d_residual" if _residual(cfg) else "native_2d"
-    m = get_model(dict(cfg, **{key: native})).to(dev).train()
+    m = get_model(dict(cfg, **{key: native}, **extra)).to(dev).train()
     return m, FusedAdam(m.parameters(), lr=1e-4, weight_decay=1e-5)
 
 
@@ -144,6 +154,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=2, help="alternating native / stock rounds of --steps each")
     ap.add_argument("--native-only", action="store_true", help="time the native path only (profiler runs)")
     ap.add_argument("--bf16", action="store_true", help="also time the step with native_2d_bf16 / native_2d_residual_bf16, alternated with the others")
+    ap.add_argument("--stem", action="store_true", help="also time the UNet2D step with native_2d_stem next to native_2d (and, with --bf16, next to native_2d_bf16)")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "unet2d_bench measures on the GPU"
     from pytorch3dunet_amd import _native as nat
@@ -163,6 +174,10 @@ def main():
             paths.insert(1, "bf16")
             if _residual(cfg):
                 paths.insert(2, "bf16_deconv")
+        if a.stem and not _residual(cfg):
+            paths.insert(1, "stem")
+            if a.bf16:
+                paths.insert(paths.index("bf16") + 1, "bf16_stem")
         runs = {p: make(cfg, p, dev) for p in paths}
         for p in paths:
             for _ in range(a.warmup):
@@ -246,6 +261,41 @@ def main():
                        bf16_deconv_convtr2d_family_ms_per_step=round(sum(v["ms"] for v in tr16.values()), 3),
                        bf16_deconv_convtr2d_calls=calls(tr16),
                        bf16_deconv_conv2d_calls=calls(dconv))
+        if "stem" in ms:
+            # the stem arms against the arms they sit on, in the same run; the new entry points per call, and the fp32 launches of the
+            # first two layers they replace as the difference of the two arms' u3d_conv2d_ex_reps / u3d_conv2d_wgrad totals
+            P = float(batch * hw[0] * hw[1])
+            m0 = runs[True][0]
+            c_in, c1, c2 = (m0.encoders[0].basic_module.SingleConv1.conv.in_channels, m0.encoders[0].basic_module.SingleConv1.conv.out_channels,
+                            m0.encoders[0].basic_module.SingleConv2.conv.out_channels)
+            must_move = {"u3d_conv2d_small_cin_fwd_reps": 4 * P * (c_in + c1), "u3d_conv2d_small_cin_bwd": 4 * P * (c_in + c1),
+                         # one 16-channel layer c1 -> c2: forward (read c1, write c2) + data gradient (read dz c2, write c1, read x c1)
+                         "u3d_conv2d_bf16_c16": 4 * P * (c1 + c2) + 4 * P * (c2 + 2 * c1), "u3d_conv2d_wgrad_bf16_c16": 4 * P * (c1 + c2)}
+            want_calls = {"u3d_conv2d_small_cin_fwd_reps": 1, "u3d_conv2d_small_cin_bwd": 1, "u3d_conv2d_bf16_c16": 2, "u3d_conv2d_wgrad_bf16_c16": 1}
+
+            def new_calls(d):
+                out = {}
+                for k, v in d.items():
+                    if k in must_move:
+                        gbs = must_move[k] / v["ms"] / 1e6 if v["ms"] and v["calls"] == want_calls[k] else None  # (else: not the one-layer stem)
+                        out[k] = {"calls": v["calls"], "ms": round(v["ms"], 3), "gb_per_s_on_bytes_it_must_move": round(gbs, 1) if gbs else None}
+                return out
+
+            def replaced(base, stem):
+                return {k: {"calls": base[k]["calls"] - stem.get(k, {"calls": 0})["calls"],
+                            "ms": round(base[k]["ms"] - stem.get(k, {"ms": 0.0})["ms"], 3)}
+                        for k in ("u3d_conv2d_ex_reps", "u3d_conv2d_wgrad") if k in base}
+
+            sfam = family_step("stem")
+            rec.update(stem_ms_per_step=[round(v, 3) for v in ms["stem"]], stem_speedup_over_native_fp32=round(best[True] / best["stem"], 3),
+                       stem_new_calls=new_calls(sfam), stem_replaced_fp32_calls=replaced(fam, sfam))
+            if "bf16_stem" in ms:
+                bsfam = family_step("bf16_stem")
+                rec.update(bf16_stem_ms_per_step=[round(v, 3) for v in ms["bf16_stem"]],
+                           bf16_stem_images_per_s=round(batch * 1000.0 / best["bf16_stem"], 2),
+                           bf16_stem_speedup_over_bf16=round(best["bf16"] / best["bf16_stem"], 3),
+                           bf16_stem_new_calls=new_calls(bsfam), bf16_stem_replaced_fp32_calls=replaced(bfam, bsfam),
+                           bf16_stem_conv2d_calls=calls({k: v for k, v in bsfam.items() if "conv2d" in k}))
         if not a.native_only:
             rec.update(stock_ms_per_step=[round(v, 3) for v in ms[False]], stock_images_per_s=round(batch * 1000.0 / best[False], 2),
                        native_speedup=round(best[False] / best[True], 3))
