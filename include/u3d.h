@@ -949,7 +949,8 @@ int u3d_convtr2d_wgrad(int device, u3d_stream_t stream, const float* x, const fl
  * (round-to-nearest-even), products accumulated in FP32; activations, outputs, statistics and dw stay fp32 tensors in HBM (NHWC, the
  * D = 1 layout).  Rounding points: the weights when the image is packed from the fp32 master copy; the activations ONCE while they are
  * staged into LDS, after the fp32 affine fmaf(a, x, b) (padding stays exactly 0, it applies after the affine); in the weight gradient
- * both g = a*x + b (zero padded) and dz.  Single-tensor sources only (no virtual concat), 16-byte aligned pointers.
+ * both g = a*x + b (zero padded) and dz.  Single-tensor sources (a decoder's virtual concat: the `_src` entry points below), 16-byte
+ * aligned pointers.
  * Envelope (the 3-D rule): the contraction channels % 16 == 0 and the produced channels % 32 == 0 —
  *   u3d_conv2d_bf16_supported(Cin, Cout)        Cin % 16 == 0 and Cout % 32 == 0 (a data gradient asks with the roles swapped)
  *   u3d_conv2d_wgrad_bf16_supported(Cin, Cout)  Cin % 32 == 0 and Cout % 32 == 0 (both are produced; the contraction runs over pixels)
@@ -1024,6 +1025,32 @@ long long u3d_wgrad2d_bf16_c16_workspace_floats(int N, int H, int W, int Cin, in
 int u3d_conv2d_wgrad_bf16_c16_variant(int N, int H, int W, int Cin, int Cout);
 int u3d_conv2d_wgrad_bf16_c16(int device, u3d_stream_t stream, const float* x, const float* affine, const float* dz, float* dw, int N,
                               int H, int W, int Cin, int Cout, float* workspace, long long workspace_floats);
+/* (Added, U3D_VERSION unchanged.)  The `_src` twins of u3d_conv2d_bf16 / u3d_conv2d_wgrad_bf16 for the first convolution of a UNet2D
+ * decoder (`native_2d_bf16_vcat: true` next to `native_2d_bf16: true`): the layer's input torch.cat((skip, F.interpolate(x, size)), dim=1)
+ * (buildingblocks.py:491) is read as a virtual source — u3d_src_t with p0 = skip (N,H,W,C0), p1 = x (N,H1,W1,C1), D1 = 1 (zmap is not
+ * read) and the general nearest tables ymap[H] / xmap[W] (any ratio; 2n + 1 <- n included) — instead of a written-out copy.  Same
+ * kernels as the entry points above compiled with a second base pointer, same images, same rounding points: the source of a staged
+ * 16-channel chunk (forward), of a 32-channel channel block (weight gradient) and of a 32-channel n-tile (gx of the data gradient) is
+ * chosen uniformly over the block / wave.  For a concat written out by u3d_nearest_cat_fwd the single-tensor entry points return the
+ * same out, dg and dw bit for bit (the same bf16 values are staged in the same order).
+ * Envelope: C0 % 32 == 0, C1 % 32 == 0, C0 > 0, C1 > 0 (C1 == 0 is the entry point above), D1 == 1, ymap and xmap present, p0 / p1 /
+ * affine 16-byte aligned, and the rule above on (C0 + C1, Cout); outside it U3D_EINVAL without a launch.
+ *   u3d_conv2d_bf16_src        out = [relu](conv2d(bf16(a * src + b), bf16(w))) with the mode-0 image of the (Cout, C0 + C1, 3, 3) weight;
+ *              the affine table src->affine (optional) is (N, C0 + C1, 2), indexed by concat channel; out_stats as u3d_conv2d_bf16
+ *   u3d_conv2d_bf16_dgrad_src  dg (N,H,W,C0 + C1) = the data gradient from dz (N,H,W,Cout) with the mode-1 image — dz in and dg out are plain
+ *              tensors; gx is the VIRTUAL forward input (its affine field is ignored): gstats double[stat_reps][N][C0 + C1][2] +=
+ *              (sum dg, sum dg * gx), required.  A split-K launch's reduction kernel reads gx the same way.
+ *   u3d_conv2d_wgrad_bf16_src  dw (Cout, C0 + C1, 3, 3) = sum bf16(dz) * bf16(g), g = a * src + b zero padded
+ * A launch plan depends on (N, H, W, C0 + C1, Cout) only: u3d_conv2d_bf16_variant / u3d_conv2d_bf16_workspace_floats (roles swapped for
+ * the data gradient, as for u3d_conv2d_bf16) and u3d_conv2d_wgrad_bf16_variant / u3d_wgrad2d_bf16_workspace_floats describe these entry
+ * points unchanged, asked with Cin = C0 + C1. */
+int u3d_conv2d_bf16_src(int device, u3d_stream_t stream, const u3d_src_t* src, const void* packed_w, float* out, int N, int H, int W,
+                        int Cout, int relu, double* out_stats, float* workspace, long long workspace_floats, int stat_reps);
+int u3d_conv2d_bf16_dgrad_src(int device, u3d_stream_t stream, const float* dz, const void* packed_w, float* dg, int N, int H, int W,
+                              int Cout, const u3d_src_t* gx, double* gstats, float* workspace, long long workspace_floats,
+                              int stat_reps);
+int u3d_conv2d_wgrad_bf16_src(int device, u3d_stream_t stream, const u3d_src_t* src, const float* dz, float* dw, int N, int H, int W,
+                              int Cout, float* workspace, long long workspace_floats);
 
 /* ---- (Added, U3D_VERSION unchanged.)  bf16-operand ConvTranspose2d of ResidualUNet2D's decoders (`native_2d_residual_bf16_deconv:
  * true`; csrc/u3d_conv2d_bf16.hip) ------

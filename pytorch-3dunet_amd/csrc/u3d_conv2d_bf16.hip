@@ -26,6 +26,12 @@
 // contiguous bytes: conflict-free).  A block owns 32 output x 32 input channels x 9 taps and a contiguous range of pixel tiles; wave w
 // takes rows 4w .. 4w + 3 of a tile, one 16-pixel row per MFMA k-step, one dz fragment feeding 9 taps.  Partial sums go to a workspace and
 // are added in a fixed order (conv2d_wgrad_bf16_reduce_kernel): the same inputs give a bitwise-identical dW.
+//
+// Virtual concat (`native_2d_bf16_vcat`, the `_src` entry points): the first convolution of a decoder reads cat(skip, nearest(low)) through
+// u3d_src_t — two base pointers and the nearest tables ymap / xmap — instead of a written-out copy.  Compile-time variants of the same
+// kernels (template parameter V / VC and a parameter struct with the second base): with both halves % 32 channels a staged 16-channel
+// chunk, a 32-channel weight-gradient block and a 32-channel n-tile of the data gradient's gx lie wholly in one source, so the choice
+// is a uniform branch; the affine, the rounding and the zero padding stay in c2b_stage8.  The single-source instantiations are unchanged.
 #include <algorithm>
 
 #include "u3d_common.h"
@@ -136,6 +142,17 @@ struct Conv2dBf16Params {
     long long part_stride;
 };
 
+// ... of the `_src` entry points (`native_2d_bf16_vcat`): ONE of the two fp32 tensors is the virtual concat cat(skip, nearest(low)) of a
+// decoder's first convolution, read through two bases — x in the forward (V = 1), gx in the data gradient (V = 2).  The base struct's
+// pointer (x / gx) is the skip half (N,H,W,C0); channels [C0, C0 + C1) come from v1 (N,H1,W1,C1) at (ymap[y], xmap[x]).  Cin (V = 1) /
+// Cout (V = 2) stay the concat width C0 + C1: the affine table, the weight image and dg are indexed by concat channel.
+struct Conv2dBf16VParams : Conv2dBf16Params {
+    const float* v1;
+    const int32_t* ymap;
+    const int32_t* xmap;
+    int C0, C1, H1, W1;
+};
+
 // per-block statistics, as c2_flush_stats of csrc/u3d_conv2d.hip: column sums s[nt][0..3] = (sum v, sum v^2, sum v, sum v * gx) combined
 // over the lane halves, over the 4 waves in LDS (fixed order), then one f64 atomic per (sample, channel, quantity) and block into replica
 // row block % reps
@@ -176,8 +193,12 @@ __device__ __forceinline__ void c2b_flush_stats(const Conv2dBf16Params& p, float
     }
 }
 
-template <int NT>
-__global__ __launch_bounds__(256, 2) void conv2d_bf16_kernel(const Conv2dBf16Params p) {
+// V = 0: single tensors (P = Conv2dBf16Params, the kernels of u3d_conv2d_bf16 / _c16 / _res).  V = 1 / 2 (P = Conv2dBf16VParams): x / gx is
+// a virtual concat.  C0 and C1 are multiples of 32, so a staged 16-channel chunk and a 32-channel n-tile lie wholly in one source: the
+// choice is uniform over the block (per chunk) / over the n-tile and costs one scalar compare.
+template <int NT, int V, typename P>
+__global__ __launch_bounds__(256, 2) void conv2d_bf16_kernel(const P p) {
+    constexpr bool VX = V == 1, VG = V == 2;
     using namespace c2b;
     extern __shared__ __attribute__((aligned(16))) char lds_c2b[];
     char* const lds = lds_c2b;
@@ -204,6 +225,7 @@ __global__ __launch_bounds__(256, 2) void conv2d_bf16_kernel(const Conv2dBf16Par
     // ---- staging descriptors (constant across chunks): item = (halo pixel, channel octet q)
     int ldsoff[NIT], cqs[NIT];
     size_t goff[NIT];
+    size_t goff1[VX ? NIT : 1];  // (V = 1) the same halo pixel in the low-res half, through the nearest maps
     bool oks[NIT];
 #pragma unroll
     for (int it = 0; it < NIT; ++it) {
@@ -216,7 +238,12 @@ __global__ __launch_bounds__(256, 2) void conv2d_bf16_kernel(const Conv2dBf16Par
         oks[it] = ok;
         ldsoff[it] = in ? hy * RS + hx * PS + 16 * q : -1;
         cqs[it] = 8 * q;
-        goff[it] = ok ? ((size_t)(n * H + gy) * W + gxx) * Cin : 0;
+        if constexpr (VX) {
+            goff[it] = ok ? ((size_t)(n * H + gy) * W + gxx) * p.C0 : 0;
+            goff1[it] = ok ? ((size_t)(n * p.H1 + p.ymap[gy]) * p.W1 + p.xmap[gxx]) * p.C1 : 0;
+        } else {
+            goff[it] = ok ? ((size_t)(n * H + gy) * W + gxx) * Cin : 0;
+        }
     }
     f32x4 raw[NIT][2];
     auto load_chunk = [&](int c) {
@@ -224,7 +251,13 @@ __global__ __launch_bounds__(256, 2) void conv2d_bf16_kernel(const Conv2dBf16Par
         for (int it = 0; it < NIT; ++it) {
             raw[it][0] = raw[it][1] = f32x4{0.f, 0.f, 0.f, 0.f};
             if (oks[it]) {
-                const float* src = p.x + goff[it] + c * CC + cqs[it];
+                const float* src;
+                if constexpr (VX) {  // (the chunk's source: block-uniform)
+                    const int ch = c * CC;
+                    src = (ch >= p.C0 ? p.v1 + goff1[it] + (ch - p.C0) : p.x + goff[it] + ch) + cqs[it];
+                } else {
+                    src = p.x + goff[it] + c * CC + cqs[it];
+                }
                 raw[it][0] = u3d_ldq(src);
                 raw[it][1] = u3d_ldq(src + 4);
             }
@@ -319,7 +352,14 @@ __global__ __launch_bounds__(256, 2) void conv2d_bf16_kernel(const Conv2dBf16Par
                 s[nt][1] += v * v;
                 if (p.gx) {
                     s[nt][2] += v;
-                    s[nt][3] += v * p.gx[o];
+                    if constexpr (VG) {  // (the n-tile's source: uniform over the wave)
+                        const float xv = (cb * NT + nt) * 32 >= p.C0
+                                             ? p.v1[((size_t)(n * p.H1 + p.ymap[y]) * p.W1 + p.xmap[x]) * p.C1 + (co - p.C0)]
+                                             : p.gx[((size_t)(n * H + y) * W + x) * p.C0 + co];
+                        s[nt][3] += v * xv;
+                    } else {
+                        s[nt][3] += v * p.gx[o];
+                    }
                 }
             }
     }
@@ -358,6 +398,35 @@ __global__ __launch_bounds__(256) void conv2d_bf16_splitk_reduce_kernel(const fl
             u3d_atomic_add_f64(gstats + ((size_t)n * Cout + co) * 2, g0);
             u3d_atomic_add_f64(gstats + ((size_t)n * Cout + co) * 2 + 1, g1);
         }
+    }
+}
+
+// ... of u3d_conv2d_bf16_dgrad_src (a data gradient: no ReLU, no output statistics, no residual): the same sums in the same order, gx read
+// as the virtual concat — skip half gx0 (N,H,W,C0), channels from C0 in gx1 (N,H1,W1,C1) through the nearest maps
+__global__ __launch_bounds__(256) void conv2d_bf16_splitk_reduce_vsrc_kernel(const float* __restrict__ part, long long part_stride,
+                                                                             int ksplit, float* __restrict__ out, int P, int Cout,
+                                                                             double* gstats, const float* __restrict__ gx0,
+                                                                             const float* __restrict__ gx1,
+                                                                             const int32_t* __restrict__ ymap,
+                                                                             const int32_t* __restrict__ xmap, int W, int C0, int C1,
+                                                                             int H1, int W1) {
+    const int n = blockIdx.y;
+    const int p0 = blockIdx.x * 64, p1 = min(P, p0 + 64);
+    for (int co = threadIdx.x; co < Cout; co += blockDim.x) {
+        double g0 = 0.0, g1 = 0.0;
+        for (int pp = p0; pp < p1; ++pp) {
+            const size_t o = ((size_t)n * P + pp) * Cout + co;
+            float v = 0.f;
+            for (int k = 0; k < ksplit; ++k) v += part[(size_t)k * part_stride + o];
+            out[o] = v;
+            const int y = pp / W, x = pp - y * W;
+            const float xv = co < C0 ? gx0[((size_t)n * P + pp) * C0 + co]
+                                     : gx1[((size_t)(n * H1 + ymap[y]) * W1 + xmap[x]) * C1 + (co - C0)];
+            g0 += v;
+            g1 += (double)v * xv;
+        }
+        u3d_atomic_add_f64(gstats + ((size_t)n * Cout + co) * 2, g0);
+        u3d_atomic_add_f64(gstats + ((size_t)n * Cout + co) * 2 + 1, g1);
     }
 }
 
@@ -402,6 +471,15 @@ struct Wgrad2dBf16Params {
     int ty, tx, ncob, ncib, ntiles, tps;
 };
 
+// ... of u3d_conv2d_wgrad_bf16_src: x is the skip half (N,H,W,C0), channels [C0, C0 + C1) of the virtual concat come from v1 (N,H1,W1,C1)
+// through the nearest maps; Cin = C0 + C1 (affine rows, dw layout).  A block's 32 input channels lie wholly in one source.
+struct Wgrad2dBf16VParams : Wgrad2dBf16Params {
+    const float* v1;
+    const int32_t* ymap;
+    const int32_t* xmap;
+    int C0, C1, H1, W1;
+};
+
 // two transposed reads of a [pixel][32 channels] bf16 image (64 bytes per pixel): pixels +0..3 and +4..7 of this lane's 8-pixel half.
 // (Every lane of the wave must be active: the gather crosses lanes.)
 __device__ __forceinline__ c2b_bf16x8 c2b_tr_frag(const char* lds_addr) {
@@ -413,7 +491,8 @@ __device__ __forceinline__ c2b_bf16x8 c2b_tr_frag(const char* lds_addr) {
     return __builtin_bit_cast(c2b_bf16x8, v);
 }
 
-__global__ __launch_bounds__(256, 2) void conv2d_wgrad_bf16_kernel(const Wgrad2dBf16Params p) {
+template <bool VC, typename P>
+__global__ __launch_bounds__(256, 2) void conv2d_wgrad_bf16_kernel(const P p) {
     using namespace c2b;
     extern __shared__ __attribute__((aligned(16))) char lds_w2b[];
     char* const lds = lds_w2b;
@@ -462,7 +541,13 @@ __global__ __launch_bounds__(256, 2) void conv2d_wgrad_bf16_kernel(const Wgrad2d
                 okg[k] = item < HY * HX * 4 && gy >= 0 && gy < H && gxx >= 0 && gxx < W && ci0 + 8 * q < Cin;
                 rg[k][0] = rg[k][1] = f32x4{0.f, 0.f, 0.f, 0.f};
                 if (okg[k]) {
-                    const float* src = p.x + ((size_t)(n * H + gy) * W + gxx) * Cin + ci0 + 8 * q;
+                    const float* src;
+                    if constexpr (VC) {  // (the channel block's source: block-uniform)
+                        src = (ci0 >= p.C0 ? p.v1 + ((size_t)(n * p.H1 + p.ymap[gy]) * p.W1 + p.xmap[gxx]) * p.C1 + (ci0 - p.C0)
+                                           : p.x + ((size_t)(n * H + gy) * W + gxx) * p.C0 + ci0) + 8 * q;
+                    } else {
+                        src = p.x + ((size_t)(n * H + gy) * W + gxx) * Cin + ci0 + 8 * q;
+                    }
                     rg[k][0] = u3d_ldq(src);
                     rg[k][1] = u3d_ldq(src + 4);
                 }
@@ -664,10 +749,19 @@ extern "C" int u3d_conv2d_bf16_c16_variant(int N, int H, int W, int Cin, int Cou
 
 namespace {
 
-// the one launcher behind u3d_conv2d_bf16 (residual == nullptr) and u3d_conv2d_bf16_res: same plan, same kernels
+// envelope of a virtual source of the `_src` entry points: both halves present and % 32 (a chunk, an n-tile and a weight-gradient
+// channel block then lie in one source), D1 = 1, the two index tables, 16-byte aligned halves
+inline bool c2b_vsrc_ok(const u3d_src_t* s) {
+    return s && s->p0 && s->p1 && s->ymap && s->xmap && s->C0 > 0 && s->C1 > 0 && s->C0 % 32 == 0 && s->C1 % 32 == 0 && s->D1 == 1 &&
+           s->H1 > 0 && s->W1 > 0 && c2b_aligned(s->p0) && c2b_aligned(s->p1);
+}
+
+// the one launcher behind u3d_conv2d_bf16 (residual == nullptr), u3d_conv2d_bf16_res and the `_src` entry points: same plan, same
+// kernels.  vmode 1: x is the virtual concat `vsrc` (x == vsrc->p0); vmode 2: gx is (gx == vsrc->p0); 0: single tensors
 int c2b_conv2d_launch(const char* who, int device, u3d_stream_t stream, const float* x, const float* affine, const void* packed_w,
                       float* out, int N, int H, int W, int Cin, int Cout, int relu, double* out_stats, const float* gx, double* gstats,
-                      float* workspace, long long workspace_floats, int stat_reps, const float* residual, bool c16 = false) {
+                      float* workspace, long long workspace_floats, int stat_reps, const float* residual, bool c16 = false,
+                      int vmode = 0, const u3d_src_t* vsrc = nullptr) {
     U3D_ENTER(device);
     U3D_REQUIRE(c2b_env_fwd(Cin, Cout, c16), "%s: (%d -> %d) channels are outside the bf16 envelope (Cin %% 16, Cout %% %d)", who, Cin,
                 Cout, c16 ? 16 : 32);
@@ -701,15 +795,36 @@ int c2b_conv2d_launch(const char* who, int device, u3d_stream_t stream, const fl
     p.part_stride = (long long)N * H * W * Cout;
     const long long blocks = (long long)N * pl.ty * pl.tx * pl.ncb * p.ksplit;
     U3D_REQUIRE(blocks < (1LL << 31), "%s: grid too large", who);
-    if (pl.nt == 2)
-        hipLaunchKernelGGL(conv2d_bf16_kernel<2>, dim3((unsigned)blocks), dim3(256), c2b::LDS_BYTES, (hipStream_t)stream, p);
-    else
-        hipLaunchKernelGGL(conv2d_bf16_kernel<1>, dim3((unsigned)blocks), dim3(256), c2b::LDS_BYTES, (hipStream_t)stream, p);
+    const dim3 grid((unsigned)blocks), block(256);
+    if (vmode == 0) {
+        if (pl.nt == 2)
+            hipLaunchKernelGGL((conv2d_bf16_kernel<2, 0, Conv2dBf16Params>), grid, block, c2b::LDS_BYTES, (hipStream_t)stream, p);
+        else
+            hipLaunchKernelGGL((conv2d_bf16_kernel<1, 0, Conv2dBf16Params>), grid, block, c2b::LDS_BYTES, (hipStream_t)stream, p);
+    } else {
+        Conv2dBf16VParams vp = {};
+        static_cast<Conv2dBf16Params&>(vp) = p;
+        vp.v1 = vsrc->p1, vp.ymap = vsrc->ymap, vp.xmap = vsrc->xmap;
+        vp.C0 = vsrc->C0, vp.C1 = vsrc->C1, vp.H1 = vsrc->H1, vp.W1 = vsrc->W1;
+        if (vmode == 1 && pl.nt == 2)
+            hipLaunchKernelGGL((conv2d_bf16_kernel<2, 1, Conv2dBf16VParams>), grid, block, c2b::LDS_BYTES, (hipStream_t)stream, vp);
+        else if (vmode == 1)
+            hipLaunchKernelGGL((conv2d_bf16_kernel<1, 1, Conv2dBf16VParams>), grid, block, c2b::LDS_BYTES, (hipStream_t)stream, vp);
+        else if (pl.nt == 2)
+            hipLaunchKernelGGL((conv2d_bf16_kernel<2, 2, Conv2dBf16VParams>), grid, block, c2b::LDS_BYTES, (hipStream_t)stream, vp);
+        else
+            hipLaunchKernelGGL((conv2d_bf16_kernel<1, 2, Conv2dBf16VParams>), grid, block, c2b::LDS_BYTES, (hipStream_t)stream, vp);
+    }
     U3D_LAUNCH_CHECK();
     if (split) {
         const int P = H * W;
-        hipLaunchKernelGGL(conv2d_bf16_splitk_reduce_kernel, dim3((unsigned)c2b_cdiv(P, 64), N), dim3(256), 0, (hipStream_t)stream, workspace,
-                           p.part_stride, p.ksplit, out, P, Cout, p.relu, out_stats, gx, gstats, residual);
+        if (vmode == 2)
+            hipLaunchKernelGGL(conv2d_bf16_splitk_reduce_vsrc_kernel, dim3((unsigned)c2b_cdiv(P, 64), N), dim3(256), 0, (hipStream_t)stream,
+                               workspace, p.part_stride, p.ksplit, out, P, Cout, gstats, vsrc->p0, vsrc->p1, vsrc->ymap, vsrc->xmap, W,
+                               vsrc->C0, vsrc->C1, vsrc->H1, vsrc->W1);
+        else
+            hipLaunchKernelGGL(conv2d_bf16_splitk_reduce_kernel, dim3((unsigned)c2b_cdiv(P, 64), N), dim3(256), 0, (hipStream_t)stream,
+                               workspace, p.part_stride, p.ksplit, out, P, Cout, p.relu, out_stats, gx, gstats, residual);
         U3D_LAUNCH_CHECK();
     }
     return 0;
@@ -742,6 +857,29 @@ extern "C" int u3d_conv2d_bf16_res(int device, u3d_stream_t stream, const float*
                              nullptr, workspace, workspace_floats, stat_reps, residual);
 }
 
+// ---- the `_src` entry points (`native_2d_bf16_vcat`): the first convolution of a decoder reads its input cat(skip, nearest(low)) through
+// two bases instead of a written-out copy.  Same plans (they depend on (N, H, W, C0 + C1, Cout) only), same images, same staged values.
+extern "C" int u3d_conv2d_bf16_src(int device, u3d_stream_t stream, const u3d_src_t* src, const void* packed_w, float* out, int N, int H,
+                                   int W, int Cout, int relu, double* out_stats, float* workspace, long long workspace_floats,
+                                   int stat_reps) {
+    U3D_REQUIRE(c2b_vsrc_ok(src), "u3d_conv2d_bf16_src: needs a virtual source with C0 %% 32 == 0, C1 %% 32 == 0, C0 > 0, C1 > 0 (C1 == 0 is "
+                "u3d_conv2d_bf16), D1 == 1, ymap / xmap and 16-byte aligned halves");
+    return c2b_conv2d_launch("u3d_conv2d_bf16_src", device, stream, src->p0, src->affine, packed_w, out, N, H, W, src->C0 + src->C1, Cout,
+                             relu, out_stats, nullptr, nullptr, workspace, workspace_floats, stat_reps, nullptr, false, 1, src);
+}
+
+// dg (N,H,W,C0 + C1) = the data gradient of that layer from dz (N,H,W,Cout) with the mode-1 image; gstats += (sum dg, sum dg * gx) with gx
+// the VIRTUAL forward input (its affine field is ignored)
+extern "C" int u3d_conv2d_bf16_dgrad_src(int device, u3d_stream_t stream, const float* dz, const void* packed_w, float* dg, int N, int H,
+                                         int W, int Cout, const u3d_src_t* gx, double* gstats, float* workspace,
+                                         long long workspace_floats, int stat_reps) {
+    U3D_REQUIRE(c2b_vsrc_ok(gx), "u3d_conv2d_bf16_dgrad_src: gx must be a virtual source with C0 %% 32 == 0, C1 %% 32 == 0, C0 > 0, C1 > 0, "
+                "D1 == 1, ymap / xmap and 16-byte aligned halves");
+    U3D_REQUIRE(gstats, "u3d_conv2d_bf16_dgrad_src: gx needs gstats");
+    return c2b_conv2d_launch("u3d_conv2d_bf16_dgrad_src", device, stream, dz, nullptr, packed_w, dg, N, H, W, Cout, gx->C0 + gx->C1, 0,
+                             nullptr, gx->p0, gstats, workspace, workspace_floats, stat_reps, nullptr, false, 2, gx);
+}
+
 namespace {
 
 long long c2b_wgrad_workspace(int N, int H, int W, int Cin, int Cout, bool c16) {
@@ -757,7 +895,8 @@ int c2b_wgrad_variant(int N, int H, int W, int Cin, int Cout, bool c16) {
 }
 
 int c2b_wgrad_launch(const char* who, int device, u3d_stream_t stream, const float* x, const float* affine, const float* dz, float* dw,
-                     int N, int H, int W, int Cin, int Cout, float* workspace, long long workspace_floats, bool c16) {
+                     int N, int H, int W, int Cin, int Cout, float* workspace, long long workspace_floats, bool c16,
+                     const u3d_src_t* vsrc = nullptr) {
     U3D_ENTER(device);
     U3D_REQUIRE(c2b_env_wgrad(Cin, Cout, c16), "%s: (%d -> %d) channels are outside the bf16 envelope (both %% %d)", who, Cin, Cout,
                 c16 ? 16 : 32);
@@ -776,7 +915,17 @@ int c2b_wgrad_launch(const char* who, int device, u3d_stream_t stream, const flo
     p.ty = pl.ty, p.tx = pl.tx, p.ncob = pl.ncob, p.ncib = pl.ncib, p.ntiles = pl.ntiles, p.tps = pl.tps;
     const long long blocks = (long long)pl.nsplit * pl.ncob * pl.ncib;
     U3D_REQUIRE(blocks < (1LL << 31), "%s: grid too large", who);
-    hipLaunchKernelGGL(conv2d_wgrad_bf16_kernel, dim3((unsigned)blocks), dim3(256), c2b::WG_LDS_BYTES, (hipStream_t)stream, p);
+    if (vsrc == nullptr) {
+        hipLaunchKernelGGL((conv2d_wgrad_bf16_kernel<false, Wgrad2dBf16Params>), dim3((unsigned)blocks), dim3(256), c2b::WG_LDS_BYTES,
+                           (hipStream_t)stream, p);
+    } else {  // (x == vsrc->p0: the skip half)
+        Wgrad2dBf16VParams vp = {};
+        static_cast<Wgrad2dBf16Params&>(vp) = p;
+        vp.v1 = vsrc->p1, vp.ymap = vsrc->ymap, vp.xmap = vsrc->xmap;
+        vp.C0 = vsrc->C0, vp.C1 = vsrc->C1, vp.H1 = vsrc->H1, vp.W1 = vsrc->W1;
+        hipLaunchKernelGGL((conv2d_wgrad_bf16_kernel<true, Wgrad2dBf16VParams>), dim3((unsigned)blocks), dim3(256), c2b::WG_LDS_BYTES,
+                           (hipStream_t)stream, vp);
+    }
     U3D_LAUNCH_CHECK();
     if (need) {
         const long long total = (long long)Cout * Cin * 9;
@@ -815,6 +964,16 @@ extern "C" int u3d_conv2d_wgrad_bf16_c16(int device, u3d_stream_t stream, const 
                                          int N, int H, int W, int Cin, int Cout, float* workspace, long long workspace_floats) {
     return c2b_wgrad_launch("u3d_conv2d_wgrad_bf16_c16", device, stream, x, affine, dz, dw, N, H, W, Cin, Cout, workspace, workspace_floats,
                             true);
+}
+
+// ... of a decoder's first convolution on its virtual concat (`native_2d_bf16_vcat`): g = affine(cat(skip, nearest(low))), dw (Cout, C0 +
+// C1, 3, 3); plan and workspace as u3d_conv2d_wgrad_bf16 for Cin = C0 + C1
+extern "C" int u3d_conv2d_wgrad_bf16_src(int device, u3d_stream_t stream, const u3d_src_t* src, const float* dz, float* dw, int N, int H,
+                                         int W, int Cout, float* workspace, long long workspace_floats) {
+    U3D_REQUIRE(c2b_vsrc_ok(src), "u3d_conv2d_wgrad_bf16_src: needs a virtual source with C0 %% 32 == 0, C1 %% 32 == 0, C0 > 0, C1 > 0 (C1 == 0 "
+                "is u3d_conv2d_wgrad_bf16), D1 == 1, ymap / xmap and 16-byte aligned halves");
+    return c2b_wgrad_launch("u3d_conv2d_wgrad_bf16_src", device, stream, src->p0, src->affine, dz, dw, N, H, W, src->C0 + src->C1, Cout,
+                            workspace, workspace_floats, false, src);
 }
 
 // =================================================================================================

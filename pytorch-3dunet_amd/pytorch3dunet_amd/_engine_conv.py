@@ -274,13 +274,25 @@ class ConvLayers:
             return False
         return self._bf16_layer(Cin, Cout) or bool(self.bf16 and getattr(self, "stem", False) and Cin % 16 == 0 and Cout % 16 == 0)
 
+    def _bf16_vcat(self, src: VSrc, Cout: int) -> bool:
+        """THE rule for a decoder's first conv under `native_2d_bf16_vcat`, stated once: the layer runs on the `_src` entry points of the
+        `conv2d_bf16` family — reading cat(skip, nearest(low)) through two bases, BF16_FWD2D / BF16_DGRAD2D images as any bf16 layer —
+        when the key is on, the model's layer order is pre-norm (as `_cat_bf16` requires), both halves are fp32 tensors with channel
+        counts % 32 (the kernels choose the source per 16-channel chunk / 32-channel block) and `_bf16_layer` holds on (C0 + C1, Cout).
+        A decoder outside it (16-channel halves under `native_2d_stem`, odd counts) keeps the written-out concat of `_cat_bf16`."""
+        return (bool(getattr(self, "vcat", False)) and not self.post_norm and src.t1 is not None and src.C0 > 0 and src.C1 > 0
+                and src.C0 % 32 == 0 and src.C1 % 32 == 0 and self._bf16_layer(src.C, Cout)
+                and src.t0.dtype == _F32 and src.t1.dtype == _F32 and os.environ.get("U3D_BF16_CAT", "1") != "0")
+
     def _c16(self, Cin: int, Cout: int) -> bool:
         """a layer `_bf16_routed_weight` accepts lies outside today's envelope: the `_c16` entry points and `*_C16` images are its"""
         return not self._bf16_layer(Cin, Cout)
 
     def _bf16_routed(self, src: VSrc, Cout: int) -> bool:
-        """`_bf16_routed_weight` for a layer about to run on `src`"""
-        return self._bf16_routed_weight(src.C, Cout, src.t1 is not None)
+        """`_bf16_routed_weight` for a layer about to run on `src` (a virtual one: `_bf16_vcat`)"""
+        if src.t1 is not None:
+            return self._bf16_vcat(src, Cout)
+        return self._bf16_routed_weight(src.C, Cout, False)
 
     def _bf16_convtr2d(self, Cin: int, Cout: int) -> bool:
         """THE rule for a decoder's ConvTranspose2d under `native_2d_residual_bf16_deconv`, stated once: forward, data gradient and weight
@@ -433,7 +445,18 @@ class ConvLayers:
         # bf16 MFMA operands, fp32 accumulation / epilogue on the D = 1 tensors (csrc/u3d_conv2d_bf16.hip): fused affine (rounded once
         # after it), ReLU and statistics as the fp32 kernel; with a residual (ResidualUNet2D's conv3 in a pre-norm order): out =
         # [relu](conv + residual), the fp32 residual added to the fp32 sum in the epilogue (u3d_conv2d_bf16_res)
-        assert c.D == 1 and c.src.t1 is None
+        assert c.D == 1
+        if c.src.t1 is not None:  # a decoder's virtual concat (`_bf16_vcat`): same plan, image and scratch, `_src` entry point
+            assert c.residual is None and not self._c16(c.Ctot, c.Cout)
+            wp = self.images.get(c.conv.weight, Kind.BF16_FWD2D, c.dev)
+            ystats = c.take_stats(self.stat_reps)
+            need = nat.get_lib().u3d_conv2d_bf16_workspace_floats(c.N, c.H, c.W, c.Ctot, c.Cout)
+            kws = _empty(need, dtype=_F32, device=c.dev) if need > 0 else None
+            yp, yr = _tab(ystats)
+            s = c.src.struct(c.affine)
+            nat.call("u3d_conv2d_bf16_src", c.dev.index, _stream(c.dev), ctypes.byref(s), _p(wp), _p(c.y), c.N, c.H, c.W, c.Cout, c.relu,
+                     yp, _p(kws), need, yr, flops=18.0 * c.Ctot * c.Cout * c.N * c.H * c.W)
+            return ystats
         c16 = self._c16(c.Ctot, c.Cout)  # (a 16-channel stem layer under `native_2d_stem`: same kernels, `_c16` envelope)
         assert not (c16 and c.residual is not None)
         wp = self.images.get(c.conv.weight, Kind.BF16_FWD2D_C16 if c16 else Kind.BF16_FWD2D, c.dev)
@@ -795,6 +818,11 @@ class ConvLayers:
         sfx = "_c16" if self._c16(src.C, c.Cout) else ""
         need = getattr(nat.get_lib(), f"u3d_wgrad2d_bf16{sfx}_workspace_floats")(c.N, c.H, c.W, src.C, c.Cout)
         ws = cx.ensure_ws(need)
+        if src.t1 is not None:  # (`_bf16_vcat`: the same plan on the virtual concat)
+            s = src.struct(rec.affine)
+            nat.call("u3d_conv2d_wgrad_bf16_src", dev.index, _stream(dev), ctypes.byref(s), _p(c.dz), _p(cx.gview(rec.idx_w)), c.N, c.H,
+                     c.W, c.Cout, _p(ws), ws.numel(), flops=18.0 * src.C * c.Cout * c.N * c.H * c.W)
+            return
         nat.call("u3d_conv2d_wgrad_bf16" + sfx, dev.index, _stream(dev), _p(src.t0), _p(rec.affine), _p(c.dz), _p(cx.gview(rec.idx_w)), c.N,
                  c.H, c.W, src.C, c.Cout, _p(ws), ws.numel(), flops=18.0 * src.C * c.Cout * c.N * c.H * c.W)
 
@@ -807,6 +835,11 @@ class ConvLayers:
         gst = cx.pool.table(c.N, src.C, c.greps)
         need = getattr(nat.get_lib(), f"u3d_conv2d_bf16{sfx}_workspace_floats")(c.N, c.H, c.W, c.Cout, src.C)  # roles swapped
         kws = cx.ensure_ws(need) if need > 0 else None
+        if src.t1 is not None:  # (`_bf16_vcat`: gx is the virtual concat; dz and dg are plain tensors of the full width)
+            s = src.struct()
+            nat.call("u3d_conv2d_bf16_dgrad_src", dev.index, _stream(dev), _p(c.dz), _p(wpd), _p(dg), c.N, c.H, c.W, c.Cout,
+                     ctypes.byref(s), _p(gst.t), _p(kws), need, gst.reps, flops=18.0 * src.C * c.Cout * c.N * c.H * c.W)
+            return dg, (gst, None)
         nat.call("u3d_conv2d_bf16" + sfx, dev.index, _stream(dev), _p(c.dz), None, _p(wpd), _p(dg), c.N, c.H, c.W, c.Cout, src.C, 0, None,
                  _p(src.t0), _p(gst.t), _p(kws), need, gst.reps, flops=18.0 * src.C * c.Cout * c.N * c.H * c.W)
         return dg, (gst, None)
@@ -949,6 +982,7 @@ class ConvLayers:
         """scratch floats the backward kernels of these recorded layers need (one shared buffer, sized once per backward)"""
         need = 0
         for r in convs:
+            # (a virtual concat the bf16 kernels read in place, `_bf16_vcat`, takes their plans like a single-source layer)
             need = max(need, self._layer_ws_floats(r.src.N, r.src.D, r.src.H, r.src.W, r.src.C, r.y.shape[-1], r.sub, r.small,
-                                                   r.src.t1 is not None))
+                                                   r.src.t1 is not None and not self._bf16_vcat(r.src, r.y.shape[-1])))
         return int(need)

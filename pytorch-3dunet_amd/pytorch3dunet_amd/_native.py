@@ -509,6 +509,12 @@ _PROTOS = {
     "u3d_conv2d_wgrad_bf16_c16_variant": (c_int, [c_int, c_int, c_int, c_int, c_int]),
     "u3d_conv2d_wgrad_bf16_c16": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
                                           c_void_p, c_int64]),
+    # ... on a decoder's virtual concat (`native_2d_bf16_vcat`): u3d_src_t* where the entry points above take x / gx
+    "u3d_conv2d_bf16_src": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                    c_int64, c_int]),
+    "u3d_conv2d_bf16_dgrad_src": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                          c_void_p, c_int64, c_int]),
+    "u3d_conv2d_wgrad_bf16_src": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int64]),
     # bf16-operand ConvTranspose2d (csrc/u3d_conv2d_bf16.hip)
     "u3d_convtr2d_bf16_supported": (c_int, [c_int, c_int]),
     "u3d_packed_convtr2d_bf16_elems": (c_int64, [c_int, c_int, c_int]),

@@ -17,7 +17,8 @@ models are outside the 3-D path and keep that warning path by default (opt-in si
 fp32 UNet2D with nearest upsampling on the 2-D kernels of csrc/u3d_conv2d.hip; `native_2d_residual: true` / U3D_NATIVE_2D_RESIDUAL=1
 does the same for a fp32 ResidualUNet2D; `native_2d_bf16: true` / U3D_NATIVE_2D_BF16=1 runs a UNet2D with bf16 MFMA operands on the kernels
 of csrc/u3d_conv2d_bf16.hip, `native_2d_residual_bf16: true` / U3D_NATIVE_2D_RESIDUAL_BF16=1 a ResidualUNet2D; `native_2d_stem: true` /
-U3D_NATIVE_2D_STEM=1 adds the small-Cin first-layer kernels to a native UNet2D); U3D_STRICT=1 makes them an error too.  Covered since round 2: every layer order with at most one
+U3D_NATIVE_2D_STEM=1 adds the small-Cin first-layer kernels to a native UNet2D, `native_2d_bf16_vcat: true` / U3D_NATIVE_2D_BF16_VCAT=1 reads
+the decoders' concat inside the bf16 kernels of a UNet2D); U3D_STRICT=1 makes them an error too.  Covered since round 2: every layer order with at most one
 GroupNorm / BatchNorm, one non-linearity and a trailing dropout, every `upsample` value the reference itself can run
 on a 3-D net, nn.DataParallel, activation checkpointing, and the opt-in compute modes `bf16` and `fp32_split`.
 """
@@ -46,7 +47,7 @@ class AbstractUNet(nn.Module):
                  conv_padding=1, conv_upscale=2, upsample="default", dropout_prob=0.1, is3d=True, compute_dtype=None,
                  checkpoint_encoders=None, hip_graph=None, activation_dtype=None, checkpoint_levels=None,
                  native_2d=None, native_2d_residual=None, native_2d_bf16=None, native_2d_residual_bf16=None,
-                 native_2d_residual_bf16_deconv=None, native_2d_stem=None):
+                 native_2d_residual_bf16_deconv=None, native_2d_stem=None, native_2d_bf16_vcat=None):
         super().__init__()
         if isinstance(f_maps, int):
             f_maps = number_of_features_per_level(f_maps, num_levels=num_levels)
@@ -109,10 +110,18 @@ class AbstractUNet(nn.Module):
         # other class ignores it, and `native_2d: true` + `compute_dtype: bf16` without it stays on the warning path
         if native_2d_bf16 is None:
             native_2d_bf16 = os.environ.get("U3D_NATIVE_2D_BF16", "0") == "1"
-        bf16_2d = bool(native_2d_bf16) and not is3d and basic_module is DoubleConv
+        # `native_2d_bf16_vcat: true` (a separate key, so that native_2d_bf16 alone stays bit-identical; U3D_NATIVE_2D_BF16_VCAT=1 sets its
+        # default): the decoders' first convolutions read torch.cat((skip, interpolate(x)), dim=1) inside the bf16 kernels through two
+        # base pointers (the `_src` entry points) instead of writing the concat out, when both halves are multiples of 32 channels; the
+        # arithmetic is unchanged.  It implies native_2d_bf16 and everything that key implies; every other class ignores it
+        if native_2d_bf16_vcat is None:
+            native_2d_bf16_vcat = os.environ.get("U3D_NATIVE_2D_BF16_VCAT", "0") == "1"
+        vcat_2d = bool(native_2d_bf16_vcat) and not is3d and basic_module is DoubleConv
+        bf16_2d = (bool(native_2d_bf16) or vcat_2d) and not is3d and basic_module is DoubleConv
         if bf16_2d:
             if compute_dtype is not None and str(compute_dtype).lower() not in ("bf16", "bfloat16"):
-                raise ValueError(f"u3d: native_2d_bf16 runs bf16 operands; compute_dtype {compute_dtype!r} contradicts it — drop one of "
+                key = "native_2d_bf16_vcat" if vcat_2d else "native_2d_bf16"
+                raise ValueError(f"u3d: {key} runs bf16 operands; compute_dtype {compute_dtype!r} contradicts it — drop one of "
                                  "the two keys (native_2d: true is the fp32 2-D path)")
             native_2d, compute_dtype = True, "bf16"
         # `native_2d_stem: true` (its own key, so that native_2d / native_2d_bf16 alone stay bit-identical; U3D_NATIVE_2D_STEM=1 sets its
@@ -127,6 +136,7 @@ class AbstractUNet(nn.Module):
         self.native_2d = bool(native_2d) and not is3d
         self.native_2d_stem = stem_2d
         self.native_2d_bf16 = bf16_2d
+        self.native_2d_bf16_vcat = vcat_2d
         self.native_2d_residual_bf16 = res2d_bf16
         self.native_2d_residual_bf16_deconv = res2d_bf16_deconv
         reasons = []
@@ -366,7 +376,7 @@ def _variant(name, basic_module, default_levels, is3d, doc):
                               native_2d_residual=kwargs.get("native_2d_residual"), native_2d_bf16=kwargs.get("native_2d_bf16"),
                               native_2d_residual_bf16=kwargs.get("native_2d_residual_bf16"),
                               native_2d_residual_bf16_deconv=kwargs.get("native_2d_residual_bf16_deconv"),
-                              native_2d_stem=kwargs.get("native_2d_stem"))
+                              native_2d_stem=kwargs.get("native_2d_stem"), native_2d_bf16_vcat=kwargs.get("native_2d_bf16_vcat"))
 
     return type(name, (AbstractUNet,), {"__init__": __init__, "__doc__": doc, "__module__": _THIS_MODULE})
 

@@ -30,7 +30,14 @@ the new entry points next to the fp32 launches of the first two layers they repl
 without the key: the difference of the two arms' totals), and the new entry points' GB/s on the bytes each launch must move (inputs read
 once, outputs written once) to hold against the chip's ~6.3 TB/s copy rate.
 
-  python tools/unet2d_bench.py [--configs confocal,dsb2018] [--batch N] [--steps 10] [--warmup 3] [--bf16] [--stem]   (--batch: every config's own default)"""
+With --vcat (next to --bf16 --stem, UNet2D configurations) the alternation gains the arm `native_2d_bf16` + `native_2d_stem` +
+`native_2d_bf16_vcat: true` (the decoders' first convolutions read their concat inside the bf16 kernels).  The record adds its ms per
+step and its speed-up over the `native_2d_bf16` + stem arm of the same run, the per-call ms of the three `_src` entry points, of the
+u3d_nearest_cat_fwd calls they replace and of the single-source bf16 calls of both arms (which the key must leave alone: the arm it sits
+on has the decoders' first convolutions among them, so the comparison is on the difference of the totals), and
+torch.cuda.max_memory_allocated over one step of every arm.
+
+  python tools/unet2d_bench.py [--configs confocal,dsb2018] [--batch N] [--steps 10] [--warmup 3] [--bf16] [--stem] [--vcat]   (--batch: every config's own default)"""
 import argparse
 import json
 import os
@@ -114,7 +121,9 @@ def make(cfg, native, dev):
 
     torch.manual_seed(0)
     extra = {}
-    if native in ("stem", "bf16_stem"):
+    if native == "bf16_stem_vcat":
+        extra, native = dict(native_2d_stem=True, native_2d_bf16_vcat=True), "bf16"
+    elif native in ("stem", "bf16_stem"):
         extra, native = dict(native_2d_stem=True), ("bf16" if native == "bf16_stem" else True)
     if native == "bf16_deconv":
         key, native = "native_2d_residual_bf16_deconv", True
@@ -155,6 +164,7 @@ def main():
     ap.add_argument("--native-only", action="store_true", help="time the native path only (profiler runs)")
     ap.add_argument("--bf16", action="store_true", help="also time the step with native_2d_bf16 / native_2d_residual_bf16, alternated with the others")
     ap.add_argument("--stem", action="store_true", help="also time the UNet2D step with native_2d_stem next to native_2d (and, with --bf16, next to native_2d_bf16)")
+    ap.add_argument("--vcat", action="store_true", help="with --bf16 --stem: also time the UNet2D step with native_2d_bf16_vcat on top of them")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "unet2d_bench measures on the GPU"
     from pytorch3dunet_amd import _native as nat
@@ -178,6 +188,8 @@ def main():
             paths.insert(1, "stem")
             if a.bf16:
                 paths.insert(paths.index("bf16") + 1, "bf16_stem")
+                if a.vcat:
+                    paths.insert(paths.index("bf16_stem") + 1, "bf16_stem_vcat")
         runs = {p: make(cfg, p, dev) for p in paths}
         for p in paths:
             for _ in range(a.warmup):
@@ -296,6 +308,40 @@ def main():
                            bf16_stem_speedup_over_bf16=round(best["bf16"] / best["bf16_stem"], 3),
                            bf16_stem_new_calls=new_calls(bsfam), bf16_stem_replaced_fp32_calls=replaced(bfam, bsfam),
                            bf16_stem_conv2d_calls=calls({k: v for k, v in bsfam.items() if "conv2d" in k}))
+        if "bf16_stem_vcat" in ms:
+            # the vcat arm against the bf16 + stem arm of the same run: every bf16 conv entry point and the concat copy, bracketed by
+            # name (u3d_nearest_cat_fwd declares no FLOPs); peak memory of one step per arm
+            names = ("u3d_conv2d_bf16", "u3d_conv2d_wgrad_bf16", "u3d_conv2d_bf16_c16", "u3d_conv2d_wgrad_bf16_c16", "u3d_nearest_cat_fwd",
+                     "u3d_conv2d_bf16_src", "u3d_conv2d_bf16_dgrad_src", "u3d_conv2d_wgrad_bf16_src")
+
+            def named_step(path):
+                prof = nat.EventProfiler(only=names, prealloc=512)
+                nat.profiler = prof
+                step(*runs[path], x, target, loss_fn)
+                torch.cuda.synchronize()
+                nat.profiler = None
+                return {k: {"calls": v["calls"], "ms": round(v["ms"], 3), "ms_per_call": round(v["ms"] / v["calls"], 4)}
+                        for k, v in prof.summary().items()}
+
+            def peak_bytes(path):
+                torch.cuda.synchronize()
+                torch.cuda.reset_peak_memory_stats(dev)
+                step(*runs[path], x, target, loss_fn)
+                torch.cuda.synchronize()
+                return torch.cuda.max_memory_allocated(dev)
+
+            base, vc = named_step("bf16_stem"), named_step("bf16_stem_vcat")
+            src_ms = sum(v["ms"] for k, v in vc.items() if k.endswith("_src"))
+            single = ("u3d_conv2d_bf16", "u3d_conv2d_wgrad_bf16")
+            rec.update(bf16_stem_vcat_ms_per_step=[round(v, 3) for v in ms["bf16_stem_vcat"]],
+                       bf16_stem_vcat_images_per_s=round(batch * 1000.0 / best["bf16_stem_vcat"], 2),
+                       bf16_stem_vcat_speedup_over_bf16_stem=round(best["bf16_stem"] / best["bf16_stem_vcat"], 4),
+                       bf16_stem_arm_calls=base, bf16_stem_vcat_arm_calls=vc,
+                       # what the three `_src` calls per decoder replace: the copy plus the same layers' single-source launches
+                       vcat_src_calls_ms=round(src_ms, 3),
+                       vcat_replaced_calls_ms=round(base.get("u3d_nearest_cat_fwd", {"ms": 0.0})["ms"] +
+                                                    sum(base[k]["ms"] - vc.get(k, {"ms": 0.0})["ms"] for k in single if k in base), 3),
+                       peak_memory_bytes={str(p): peak_bytes(p) for p in paths if p is not False})
         if not a.native_only:
             rec.update(stock_ms_per_step=[round(v, 3) for v in ms[False]], stock_images_per_s=round(batch * 1000.0 / best[False], 2),
                        native_speedup=round(best[False] / best[True], 3))
