@@ -891,6 +891,50 @@ int u3d_conv2d_res_reps(int device, u3d_stream_t stream, const u3d_src_t* src, c
 size_t u3d_wgrad2d_workspace_floats(int N, int H, int W, int Cin, int Cout);
 int u3d_conv2d_wgrad(int device, u3d_stream_t stream, const u3d_src_t* src, const float* dz, float* dw, int N, int H, int W, int Cout,
                      float* workspace, size_t workspace_floats);
+/* (Added, U3D_VERSION unchanged.)  Sub-pixel decoder convolutions of a UNet2D (`native_2d_subpixel: true`; csrc/u3d_subpix2d.hip): the
+ * 2-D twins of u3d_subpixel_conv_fwd / _dgrad_reps / _wgrad.  The upsampled half of cat(skip, F.interpolate(low, nearest))
+ * (buildingblocks.py:491,:614) feeding a decoder's first Conv2d: for an output pixel of parity p the three taps per axis read only two
+ * low-res pixels, so each of the 4 parity classes is a 2x2 convolution over the low-res grid with pre-summed weights — 4/9 of the
+ * multiply-adds.  Requires an exact 2x upsampling on both axes (output 2*H1 x 2*W1), C1 % 4 == Cout % 4 == 0, 16-byte aligned tensors;
+ * any H1, W1 >= 1.  fp32 NHWC, v_mfma_f32_32x32x2_f32.
+ *   u3d_pack_subpixel2d_weights        w is the full (Cout, Cin_total, 3, 3) weight, channels [c_off, c_off + C1) are packed
+ *              (u3d_subpixel2d_packed_floats(C1, Cout) floats): per axis parity 0 reads low-res offsets (-1, 0) with taps {t0}, {t1 + t2},
+ *              parity 1 reads (0, +1) with {t0 + t1}, {t2}
+ *   u3d_subpixel2d_conv_fwd            low (N,H1,W1,C1); affine optional GroupNorm (a,b) rows of those channels, sample n at affine +
+ *              n * affine_sample_stride (floats) — a slice of the layer's [N][Ctot][2] table works in place; padding stays exactly 0 after
+ *              the affine; out (N,2*H1,2*W1,Cout) receives the plain partial sums (no ReLU / statistics): add the skip half with
+ *              u3d_conv2d_res_reps(skip, image of the first C0 channels, residual = out).  workspace is accepted and not used (no split-K:
+ *              grids with fewer blocks than CUs run on few blocks)
+ *   u3d_subpixel2d_conv_dgrad_reps     the data gradient with respect to the LOW-RES tensor, the children sum of the upsampling included:
+ *              a 4x4-tap, stride-2 gather of dz (N,2*H1,2*W1,Cout) with pre-summed taps (per axis dz[2j-1 .. 2j+2] carry t2, t1 + t2,
+ *              t0 + t1, t0); image: u3d_pack_subpixel2d_dgrad_weights (u3d_subpixel2d_dgrad_packed_floats(Cout, C1) floats); dlow
+ *              (N,H1,W1,C1); optional gstats double[reps][N][C1][2] += (sum dlow, sum dlow * x_low), zeroed by the caller
+ *   u3d_subpixel2d_conv_wgrad          the 16 (parity class, tap half) matrices over the low-res grid, folded into the 9 taps and added over
+ *              the blocks in a fixed order (no atomics: bitwise deterministic); dw points at the first upsampled input channel inside the
+ *              (Cout, dw_cin_stride, 3, 3) gradient; workspace: u3d_subpixel2d_wgrad_workspace_floats() floats (always needed)
+ *   u3d_pack_weights2d_slice           u3d_pack_weights2d of the input channels [c_off, c_off + Cin) of a (Cout, cin_stride, 3, 3) weight
+ *   u3d_conv2d_wgrad_strided           u3d_conv2d_wgrad writing a CHANNEL SLICE of a wider gradient: dw points at the slice's first input
+ *              channel inside (Cout, dw_cin_stride, 3, 3); src holds only the slice's channels; dw_cin_stride == the source's channel
+ *              count gives u3d_conv2d_wgrad bit for bit */
+long long u3d_subpixel2d_packed_floats(int C1, int Cout);
+long long u3d_subpixel2d_dgrad_packed_floats(int Cout, int C1);
+int u3d_pack_subpixel2d_weights(int device, u3d_stream_t stream, const float* w, int Cout, int Cin_total, int c_off, int C1,
+                                float* packed);
+int u3d_pack_subpixel2d_dgrad_weights(int device, u3d_stream_t stream, const float* w, int Cout, int Cin_total, int c_off, int C1,
+                                      float* packed);
+int u3d_subpixel2d_conv_fwd(int device, u3d_stream_t stream, const float* low, const float* affine, long long affine_sample_stride,
+                            const float* packed, float* out, int N, int H1, int W1, int C1, int Cout, float* workspace,
+                            long long workspace_floats);
+int u3d_subpixel2d_conv_dgrad_reps(int device, u3d_stream_t stream, const float* dz, const float* packed, const float* x_low, float* dlow,
+                                   double* gstats, int N, int H1, int W1, int C1, int Cout, int reps);
+long long u3d_subpixel2d_wgrad_workspace_floats(int N, int H1, int W1, int C1, int Cout);
+int u3d_subpixel2d_conv_wgrad(int device, u3d_stream_t stream, const float* low, const float* affine, long long affine_sample_stride,
+                              const float* dz, float* dw, int dw_cin_stride, int N, int H1, int W1, int C1, int Cout, float* workspace,
+                              long long workspace_floats);
+int u3d_pack_weights2d_slice(int device, u3d_stream_t stream, const float* w, int Cout, int Cin, int mode, int cin_stride, int c_off,
+                             float* packed);
+int u3d_conv2d_wgrad_strided(int device, u3d_stream_t stream, const u3d_src_t* src, const float* dz, float* dw, int dw_cin_stride, int N,
+                             int H, int W, int Cout, float* workspace, size_t workspace_floats);
 /* (Added, U3D_VERSION unchanged.)  The first convolution of a 2-D net (`native_2d_stem: true`): the 2-D twins of
  * u3d_conv3d_small_cin_fwd_reps / u3d_conv3d_small_cin_bwd for Cin <= 4, Cout <= 32, exact fp32 (csrc/u3d_conv2d.hip).  x is a plain
  * (N,H,W,Cin) tensor, w the reference (Cout,Cin,3,3) layout — no packed image.  N <= 65535, N*H*W < 2^31.

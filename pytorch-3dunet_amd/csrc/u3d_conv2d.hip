@@ -77,8 +77,9 @@ extern "C" size_t u3d_packed_weight2d_floats(int Cin, int Cout, int mode) {
     return (size_t)c2_cdiv(K, c2::CC) * 9 * 2 * c2_cdiv(Nn, 32) * 256;
 }
 
+// (w row = `ld` input channels, the packed ones start at channel `off`: a whole weight has ld = Cin, off = 0)
 __global__ void pack_weights2d_kernel(const float* __restrict__ w, int Cout, int Cin, int mode, int K, int Nn, int ntg,
-                                      long long total, float* __restrict__ packed) {
+                                      long long total, float* __restrict__ packed, int ld, int off) {
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
         const int j = (int)(i & 3);
         const int lane = (int)((i >> 2) & 63);
@@ -93,23 +94,35 @@ __global__ void pack_weights2d_kernel(const float* __restrict__ w, int Cout, int
         const int nn = nt * 32 + (lane & 31);
         float v = 0.f;
         if (k < K && nn < Nn)
-            v = mode == 0 ? w[((size_t)nn * Cin + k) * 9 + tap] : w[((size_t)k * Cin + nn) * 9 + (8 - tap)];
+            v = mode == 0 ? w[((size_t)nn * ld + off + k) * 9 + tap] : w[((size_t)k * ld + off + nn) * 9 + (8 - tap)];
         packed[i] = v;
     }
 }
 
-extern "C" int u3d_pack_weights2d(int device, u3d_stream_t stream, const float* w, int Cout, int Cin, int mode, float* packed) {
+static int pack_weights2d_impl(int device, u3d_stream_t stream, const float* w, int Cout, int Cin, int mode, int ld, int off,
+                               float* packed) {
     U3D_ENTER(device);
-    U3D_REQUIRE(w && packed && Cout > 0 && Cin > 0 && (mode == 0 || mode == 1), "u3d_pack_weights2d: bad argument");
+    U3D_REQUIRE(w && packed && Cout > 0 && Cin > 0 && (mode == 0 || mode == 1) && off >= 0 && off + Cin <= ld,
+                "u3d_pack_weights2d: bad argument");
     int K, Nn;
     c2_dims(Cin, Cout, mode, K, Nn);
     const long long total = (long long)u3d_packed_weight2d_floats(Cin, Cout, mode);
     long long blocks = c2_cdiv(total, 256);
     if (blocks > 4096) blocks = 4096;
     hipLaunchKernelGGL(pack_weights2d_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, w, Cout, Cin, mode, K, Nn,
-                       (int)c2_cdiv(Nn, 32), total, packed);
+                       (int)c2_cdiv(Nn, 32), total, packed, ld, off);
     U3D_LAUNCH_CHECK();
     return 0;
+}
+
+extern "C" int u3d_pack_weights2d(int device, u3d_stream_t stream, const float* w, int Cout, int Cin, int mode, float* packed) {
+    return pack_weights2d_impl(device, stream, w, Cout, Cin, mode, Cin, 0, packed);
+}
+
+// the same image of the input channels [c_off, c_off + Cin) of a (Cout, cin_stride, 3, 3) weight (the skip half of a sub-pixel layer)
+extern "C" int u3d_pack_weights2d_slice(int device, u3d_stream_t stream, const float* w, int Cout, int Cin, int mode, int cin_stride,
+                                        int c_off, float* packed) {
+    return pack_weights2d_impl(device, stream, w, Cout, Cin, mode, cin_stride, c_off, packed);
 }
 
 // =================================================================================================
@@ -489,6 +502,7 @@ struct Wgrad2dParams {
     int N, H, W, Cin, Cout;
     int ty, tx, ncob, ncib, ntiles, tps;
     int vec_dz;
+    int dst_cin;  // input channels per row of dst: Cin, or the parent's count when dw is a channel slice written directly
 };
 
 template <bool VEC>
@@ -589,7 +603,7 @@ __global__ __launch_bounds__(256, 2) void conv2d_wgrad_kernel(const Wgrad2dParam
             const float v = ((red[(0 * 32 + row) * 32 + col] + red[(1 * 32 + row) * 32 + col]) + red[(2 * 32 + row) * 32 + col]) +
                             red[(3 * 32 + row) * 32 + col];
             const int co = co0 + row, ci = ci0 + col;
-            if (co < p.Cout && ci < Cin) p.dst[(size_t)split * p.Cout * Cin * 9 + ((size_t)co * Cin + ci) * 9 + tap] = v;
+            if (co < p.Cout && ci < Cin) p.dst[(size_t)split * p.Cout * Cin * 9 + ((size_t)co * p.dst_cin + ci) * 9 + tap] = v;
         }
         __syncthreads();
     }
@@ -601,6 +615,16 @@ __global__ void conv2d_wgrad_reduce_kernel(const float* __restrict__ ws, int nsp
         float v = 0.f;
         for (int s = 0; s < nsplit; ++s) v += ws[(size_t)s * total + i];
         dw[i] = v;
+    }
+}
+
+// ... into a channel slice: row (output channel) i / row of `row` floats lands at dw + (i / row) * dw_row
+__global__ void conv2d_wgrad_reduce_strided_kernel(const float* __restrict__ ws, int nsplit, long long total, int row, int dw_row,
+                                                   float* __restrict__ dw) {
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        float v = 0.f;
+        for (int s = 0; s < nsplit; ++s) v += ws[(size_t)s * total + i];
+        dw[(i / row) * dw_row + (i % row)] = v;
     }
 }
 
@@ -631,8 +655,8 @@ extern "C" size_t u3d_wgrad2d_workspace_floats(int N, int H, int W, int Cin, int
     return pl.nsplit > 1 ? (size_t)pl.nsplit * Cout * Cin * 9 : 0;
 }
 
-extern "C" int u3d_conv2d_wgrad(int device, u3d_stream_t stream, const u3d_src_t* src, const float* dz, float* dw, int N, int H, int W,
-                                int Cout, float* workspace, size_t workspace_floats) {
+static int conv2d_wgrad_impl(int device, u3d_stream_t stream, const u3d_src_t* src, const float* dz, float* dw, int dw_cin_stride, int N,
+                             int H, int W, int Cout, float* workspace, size_t workspace_floats) {
     U3D_ENTER(device);
     U3D_REQUIRE(src && src->p0 && dz && dw && N > 0 && H > 0 && W > 0 && Cout > 0 && src->C0 >= 0 && src->C1 >= 0 &&
                     src->C0 + src->C1 > 0 && (long long)N * H * W < (1LL << 31),
@@ -640,6 +664,8 @@ extern "C" int u3d_conv2d_wgrad(int device, u3d_stream_t stream, const u3d_src_t
     U3D_REQUIRE(src->C1 == 0 || (src->p1 && src->ymap && src->xmap && src->D1 == 1 && src->H1 > 0 && src->W1 > 0),
                 "u3d_conv2d_wgrad: virtual source needs p1, ymap, xmap and D1 == 1");
     const int Cin = src->C0 + src->C1;
+    if (dw_cin_stride == 0) dw_cin_stride = Cin;
+    U3D_REQUIRE(dw_cin_stride >= Cin, "u3d_conv2d_wgrad_strided: dw_cin_stride below the source's channel count");
     const W2Plan pl = w2_plan(device, N, H, W, Cin, Cout);
     const size_t need = pl.nsplit > 1 ? (size_t)pl.nsplit * Cout * Cin * 9 : 0;
     U3D_REQUIRE(need == 0 || (workspace && workspace_floats >= need), "u3d_conv2d_wgrad: workspace too small (%zu < %zu floats)",
@@ -651,6 +677,7 @@ extern "C" int u3d_conv2d_wgrad(int device, u3d_stream_t stream, const u3d_src_t
     p.N = N, p.H = H, p.W = W, p.Cin = Cin, p.Cout = Cout;
     p.ty = pl.ty, p.tx = pl.tx, p.ncob = pl.ncob, p.ncib = pl.ncib, p.ntiles = pl.ntiles, p.tps = pl.tps;
     p.vec_dz = (Cout % 4 == 0 && ((uintptr_t)dz & 15) == 0) ? 1 : 0;
+    p.dst_cin = need ? Cin : dw_cin_stride;
     const size_t lds = c2::WG_LDS_FLOATS * sizeof(float);
     static bool attr_set[2] = {false, false};
     if (!attr_set[0]) {
@@ -670,11 +697,27 @@ extern "C" int u3d_conv2d_wgrad(int device, u3d_stream_t stream, const u3d_src_t
         const long long total = (long long)Cout * Cin * 9;
         long long rb = c2_cdiv(total, 256);
         if (rb > 4096) rb = 4096;
-        hipLaunchKernelGGL(conv2d_wgrad_reduce_kernel, dim3((unsigned)rb), dim3(256), 0, (hipStream_t)stream, workspace, pl.nsplit, total,
-                           dw);
+        if (dw_cin_stride == Cin)
+            hipLaunchKernelGGL(conv2d_wgrad_reduce_kernel, dim3((unsigned)rb), dim3(256), 0, (hipStream_t)stream, workspace, pl.nsplit,
+                               total, dw);
+        else
+            hipLaunchKernelGGL(conv2d_wgrad_reduce_strided_kernel, dim3((unsigned)rb), dim3(256), 0, (hipStream_t)stream, workspace,
+                               pl.nsplit, total, Cin * 9, dw_cin_stride * 9, dw);
         U3D_LAUNCH_CHECK();
     }
     return 0;
+}
+
+extern "C" int u3d_conv2d_wgrad(int device, u3d_stream_t stream, const u3d_src_t* src, const float* dz, float* dw, int N, int H, int W,
+                                int Cout, float* workspace, size_t workspace_floats) {
+    return conv2d_wgrad_impl(device, stream, src, dz, dw, 0, N, H, W, Cout, workspace, workspace_floats);
+}
+
+// the same, writing the gradient of a CHANNEL SLICE of a wider weight: dw points at the slice's first input channel inside the
+// (Cout, dw_cin_stride, 3, 3) gradient; src holds only the slice's channels (the skip half of a sub-pixel layer)
+extern "C" int u3d_conv2d_wgrad_strided(int device, u3d_stream_t stream, const u3d_src_t* src, const float* dz, float* dw,
+                                        int dw_cin_stride, int N, int H, int W, int Cout, float* workspace, size_t workspace_floats) {
+    return conv2d_wgrad_impl(device, stream, src, dz, dw, dw_cin_stride, N, H, W, Cout, workspace, workspace_floats);
 }
 
 // =================================================================================================

@@ -108,18 +108,25 @@ class ConvLayers:
             nat.call("u3d_act_bwd", dev.index, _stream(dev), _p(g), _p(y), g.numel(), self.act, self.slope, _p(g))
 
     def _up_scale(self, dev):
-        """(1, 8, 8) on the (p, q, r) rows of a GroupNorm-backward coefficient table: a low-res voxel stands for 8 children"""
+        """(1, 8, 8) on the (p, q, r) rows of a GroupNorm-backward coefficient table: a low-res voxel stands for 8 children (a 2-D
+        net: 4, `self.children`)"""
         t = getattr(self, "_up_scale_t", None)
         if t is None or t.device != dev:
-            t = self._up_scale_t = torch.tensor([1.0, 8.0, 8.0], dtype=_F32, device=dev).view(1, 3, 1)
+            ch = float(getattr(self, "children", 8.0))
+            t = self._up_scale_t = torch.tensor([1.0, ch, ch], dtype=_F32, device=dev).view(1, 3, 1)
         return t
+
+    def _src_plus(self, src: VSrc):
+        """`src.plus` of a sub-pixel layer's source; a 2-D net's sub-pixel levels are exact 2x on H and W (D = D1 = 1 is no axis)"""
+        return (0, 0, 0) if getattr(self, "is2d", False) else src.plus
 
     def _subpixel_layers(self, size):
         """decoder first convs whose low-res input is upsampled by exactly 2 — or, round 5, from n to 2n + 1 voxels — in every dimension at
         this input size: {id(weight): (C0, C1)} (+ `.plus`: the ids with an n -> 2n + 1 axis) — per-call state, handed down as `sub`"""
-        if not self.subpixel or getattr(self, "is2d", False) or any(ct is not None for ct in self.dec_up) or any(self.dec_interp):
+        is2d = getattr(self, "is2d", False)
+        if not self.subpixel or any(ct is not None for ct in self.dec_up) or any(self.dec_interp):
             return _SubLayers()  # (a transposed convolution yields 2n-1 voxels, resized to the skip: never an exact 2x replication)
-        dims = [tuple(size)]
+        dims = [tuple(size)[1:] if is2d else tuple(size)]  # (2-D, `native_2d_subpixel`: H and W only)
         for has_pool, _, _ in self.enc:
             if has_pool:
                 dims.append(tuple(d // 2 for d in dims[-1]))
@@ -134,7 +141,8 @@ class ConvLayers:
             # every axis upsampled by exactly 2, or n -> 2n + 1 (the pooled size of an odd level; round 5: the sub-pixel kernels on a
             # shifted window + the general kernels on the near-boundary slab, _fwd_subpixel / _dgrad_subpixel / _wgrad_subpixel)
             ratio = [a - 2 * b for a, b in zip(dims[skip_lvl], dims[low_lvl])]
-            if (all(r in (0, 1) for r in ratio) and (self.subpixel_plus or not any(ratio)) and C0 > 0 and C1 > 0 and C0 % 4 == 0
+            # (2-D: exact 2x only — the windowed / slab form of an n -> 2n + 1 level is 3-D only, such a level keeps its virtual concat)
+            if (all(r in (0, 1) for r in ratio) and ((self.subpixel_plus and not is2d) or not any(ratio)) and C0 > 0 and C1 > 0 and C0 % 4 == 0
                     and C1 % 4 == 0 and c1.conv.out_channels % 4 == 0):
                 out[id(c1.conv.weight)] = (C0, C1)
                 if any(ratio):
@@ -154,6 +162,10 @@ class ConvLayers:
         if st0 is not None and st1 is not None and src.exact2x and self.fused_stats:
             # every low-res voxel is replicated exactly 8x: reuse the producer's sums
             return st0, dataclasses.replace(st1, scale=8.0)
+        if (st0 is not None and st1 is not None and getattr(self, "subpixel2d", False) and self.fused_stats and src.D == 1
+                and src.H == 2 * src.H1 and src.W == 2 * src.W1):
+            # `native_2d_subpixel`, an exact-2x level of a 2-D net: every low-res pixel is replicated exactly 4x
+            return st0, dataclasses.replace(st1, scale=4.0)
         plus = src.plus
         if st0 is not None and plus is not None and any(plus) and self.fused_stats and src.C1 % 4 == 0 and src.t1.dtype == _F32:
             # n -> 2n + 1 along some axes: the first low-res cell of such an axis has three children, every other cell two — the sums of
@@ -222,8 +234,9 @@ class ConvLayers:
         coef_hi = None
         job.gstats_lo, job.C0, job.reps_lo = _p(lo.t), lo.C, lo.reps
         if hi is not None:
-            coef_hi = _empty((N, 3, hi.C), dtype=_F32, device=dev) if not any(rec.src.plus) else None
-            job.gstats_hi, job.C1, job.hi_scale, job.reps_hi, job.coef_hi = _p(hi.t), hi.C, 8.0, hi.reps, _p(coef_hi)
+            coef_hi = _empty((N, 3, hi.C), dtype=_F32, device=dev) if not any(self._src_plus(rec.src)) else None
+            job.gstats_hi, job.C1, job.hi_scale, job.reps_hi, job.coef_hi = (_p(hi.t), hi.C, float(getattr(self, "children", 8.0)), hi.reps,
+                                                                             _p(coef_hi))
         else:
             job.gstats_hi, job.C1, job.hi_scale, job.reps_hi, job.coef_hi = None, 0, 1.0, 1, None
         job.mean_rstd, job.gamma = _p(rec.mean_rstd), _p(rec.gn_w.detach())
@@ -244,9 +257,10 @@ class ConvLayers:
             C = lo.C + hi.C
             if rec.norm == "g" and nat.get_lib().u3d_gn_bwd_finalize_split_supported(N, C, rec.G) == 1:
                 # ... and the low-res apply pass of an exact-2x level wants the upper channels' (p, 8q, 8r) as a compact table
-                coef_hi = _empty((N, 3, hi.C), dtype=_F32, device=dev) if not any(rec.src.plus) else None
+                coef_hi = _empty((N, 3, hi.C), dtype=_F32, device=dev) if not any(self._src_plus(rec.src)) else None
                 nat.call("u3d_gn_bwd_finalize_split", dev.index, _stream(dev), _p(lo.t), lo.C, _p(hi.t), hi.C, _p(rec.mean_rstd),
-                         _p(rec.gn_w.detach()), N, rec.G, count, _p(gview(rec.idx_gw)), _p(gview(rec.idx_gb)), _p(coef), 8.0, _p(coef_hi))
+                         _p(rec.gn_w.detach()), N, rec.G, count, _p(gview(rec.idx_gw)), _p(gview(rec.idx_gb)), _p(coef),
+                         float(getattr(self, "children", 8.0)), _p(coef_hi))
                 return coef_hi
             g = torch.cat((lo.t.view(N, lo.C, 2), hi.t.view(N, hi.C, 2)), dim=1)
         if rec.norm == "g":
@@ -321,12 +335,15 @@ class ConvLayers:
         "conv2d": "_fwd_conv2d",      # u3d_conv2d.hip: 3x3 convolutions of a 2-D net (native_2d), every layer and only those ...
         "conv2d_bf16": "_fwd_conv2d_bf16",  # u3d_conv2d_bf16.hip: ... except, in bf16, the single-source layers that fit (`_bf16_routed`)
         "small2d": "_fwd_small2d",    # u3d_conv2d.hip: ... and, under `native_2d_stem`, the first layer, Cin <= 4 (the 3-D `small` rule)
+        "subpixel2d": "_fwd_subpixel2d",  # u3d_subpix2d.hip + u3d_conv2d.hip: `native_2d_subpixel`, cat(skip, nearest2x(low)), 4/9 of the MACs
     }
 
     def _fwd_family(self, c: "_ConvCall", residual) -> str:
         if getattr(self, "is2d", False):
             if self._small2d(c.Ctot, c.Cout, c.src.t1 is not None) and residual is None:
                 return "small2d"
+            if c.src.t1 is not None and residual is None and id(c.conv.weight) in c.sub:
+                return "subpixel2d"
             # (a decoder's first conv reaches here on its materialised concat when it fits: `_cat_bf16`; forward and data gradient
             # are covered together by the one channel rule; a residual rides in either family's epilogue)
             return "conv2d_bf16" if self._bf16_routed(c.src, c.Cout) else "conv2d"
@@ -400,6 +417,26 @@ class ConvLayers:
             nat.call("u3d_conv3d_ex_reps", dev.index, _stream(dev), ctypes.byref(s0), _p(self.images.get(conv.weight, Kind.SKIP_FWD, dev, pair)),
                      _p(c.y), N, D, H, W, Cout, c.relu, yp, None, None, _p(part), None, 0, yr,
                      flops=54.0 * C0 * Cout * N * D * H * W)
+        return ystats
+
+    def _fwd_subpixel2d(self, c: "_ConvCall"):
+        # `native_2d_subpixel`: the upsampled half as 4 parity-class 2x2 convolutions over the low-res tensor (4/9 of the multiply-adds,
+        # csrc/u3d_subpix2d.hip), then the skip half, whose epilogue adds the partial sums before ReLU / statistics (u3d_conv2d_res_reps)
+        dev, conv, src, N, H, W, Cout = c.dev, c.conv, c.src, c.N, c.H, c.W, c.Cout
+        assert c.D == 1 and H == 2 * src.H1 and W == 2 * src.W1
+        pair = C0, C1 = c.sub[id(conv.weight)]
+        ystats = c.take_stats(self.stat_reps)
+        part = _empty((N, 1, H, W, Cout), dtype=_F32, device=dev)
+        nat.call("u3d_subpixel2d_conv_fwd", dev.index, _stream(dev), _p(src.t1), _p(c.affine.view(-1)[2 * C0:]), c.Ctot * 2,
+                 _p(self.images.get(conv.weight, Kind.UP_FWD2D, dev, pair)), _p(part), N, src.H1, src.W1, C1, Cout, None, 0,
+                 flops=32.0 * C1 * Cout * N * src.H1 * src.W1)
+        a0 = c.affine_lo if c.affine_lo is not None else c.affine[:, :C0].contiguous()
+        s0 = VSrc(src.t0).struct(a0)
+        need = nat.get_lib().u3d_conv2d_workspace_floats(N, H, W, C0, Cout)  # split-K scratch on small grids
+        kws = _empty(need, dtype=_F32, device=dev) if need > 0 else None
+        yp, yr = _tab(ystats)
+        nat.call("u3d_conv2d_res_reps", dev.index, _stream(dev), ctypes.byref(s0), _p(self.images.get(conv.weight, Kind.SKIP_FWD2D, dev, pair)),
+                 _p(c.y), N, H, W, Cout, c.relu, yp, None, None, _p(kws), need, yr, _p(part), flops=18.0 * C0 * Cout * N * H * W)
         return ystats
 
     def _fwd_f32s(self, c: "_ConvCall"):
@@ -523,7 +560,7 @@ class ConvLayers:
                 # sub-pixel layer: its two halves are read by different kernels as plain tensors
                 Cs0, Cs1 = sub[id(conv.weight)]
                 split = (Cs0, _empty((N, Cs0, 2), dtype=_F32, device=dev),
-                         _empty((N, Cs1, 2), dtype=_F32, device=dev) if any(src.plus) else None)
+                         _empty((N, Cs1, 2), dtype=_F32, device=dev) if any(self._src_plus(src)) else None)
             mean_rstd = self._norm_finalize(spec.norm, gn, *st_in, G, float(D * H * W), affine, dev, split)
         # y_out: recomputation under activation checkpointing rewrites the (still alive) block output in place with the
         # bit-identical values instead of allocating a second copy
@@ -616,6 +653,7 @@ class ConvLayers:
         "fp32": "_wgrad_fp32",          # u3d_conv.hip
         "conv2d": "_wgrad_conv2d",      # u3d_conv2d.hip (2-D nets)
         "conv2d_bf16": "_wgrad_conv2d_bf16",  # u3d_conv2d_bf16.hip (2-D nets in bf16: every layer the bf16 forward covers)
+        "subpixel2d": "_wgrad_subpixel2d",  # u3d_subpix2d.hip (upsampled channels) + u3d_conv2d.hip strided (skip channels)
     }
     _DGRAD_KERNELS = {
         "subpixel": "_dgrad_subpixel",  # skip half at full resolution + upsampled half directly at LOW resolution
@@ -624,9 +662,12 @@ class ConvLayers:
         "fp32": "_dgrad_fp32",
         "conv2d": "_dgrad_conv2d",  # u3d_conv2d.hip (2-D nets)
         "conv2d_bf16": "_dgrad_conv2d_bf16",  # u3d_conv2d_bf16.hip
+        "subpixel2d": "_dgrad_subpixel2d",  # u3d_conv2d.hip (skip half) + u3d_subpix2d.hip (upsampled half at LOW resolution)
     }
 
     def _wgrad_family(self, c: "_BwdCall") -> str:
+        if getattr(self, "is2d", False) and c.rec.sub is not None:
+            return "subpixel2d"
         if getattr(self, "is2d", False):
             return "conv2d_bf16" if c.bf16 else "conv2d"
         if c.bf16 and c.Cout % 32 == 0:  # (Cout % 64 == 32 since round 4: 64-column blocks with a zero upper half)
@@ -638,6 +679,8 @@ class ConvLayers:
         return "fp32"
 
     def _dgrad_family(self, c: "_BwdCall") -> str:
+        if getattr(self, "is2d", False) and c.rec.sub is not None:
+            return "subpixel2d"
         if getattr(self, "is2d", False):
             return "conv2d_bf16" if c.bf16 else "conv2d"
         if c.rec.sub is not None:
@@ -811,6 +854,40 @@ class ConvLayers:
                  ctypes.byref(s_x), _p(gst.t), _p(ws), ws.numel(), gst.reps, flops=18.0 * src.C * c.Cout * c.N * c.H * c.W)
         return dg, (gst, None)
 
+    def _wgrad_subpixel2d(self, c: "_BwdCall"):
+        # `native_2d_subpixel`: the weight gradient in two channel slices of the same (Cout, Ctot, 9) buffer — upsampled channels from the
+        # 16 (parity class, tap half) matrices over the low-res grid, skip channels from the standard kernel (takes no job, as `conv2d`)
+        cx, dev, src, rec, ws = c.cx, c.cx.dev, c.src, c.rec, c.cx.ws
+        C0, C1 = rec.sub
+        Ct = src.C
+        dwv = cx.gview(rec.idx_w)
+        nat.call("u3d_subpixel2d_conv_wgrad", dev.index, _stream(dev), _p(src.t1), _p(rec.affine.view(-1)[2 * C0:]), Ct * 2, _p(c.dz),
+                 _p(dwv[C0 * 9:]), Ct, c.N, src.H1, src.W1, C1, c.Cout, _p(ws), ws.numel(), flops=32.0 * C1 * c.Cout * c.N * src.H1 * src.W1)
+        a0 = rec.affine_lo if rec.affine_lo is not None else rec.affine[:, :C0].contiguous()
+        s0 = VSrc(src.t0).struct(a0)
+        nat.call("u3d_conv2d_wgrad_strided", dev.index, _stream(dev), ctypes.byref(s0), _p(c.dz), _p(dwv), Ct, c.N, c.H, c.W, c.Cout,
+                 _p(ws), ws.numel(), flops=18.0 * C0 * c.Cout * c.N * c.H * c.W)
+
+    def _dgrad_subpixel2d(self, c: "_BwdCall"):
+        # skip half at full resolution (mode-1 image of channels [0, C0)); upsampled half directly at LOW resolution, the children sum
+        # of the nearest upsampling folded into the 4x4-tap stride-2 gather.  dg = (dg_skip, dlow)
+        cx, dev, src, rec, ws, pool = c.cx, c.cx.dev, c.src, c.rec, c.cx.ws, c.cx.pool
+        C0, C1 = rec.sub
+        w, pair = rec.conv_w, tuple(rec.sub)
+        dg0 = _empty((c.N, 1, c.H, c.W, C0), dtype=_F32, device=dev)
+        dlow = _empty_like(src.t1)
+        gst0 = pool.table(c.N, C0, c.greps)
+        gst1 = pool.table(c.N, C1, c.greps)
+        s_dz = VSrc(c.dz).struct()
+        s_x0 = VSrc(src.t0).struct()
+        nat.call("u3d_conv2d_ex_reps", dev.index, _stream(dev), ctypes.byref(s_dz), _p(self.images.get(w, Kind.SKIP_DGRAD2D, dev, pair)), _p(dg0),
+                 c.N, c.H, c.W, C0, 0, None, ctypes.byref(s_x0), _p(gst0.t), _p(ws), ws.numel(), gst0.reps,
+                 flops=18.0 * C0 * c.Cout * c.N * c.H * c.W)
+        nat.call("u3d_subpixel2d_conv_dgrad_reps", dev.index, _stream(dev), _p(c.dz), _p(self.images.get(w, Kind.UP_DGRAD2D, dev, pair)),
+                 _p(src.t1), _p(dlow), _p(gst1.t), c.N, src.H1, src.W1, C1, c.Cout, gst1.reps,
+                 flops=32.0 * C1 * c.Cout * c.N * src.H1 * src.W1)
+        return (dg0, dlow), (gst0, gst1)
+
     def _wgrad_conv2d_bf16(self, c: "_BwdCall"):
         # both operands rounded to bf16 while staged (g = a*x + b and dz), fp32 sums added in a fixed order; takes no GroupNorm-backward
         # job, like the fp32 2-D kernel
@@ -955,6 +1032,10 @@ class ConvLayers:
         """scratch floats one 3x3x3 layer's backward needs from the shared buffer, for the kernels it will actually run"""
         lib = nat.get_lib()
         if getattr(self, "is2d", False):  # weight gradient + the data gradient's split-K scratch (roles swapped)
+            if sub is not None:  # (`native_2d_subpixel`: skip slice on the conv2d kernels + the sub-pixel slice's block slots)
+                return max(lib.u3d_wgrad2d_workspace_floats(N, H, W, sub[0], Cout),
+                           lib.u3d_subpixel2d_wgrad_workspace_floats(N, H // 2, W // 2, sub[1], Cout),
+                           lib.u3d_conv2d_workspace_floats(N, H, W, Cout, sub[0]))
             if small:  # (the one-pass backward, or — when a data gradient is needed — the fall-through to the fp32 family)
                 return max(lib.u3d_small_cin2d_bwd_workspace_floats(N, H, W, Cin, Cout), lib.u3d_wgrad2d_workspace_floats(N, H, W, Cin, Cout),
                            lib.u3d_conv2d_workspace_floats(N, H, W, Cout, Cin))

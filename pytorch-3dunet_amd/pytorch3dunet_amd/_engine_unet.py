@@ -33,7 +33,7 @@ class UNet3DEngine(ConvLayers):
         self.debug = None  # dict -> backward stores clones of per-layer dz / dg (tools/gpu_layer_diag.py)
         self.fused_stats = True
         # UNet2D under `native_2d` (unet3d/model.py): (N,C,H,W) runs as (N,C,1,H,W) — every 3x3 convolution on the 2-D kernel family
-        # (csrc/u3d_conv2d.hip, `conv2d` in the family tables), 2x2 pooling, no sub-pixel decoder kernels
+        # (csrc/u3d_conv2d.hip, `conv2d` in the family tables), 2x2 pooling; sub-pixel decoder kernels only under `native_2d_subpixel` (below)
         self.is2d = bool(getattr(model, "native_2d", False))
         # opt-in `native_2d_stem` (a UNet2D): the first layer on the small-Cin kernels of csrc/u3d_conv2d.hip (`_small2d`)
         self.stem = self.is2d and bool(getattr(model, "native_2d_stem", False))
@@ -42,7 +42,10 @@ class UNet3DEngine(ConvLayers):
         self.small_cin = True  # dedicated kernels for the in_channels<=4 first layer
         self.overlap_small_wgrad = True  # weight gradients of small layers on a second HIP stream (see _BwdCtx)
         # decoder first convs over an exact-2x upsampling: sub-pixel convolution of the upsampled half (csrc/u3d_subpix.hip)
-        self.subpixel = os.environ.get("U3D_SUBPIXEL", "1") != "0" and not self.is2d
+        # (a 2-D net: only under the opt-in `native_2d_subpixel`, a fp32 UNet2D — csrc/u3d_subpix2d.hip, exact-2x levels only)
+        self.subpixel2d = self.is2d and bool(getattr(model, "native_2d_subpixel", False)) and not bool(getattr(model, "compute_bf16", False))
+        self.subpixel = os.environ.get("U3D_SUBPIXEL", "1") != "0" and (not self.is2d or self.subpixel2d)
+        self.children = 4.0 if self.is2d else 8.0  # full-res voxels a low-res voxel of an exact-2x level stands for
         # ... and over a level that upsamples n -> 2n + 1 along some axes (an odd skip size: 42 -> 85 in the shipped 80 x 170 x 170 patch):
         # sub-pixel kernels on a shifted window + the general kernels on the near-boundary slab (round 5; U3D_SUBPIXEL_PLUS=0: such
         # levels keep the 27-tap virtual-concat kernels)
@@ -400,12 +403,12 @@ class UNet3DEngine(ConvLayers):
             if r1.sub is not None:
                 dg0, dlow = dg1
                 skip_grad[lvl] = (dg0, C0, coef1, Ct)
-                if any(src.plus):
+                if any(self._src_plus(src)):
                     # n -> 2n + 1 along some axes: the first low-res cell of such an axis has three children
                     nat.call("u3d_gn_bwd_apply_children", dev.index, _stream(dev), _p(dlow), _p(src.t1), _p(coef1), Ct, C0, src.N, src.D1,
                              src.H1, src.W1, C1, *src.plus, mk, _p(dzl))
                 else:
-                    # dlow already holds the children sums: (p*dlow + 8*(q*x + r)) * (x > 0) on the low-res producer
+                    # dlow already holds the children sums: (p*dlow + 8*(q*x + r)) * (x > 0) on the low-res producer (2-D: 4 children)
                     coef_up = coef_hi if coef_hi is not None else coef1[:, :, C0:] * self._up_scale(dev)
                     nat.call("u3d_gn_bwd_apply", dev.index, _stream(dev), _p(dlow), C1, 0, _p(src.t1), C1, _p(coef_up), C1,
                              src.D1 * src.H1 * src.W1, src.N, mk, _p(dzl))

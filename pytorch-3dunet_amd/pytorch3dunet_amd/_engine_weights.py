@@ -50,6 +50,10 @@ class Kind(enum.IntEnum):
     BF16_DGRAD2D_C16 = enum.auto()
     CONVTR2D_BF16_FWD = enum.auto()    # ConvTranspose2d on the bf16 kernels (`native_2d_residual_bf16_deconv`): B[ci][co] per tap ...
     CONVTR2D_BF16_DGRAD = enum.auto()  # ... B[co][ci] per tap
+    SKIP_FWD2D = enum.auto()    # sub-pixel layer of a 2-D net (`native_2d_subpixel`): the first C0 (skip) input channels ...
+    SKIP_DGRAD2D = enum.auto()
+    UP_FWD2D = enum.auto()      # ... the pre-summed parity-class images of the remaining C1 (upsampled) channels
+    UP_DGRAD2D = enum.auto()
 
 
 @dataclass(frozen=True)
@@ -61,6 +65,7 @@ class _Spec:
     batch: Optional[int] = None   # C-ABI mode of the image's row in the per-step batch launch of its dtype (None: packed on demand)
     half: Optional[int] = None    # the image may be / is of one half of a sub-pixel pair (C0, C1): 0 = skip, 1 = upsampled channels
     transposed: bool = False      # ConvTranspose weight (Cin, Cout, ...): the entry point takes (Cin, Cout), else (Cout, Cin)
+    up2d: bool = False            # u3d_pack_subpixel2d_*: the entry point takes (Cout, Cin_total, c_off, C1)
 
 
 _f32 = lambda lib, ci, co, m: lib.u3d_packed_weight_floats(ci, co, m)  # noqa: E731
@@ -104,6 +109,12 @@ _KINDS = {
     Kind.BF16_DGRAD2D_C16: _Spec(_2db16, _BF16, "u3d_pack_weights2d_bf16_c16", 1),
     Kind.CONVTR2D_BF16_FWD: _Spec(_tr2db, _BF16, "u3d_pack_convtr2d_bf16", 0, transposed=True),
     Kind.CONVTR2D_BF16_DGRAD: _Spec(_tr2db, _BF16, "u3d_pack_convtr2d_bf16", 1, transposed=True),
+    Kind.SKIP_FWD2D: _Spec(_2d, _F32, "u3d_pack_weights2d_slice", 0, half=0),
+    Kind.SKIP_DGRAD2D: _Spec(_2d, _F32, "u3d_pack_weights2d_slice", 1, half=0),
+    Kind.UP_FWD2D: _Spec(lambda lib, ci, co, m: lib.u3d_subpixel2d_packed_floats(ci, co), _F32, "u3d_pack_subpixel2d_weights", None,
+                         half=1, up2d=True),
+    Kind.UP_DGRAD2D: _Spec(lambda lib, ci, co, m: lib.u3d_subpixel2d_dgrad_packed_floats(co, ci), _F32,
+                           "u3d_pack_subpixel2d_dgrad_weights", None, half=1, up2d=True),
 }
 _BF16_BOTH = 6  # batch row that writes BF16_FWD and, right behind it in one buffer, BF16_DGRAD from one read of the weight
 
@@ -183,6 +194,8 @@ class WeightImages:
             args = (ci, co) if spec.transposed else (co, ci)
             args += () if spec.mode is None else (spec.mode,)
             args += (ld, off) if spec.half is not None else ()
+            if spec.up2d:
+                args = (co, ld, off, ci)
             nat.call(spec.entry, dev.index, _stream(dev), _p(w.detach()), *args, _p(out))
         self._images[key] = (ver, out)
         return out
@@ -224,6 +237,11 @@ class WeightImages:
         {id(weight): (C0, C1)} of the layers on the sub-pixel path in this forward, `plus` the ids among them with slab images."""
         nd = 2 if grads else 1
         for w in self._each:  # 2-D images: one small launch per weight and image (u3d_pack_weights2d)
+            pair = sub.get(id(w)) if sub else None
+            if pair is not None:  # (`native_2d_subpixel`: the images of the two input-channel halves instead)
+                for kind in (Kind.SKIP_FWD2D, Kind.SKIP_DGRAD2D)[:nd] + (Kind.UP_FWD2D, Kind.UP_DGRAD2D)[:nd]:
+                    self.get(w, kind, dev, pair)
+                continue
             for kind in (Kind.FWD2D, Kind.DGRAD2D)[:nd]:
                 self.get(w, kind, dev)
         for w in self._each_bf16:  # ... and of the 2-D layers on the bf16 kernels (u3d_pack_weights2d_bf16)

@@ -473,6 +473,21 @@ _PROTOS = {
                                    c_size_t]),
     "u3d_wgrad2d_workspace_floats": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "u3d_conv2d_wgrad": (c_int, [c_int, c_void_p, POINTER(U3DSrc), c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t]),
+    "u3d_pack_weights2d_slice": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "u3d_conv2d_wgrad_strided": (c_int, [c_int, c_void_p, POINTER(U3DSrc), c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                                         c_size_t]),
+    # sub-pixel decoder convolutions of a 2-D net (`native_2d_subpixel`; csrc/u3d_subpix2d.hip)
+    "u3d_subpixel2d_packed_floats": (c_int64, [c_int, c_int]),
+    "u3d_subpixel2d_dgrad_packed_floats": (c_int64, [c_int, c_int]),
+    "u3d_pack_subpixel2d_weights": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "u3d_pack_subpixel2d_dgrad_weights": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "u3d_subpixel2d_conv_fwd": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                                        c_int, c_void_p, c_int64]),
+    "u3d_subpixel2d_conv_dgrad_reps": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                               c_int, c_int, c_int]),
+    "u3d_subpixel2d_wgrad_workspace_floats": (c_int64, [c_int, c_int, c_int, c_int, c_int]),
+    "u3d_subpixel2d_conv_wgrad": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                                          c_int, c_int, c_void_p, c_int64]),
     # small-Cin first layer of a 2-D net (`native_2d_stem`; csrc/u3d_conv2d.hip)
     "u3d_conv2d_small_cin_fwd_variant": (c_int, [c_int, c_int, c_int, c_int, c_int]),
     "u3d_conv2d_small_cin_fwd_reps": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,

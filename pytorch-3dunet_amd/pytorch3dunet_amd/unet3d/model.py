@@ -18,7 +18,9 @@ fp32 UNet2D with nearest upsampling on the 2-D kernels of csrc/u3d_conv2d.hip; `
 does the same for a fp32 ResidualUNet2D; `native_2d_bf16: true` / U3D_NATIVE_2D_BF16=1 runs a UNet2D with bf16 MFMA operands on the kernels
 of csrc/u3d_conv2d_bf16.hip, `native_2d_residual_bf16: true` / U3D_NATIVE_2D_RESIDUAL_BF16=1 a ResidualUNet2D; `native_2d_stem: true` /
 U3D_NATIVE_2D_STEM=1 adds the small-Cin first-layer kernels to a native UNet2D, `native_2d_bf16_vcat: true` / U3D_NATIVE_2D_BF16_VCAT=1 reads
-the decoders' concat inside the bf16 kernels of a UNet2D); U3D_STRICT=1 makes them an error too.  Covered since round 2: every layer order with at most one
+the decoders' concat inside the bf16 kernels of a UNet2D, `native_2d_subpixel: true` / U3D_NATIVE_2D_SUBPIXEL=1 runs the upsampled half of a
+fp32 UNet2D's decoder first convolutions on the sub-pixel kernels of csrc/u3d_subpix2d.hip at levels that upsample by exactly 2);
+U3D_STRICT=1 makes them an error too.  Covered since round 2: every layer order with at most one
 GroupNorm / BatchNorm, one non-linearity and a trailing dropout, every `upsample` value the reference itself can run
 on a 3-D net, nn.DataParallel, activation checkpointing, and the opt-in compute modes `bf16` and `fp32_split`.
 """
@@ -47,7 +49,7 @@ class AbstractUNet(nn.Module):
                  conv_padding=1, conv_upscale=2, upsample="default", dropout_prob=0.1, is3d=True, compute_dtype=None,
                  checkpoint_encoders=None, hip_graph=None, activation_dtype=None, checkpoint_levels=None,
                  native_2d=None, native_2d_residual=None, native_2d_bf16=None, native_2d_residual_bf16=None,
-                 native_2d_residual_bf16_deconv=None, native_2d_stem=None, native_2d_bf16_vcat=None):
+                 native_2d_residual_bf16_deconv=None, native_2d_stem=None, native_2d_bf16_vcat=None, native_2d_subpixel=None):
         super().__init__()
         if isinstance(f_maps, int):
             f_maps = number_of_features_per_level(f_maps, num_levels=num_levels)
@@ -133,8 +135,23 @@ class AbstractUNet(nn.Module):
         stem_2d = bool(native_2d_stem) and not is3d and basic_module is DoubleConv
         if stem_2d:
             native_2d = True
+        # `native_2d_subpixel: true` (its own key, so that native_2d alone stays bit-identical; U3D_NATIVE_2D_SUBPIXEL=1 sets its default):
+        # a fp32 UNet2D (DoubleConv blocks, nearest upsampling) runs the UPSAMPLED half of every decoder's first convolution whose level
+        # upsamples by exactly 2 on both axes (C0, C1, Cout multiples of 4) as four parity-class 2x2 convolutions over the low-res tensor
+        # — 4/9 of that half's multiply-adds in forward, data gradient and weight gradient (csrc/u3d_subpix2d.hip); the skip half and every
+        # other level (n -> 2n + 1) keep the kernels of native_2d.  It implies native_2d and is allowed next to native_2d_stem; next to
+        # native_2d_bf16 / native_2d_bf16_vcat it is a contradiction (there is no bf16 sub-pixel form).  Every other class ignores it
+        if native_2d_subpixel is None:
+            native_2d_subpixel = os.environ.get("U3D_NATIVE_2D_SUBPIXEL", "0") == "1"
+        subpixel_2d = bool(native_2d_subpixel) and not is3d and basic_module is DoubleConv
+        if subpixel_2d:
+            if bf16_2d:
+                raise ValueError("u3d: native_2d_subpixel is the fp32 sub-pixel decoder path; "
+                                 f"{'native_2d_bf16_vcat' if vcat_2d else 'native_2d_bf16'} contradicts it — drop one of the two keys")
+            native_2d = True
         self.native_2d = bool(native_2d) and not is3d
         self.native_2d_stem = stem_2d
+        self.native_2d_subpixel = subpixel_2d
         self.native_2d_bf16 = bf16_2d
         self.native_2d_bf16_vcat = vcat_2d
         self.native_2d_residual_bf16 = res2d_bf16
@@ -376,7 +393,8 @@ def _variant(name, basic_module, default_levels, is3d, doc):
                               native_2d_residual=kwargs.get("native_2d_residual"), native_2d_bf16=kwargs.get("native_2d_bf16"),
                               native_2d_residual_bf16=kwargs.get("native_2d_residual_bf16"),
                               native_2d_residual_bf16_deconv=kwargs.get("native_2d_residual_bf16_deconv"),
-                              native_2d_stem=kwargs.get("native_2d_stem"), native_2d_bf16_vcat=kwargs.get("native_2d_bf16_vcat"))
+                              native_2d_stem=kwargs.get("native_2d_stem"), native_2d_bf16_vcat=kwargs.get("native_2d_bf16_vcat"),
+                              native_2d_subpixel=kwargs.get("native_2d_subpixel"))
 
     return type(name, (AbstractUNet,), {"__init__": __init__, "__doc__": doc, "__module__": _THIS_MODULE})
 

@@ -37,7 +37,13 @@ u3d_nearest_cat_fwd calls they replace and of the single-source bf16 calls of bo
 on has the decoders' first convolutions among them, so the comparison is on the difference of the totals), and
 torch.cuda.max_memory_allocated over one step of every arm.
 
-  python tools/unet2d_bench.py [--configs confocal,dsb2018] [--batch N] [--steps 10] [--warmup 3] [--bf16] [--stem] [--vcat]   (--batch: every config's own default)"""
+With --subpixel (UNet2D configurations) the alternation gains the arm `native_2d` + `native_2d_subpixel: true` (the upsampled half of the
+decoders' first convolutions on the sub-pixel kernels of csrc/u3d_subpix2d.hip at the levels that upsample by exactly 2).  The record adds
+its ms per step, its speed-up over the `native_2d` arm of the same run and the verdict against the project's bar for a speed mode (more
+than 5 % faster), the decoder levels it took, the 3x3 FLOPs per image it executes (16 instead of 36 multiply-adds per low-res pixel for
+the upsampled half of those levels) and the per-entry-point times of its convolution launches.
+
+  python tools/unet2d_bench.py [--configs confocal,dsb2018] [--batch N] [--steps 10] [--warmup 3] [--bf16] [--stem] [--vcat] [--subpixel]   (--batch: every config's own default)"""
 import argparse
 import json
 import os
@@ -91,8 +97,10 @@ def layer_flops_per_image(cfg, hw):
     return tot["conv"], tot["convtr"]
 
 
-def conv_flops_per_image(cfg, hw):
-    """18 * Cin * Cout * pixels summed over the 3x3 layers (one direction), counted from the module tree"""
+def conv_flops_per_image(cfg, hw, subpixel=False):
+    """18 * Cin * Cout * pixels summed over the 3x3 layers (one direction), counted from the module tree.  `subpixel`: the FLOPs the
+    `native_2d_subpixel` arm EXECUTES — at a decoder level that upsamples by exactly 2 (C0, C1, Cout multiples of 4) the C1 upsampled
+    input channels of the first convolution cost 2 * 16 * C1 * Cout per LOW-RES pixel = 8 * C1 * Cout per output pixel instead of 18"""
     from pytorch3dunet_amd.unet3d.model import get_model
 
     m = get_model(dict(cfg))
@@ -109,9 +117,15 @@ def conv_flops_per_image(cfg, hw):
         if enc.pooling is not None:
             H, W = H // 2, W // 2
         sizes.append((H, W))
-    for dec, (h, w) in zip(m.decoders, sizes[:-1][::-1]):
-        for sc in (dec.basic_module.SingleConv1, dec.basic_module.SingleConv2):
-            tot += 18.0 * sc.conv.in_channels * sc.conv.out_channels * h * w
+    lows = sizes[1:][::-1]
+    for dec, (h, w), (h1, w1) in zip(m.decoders, sizes[:-1][::-1], lows):
+        for i, sc in enumerate((dec.basic_module.SingleConv1, dec.basic_module.SingleConv2)):
+            ci, co = sc.conv.in_channels, sc.conv.out_channels
+            c1 = (ci - co) if i == 0 else 0  # (a DoubleConv decoder's first conv: C0 = Cout skip channels, C1 = Cin - C0 upsampled)
+            if subpixel and i == 0 and h == 2 * h1 and w == 2 * w1 and c1 > 0 and c1 % 4 == 0 and (ci - c1) % 4 == 0 and co % 4 == 0:
+                tot += (18.0 * (ci - c1) + 8.0 * c1) * co * h * w
+            else:
+                tot += 18.0 * ci * co * h * w
     return tot
 
 
@@ -121,7 +135,9 @@ def make(cfg, native, dev):
 
     torch.manual_seed(0)
     extra = {}
-    if native == "bf16_stem_vcat":
+    if native == "subpixel":
+        extra, native = dict(native_2d_subpixel=True), True
+    elif native == "bf16_stem_vcat":
         extra, native = dict(native_2d_stem=True, native_2d_bf16_vcat=True), "bf16"
     elif native in ("stem", "bf16_stem"):
         extra, native = dict(native_2d_stem=True), ("bf16" if native == "bf16_stem" else True)
@@ -165,6 +181,7 @@ def main():
     ap.add_argument("--bf16", action="store_true", help="also time the step with native_2d_bf16 / native_2d_residual_bf16, alternated with the others")
     ap.add_argument("--stem", action="store_true", help="also time the UNet2D step with native_2d_stem next to native_2d (and, with --bf16, next to native_2d_bf16)")
     ap.add_argument("--vcat", action="store_true", help="with --bf16 --stem: also time the UNet2D step with native_2d_bf16_vcat on top of them")
+    ap.add_argument("--subpixel", action="store_true", help="also time the UNet2D step with native_2d_subpixel next to native_2d")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "unet2d_bench measures on the GPU"
     from pytorch3dunet_amd import _native as nat
@@ -190,6 +207,8 @@ def main():
                 paths.insert(paths.index("bf16") + 1, "bf16_stem")
                 if a.vcat:
                     paths.insert(paths.index("bf16_stem") + 1, "bf16_stem_vcat")
+        if a.subpixel and not _residual(cfg):
+            paths.insert(1, "subpixel")
         runs = {p: make(cfg, p, dev) for p in paths}
         for p in paths:
             for _ in range(a.warmup):
@@ -249,6 +268,23 @@ def main():
             return {k: {"calls": v["calls"], "ms": round(v["ms"], 3), "tflops_executed": round(v["flops"] / v["ms"] / 1e9, 2) if v["ms"] else None}
                     for k, v in d.items()}
 
+        if "subpixel" in ms:
+            # the sub-pixel arm against the native_2d arm of the same run; its convolution launches by entry point (the three new ones
+            # and the skip halves on the conv2d family), and the 3x3 FLOPs per image it executes
+            spfam = family_step("subpixel")
+            spconv = {k: v for k, v in spfam.items() if "conv2d" in k or "subpixel2d" in k}
+            eng = runs["subpixel"][0]._get_engine()
+            taken = eng._subpixel_layers((1,) + tuple(hw))
+            ratio = best[True] / best["subpixel"]
+            rec.update(subpixel_ms_per_step=[round(v, 3) for v in ms["subpixel"]],
+                       subpixel_images_per_s=round(batch * 1000.0 / best["subpixel"], 2),
+                       subpixel_speedup_over_native_fp32=round(ratio, 4),
+                       subpixel_bar="more than 1.05x the native_2d arm of the same run",
+                       subpixel_meets_bar=bool(ratio > 1.05),
+                       subpixel_decoder_levels_taken=f"{len(taken)} of {len(eng.dec)}",
+                       subpixel_conv2d_gflop_fwd_per_image_executed=round(conv_flops_per_image(cfg, hw, subpixel=True) / 1e9, 2),
+                       subpixel_conv_family_ms_per_step=round(sum(v["ms"] for v in spconv.values()), 3),
+                       subpixel_conv_calls=calls(spconv))
         if "bf16" in ms:
             bfam = family_step("bf16")
             bconv = {k: v for k, v in bfam.items() if "conv2d" in k}
