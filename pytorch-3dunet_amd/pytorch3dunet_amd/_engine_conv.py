@@ -110,20 +110,19 @@ class ConvLayers:
     def _up_scale(self, dev):
         """(1, 8, 8) on the (p, q, r) rows of a GroupNorm-backward coefficient table: a low-res voxel stands for 8 children (a 2-D
         net: 4, `self.children`)"""
-        t = getattr(self, "_up_scale_t", None)
+        t = self._up_scale_t
         if t is None or t.device != dev:
-            ch = float(getattr(self, "children", 8.0))
-            t = self._up_scale_t = torch.tensor([1.0, ch, ch], dtype=_F32, device=dev).view(1, 3, 1)
+            t = self._up_scale_t = torch.tensor([1.0, self.children, self.children], dtype=_F32, device=dev).view(1, 3, 1)
         return t
 
     def _src_plus(self, src: VSrc):
         """`src.plus` of a sub-pixel layer's source; a 2-D net's sub-pixel levels are exact 2x on H and W (D = D1 = 1 is no axis)"""
-        return (0, 0, 0) if getattr(self, "is2d", False) else src.plus
+        return (0, 0, 0) if self.is2d else src.plus
 
     def _subpixel_layers(self, size):
         """decoder first convs whose low-res input is upsampled by exactly 2 — or, round 5, from n to 2n + 1 voxels — in every dimension at
         this input size: {id(weight): (C0, C1)} (+ `.plus`: the ids with an n -> 2n + 1 axis) — per-call state, handed down as `sub`"""
-        is2d = getattr(self, "is2d", False)
+        is2d = self.is2d
         if not self.subpixel or any(ct is not None for ct in self.dec_up) or any(self.dec_interp):
             return _SubLayers()  # (a transposed convolution yields 2n-1 voxels, resized to the skip: never an exact 2x replication)
         dims = [tuple(size)[1:] if is2d else tuple(size)]  # (2-D, `native_2d_subpixel`: H and W only)
@@ -162,7 +161,7 @@ class ConvLayers:
         if st0 is not None and st1 is not None and src.exact2x and self.fused_stats:
             # every low-res voxel is replicated exactly 8x: reuse the producer's sums
             return st0, dataclasses.replace(st1, scale=8.0)
-        if (st0 is not None and st1 is not None and getattr(self, "subpixel2d", False) and self.fused_stats and src.D == 1
+        if (st0 is not None and st1 is not None and self.subpixel2d and self.fused_stats and src.D == 1
                 and src.H == 2 * src.H1 and src.W == 2 * src.W1):
             # `native_2d_subpixel`, an exact-2x level of a 2-D net: every low-res pixel is replicated exactly 4x
             return st0, dataclasses.replace(st1, scale=4.0)
@@ -211,7 +210,7 @@ class ConvLayers:
         momentum = 0.0
         rm, rv = mod.running_mean, mod.running_var
         if training and rm is not None:
-            if getattr(self, "_in_recompute", False):
+            if self._in_recompute:
                 rm = rv = None  # activation checkpointing re-runs this forward in backward: the estimates were updated the first time
             else:
                 mod.num_batches_tracked.add_(1)  # (ATen's batch_norm does the same before the kernel)
@@ -235,7 +234,7 @@ class ConvLayers:
         job.gstats_lo, job.C0, job.reps_lo = _p(lo.t), lo.C, lo.reps
         if hi is not None:
             coef_hi = _empty((N, 3, hi.C), dtype=_F32, device=dev) if not any(self._src_plus(rec.src)) else None
-            job.gstats_hi, job.C1, job.hi_scale, job.reps_hi, job.coef_hi = (_p(hi.t), hi.C, float(getattr(self, "children", 8.0)), hi.reps,
+            job.gstats_hi, job.C1, job.hi_scale, job.reps_hi, job.coef_hi = (_p(hi.t), hi.C, self.children, hi.reps,
                                                                              _p(coef_hi))
         else:
             job.gstats_hi, job.C1, job.hi_scale, job.reps_hi, job.coef_hi = None, 0, 1.0, 1, None
@@ -260,7 +259,7 @@ class ConvLayers:
                 coef_hi = _empty((N, 3, hi.C), dtype=_F32, device=dev) if not any(self._src_plus(rec.src)) else None
                 nat.call("u3d_gn_bwd_finalize_split", dev.index, _stream(dev), _p(lo.t), lo.C, _p(hi.t), hi.C, _p(rec.mean_rstd),
                          _p(rec.gn_w.detach()), N, rec.G, count, _p(gview(rec.idx_gw)), _p(gview(rec.idx_gb)), _p(coef),
-                         float(getattr(self, "children", 8.0)), _p(coef_hi))
+                         self.children, _p(coef_hi))
                 return coef_hi
             g = torch.cat((lo.t.view(N, lo.C, 2), hi.t.view(N, hi.C, 2)), dim=1)
         if rec.norm == "g":
@@ -286,7 +285,7 @@ class ConvLayers:
         `_c16` entry points with the `*_C16` images (`_c16`), a layer inside the old one keeps today's."""
         if virtual:
             return False
-        return self._bf16_layer(Cin, Cout) or bool(self.bf16 and getattr(self, "stem", False) and Cin % 16 == 0 and Cout % 16 == 0)
+        return self._bf16_layer(Cin, Cout) or bool(self.bf16 and self.stem and Cin % 16 == 0 and Cout % 16 == 0)
 
     def _bf16_vcat(self, src: VSrc, Cout: int) -> bool:
         """THE rule for a decoder's first conv under `native_2d_bf16_vcat`, stated once: the layer runs on the `_src` entry points of the
@@ -294,7 +293,7 @@ class ConvLayers:
         when the key is on, the model's layer order is pre-norm (as `_cat_bf16` requires), both halves are fp32 tensors with channel
         counts % 32 (the kernels choose the source per 16-channel chunk / 32-channel block) and `_bf16_layer` holds on (C0 + C1, Cout).
         A decoder outside it (16-channel halves under `native_2d_stem`, odd counts) keeps the written-out concat of `_cat_bf16`."""
-        return (bool(getattr(self, "vcat", False)) and not self.post_norm and src.t1 is not None and src.C0 > 0 and src.C1 > 0
+        return (self.vcat and not self.post_norm and src.t1 is not None and src.C0 > 0 and src.C1 > 0
                 and src.C0 % 32 == 0 and src.C1 % 32 == 0 and self._bf16_layer(src.C, Cout)
                 and src.t0.dtype == _F32 and src.t1.dtype == _F32 and os.environ.get("U3D_BF16_CAT", "1") != "0")
 
@@ -323,7 +322,7 @@ class ConvLayers:
 
     def _convtr_t8(self, Cl: int, Cs: int) -> bool:
         """the transposed convolution and its gradients run in space-to-depth form on the bf16 MFMA kernels"""
-        return self.bf16 and not getattr(self, "is2d", False) and nat.get_lib().u3d_convtr3d_t8_supported(Cl, Cs) == 1
+        return self.bf16 and not self.is2d and nat.get_lib().u3d_convtr3d_t8_supported(Cl, Cs) == 1
 
     # ---- forward kernel families (csrc file; what selects it) -------------------------------------------------------------------
     _FWD_KERNELS = {
@@ -338,15 +337,40 @@ class ConvLayers:
         "subpixel2d": "_fwd_subpixel2d",  # u3d_subpix2d.hip + u3d_conv2d.hip: `native_2d_subpixel`, cat(skip, nearest2x(low)), 4/9 of the MACs
     }
 
+    # ---- a 2-D net (`is2d`): small2d -> subpixel2d -> conv2d_bf16 | conv2d, stated once per direction --------------------------------
+    def _fwd_family_2d(self, c: "_ConvCall", residual) -> str:
+        if self._small2d(c.Ctot, c.Cout, c.src.t1 is not None) and residual is None:
+            return "small2d"
+        if c.src.t1 is not None and residual is None and id(c.conv.weight) in c.sub:
+            return "subpixel2d"
+        # (a decoder's first conv reaches here on its materialised concat when it fits: `_cat_bf16`; forward and data gradient
+        # are covered together by the one channel rule; a residual rides in either family's epilogue)
+        return "conv2d_bf16" if self._bf16_routed(c.src, c.Cout) else "conv2d"
+
+    def _bwd_family_2d(self, c: "_BwdCall") -> str:
+        """data gradient and weight gradient alike (a small2d layer that needs a data gradient arrives with `c.bf16` False: `_conv_bwd`)"""
+        if c.rec.sub is not None:
+            return "subpixel2d"
+        return "conv2d_bf16" if c.bf16 else "conv2d"
+
+    def _layer_ws_floats_2d(self, N, H, W, Cin, Cout, sub, small, virtual):
+        """weight gradient + the data gradient's split-K scratch (roles swapped)"""
+        lib = nat.get_lib()
+        if sub is not None:  # (`native_2d_subpixel`: skip slice on the conv2d kernels + the sub-pixel slice's block slots)
+            return max(lib.u3d_wgrad2d_workspace_floats(N, H, W, sub[0], Cout),
+                       lib.u3d_subpixel2d_wgrad_workspace_floats(N, H // 2, W // 2, sub[1], Cout),
+                       lib.u3d_conv2d_workspace_floats(N, H, W, Cout, sub[0]))
+        if not small and self._bf16_routed_weight(Cin, Cout, virtual):  # (the bf16 kernels' plans, csrc/u3d_conv2d_bf16.hip)
+            sfx = "_c16" if self._c16(Cin, Cout) else ""
+            return max(getattr(lib, f"u3d_wgrad2d_bf16{sfx}_workspace_floats")(N, H, W, Cin, Cout),
+                       getattr(lib, f"u3d_conv2d_bf16{sfx}_workspace_floats")(N, H, W, Cout, Cin))
+        need = max(lib.u3d_wgrad2d_workspace_floats(N, H, W, Cin, Cout), lib.u3d_conv2d_workspace_floats(N, H, W, Cout, Cin))
+        # (a small layer: the one-pass backward, or — when a data gradient is needed — the fall-through to the fp32 family)
+        return max(need, lib.u3d_small_cin2d_bwd_workspace_floats(N, H, W, Cin, Cout)) if small else need
+
     def _fwd_family(self, c: "_ConvCall", residual) -> str:
-        if getattr(self, "is2d", False):
-            if self._small2d(c.Ctot, c.Cout, c.src.t1 is not None) and residual is None:
-                return "small2d"
-            if c.src.t1 is not None and residual is None and id(c.conv.weight) in c.sub:
-                return "subpixel2d"
-            # (a decoder's first conv reaches here on its materialised concat when it fits: `_cat_bf16`; forward and data gradient
-            # are covered together by the one channel rule; a residual rides in either family's epilogue)
-            return "conv2d_bf16" if self._bf16_routed(c.src, c.Cout) else "conv2d"
+        if self.is2d:
+            return self._fwd_family_2d(c, residual)
         if self.small_cin and c.src.t1 is None and c.Ctot <= 4 and c.Cout <= 32 and residual is None and not c.b16:
             return "small"
         if c.src.t1 is not None and residual is None and id(c.conv.weight) in c.sub:
@@ -368,7 +392,7 @@ class ConvLayers:
         """THE rule for the small-Cin family of a 2-D net under `native_2d_stem`, the 3-D `small` rule: a single real source with
         Cin <= 4 and Cout <= 32 (no residual: DoubleConv nets have none).  Asked by `_fwd_family`, `_weight_images` (such a layer gets no
         packed image up front) and `_layer_ws_floats`."""
-        return bool(getattr(self, "stem", False)) and self.small_cin and not virtual and Cin <= 4 and Cout <= 32
+        return self.stem and self.small_cin and not virtual and Cin <= 4 and Cout <= 32
 
     def _fwd_small2d(self, c: "_ConvCall"):
         # first layer of a 2-D net under `native_2d_stem`: direct / 16x16x4-MFMA kernels on the reference weight layout (csrc/u3d_conv2d.hip)
@@ -666,10 +690,8 @@ class ConvLayers:
     }
 
     def _wgrad_family(self, c: "_BwdCall") -> str:
-        if getattr(self, "is2d", False) and c.rec.sub is not None:
-            return "subpixel2d"
-        if getattr(self, "is2d", False):
-            return "conv2d_bf16" if c.bf16 else "conv2d"
+        if self.is2d:
+            return self._bwd_family_2d(c)
         if c.bf16 and c.Cout % 32 == 0:  # (Cout % 64 == 32 since round 4: 64-column blocks with a zero upper half)
             return "bf16"
         if c.rec.sub is not None:
@@ -679,10 +701,8 @@ class ConvLayers:
         return "fp32"
 
     def _dgrad_family(self, c: "_BwdCall") -> str:
-        if getattr(self, "is2d", False) and c.rec.sub is not None:
-            return "subpixel2d"
-        if getattr(self, "is2d", False):
-            return "conv2d_bf16" if c.bf16 else "conv2d"
+        if self.is2d:
+            return self._bwd_family_2d(c)
         if c.rec.sub is not None:
             return "subpixel"
         if c.src.t1 is None and not c.rec.small and self._split_dgrad(c.src.C, c.Cout):
@@ -970,7 +990,7 @@ class ConvLayers:
         if rec.small and not need_dg:
             # one pass gives dw and the GroupNorm-backward sums; no data gradient needed (csrc/u3d_smallc.hip)
             gst = pool.table(Nn, src.C)
-            if getattr(self, "is2d", False):  # (D = 1: the 2-D twin, csrc/u3d_conv2d.hip)
+            if self.is2d:  # (D = 1: the 2-D twin, csrc/u3d_conv2d.hip)
                 nat.call("u3d_conv2d_small_cin_bwd", dev.index, _stream(dev), _p(src.t0), _p(rec.affine), _p(dz_),
                          _p(rec.conv_w.detach()), _p(gview(rec.idx_w)), _p(gst.t), Nn, Hh, Ww, src.C, Cout, _p(ws), ws.numel(),
                          flops=2 * 18.0 * src.C * Cout * Nn * Hh * Ww)
@@ -1030,20 +1050,9 @@ class ConvLayers:
 
     def _layer_ws_floats(self, N, D, H, W, Cin, Cout, sub=None, small=False, virtual=False):
         """scratch floats one 3x3x3 layer's backward needs from the shared buffer, for the kernels it will actually run"""
+        if self.is2d:
+            return self._layer_ws_floats_2d(N, H, W, Cin, Cout, sub, small, virtual)
         lib = nat.get_lib()
-        if getattr(self, "is2d", False):  # weight gradient + the data gradient's split-K scratch (roles swapped)
-            if sub is not None:  # (`native_2d_subpixel`: skip slice on the conv2d kernels + the sub-pixel slice's block slots)
-                return max(lib.u3d_wgrad2d_workspace_floats(N, H, W, sub[0], Cout),
-                           lib.u3d_subpixel2d_wgrad_workspace_floats(N, H // 2, W // 2, sub[1], Cout),
-                           lib.u3d_conv2d_workspace_floats(N, H, W, Cout, sub[0]))
-            if small:  # (the one-pass backward, or — when a data gradient is needed — the fall-through to the fp32 family)
-                return max(lib.u3d_small_cin2d_bwd_workspace_floats(N, H, W, Cin, Cout), lib.u3d_wgrad2d_workspace_floats(N, H, W, Cin, Cout),
-                           lib.u3d_conv2d_workspace_floats(N, H, W, Cout, Cin))
-            if self._bf16_routed_weight(Cin, Cout, virtual):  # (the bf16 kernels' plans, csrc/u3d_conv2d_bf16.hip)
-                sfx = "_c16" if self._c16(Cin, Cout) else ""
-                return max(getattr(lib, f"u3d_wgrad2d_bf16{sfx}_workspace_floats")(N, H, W, Cin, Cout),
-                           getattr(lib, f"u3d_conv2d_bf16{sfx}_workspace_floats")(N, H, W, Cout, Cin))
-            return max(lib.u3d_wgrad2d_workspace_floats(N, H, W, Cin, Cout), lib.u3d_conv2d_workspace_floats(N, H, W, Cout, Cin))
         if small:
             return lib.u3d_small_cin_bwd_workspace_floats(N, D, H, W, Cin, Cout)
         if sub is not None:  # skip slice (fp32 kernels) + sub-pixel slice + the slab boxes of an n -> 2n + 1 level

@@ -32,13 +32,10 @@ class ResUNetEngine(UNet3DEngine):
     residual come out of the 1x1x1 conv's / the joining kernel's epilogue.  The 1x1x1 convolutions and the transposed
     convolution run on the FP32 vector units (csrc/u3d_res.hip).
 
-    ResidualUNet2D under `native_2d_residual` (unet3d/model.py sets model.native_2d, hence self.is2d): (N,C,H,W) runs as
-    (N,C,1,H,W); the 3x3 convolutions take the `conv2d` family (u3d_conv2d_res_reps fuses `out += residual`), the pools the
-    u3d_maxpool2d_* twins and the decoders ConvTranspose2d (u3d_convtr2d_*) before the same joining kernels at D = 1; the t8 and
-    sub-pixel branches stay off.  Under `native_2d_residual_bf16` conv2 / conv3 of the blocks whose width is a multiple of 32 take the
-    `conv2d_bf16` family in all three directions (`_bf16_routed`; u3d_conv2d_bf16_res fuses `out += residual`); the 1x1 convolutions,
-    ConvTranspose2d and every activation tensor stay fp32.  `native_2d_residual_bf16_deconv` adds the decoders' ConvTranspose2d whose
-    channel counts are both multiples of 32 (`_bf16_convtr2d`; u3d_convtr2d_*_bf16): t, the resize + join and the tape are unchanged."""
+    ResidualUNet2D under `native_2d_residual` and the keys that imply it (unet3d/native2d.py; `self.is2d`): (N,C,H,W) runs as (N,C,1,H,W);
+    the 3x3 convolutions take the `conv2d` / `conv2d_bf16` families (`_bf16_routed`; both fuse `out += residual`), the pools the
+    u3d_maxpool2d_* twins and the decoders ConvTranspose2d (u3d_convtr2d_*; `_bf16_convtr2d`: the bf16 twins) before the same joining
+    kernels at D = 1; the t8 and sub-pixel branches stay off, the 1x1 convolutions and every activation tensor stay fp32."""
 
     def __init__(self, model):
         super().__init__(model)
@@ -46,17 +43,17 @@ class ResUNetEngine(UNet3DEngine):
         # two non-linearities per block: conv2's own (from the order string, nn defaults: LeakyReLU 0.01) and the block's final
         # one after `out += residual` (buildingblocks.py:270-275: LeakyReLU(0.1) if 'l', ELU if 'e', else ReLU).  self.act /
         # self.slope / self.mask describe the BLOCK outputs (what pooling, joining and the head consume).
-        order = getattr(model, "layer_order", "gcr")
+        order = model.layer_order
         self.act2, self.slope2 = self.act, self.slope
         self.act, self.slope = (ACT_LEAKY, 0.1) if "l" in order else ((ACT_ELU, 0.0) if "e" in order else (ACT_RELU, 0.0))
         self.mask = 1 if self.act == ACT_RELU else 0
         self.lean_tape = self.checkpoint_encoders and os.environ.get("U3D_LEAN_TAPE", "1") != "0"
         self.adt = _F32
-        if bool(getattr(model, "activation_bf16", False)):
+        if model.activation_bf16:
             why = self._act_bf16_blocker(model, order)
             if why is None:
                 self.act_bf16, self.adt = True, torch.bfloat16
-            elif getattr(model, "activation_dtype", "bf16") != "auto":
+            elif model.activation_dtype != "auto":
                 import warnings
 
                 warnings.warn(f"u3d: activation_dtype bf16 requested but {why}; activations stay fp32 in HBM", stacklevel=3)
@@ -132,7 +129,7 @@ class ResUNetEngine(UNet3DEngine):
         # (recomputation under checkpointing: the block output is still alive in y_out — conv3 is NOT run again, only its record is
         # rebuilt; U3D_CKPT_RERUN_LAST=1 re-runs it as rounds 4-5 did (A/B; bit-identical).  An SE block's backward needs conv3's own
         # output, which the forward pass did not keep: re-run.)
-        skip3 = (getattr(self, "_in_recompute", False) and se_mod is None and y_out is not None and not _CKPT_RERUN_LAST)
+        skip3 = (self._in_recompute and se_mod is None and y_out is not None and not _CKPT_RERUN_LAST)
         y, y_st = self._single_conv_fwd(bm.conv3, name + ".c3", src3, (st2, None), pool, tape,
                                         want_stats=se_mod is not None, residual=r, y_out=y_out if se_mod is None else None,
                                         act=(self.act, self.slope), record_only=skip3)

@@ -32,20 +32,22 @@ class UNet3DEngine(ConvLayers):
         self.grad_sync = None  # set by parallel.GradSync (RCCL all-reduce overlapped with the encoder backward)
         self.debug = None  # dict -> backward stores clones of per-layer dz / dg (tools/gpu_layer_diag.py)
         self.fused_stats = True
-        # UNet2D under `native_2d` (unet3d/model.py): (N,C,H,W) runs as (N,C,1,H,W) — every 3x3 convolution on the 2-D kernel family
-        # (csrc/u3d_conv2d.hip, `conv2d` in the family tables), 2x2 pooling; sub-pixel decoder kernels only under `native_2d_subpixel` (below)
-        self.is2d = bool(getattr(model, "native_2d", False))
-        # opt-in `native_2d_stem` (a UNet2D): the first layer on the small-Cin kernels of csrc/u3d_conv2d.hip (`_small2d`)
-        self.stem = self.is2d and bool(getattr(model, "native_2d_stem", False))
+        # (unet3d/native2d.py: a bf16 key has compute_bf16, `native_2d_subpixel` stands next to no bf16 mode on a model the executor covers)
+        keys = model.keys_2d
+        self.is2d = keys.native_2d  # (N,C,H,W) runs as (N,C,1,H,W): 3x3 convolutions on the `conv2d` families, 2x2 pooling
+        self.stem = keys.native_2d_stem  # the first layer on the small-Cin 2-D kernels (`_small2d`)
+        self.subpixel2d = keys.native_2d_subpixel  # exact-2x decoder levels on csrc/u3d_subpix2d.hip
+        self.vcat = keys.native_2d_bf16_vcat  # a decoder's first conv reads its concat inside the bf16 kernels (`_bf16_vcat`)
+        self.bf16_deconv = keys.native_2d_residual_bf16_deconv  # the decoders' ConvTranspose2d on the bf16 matrix pipe (`_bf16_convtr2d`)
+        self.children = 4.0 if self.is2d else 8.0  # full-res voxels a low-res voxel of an exact-2x level stands for
+        self._up_scale_t = None  # `_up_scale`'s memo
+        self._in_recompute = False  # activation checkpointing is re-running a block's forward inside backward (ResUNetEngine)
         # replica rows of the statistics tables the persistent fp32 convolutions write (u3d_conv3d_ex_reps; 1 = plain tables)
         self.stat_reps = max(1, min(64, int(os.environ.get("U3D_STAT_REPS", "8"))))
         self.small_cin = True  # dedicated kernels for the in_channels<=4 first layer
         self.overlap_small_wgrad = True  # weight gradients of small layers on a second HIP stream (see _BwdCtx)
         # decoder first convs over an exact-2x upsampling: sub-pixel convolution of the upsampled half (csrc/u3d_subpix.hip)
-        # (a 2-D net: only under the opt-in `native_2d_subpixel`, a fp32 UNet2D — csrc/u3d_subpix2d.hip, exact-2x levels only)
-        self.subpixel2d = self.is2d and bool(getattr(model, "native_2d_subpixel", False)) and not bool(getattr(model, "compute_bf16", False))
         self.subpixel = os.environ.get("U3D_SUBPIXEL", "1") != "0" and (not self.is2d or self.subpixel2d)
-        self.children = 4.0 if self.is2d else 8.0  # full-res voxels a low-res voxel of an exact-2x level stands for
         # ... and over a level that upsamples n -> 2n + 1 along some axes (an odd skip size: 42 -> 85 in the shipped 80 x 170 x 170 patch):
         # sub-pixel kernels on a shifted window + the general kernels on the near-boundary slab (round 5; U3D_SUBPIXEL_PLUS=0: such
         # levels keep the 27-tap virtual-concat kernels)
@@ -54,18 +56,13 @@ class UNet3DEngine(ConvLayers):
         # counts allow it (csrc/u3d_bf16.hip), fp32 master weights / activations / statistics; and recomputation of the
         # encoder blocks in backward instead of keeping their intermediates.  Set through the model
         # (`compute_dtype: bf16`, `checkpoint_encoders: true` in the YAML's model section, or U3D_BF16=1 / U3D_CHECKPOINT=1).
-        self.bf16 = bool(getattr(model, "compute_bf16", False))
-        # opt-in `native_2d_residual_bf16_deconv` (a ResidualUNet2D in bf16): the decoders' ConvTranspose2d on the bf16 matrix pipe too
-        # (`_bf16_convtr2d`)
-        # opt-in `native_2d_bf16_vcat` (a UNet2D in bf16): a decoder's first conv reads its concat inside the bf16 kernels (`_bf16_vcat`)
-        self.vcat = self.is2d and self.bf16 and bool(getattr(model, "native_2d_bf16_vcat", False))
-        self.bf16_deconv = self.is2d and self.bf16 and bool(getattr(model, "native_2d_residual_bf16_deconv", False))
+        self.bf16 = model.compute_bf16
         # opt-in `compute_dtype: fp32_split`: FP32-grade convolutions on the bf16 matrix pipe — every fp32 operand split exactly
         # into three bf16 values, six partial products per multiply accumulated in fp32 (csrc/u3d_bf16.hip, u3d_conv3d_f32s);
         # forward and data gradients only, weight gradients stay on the fp32 MFMA kernels
-        self.split = bool(getattr(model, "compute_split", False)) and not self.bf16
-        self.checkpoint_encoders = bool(getattr(model, "checkpoint_encoders", False))
-        self.checkpoint_levels = getattr(model, "checkpoint_levels", None)  # None: every encoder level; k: the k highest-resolution ones
+        self.split = model.compute_split
+        self.checkpoint_encoders = model.checkpoint_encoders
+        self.checkpoint_levels = model.checkpoint_levels  # None: every encoder level; k: the k highest-resolution ones
         # with activation checkpointing the tape is also RELEASED block by block during backward (ResUNetEngine.backward): a feature
         # whose only purpose is memory must move the peak, and with one autograd node owning the whole tape it otherwise does not
         self.lean_tape = False  # (ResUNetEngine turns it on together with checkpoint_encoders)
@@ -78,13 +75,13 @@ class UNet3DEngine(ConvLayers):
         self._lock = threading.RLock()  # host-side enqueue of one forward / backward at a time per engine
         # opt-in static-shape step runner (`hip_graph: true` in the YAML's model section or U3D_GRAPH=1): the ~70 forward and ~110
         # backward launches of a TRAINING step are captured once per input shape in two hipGraphs and replayed (GraphStep below)
-        self.hip_graph = bool(getattr(model, "hip_graph", False))
+        self.hip_graph = model.hip_graph
         self._graph_steps: dict = {}
         self._graph_off_reason = None
         self._placed = None  # check_placement's memo
         self._const: dict = {}
         # the model-wide layer order (every SingleConv of a DoubleConv net shares it): non-linearity of the layer outputs
-        spec = parse_order(getattr(model, "layer_order", "gcr")) or (False, ACT_RELU, 0.0)
+        spec = parse_order(model.layer_order) or (False, ACT_RELU, 0.0)
         self.post_norm, self.act, self.slope = spec
         self.mask = 1 if self.act == ACT_RELU else 0  # ReLU backward is a fused mask in the consumer kernels
         self.params = module_params(model)
@@ -349,7 +346,7 @@ class UNet3DEngine(ConvLayers):
         fc = m.final_conv
         Co, Cf = fc.out_channels, fc.in_channels
         tot = self.stat_reps * (Co * Cf + Co) + sum(self.stat_reps * N * r.src.C * 2 for r in tape.convs)
-        pool = getattr(tape, "bwd_pool", None)  # zeroed by the forward's fill launch; a second backward over the tape takes a fresh one
+        pool = tape.bwd_pool  # zeroed by the forward's fill launch; a second backward over the tape takes a fresh one
         tape.bwd_pool = None
         # (a backward pass being captured into a hipGraph is replayed without its forward: it zeroes its own scratch inside the graph;
         # claim() last: only the pass that takes the pool marks it used)

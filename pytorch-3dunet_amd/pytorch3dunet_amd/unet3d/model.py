@@ -13,27 +13,29 @@ libu3d_hip.so is missing (no silent fallback).  CPU tensors (`device: cpu`) run 
 made of.  ONE backend: a 3-D model variant the executor does not cover (layer orders outside engine.layer_spec's grammar,
 conv kernels other than 3/pad 1, `pool_type: avg`) RAISES on a HIP device; U3D_ALLOW_TORCH_FALLBACK=1 opts into running
 the same module tree through stock PyTorch-ROCm operators after a one-time warning (never counted as covered).  2-D
-models are outside the 3-D path and keep that warning path by default (opt-in since round 7: `native_2d: true` / U3D_NATIVE_2D=1 runs a
-fp32 UNet2D with nearest upsampling on the 2-D kernels of csrc/u3d_conv2d.hip; `native_2d_residual: true` / U3D_NATIVE_2D_RESIDUAL=1
-does the same for a fp32 ResidualUNet2D; `native_2d_bf16: true` / U3D_NATIVE_2D_BF16=1 runs a UNet2D with bf16 MFMA operands on the kernels
-of csrc/u3d_conv2d_bf16.hip, `native_2d_residual_bf16: true` / U3D_NATIVE_2D_RESIDUAL_BF16=1 a ResidualUNet2D; `native_2d_stem: true` /
-U3D_NATIVE_2D_STEM=1 adds the small-Cin first-layer kernels to a native UNet2D, `native_2d_bf16_vcat: true` / U3D_NATIVE_2D_BF16_VCAT=1 reads
-the decoders' concat inside the bf16 kernels of a UNet2D, `native_2d_subpixel: true` / U3D_NATIVE_2D_SUBPIXEL=1 runs the upsampled half of a
-fp32 UNet2D's decoder first convolutions on the sub-pixel kernels of csrc/u3d_subpix2d.hip at levels that upsample by exactly 2);
-U3D_STRICT=1 makes them an error too.  Covered since round 2: every layer order with at most one
+models are outside the 3-D path and keep that warning path by default (U3D_STRICT=1 makes them an error too); the opt-in keys that
+run them natively (resolved by unet3d/native2d.py, which says more about each):
+
+{native_2d_keys}
+
+Covered since round 2: every layer order with at most one
 GroupNorm / BatchNorm, one non-linearity and a trailing dropout, every `upsample` value the reference itself can run
 on a 3-D net, nn.DataParallel, activation checkpointing, and the opt-in compute modes `bf16` and `fp32_split`.
 """
+import dataclasses
 import os
 import warnings
 
 import torch
 from torch import nn
 
+from . import native2d
 from .buildingblocks import DoubleConv, ResNetBlock, ResNetBlockSE, create_decoders, create_encoders
 from .utils import get_class, number_of_features_per_level
 
 _THIS_MODULE = __name__
+__doc__ = __doc__.replace("{native_2d_keys}", native2d.TABLE)
+_OPT_IN_KEYS = ("compute_dtype", "checkpoint_encoders", "hip_graph", "activation_dtype", "checkpoint_levels") + native2d.NAMES
 
 
 def _mark_engine_stale(module, incompatible_keys):
@@ -48,8 +50,7 @@ class AbstractUNet(nn.Module):
                  num_groups=8, num_levels=4, is_segmentation=True, conv_kernel_size=3, pool_kernel_size=2,
                  conv_padding=1, conv_upscale=2, upsample="default", dropout_prob=0.1, is3d=True, compute_dtype=None,
                  checkpoint_encoders=None, hip_graph=None, activation_dtype=None, checkpoint_levels=None,
-                 native_2d=None, native_2d_residual=None, native_2d_bf16=None, native_2d_residual_bf16=None,
-                 native_2d_residual_bf16_deconv=None, native_2d_stem=None, native_2d_bf16_vcat=None, native_2d_subpixel=None):
+                 **native_2d_keys):
         super().__init__()
         if isinstance(f_maps, int):
             f_maps = number_of_features_per_level(f_maps, num_levels=num_levels)
@@ -70,104 +71,21 @@ class AbstractUNet(nn.Module):
             self.final_activation = None
 
         # ---- native-path eligibility (everything the gfx950 executor implements today)
-        # `native_2d: true` (model-section key; U3D_NATIVE_2D=1 sets its default): a UNet2D runs on the 2-D kernels of
-        # csrc/u3d_conv2d.hip through the DoubleConv executor with D = 1 (fp32, nearest upsampling); off by default
-        if native_2d is None:
-            native_2d = os.environ.get("U3D_NATIVE_2D", "0") == "1"
-        # `native_2d_residual: true` (its own key; U3D_NATIVE_2D_RESIDUAL=1 sets its default): a ResidualUNet2D runs on the same 2-D
-        # kernels through the residual executor (plus the residual conv2d epilogue and ConvTranspose2d of csrc/u3d_res.hip); it implies
-        # native_2d.  Every other class ignores it, and `native_2d: true` alone leaves a ResidualUNet2D on the warning path
-        if native_2d_residual is None:
-            native_2d_residual = os.environ.get("U3D_NATIVE_2D_RESIDUAL", "0") == "1"
-        # `native_2d_residual_bf16: true` (its own key; U3D_NATIVE_2D_RESIDUAL_BF16=1 sets its default): a ResidualUNet2D runs natively with
-        # bf16 MFMA operands on csrc/u3d_conv2d_bf16.hip for every 3x3 layer whose channel counts are both multiples of 32 (conv2 and conv3
-        # of a ResNetBlock map C -> C: at the reference's f_maps every one of them; conv3's `out += residual` is the fp32 epilogue of
-        # u3d_conv2d_bf16_res).  The 1x1 convolutions, ConvTranspose2d, pooling, joining, the head and the activations in HBM stay fp32.  It
-        # implies native_2d_residual (hence native_2d) and compute_dtype bf16; an explicit fp32 / fp32_split compute_dtype next to it is a
-        # contradiction.  Every other class ignores it, and `native_2d_residual: true` + `compute_dtype: bf16` without it stays on the
-        # warning path
-        if native_2d_residual_bf16 is None:
-            native_2d_residual_bf16 = os.environ.get("U3D_NATIVE_2D_RESIDUAL_BF16", "0") == "1"
-        # `native_2d_residual_bf16_deconv: true` (a separate key, so that native_2d_residual_bf16 alone stays bit-identical;
-        # U3D_NATIVE_2D_RESIDUAL_BF16_DECONV=1 sets its default): in addition the decoders' ConvTranspose2d whose channel counts are both
-        # multiples of 32 run forward, data gradient and weight gradient with bf16 operands (u3d_convtr2d_*_bf16).  It implies
-        # native_2d_residual_bf16 and everything that key implies; every other class ignores it
-        if native_2d_residual_bf16_deconv is None:
-            native_2d_residual_bf16_deconv = os.environ.get("U3D_NATIVE_2D_RESIDUAL_BF16_DECONV", "0") == "1"
-        res2d_bf16_deconv = bool(native_2d_residual_bf16_deconv) and not is3d and basic_module is ResNetBlock
-        res2d_bf16 = (bool(native_2d_residual_bf16) or res2d_bf16_deconv) and not is3d and basic_module is ResNetBlock
-        if res2d_bf16:
-            key = "native_2d_residual_bf16_deconv" if res2d_bf16_deconv else "native_2d_residual_bf16"
-            if compute_dtype is not None and str(compute_dtype).lower() not in ("bf16", "bfloat16"):
-                raise ValueError(f"u3d: {key} runs bf16 operands; compute_dtype {compute_dtype!r} contradicts it — drop "
-                                 "one of the two keys (native_2d_residual: true is the fp32 2-D path)")
-            native_2d_residual, compute_dtype = True, "bf16"
-        res2d = bool(native_2d_residual) and not is3d and basic_module is ResNetBlock
-        if res2d:
-            native_2d = True
-        # `native_2d_bf16: true` (its own key; U3D_NATIVE_2D_BF16=1 sets its default): a UNet2D (DoubleConv blocks) runs natively with
-        # bf16 MFMA operands — fp32 accumulation, master weights, activations and statistics — on csrc/u3d_conv2d_bf16.hip for every
-        # single-source 3x3 layer whose channel counts are both multiples of 32 (the other layers stay on the fp32 2-D kernels).  It
-        # implies native_2d and compute_dtype bf16; an explicit fp32 / fp32_split compute_dtype next to it is a contradiction.  Every
-        # other class ignores it, and `native_2d: true` + `compute_dtype: bf16` without it stays on the warning path
-        if native_2d_bf16 is None:
-            native_2d_bf16 = os.environ.get("U3D_NATIVE_2D_BF16", "0") == "1"
-        # `native_2d_bf16_vcat: true` (a separate key, so that native_2d_bf16 alone stays bit-identical; U3D_NATIVE_2D_BF16_VCAT=1 sets its
-        # default): the decoders' first convolutions read torch.cat((skip, interpolate(x)), dim=1) inside the bf16 kernels through two
-        # base pointers (the `_src` entry points) instead of writing the concat out, when both halves are multiples of 32 channels; the
-        # arithmetic is unchanged.  It implies native_2d_bf16 and everything that key implies; every other class ignores it
-        if native_2d_bf16_vcat is None:
-            native_2d_bf16_vcat = os.environ.get("U3D_NATIVE_2D_BF16_VCAT", "0") == "1"
-        vcat_2d = bool(native_2d_bf16_vcat) and not is3d and basic_module is DoubleConv
-        bf16_2d = (bool(native_2d_bf16) or vcat_2d) and not is3d and basic_module is DoubleConv
-        if bf16_2d:
-            if compute_dtype is not None and str(compute_dtype).lower() not in ("bf16", "bfloat16"):
-                key = "native_2d_bf16_vcat" if vcat_2d else "native_2d_bf16"
-                raise ValueError(f"u3d: {key} runs bf16 operands; compute_dtype {compute_dtype!r} contradicts it — drop one of "
-                                 "the two keys (native_2d: true is the fp32 2-D path)")
-            native_2d, compute_dtype = True, "bf16"
-        # `native_2d_stem: true` (its own key, so that native_2d / native_2d_bf16 alone stay bit-identical; U3D_NATIVE_2D_STEM=1 sets its
-        # default): the first layer of a UNet2D (DoubleConv blocks; a single real source with Cin <= 4 and Cout <= 32, the 3-D path's
-        # rule) runs on the small-Cin kernels of csrc/u3d_conv2d.hip — exact fp32 in either precision mode.  It implies native_2d and no
-        # precision: next to native_2d_bf16 every other layer keeps that mode's routing.  Every other class ignores it
-        if native_2d_stem is None:
-            native_2d_stem = os.environ.get("U3D_NATIVE_2D_STEM", "0") == "1"
-        stem_2d = bool(native_2d_stem) and not is3d and basic_module is DoubleConv
-        if stem_2d:
-            native_2d = True
-        # `native_2d_subpixel: true` (its own key, so that native_2d alone stays bit-identical; U3D_NATIVE_2D_SUBPIXEL=1 sets its default):
-        # a fp32 UNet2D (DoubleConv blocks, nearest upsampling) runs the UPSAMPLED half of every decoder's first convolution whose level
-        # upsamples by exactly 2 on both axes (C0, C1, Cout multiples of 4) as four parity-class 2x2 convolutions over the low-res tensor
-        # — 4/9 of that half's multiply-adds in forward, data gradient and weight gradient (csrc/u3d_subpix2d.hip); the skip half and every
-        # other level (n -> 2n + 1) keep the kernels of native_2d.  It implies native_2d and is allowed next to native_2d_stem; next to
-        # native_2d_bf16 / native_2d_bf16_vcat it is a contradiction (there is no bf16 sub-pixel form).  Every other class ignores it
-        if native_2d_subpixel is None:
-            native_2d_subpixel = os.environ.get("U3D_NATIVE_2D_SUBPIXEL", "0") == "1"
-        subpixel_2d = bool(native_2d_subpixel) and not is3d and basic_module is DoubleConv
-        if subpixel_2d:
-            if bf16_2d:
-                raise ValueError("u3d: native_2d_subpixel is the fp32 sub-pixel decoder path; "
-                                 f"{'native_2d_bf16_vcat' if vcat_2d else 'native_2d_bf16'} contradicts it — drop one of the two keys")
-            native_2d = True
-        self.native_2d = bool(native_2d) and not is3d
-        self.native_2d_stem = stem_2d
-        self.native_2d_subpixel = subpixel_2d
-        self.native_2d_bf16 = bf16_2d
-        self.native_2d_bf16_vcat = vcat_2d
-        self.native_2d_residual_bf16 = res2d_bf16
-        self.native_2d_residual_bf16_deconv = res2d_bf16_deconv
+        # the native_2d* keys, resolved once (unet3d/native2d.py) into the record the executors read; a bf16 key among them forces compute_dtype
+        self.keys_2d, compute_dtype = native2d.resolve(native_2d_keys, is3d, basic_module, compute_dtype)
+        self.__dict__.update(dataclasses.asdict(self.keys_2d))  # model.native_2d, model.native_2d_bf16, ...: the same facts as plain bools
         reasons = []
         if not is3d and not self.native_2d:
             reasons.append("2-D model")
         elif not is3d:
-            if basic_module is not DoubleConv and not res2d:
+            if basic_module is not DoubleConv and not self.keys_2d.native_2d_residual:
                 reasons.append(f"2-D model with {basic_module.__name__} (native_2d covers DoubleConv blocks; a ResidualUNet2D needs "
                                "native_2d_residual: true)")
-            if not (bf16_2d or res2d_bf16) and (compute_dtype not in (None, "fp32", "float32") or os.environ.get("U3D_BF16", "0") == "1" or
-                                                os.environ.get("U3D_F32_SPLIT", "0") == "1"):
+            if not (self.keys_2d.native_2d_bf16 or self.keys_2d.native_2d_residual_bf16) and (compute_dtype not in (None, "fp32", "float32") or
+                    os.environ.get("U3D_BF16", "0") == "1" or os.environ.get("U3D_F32_SPLIT", "0") == "1"):
                 reasons.append(f"2-D model with compute_dtype {compute_dtype!r} (native_2d is fp32; a UNet2D in bf16 needs "
                                "native_2d_bf16: true, a ResidualUNet2D native_2d_residual_bf16: true)")
-            if upsample not in ("default", "nearest") and not res2d:  # (residual nets: the residual rule below)
+            if upsample not in ("default", "nearest") and not self.keys_2d.native_2d_residual:  # (residual nets: the residual rule below)
                 reasons.append(f"2-D model with upsample '{upsample}' (native_2d: nearest upsampling)")
         if basic_module not in (DoubleConv, ResNetBlock, ResNetBlockSE):
             reasons.append(f"basic_module {basic_module.__name__}")
@@ -222,8 +140,6 @@ class AbstractUNet(nn.Module):
                 raise ValueError(f"checkpoint_levels must be a positive number of encoder levels, got {checkpoint_levels!r} "
                                  "(to switch checkpointing off set checkpoint_encoders: false)")
             if checkpoint_levels > len(f_maps):
-                import warnings
-
                 warnings.warn(f"u3d: checkpoint_levels={checkpoint_levels} exceeds the {len(f_maps)} encoder levels of this model: every level is recomputed")
                 checkpoint_levels = len(f_maps)
         self.checkpoint_encoders = bool(checkpoint_encoders)
@@ -245,7 +161,7 @@ class AbstractUNet(nn.Module):
         if self.native_2d and self.hip_graph:
             raise ValueError("u3d: hip_graph is not available with native_2d (the captured training step is 3-D only); "
                              "drop one of the two keys")
-        if res2d and (self.checkpoint_encoders or self.checkpoint_levels is not None):
+        if self.keys_2d.native_2d_residual and (self.checkpoint_encoders or self.checkpoint_levels is not None):
             raise ValueError("u3d: checkpoint_encoders / checkpoint_levels are not available with native_2d_residual (the 2-D residual "
                              "executor keeps every activation); drop one of the keys")
         self._native_blockers = reasons
@@ -387,14 +303,7 @@ def _variant(name, basic_module, default_levels, is3d, doc):
                               basic_module=basic_module, f_maps=f_maps, layer_order=layer_order, num_groups=num_groups,
                               num_levels=num_levels, is_segmentation=is_segmentation, conv_padding=conv_padding,
                               conv_upscale=conv_upscale, upsample=upsample, dropout_prob=dropout_prob, is3d=is3d,
-                              compute_dtype=kwargs.get("compute_dtype"), checkpoint_encoders=kwargs.get("checkpoint_encoders"),
-                              hip_graph=kwargs.get("hip_graph"), activation_dtype=kwargs.get("activation_dtype"),
-                              checkpoint_levels=kwargs.get("checkpoint_levels"), native_2d=kwargs.get("native_2d"),
-                              native_2d_residual=kwargs.get("native_2d_residual"), native_2d_bf16=kwargs.get("native_2d_bf16"),
-                              native_2d_residual_bf16=kwargs.get("native_2d_residual_bf16"),
-                              native_2d_residual_bf16_deconv=kwargs.get("native_2d_residual_bf16_deconv"),
-                              native_2d_stem=kwargs.get("native_2d_stem"), native_2d_bf16_vcat=kwargs.get("native_2d_bf16_vcat"),
-                              native_2d_subpixel=kwargs.get("native_2d_subpixel"))
+                              **{k: kwargs[k] for k in _OPT_IN_KEYS if k in kwargs})  # (extra keys of the YAML's model section; any other is swallowed)
 
     return type(name, (AbstractUNet,), {"__init__": __init__, "__doc__": doc, "__module__": _THIS_MODULE})
 
