@@ -434,7 +434,7 @@ class Tape:
     dims: tuple = ()
     x0: Optional[torch.Tensor] = None
     blocks: list = field(default_factory=list)  # residual executor: ResRec per block (encoders, then decoders)
-    ups: list = field(default_factory=list)     # residual executor: UpRec per decoder
+    ups: list = field(default_factory=list)     # both executors: UpRec per decoder whose up-sampling is a tensor (nearest: none)
     cats: dict = field(default_factory=dict)    # DoubleConv executor, bf16 mode: decoder index -> the VIRTUAL source whose concat was materialised
     lean: bool = False      # memory-lean mode (checkpoint_encoders): backward releases every block's tensors as soon as it is done
     consumed: bool = False  # ... so the tape can be walked only once
@@ -591,13 +591,14 @@ class CkptRec:
 
 @dataclass
 class UpRec:
-    """TransposeConvUpsampling + summation joining of one decoder (buildingblocks.py:617-664, :493)"""
+    """the up-sampling of one decoder: TransposeConvUpsampling (buildingblocks.py:617-664) before either joining, or the DoubleConv
+    executor's trilinear / area resampling (weight None, `los` its tables)"""
 
     x_low: torch.Tensor
     weight: torch.Tensor  # (Cin, Cout, 3, 3, 3)
     los: tuple            # children tables of the nearest resize (2n-1 -> skip size)
     tdims: tuple          # (Dt, Ht, Wt)
-    t8: bool = False      # ran in space-to-depth form on the bf16 kernels (csrc/u3d_bf16.hip)
+    family: str           # the `ConvLayers._UP_KERNELS` row forward chose: all that backward dispatches on (resampling: its mode)
     concat: Optional[tuple] = None  # explicit upsample='deconv' on a residual net: concat joining, (Cs skip, Ct upsampled) channels
 
 

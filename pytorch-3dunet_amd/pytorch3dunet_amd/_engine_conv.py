@@ -309,8 +309,8 @@ class ConvLayers:
 
     def _bf16_convtr2d(self, Cin: int, Cout: int) -> bool:
         """THE rule for a decoder's ConvTranspose2d under `native_2d_residual_bf16_deconv`, stated once: forward, data gradient and weight
-        gradient run on the bf16 u3d_convtr2d_*_bf16 kernels when both channel counts are multiples of 32 (their envelope).  Asked by the
-        residual executor's forward (which image kind, which entry point) and backward (entry points, scratch size)."""
+        gradient run on the bf16 u3d_convtr2d_*_bf16 kernels when both channel counts are multiples of 32 (their envelope).  Asked by
+        `_up_family` alone."""
         return self.bf16_deconv and Cin % 32 == 0 and Cout % 32 == 0
 
     def _split_fwd(self, Cin: int, Cout: int) -> bool:
@@ -323,6 +323,136 @@ class ConvLayers:
     def _convtr_t8(self, Cl: int, Cs: int) -> bool:
         """the transposed convolution and its gradients run in space-to-depth form on the bf16 MFMA kernels"""
         return self.bf16 and not self.is2d and nat.get_lib().u3d_convtr3d_t8_supported(Cl, Cs) == 1
+
+    # ---- up-sampling families: a decoder's transposed convolution (csrc file; what selects it) ---------------------------------------
+    # (forward launcher (dev, ct, cur) -> up-sampled tensor; backward launcher (cx, up, dt, mk) -> dL/d(x_low), dw written into cx.gview;
+    # space-to-depth: between launchers and joining lies T8[i][parity * Ct + c] = t[2i + parity], which the `*_t8` joining kernels take)
+    _UP_KERNELS = {
+        "t8": ("_up_fwd_t8", "_up_bwd_t8", True),  # u3d_bf16.hip: compute_dtype bf16, summation joining, channels the library takes
+        "convtr2d_bf16": ("_up_fwd_convtr2d_bf16", "_up_bwd_convtr2d_bf16", False),  # u3d_conv2d_bf16.hip: `_bf16_convtr2d`
+        "convtr2d": ("_up_fwd_convtr2d", "_up_bwd_convtr2d", False),  # u3d_res.hip: every other ConvTranspose2d of a 2-D net
+        "convtr3d_subpixel": ("_up_fwd_convtr3d_subpixel", "_up_bwd_convtr3d", False),  # u3d_subpix.hip: both channel counts % 4 == 0
+        "convtr3d": ("_up_fwd_convtr3d", "_up_bwd_convtr3d", False),  # u3d_res.hip: the generic gather
+    }
+
+    def _up_family(self, Cl: int, Ct: int, concat: bool) -> str:
+        """THE rule for a decoder's ConvTranspose (Cl -> Ct, k3 s2 p1), stated once; `concat`: the joining is a concat (the DoubleConv
+        executor's virtual one, a residual net's explicit upsample='deconv'), not the sum.  Forward asks and records the answer in
+        `UpRec.family`; backward reads the record.  (`_convtr_t8` holds on 3-D nets only: the 2-D rows cannot come before it.)"""
+        if self._convtr_t8(Cl, Ct) and not concat:
+            return "t8"
+        if self.is2d:
+            return "convtr2d_bf16" if self._bf16_convtr2d(Cl, Ct) else "convtr2d"
+        return "convtr3d_subpixel" if self.subpixel and Cl % 4 == 0 and Ct % 4 == 0 else "convtr3d"
+
+    @staticmethod
+    def _up_flops3d(xl, Ct: int) -> float:
+        """one pass of a ConvTranspose3d over x_low `xl` (forward; each of the two gradients)"""
+        N, D1, H1, W1, Cl = xl.shape
+        return 2.0 * 27 * Cl * Ct * N * D1 * H1 * W1
+
+    @staticmethod
+    def _up_flops2d(xl, Ct: int) -> float:
+        """... of a ConvTranspose2d: 9 taps over the four parity classes of the (2 H1 - 1) x (2 W1 - 1) outputs"""
+        N, _, H1, W1, Cl = xl.shape
+        return 4.5 * Cl * Ct * N * (2 * H1 - 1) * (2 * W1 - 1)
+
+    def _up_fwd_t8(self, dev, ct, cur):
+        # 2x2x2 convolution on the low-res grid into the space-to-depth layout; the resize + join reads that layout directly
+        N, D1, H1, W1, Cl = cur.shape
+        Ct = ct.out_channels
+        t = _empty((N, D1, H1, W1, 8 * Ct), dtype=self.adt, device=dev)
+        pk = self.images.get(ct.weight, Kind.T8_FWD, dev)
+        need = nat.get_lib().u3d_convtr3d_fwd_t8_workspace_floats(N, D1, H1, W1, Cl, Ct) if self.act_bf16 else 0
+        if need > 0:  # small grid, many channels: the flat tile with a split channel reduction (csrc/u3d_bf16.hip)
+            kws = _empty(need, dtype=_F32, device=dev)
+            nat.call("u3d_convtr3d_fwd_t8_b16_ex", dev.index, _stream(dev), _p(cur), _p(pk), _p(t), N, D1, H1, W1, Cl, Ct, _p(kws), need,
+                     flops=self._up_flops3d(cur, Ct))
+        else:
+            nat.call("u3d_convtr3d_fwd_t8" + ("_b16" if self.act_bf16 else ""), dev.index, _stream(dev), _p(cur), _p(pk), _p(t), N, D1, H1,
+                     W1, Cl, Ct, flops=self._up_flops3d(cur, Ct))
+        return t
+
+    def _up_fwd_convtr2d(self, dev, ct, cur, entry="u3d_convtr2d_fwd", kind=Kind.CONVTR2D_FWD):
+        # four parity-class gather GEMMs (D1 = Dt = 1)
+        N, _, H1, W1, Cl = cur.shape
+        Ct = ct.out_channels
+        t = _empty((N, 1, 2 * H1 - 1, 2 * W1 - 1, Ct), dtype=_F32, device=dev)
+        nat.call(entry, dev.index, _stream(dev), _p(cur), _p(self.images.get(ct.weight, kind, dev)), _p(t), N, H1, W1, Cl, Ct,
+                 flops=self._up_flops2d(cur, Ct))
+        return t
+
+    def _up_fwd_convtr2d_bf16(self, dev, ct, cur):
+        # ... on the bf16 matrix pipe, one sub-pixel launch: the same argument list
+        return self._up_fwd_convtr2d(dev, ct, cur, "u3d_convtr2d_fwd_bf16", Kind.CONVTR2D_BF16_FWD)
+
+    def _up_fwd_convtr3d_subpixel(self, dev, ct, cur):
+        # 8 output parity classes accumulated from one staged input halo tile (scheme Deconv3s2)
+        N, D1, H1, W1, Cl = cur.shape
+        Ct = ct.out_channels
+        t = _empty((N, 2 * D1 - 1, 2 * H1 - 1, 2 * W1 - 1, Ct), dtype=_F32, device=dev)
+        nat.call("u3d_convtr3d_fwd_subpixel", dev.index, _stream(dev), _p(cur), _p(self.images.get(ct.weight, Kind.CONVTR_SUBPIXEL, dev)),
+                 _p(t), N, D1, H1, W1, Cl, Ct, flops=self._up_flops3d(cur, Ct))
+        return t
+
+    def _up_fwd_convtr3d(self, dev, ct, cur):
+        N, D1, H1, W1, Cl = cur.shape
+        Ct = ct.out_channels
+        t = _empty((N, 2 * D1 - 1, 2 * H1 - 1, 2 * W1 - 1, Ct), dtype=_F32, device=dev)
+        nat.call("u3d_convtr3d_fwd", dev.index, _stream(dev), _p(cur), _p(ct.weight.detach()), _p(t), N, D1, H1, W1, Cl, Ct,
+                 _p(self.images.get(ct.weight, Kind.CONVTR_FWD, dev)), flops=self._up_flops3d(cur, Ct))
+        return t
+
+    def _up_bwd_t8(self, cx, up, dt, mk):
+        """`dt` in space-to-depth form; dw through the shared fp32 scratch, then dx (ReLU blocks: masked by x_low > 0)"""
+        dev, xl = cx.dev, up.x_low
+        N, D1, H1, W1, Cl = xl.shape
+        Ct = up.weight.shape[1]
+        sfx = "_b16" if self.act_bf16 else ""
+        lib = nat.get_lib()
+        need = max(lib.u3d_convtr3d_wgrad_t8_workspace_floats(N, D1, H1, W1, Cl, Ct),
+                   lib.u3d_convtr3d_dgrad_t8_workspace_floats(N, D1, H1, W1, Cl, Ct))  # (both kernels: same stream, one after the other)
+        wsb = cx.ensure_ws(need)
+        nat.call("u3d_convtr3d_wgrad_t8" + sfx, dev.index, _stream(dev), _p(xl), _p(dt), _p(cx.gview(self._pindex[id(up.weight)])), N, D1,
+                 H1, W1, Cl, Ct, _p(wsb), wsb.numel(), flops=self._up_flops3d(xl, Ct))
+        dxl = _empty_like(xl)
+        nat.call("u3d_convtr3d_dgrad_t8" + sfx + "_ex", dev.index, _stream(dev), _p(dt), _p(self.images.get(up.weight, Kind.T8_DGRAD, dev)),
+                 _p(xl) if mk else None, _p(dxl), N, D1, H1, W1, Cl, Ct, _p(wsb), wsb.numel(), flops=self._up_flops3d(xl, Ct))
+        return dxl
+
+    def _up_bwd_convtr2d(self, cx, up, dt, mk, bf16=False):
+        """dw (double sums in the pool's scratch, written into the flat gradient), then dx masked by x_low > 0"""
+        dev, xl = cx.dev, up.x_low
+        N, _, H1, W1, Cl = xl.shape
+        Ct = up.weight.shape[1]
+        sfx = "_bf16" if bf16 else ""
+        if bf16:
+            scr = cx.ensure_ws(nat.get_lib().u3d_convtr2d_wgrad_bf16_workspace_floats(N, H1, W1, Cl, Ct))
+        else:
+            scr = cx.pool.take(up.weight.numel())
+        nat.call("u3d_convtr2d_wgrad" + sfx, dev.index, _stream(dev), _p(xl), _p(dt), _p(cx.gview(self._pindex[id(up.weight)])), N, H1, W1,
+                 Cl, Ct, 0, _p(scr), scr.numel(), flops=self._up_flops2d(xl, Ct))
+        dxl = _empty_like(xl)
+        kind = Kind.CONVTR2D_BF16_DGRAD if bf16 else Kind.CONVTR2D_DGRAD
+        nat.call("u3d_convtr2d_dgrad" + sfx, dev.index, _stream(dev), _p(dt), _p(self.images.get(up.weight, kind, dev)),
+                 _p(xl) if mk else None, _p(dxl), N, H1, W1, Cl, Ct, flops=self._up_flops2d(xl, Ct))
+        return dxl
+
+    def _up_bwd_convtr2d_bf16(self, cx, up, dt, mk):
+        """... with bf16 operands: dw through the shared fp32 scratch in a fixed order; the same argument lists"""
+        return self._up_bwd_convtr2d(cx, up, dt, mk, True)
+
+    def _up_bwd_convtr3d(self, cx, up, dt, mk):
+        """both gradients in one launch (dx masked by x_low > 0 under `mk`), dw from its double accumulator"""
+        dev, xl = cx.dev, up.x_low
+        N, D1, H1, W1, Cl = xl.shape
+        Ct = up.weight.shape[1]
+        acc = cx.pool.take(up.weight.numel())
+        dxl = _empty_like(xl)
+        nat.call("u3d_convtr3d_bwd", dev.index, _stream(dev), _p(dt), _p(xl), _p(up.weight.detach()), N, D1, H1, W1, Cl, Ct, mk, _p(dxl),
+                 _p(acc), _p(self.images.get(up.weight, Kind.CONVTR_DGRAD, dev)), flops=2 * self._up_flops3d(xl, Ct))
+        nat.call("u3d_cvt_f64_f32", dev.index, _stream(dev), _p(acc), _p(cx.gview(self._pindex[id(up.weight)])), up.weight.numel())
+        return dxl
 
     # ---- forward kernel families (csrc file; what selects it) -------------------------------------------------------------------
     _FWD_KERNELS = {

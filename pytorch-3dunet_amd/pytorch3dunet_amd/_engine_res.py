@@ -18,7 +18,6 @@ from ._native import U3DSrc
 
 from ._engine_base import *  # noqa: F401,F403  (explicit __all__: helpers, records, activation codes)
 from ._engine_unet import UNet3DEngine
-from ._engine_weights import Kind
 
 _CKPT_RERUN_LAST = os.environ.get("U3D_CKPT_RERUN_LAST", "0") == "1"  # A/B: recomputation re-runs a block's last convolution too (rounds 4-5)
 
@@ -48,7 +47,6 @@ class ResUNetEngine(UNet3DEngine):
         self.act, self.slope = (ACT_LEAKY, 0.1) if "l" in order else ((ACT_ELU, 0.0) if "e" in order else (ACT_RELU, 0.0))
         self.mask = 1 if self.act == ACT_RELU else 0
         self.lean_tape = self.checkpoint_encoders and os.environ.get("U3D_LEAN_TAPE", "1") != "0"
-        self.adt = _F32
         if model.activation_bf16:
             why = self._act_bf16_blocker(model, order)
             if why is None:
@@ -87,7 +85,8 @@ class ResUNetEngine(UNet3DEngine):
         return set()  # summation joining: every 3x3x3 conv reads one real tensor
 
     def _t8_weights(self):
-        return [ct.weight for (ct, _), concat in zip(self.dec, self.dec_concat) if isinstance(ct, torch.nn.ConvTranspose3d) and not concat]
+        # (`_up_family`'s "t8" row without the library's word on the channel counts: the cache packs those the library takes)
+        return [ct.weight for (ct, _), concat in zip(self.dec, self.dec_concat) if not self.is2d and not concat]
 
     def _build_layer_table(self, model):
         self.enc = [(e.pooling is not None, e.basic_module) for e in model.encoders]
@@ -210,24 +209,9 @@ class ResUNetEngine(UNet3DEngine):
         return m_
 
     def forward(self, x: torch.Tensor, save: bool):
-        m = self.model
         dev = x.device
-        if self.is2d:
-            assert x.dim() == 4, "the 2-D executor takes (N,C,H,W)"
-            x = x.unsqueeze(2)  # (N,C,1,H,W): NHWC is NDHWC with D = 1
-        N, Cin, D, H, W = x.shape
-        x = x.contiguous()
-        if Cin == 1:
-            x0 = x.view(N, D, H, W, 1)
-        else:
-            x0 = _empty((N, D, H, W, Cin), dtype=_F32, device=dev)
-            nat.call("u3d_ncdhw_to_ndhwc", dev.index, _stream(dev), _p(x), _p(x0), N, Cin, D * H * W)
-        tape = Tape() if save else None
-        if tape is not None:
-            tape.x0 = x0
-            tape.dims = (N, Cin, D, H, W)
-            tape.blocks = []
-            tape.ups = []
+        x0, dims, tape = self._enter(x, save)
+        N = dims[0]
         self.images.repack(dev, save)
         widths = [bm.conv2.conv.in_channels for _, bm in self.enc]
         pool = _StatPool(dev, 16 * N * sum(widths) * 2 + 64)
@@ -236,16 +220,7 @@ class ResUNetEngine(UNet3DEngine):
         cur = x0
         for i, (has_pool, bm) in enumerate(self.enc):
             if has_pool:
-                Np, Dp, Hp, Wp, Cp = cur.shape
-                pooled = _empty((Np, Dp if self.is2d else Dp // 2, Hp // 2, Wp // 2, Cp), dtype=self.adt, device=dev)
-                argmax = _empty(pooled.shape, dtype=torch.uint8, device=dev)
-                if self.is2d:  # (MaxPool2d: D stays 1)
-                    nat.call("u3d_maxpool2d_fwd", dev.index, _stream(dev), _p(cur), Np, Hp, Wp, Cp, _p(pooled), _p(argmax), None)
-                elif self.act_bf16:
-                    nat.call("u3d_maxpool2_fwd_b16", dev.index, _stream(dev), _p(cur), Np, Dp, Hp, Wp, Cp, _p(pooled), _p(argmax))
-                else:
-                    nat.call("u3d_maxpool2_fwd", dev.index, _stream(dev), _p(cur), Np, Dp, Hp, Wp, Cp, _p(pooled), _p(argmax),
-                             None)
+                pooled, argmax = self._maxpool_fwd(cur, dev)
                 if tape is not None:
                     tape.pools.append((pooled, argmax, cur))
                 cur = pooled
@@ -265,74 +240,24 @@ class ResUNetEngine(UNet3DEngine):
             Dt, Ht, Wt = 2 * D1 - 1, 2 * H1 - 1, 2 * W1 - 1
             concat = self.dec_concat[j]
             Ct = ct.out_channels  # (== Cs for summation joining)
-            t8 = self._convtr_t8(Cl, Cs) and not concat
+            family = self._up_family(Cl, Ct, concat)
+            fwd, _, s2d = self._UP_KERNELS[family]
             (mz, lz), (my, ly), (mx, lx) = _maps(dev, Dt, Ds), _maps(dev, Ht, Hs), _maps(dev, Wt, Ws)
             joined = _empty((Nl, Ds, Hs, Ws, Cs + Ct), dtype=_F32, device=dev) if concat else _empty_like(sk)
             j_st = None if concat else pool.table(Nl, Cs)
-            if t8:
-                # bf16 mode: 2x2x2 convolution on the low-res grid into the space-to-depth layout T8[i][parity*Cs + c] = t[2i + parity];
-                # the resize + join reads that layout directly
-                sfx = "_b16" if self.act_bf16 else ""
-                t = _empty((Nl, D1, H1, W1, 8 * Cs), dtype=self.adt, device=dev)
-                need = nat.get_lib().u3d_convtr3d_fwd_t8_workspace_floats(Nl, D1, H1, W1, Cl, Cs) if self.act_bf16 else 0
-                if need > 0:  # small grid, many channels: the flat tile with a split channel reduction (csrc/u3d_bf16.hip)
-                    kws = _empty(need, dtype=_F32, device=dev)
-                    nat.call("u3d_convtr3d_fwd_t8_b16_ex", dev.index, _stream(dev), _p(cur), _p(self.images.get(ct.weight, Kind.T8_FWD, dev)),
-                             _p(t), Nl, D1, H1, W1, Cl, Cs, _p(kws), need, flops=2.0 * 27 * Cl * Cs * Nl * D1 * H1 * W1)
-                else:
-                    nat.call("u3d_convtr3d_fwd_t8" + sfx, dev.index, _stream(dev), _p(cur), _p(self.images.get(ct.weight, Kind.T8_FWD, dev)),
-                             _p(t), Nl, D1, H1, W1, Cl, Cs, flops=2.0 * 27 * Cl * Cs * Nl * D1 * H1 * W1)
-                nat.call("u3d_nearest_add_fwd_t8" + sfx, dev.index, _stream(dev), _p(sk), _p(t), _p(mz), _p(my), _p(mx), Nl, Ds, Hs,
-                         Ws, Dt, Ht, Wt, Cs, _p(joined), _p(j_st.t))
-                del t
-                if tape is not None:
-                    tape.ups.append(UpRec(cur, ct.weight, (lz, ly, lx), (Dt, Ht, Wt), True))
-                cur = self._block_fwd(bm, f"dec{j}", joined, j_st, pool, tape, dev)
-                continue
-            t = _empty((Nl, Dt, Ht, Wt, Ct), dtype=_F32, device=dev)
-            if self.is2d and self._bf16_convtr2d(Cl, Ct):  # ... on the bf16 matrix pipe: one sub-pixel launch
-                nat.call("u3d_convtr2d_fwd_bf16", dev.index, _stream(dev), _p(cur), _p(self.images.get(ct.weight, Kind.CONVTR2D_BF16_FWD, dev)),
-                         _p(t), Nl, H1, W1, Cl, Ct, flops=4.5 * Cl * Ct * Nl * Ht * Wt)
-            elif self.is2d:  # ConvTranspose2d: four parity-class gather GEMMs (D1 = Dt = 1)
-                nat.call("u3d_convtr2d_fwd", dev.index, _stream(dev), _p(cur), _p(self.images.get(ct.weight, Kind.CONVTR2D_FWD, dev)), _p(t), Nl,
-                         H1, W1, Cl, Ct, flops=4.5 * Cl * Ct * Nl * Ht * Wt)
-            elif self.subpixel and Cl % 4 == 0 and Ct % 4 == 0:
-                # 8 output parity classes accumulated from one staged input halo tile (csrc/u3d_subpix.hip, scheme Deconv3s2)
-                nat.call("u3d_convtr3d_fwd_subpixel", dev.index, _stream(dev), _p(cur), _p(self.images.get(ct.weight, Kind.CONVTR_SUBPIXEL, dev)),
-                         _p(t), Nl, D1, H1, W1, Cl, Ct, flops=2.0 * 27 * Cl * Ct * Nl * D1 * H1 * W1)
-            else:
-                nat.call("u3d_convtr3d_fwd", dev.index, _stream(dev), _p(cur), _p(ct.weight.detach()), _p(t), Nl, D1, H1, W1, Cl,
-                         Ct, _p(self.images.get(ct.weight, Kind.CONVTR_FWD, dev)), flops=2.0 * 27 * Cl * Ct * Nl * D1 * H1 * W1)
+            t = getattr(self, fwd)(dev, ct, cur)
             if concat:
                 nat.call("u3d_nearest_cat_fwd", dev.index, _stream(dev), _p(sk), _p(t), _p(mz), _p(my), _p(mx), Nl, Ds, Hs, Ws, Dt, Ht,
                          Wt, Cs, Ct, _p(joined))
-            else:
-                nat.call("u3d_nearest_add_fwd", dev.index, _stream(dev), _p(sk), _p(t), _p(mz), _p(my), _p(mx), Nl, Ds, Hs, Ws, Dt, Ht,
-                         Wt, Cs, _p(joined), _p(j_st.t))
+            else:  # (a space-to-depth `t`: the resize + join reads that layout directly)
+                nat.call("u3d_nearest_add_fwd" + (("_t8_b16" if self.act_bf16 else "_t8") if s2d else ""), dev.index, _stream(dev), _p(sk),
+                         _p(t), _p(mz), _p(my), _p(mx), Nl, Ds, Hs, Ws, Dt, Ht, Wt, Cs, _p(joined), _p(j_st.t))
             del t
             if tape is not None:
-                tape.ups.append(UpRec(cur, ct.weight, (lz, ly, lx), (Dt, Ht, Wt), False, (Cs, Ct) if concat else None))
+                tape.ups.append(UpRec(cur, ct.weight, (lz, ly, lx), (Dt, Ht, Wt), family, (Cs, Ct) if concat else None))
             cur = self._block_fwd(bm, f"dec{j}", joined, j_st, pool, tape, dev)
 
-        fc = m.final_conv
-        Co, Cf = fc.out_channels, fc.in_channels
-        V = D * H * W
-        logits = _empty((N, Co, D, H, W), dtype=_F32, device=dev)
-        act = 0
-        probs = None
-        if m.final_activation is not None:
-            act = 1 if isinstance(m.final_activation, torch.nn.Sigmoid) else 2
-            probs = _empty_like(logits)
-        nat.call("u3d_conv1x1_head_fwd" + ("_b16" if self.act_bf16 else ""), dev.index, _stream(dev), _p(cur), _p(fc.weight.detach()),
-                 _p(fc.bias.detach()), N, V, Cf, Co, act, _p(logits), _p(probs))
-        if tape is not None:
-            tape.head_x = cur
-            if self.debug is not None:
-                self.debug["tape"] = tape
-        if self.is2d:  # (N,Cout,H,W), the reference's 2-D layout
-            logits = logits.view(N, Co, H, W)
-            probs = probs.view(N, Co, H, W) if probs is not None else None
-        return logits, probs, tape
+        return (*self._head_fwd(cur, dims, tape), tape)
 
     # -- backward -----------------------------------------------------------------------------------
     def _block_bwd(self, cx, rec: ResRec, m_):
@@ -383,13 +308,12 @@ class ResUNetEngine(UNet3DEngine):
         return dxin
 
     def backward(self, tape: Tape, dlogits: torch.Tensor, need_input_grad: bool):
-        m = self.model
         dev = dlogits.device
-        N, Cin, D, H, W = tape.dims
+        N, _, D, H, W = tape.dims
         V = D * H * W
         dlogits = dlogits.contiguous()
         flat = _empty(self.n_params, dtype=_F32, device=dev)
-        fc = m.final_conv
+        fc = self.model.final_conv
         Co, Cf = fc.out_channels, fc.in_channels
         tot = Co * Cf + Co + sum(N * r.src.C * 2 for r in tape.convs)
         for b in tape.blocks:
@@ -457,60 +381,17 @@ class ResUNetEngine(UNet3DEngine):
                 assert rec.conv1 is None
                 skip_grad[n_levels - 2 - j] = dj   # summation joining: the skip receives dj as is
             rec = None  # (lean tape: the block's activations go back to the allocator before the transposed convolution's buffers)
-            xl = up.x_low
-            Nl, D1, H1, W1, Cl = xl.shape
-            _, Ds, Hs, Ws, Cs = dj.shape
+            Nl, D1, H1, W1, _ = up.x_low.shape
+            _, Ds, Hs, Ws, Ct = dj.shape
             Dt, Ht, Wt = up.tdims
             lz, ly, lx = up.los
-            if up.t8:
-                sfx = "_b16" if self.act_bf16 else ""
-                dt8 = _empty((Nl, D1, H1, W1, 8 * Cs), dtype=self.adt, device=dev)
-                nat.call("u3d_nearest_sum_bwd_t8" + sfx, dev.index, _stream(dev), _p(dj), _p(lz), _p(ly), _p(lx), Nl, Ds, Hs, Ws, Dt, Ht,
-                         Wt, Cs, _p(dt8))
-                lib = nat.get_lib()
-                need = max(lib.u3d_convtr3d_wgrad_t8_workspace_floats(Nl, D1, H1, W1, Cl, Cs),
-                           lib.u3d_convtr3d_dgrad_t8_workspace_floats(Nl, D1, H1, W1, Cl, Cs))  # (both kernels: same stream, one after the other)
-                wsb = cx.ensure_ws(need)
-                nat.call("u3d_convtr3d_wgrad_t8" + sfx, dev.index, _stream(dev), _p(xl), _p(dt8),
-                         _p(gview(self._pindex[id(up.weight)])), Nl, D1, H1, W1, Cl, Cs, _p(wsb), wsb.numel(),
-                         flops=2.0 * 27 * Cl * Cs * Nl * D1 * H1 * W1)
-                dxl = _empty_like(xl)
-                nat.call("u3d_convtr3d_dgrad_t8" + sfx + "_ex", dev.index, _stream(dev), _p(dt8), _p(self.images.get(up.weight, Kind.T8_DGRAD, dev)),
-                         _p(xl) if mk else None, _p(dxl), Nl, D1, H1, W1, Cl, Cs, _p(wsb), wsb.numel(),
-                         flops=2.0 * 27 * Cl * Cs * Nl * D1 * H1 * W1)
-                del dt8
-                dz = dxl  # ReLU blocks: masked by (x_low > 0)
-                continue
-            dt = _empty((Nl, Dt, Ht, Wt, Cs), dtype=_F32, device=dev)
-            nat.call("u3d_nearest_sum_bwd", dev.index, _stream(dev), _p(dj), _p(lz), _p(ly), _p(lx), Nl, Ds, Hs, Ws, Dt, Ht, Wt,
-                     Cs, _p(dt))
-            if self.is2d and self._bf16_convtr2d(Cl, Cs):  # bf16 operands: dw through the fp32 scratch in a fixed order, then dx
-                wsb = cx.ensure_ws(nat.get_lib().u3d_convtr2d_wgrad_bf16_workspace_floats(Nl, H1, W1, Cl, Cs))
-                nat.call("u3d_convtr2d_wgrad_bf16", dev.index, _stream(dev), _p(xl), _p(dt), _p(gview(self._pindex[id(up.weight)])), Nl, H1,
-                         W1, Cl, Cs, 0, _p(wsb), wsb.numel(), flops=4.5 * Cl * Cs * Nl * Ht * Wt)
-                dxl = _empty_like(xl)
-                nat.call("u3d_convtr2d_dgrad_bf16", dev.index, _stream(dev), _p(dt), _p(self.images.get(up.weight, Kind.CONVTR2D_BF16_DGRAD, dev)),
-                         _p(xl) if mk else None, _p(dxl), Nl, H1, W1, Cl, Cs, flops=4.5 * Cl * Cs * Nl * Ht * Wt)
-                del dt
-                dz = dxl
-                continue
-            acc = pool.take(up.weight.numel())
-            if self.is2d:  # ConvTranspose2d: dw (double sums in `acc`, written into the flat gradient), then dx masked by x_low > 0
-                nat.call("u3d_convtr2d_wgrad", dev.index, _stream(dev), _p(xl), _p(dt), _p(gview(self._pindex[id(up.weight)])), Nl, H1,
-                         W1, Cl, Cs, 0, _p(acc), acc.numel(), flops=4.5 * Cl * Cs * Nl * Ht * Wt)
-                dxl = _empty_like(xl)
-                nat.call("u3d_convtr2d_dgrad", dev.index, _stream(dev), _p(dt), _p(self.images.get(up.weight, Kind.CONVTR2D_DGRAD, dev)),
-                         _p(xl) if mk else None, _p(dxl), Nl, H1, W1, Cl, Cs, flops=4.5 * Cl * Cs * Nl * Ht * Wt)
-                del dt
-                dz = dxl
-                continue
-            dxl = _empty_like(xl)
-            nat.call("u3d_convtr3d_bwd", dev.index, _stream(dev), _p(dt), _p(xl), _p(up.weight.detach()), Nl, D1, H1, W1, Cl, Cs,
-                     mk, _p(dxl), _p(acc), _p(self.images.get(up.weight, Kind.CONVTR_DGRAD, dev)), flops=4.0 * 27 * Cl * Cs * Nl * D1 * H1 * W1)
-            nat.call("u3d_cvt_f64_f32", dev.index, _stream(dev), _p(acc), _p(gview(self._pindex[id(up.weight)])),
-                     up.weight.numel())
+            _, bwd, s2d = self._UP_KERNELS[up.family]
+            # (space-to-depth: the resize's adjoint writes the layout the family's gradients read)
+            dt = _empty((Nl, D1, H1, W1, 8 * Ct) if s2d else (Nl, Dt, Ht, Wt, Ct), dtype=self.adt if s2d else _F32, device=dev)
+            nat.call("u3d_nearest_sum_bwd" + (("_t8_b16" if self.act_bf16 else "_t8") if s2d else ""), dev.index, _stream(dev), _p(dj),
+                     _p(lz), _p(ly), _p(lx), Nl, Ds, Hs, Ws, Dt, Ht, Wt, Ct, _p(dt))
+            dz = getattr(self, bwd)(cx, up, dt, mk)  # ReLU blocks: masked by (x_low > 0), x_low being the output of the block below
             del dt
-            dz = dxl  # ReLU blocks: masked by (x_low > 0), x_low being the output of the block below
 
         rec = up = None
         if self.grad_sync is not None:
@@ -569,15 +450,4 @@ class ResUNetEngine(UNet3DEngine):
         if self.grad_sync is not None:
             self.grad_sync.finish()
 
-        dx = None
-        if dx0 is not None:
-            if dx0.dtype != _F32:
-                dx0 = dx0.to(_F32)  # (input gradients are rare; the network input and its gradient are fp32 tensors)
-            if Cin == 1:
-                dx = dx0.reshape(N, 1, D, H, W)
-            else:
-                dx = _empty((N, Cin, D, H, W), dtype=_F32, device=dev)
-                nat.call("u3d_ndhwc_to_ncdhw", dev.index, _stream(dev), _p(dx0), _p(dx), N, Cin, V)
-            if self.is2d:
-                dx = dx.view(N, Cin, H, W)
-        return flat, dx
+        return flat, self._exit_dx(dx0, tape.dims)

@@ -18,7 +18,7 @@ from ._native import U3DSrc
 
 from ._engine_base import *  # noqa: F401,F403  (explicit __all__: helpers, records, activation codes)
 from ._engine_conv import ConvLayers
-from ._engine_weights import Kind, WeightImages
+from ._engine_weights import WeightImages
 
 
 
@@ -69,6 +69,7 @@ class UNet3DEngine(ConvLayers):
         # bf16 ACTIVATION STORAGE (`activation_dtype: bf16`; ResUNetEngine decides whether the model qualifies): every NDHWC
         # activation / gradient tensor between kernels is bf16, through the `_b16` entry points of include/u3d.h
         self.act_bf16 = False
+        self.adt = _F32  # ... and their dtype
         # WHICH decoder first convs take the sub-pixel path depends on the input size and is per-call state (`sub` argument /
         # ConvRec.sub, handed to `images` with every lookup), never stored on the engine: forwards at different sizes, other threads
         # and nn.DataParallel replicas must not see each other's choice
@@ -185,11 +186,9 @@ class UNet3DEngine(ConvLayers):
         self.dec_interp = [getattr(dec.upsampling, "mode", None) if getattr(dec.upsampling, "mode", None) in ("trilinear", "area")
                            else None for dec in model.decoders]
 
-    # -- forward ------------------------------------------------------------------------------------
-    def forward(self, x: torch.Tensor, save: bool):
-        """x: (N,C,D,H,W) fp32 on a gfx950 device.  Returns (logits, probs_or_None, tape_or_None), both
-        outputs in the reference's NCDHW layout."""
-        m = self.model
+    # -- the frame around the level loops, shared with ResUNetEngine ----------------------------------
+    def _enter(self, x: torch.Tensor, save: bool):
+        """(x0, dims, tape_or_None): the network input as NDHWC, its (N, Cin, D, H, W), the tape when `save`"""
         dev = x.device
         if self.is2d:
             assert x.dim() == 4, "the 2-D executor takes (N,C,H,W)"
@@ -205,6 +204,65 @@ class UNet3DEngine(ConvLayers):
         if tape is not None:
             tape.x0 = x0
             tape.dims = (N, Cin, D, H, W)
+        return x0, (N, Cin, D, H, W), tape
+
+    def _maxpool_fwd(self, cur, dev):
+        """(pooled, argmax) of MaxPool3d(2) (2-D: MaxPool2d, D stays 1)"""
+        Np, Dp, Hp, Wp, Cp = cur.shape
+        pooled = _empty((Np, Dp if self.is2d else Dp // 2, Hp // 2, Wp // 2, Cp), dtype=self.adt, device=dev)
+        argmax = _empty(pooled.shape, dtype=torch.uint8, device=dev)
+        if self.is2d:
+            nat.call("u3d_maxpool2d_fwd", dev.index, _stream(dev), _p(cur), Np, Hp, Wp, Cp, _p(pooled), _p(argmax), None)
+        elif self.act_bf16:
+            nat.call("u3d_maxpool2_fwd_b16", dev.index, _stream(dev), _p(cur), Np, Dp, Hp, Wp, Cp, _p(pooled), _p(argmax))
+        else:
+            nat.call("u3d_maxpool2_fwd", dev.index, _stream(dev), _p(cur), Np, Dp, Hp, Wp, Cp, _p(pooled), _p(argmax), None)
+        return pooled, argmax
+
+    def _head_fwd(self, cur, dims, tape):
+        """(logits, probs_or_None): 1x1x1 conv + bias + activation (model.py:141-147), outputs in the reference's layout"""
+        dev = cur.device
+        N, _, D, H, W = dims
+        fc = self.model.final_conv
+        Co = fc.out_channels
+        logits = _empty((N, Co, D, H, W), dtype=_F32, device=dev)
+        act = 0
+        probs = None
+        if self.model.final_activation is not None:
+            act = 1 if isinstance(self.model.final_activation, torch.nn.Sigmoid) else 2
+            probs = _empty_like(logits)
+        nat.call("u3d_conv1x1_head_fwd" + ("_b16" if self.act_bf16 else ""), dev.index, _stream(dev), _p(cur), _p(fc.weight.detach()),
+                 _p(fc.bias.detach()), N, D * H * W, fc.in_channels, Co, act, _p(logits), _p(probs))
+        if tape is not None:
+            tape.head_x = cur
+            if self.debug is not None:
+                self.debug["tape"] = tape
+        if self.is2d:  # (N,Cout,H,W), the reference's 2-D layout
+            logits = logits.view(N, Co, H, W)
+            probs = probs.view(N, Co, H, W) if probs is not None else None
+        return logits, probs
+
+    def _exit_dx(self, dx0, dims):
+        """the input gradient in the reference's layout from its NDHWC form (None: not asked for)"""
+        if dx0 is None:
+            return None
+        N, Cin, D, H, W = dims
+        if dx0.dtype != _F32:
+            dx0 = dx0.to(_F32)  # (input gradients are rare; the network input and its gradient are fp32 tensors)
+        if Cin == 1:
+            dx = dx0.reshape(N, 1, D, H, W)
+        else:
+            dx = _empty((N, Cin, D, H, W), dtype=_F32, device=dx0.device)
+            nat.call("u3d_ndhwc_to_ncdhw", dx0.device.index, _stream(dx0.device), _p(dx0), _p(dx), N, Cin, D * H * W)
+        return dx.view(N, Cin, H, W) if self.is2d else dx
+
+    # -- forward ------------------------------------------------------------------------------------
+    def forward(self, x: torch.Tensor, save: bool):
+        """x: (N,C,D,H,W) fp32 on a gfx950 device.  Returns (logits, probs_or_None, tape_or_None), both
+        outputs in the reference's NCDHW layout."""
+        dev = x.device
+        x0, dims, tape = self._enter(x, save)
+        N, _, D, H, W = dims
         sub = self._subpixel_layers((D, H, W))
         self.images.repack(dev, save, sub, sub.plus)
         # stat doubles: every conv output + every GN input computed standalone; generous upper bound
@@ -232,18 +290,11 @@ class UNet3DEngine(ConvLayers):
         cur, cur_st = x0, None
         for i, (has_pool, c1, c2) in enumerate(self.enc):
             if has_pool:
-                Np, Dp, Hp, Wp, Cp = cur.shape
-                Dq = Dp if self.is2d else Dp // 2  # (2-D: MaxPool2d, D stays 1)
-                pooled = _empty((Np, Dq, Hp // 2, Wp // 2, Cp), dtype=_F32, device=dev)
-                argmax = _empty(pooled.shape, dtype=torch.uint8, device=dev)
-                pst = None if self.post_norm else pool.table(Np, Cp, self.stat_reps)
-                if self.is2d:
-                    nat.call("u3d_maxpool2d_fwd", dev.index, _stream(dev), _p(cur), Np, Hp, Wp, Cp, _p(pooled), _p(argmax), None)
-                else:
-                    nat.call("u3d_maxpool2_fwd", dev.index, _stream(dev), _p(cur), Np, Dp, Hp, Wp, Cp, _p(pooled), _p(argmax), None)
+                pst = None if self.post_norm else pool.table(cur.shape[0], cur.shape[-1], self.stat_reps)
+                pooled, argmax = self._maxpool_fwd(cur, dev)
                 if pst is not None:  # (the pooled tensor's statistics: a pass of its own — fused into the pool it was slower — into replica rows)
                     s_p = VSrc(pooled).struct()
-                    nat.call("u3d_chan_stats_reps", dev.index, _stream(dev), ctypes.byref(s_p), Np, Dq, Hp // 2, Wp // 2, *_tab(pst))
+                    nat.call("u3d_chan_stats_reps", dev.index, _stream(dev), ctypes.byref(s_p), *pooled.shape[:4], *_tab(pst))
                 if tape is not None:
                     tape.pools.append((pooled, argmax, cur))
                 cur, cur_st = pooled, pst
@@ -261,17 +312,10 @@ class UNet3DEngine(ConvLayers):
             if ct is not None:
                 # upsample='deconv': ConvTranspose3d(k3, s2, p1) -> 2n-1 voxels (buildingblocks.py:617-664); the nearest resize
                 # to the skip's size (:650-651) and the concat are virtual, like the interpolation path
-                Nl, D1, H1, W1, Cl = cur.shape
-                Cs = ct.out_channels
-                t = _empty((Nl, 2 * D1 - 1, 2 * H1 - 1, 2 * W1 - 1, Cs), dtype=_F32, device=dev)
-                if self.subpixel and Cl % 4 == 0 and Cs % 4 == 0:
-                    nat.call("u3d_convtr3d_fwd_subpixel", dev.index, _stream(dev), _p(cur), _p(self.images.get(ct.weight, Kind.CONVTR_SUBPIXEL, dev)),
-                             _p(t), Nl, D1, H1, W1, Cl, Cs, flops=2.0 * 27 * Cl * Cs * Nl * D1 * H1 * W1)
-                else:
-                    nat.call("u3d_convtr3d_fwd", dev.index, _stream(dev), _p(cur), _p(ct.weight.detach()), _p(t), Nl, D1, H1, W1, Cl,
-                             Cs, _p(self.images.get(ct.weight, Kind.CONVTR_FWD, dev)), flops=2.0 * 27 * Cl * Cs * Nl * D1 * H1 * W1)
+                family = self._up_family(cur.shape[-1], ct.out_channels, True)
+                t = getattr(self, self._UP_KERNELS[family][0])(dev, ct, cur)
                 if tape is not None:
-                    tape.ups.append(UpRec(cur, ct.weight, None, tuple(t.shape[1:4])))
+                    tape.ups.append(UpRec(cur, ct.weight, None, tuple(t.shape[1:4]), family))
                 cur, cur_st = t, None
             elif self.dec_interp[j] is not None:
                 # F.interpolate(mode='trilinear' | 'area') to the skip's size: a real tensor (2-tap separable gather), joined by
@@ -283,7 +327,7 @@ class UNet3DEngine(ConvLayers):
                 nat.call("u3d_resample2_fwd", dev.index, _stream(dev), _p(cur), _p(tabs[0][0]), _p(tabs[1][0]), _p(tabs[2][0]),
                          _p(tabs[0][1]), _p(tabs[1][1]), _p(tabs[2][1]), Nl, D1, H1, W1, Ds, Hs, Ws, Cl, _p(up))
                 if tape is not None:
-                    tape.ups.append(UpRec(cur, None, tabs, (Ds, Hs, Ws)))
+                    tape.ups.append(UpRec(cur, None, tabs, (Ds, Hs, Ws), self.dec_interp[j]))
                 cur, cur_st = up, None
             src = VSrc(sk, cur)  # skip channels first (buildingblocks.py:491)
             st_in = stats_of(src, sk_st, cur_st, pool, dev)
@@ -307,43 +351,18 @@ class UNet3DEngine(ConvLayers):
             y2, s2 = self._single_conv_fwd(c2, f"dec{j}.c2", src2, stats_of(src2, s1, None, pool, dev), pool, tape)
             cur, cur_st = y2, s2
 
-        # head: 1x1x1 conv + bias + activation (model.py:141-147), NCDHW outputs
-        fc = m.final_conv
-        Co, Cf = fc.out_channels, fc.in_channels
-        V = D * H * W
-        logits = _empty((N, Co, D, H, W), dtype=_F32, device=dev)
-        act = 0
-        probs = None
-        if m.final_activation is not None:
-            act = 1 if isinstance(m.final_activation, torch.nn.Sigmoid) else 2
-            probs = _empty_like(logits)
-        nat.call("u3d_conv1x1_head_fwd", dev.index, _stream(dev), _p(cur), _p(fc.weight.detach()), _p(fc.bias.detach()), N, V,
-                 Cf, Co, act, _p(logits), _p(probs))
-        if tape is not None:
-            tape.head_x = cur
-            if self.debug is not None:
-                self.debug["tape"] = tape
-        if self.is2d:  # (N,Cout,H,W), the reference's 2-D layout
-            logits = logits.view(N, Co, H, W)
-            probs = probs.view(N, Co, H, W) if probs is not None else None
-        return logits, probs, tape
+        return (*self._head_fwd(cur, dims, tape), tape)
 
     # -- backward -----------------------------------------------------------------------------------
     def backward(self, tape: Tape, dlogits: torch.Tensor, need_input_grad: bool):
         """Returns (flat_grad, dx_or_None).  flat_grad holds every parameter gradient in module order."""
-        m = self.model
         dev = dlogits.device
-        N, Cin, D, H, W = tape.dims
+        N, _, D, H, W = tape.dims
         V = D * H * W
         dlogits = dlogits.contiguous()
         flat = _empty(self.n_params, dtype=_F32, device=dev)
-
-        def gview(idx):
-            p = self.params[idx]
-            return flat[self.poffs[idx] : self.poffs[idx] + p.numel()]
-
         # zeroed double scratch: head (dw,db) + 2 doubles per (n, channel) per conv layer
-        fc = m.final_conv
+        fc = self.model.final_conv
         Co, Cf = fc.out_channels, fc.in_channels
         tot = self.stat_reps * (Co * Cf + Co) + sum(self.stat_reps * N * r.src.C * 2 for r in tape.convs)
         pool = tape.bwd_pool  # zeroed by the forward's fill launch; a second backward over the tape takes a fresh one
@@ -354,6 +373,7 @@ class UNet3DEngine(ConvLayers):
                 or not pool.claim()):
             pool = _StatPool(dev, tot)
         ws = self._wgrad_workspace(tape, dev)
+        cx = _BwdCtx(dev, pool, ws, flat, self)
 
         # ---- head backward: dz of the last decoder conv (ReLU mask fused)
         hreps = self.stat_reps  # (replica rows of the head's f64 accumulator: 2048 blocks on the same Co * (Cf + 1) doubles)
@@ -364,20 +384,12 @@ class UNet3DEngine(ConvLayers):
         self._unact(dev, dz, tape.head_x)
         iw, ib = self._pindex[id(fc.weight)], self._pindex[id(fc.bias)]
         assert self.poffs[ib] == self.poffs[iw] + Co * Cf
-        nat.call("u3d_cvt_f64_f32_sum", dev.index, _stream(dev), _p(hacc), _p(gview(iw)), Co * Cf + Co, hreps)
+        nat.call("u3d_cvt_f64_f32_sum", dev.index, _stream(dev), _p(hacc), _p(cx.gview(iw)), Co * Cf + Co, hreps)
 
         n_levels = len(self.enc)
         n_dec = len(self.dec)
         mk = self.mask  # 1: the producers' ReLU masks are applied inside the consumer kernels; else _unact afterwards
         skip_grad = {}  # encoder level -> gradient arriving through the skip connection (pre-mask)
-
-        cx = _BwdCtx(dev, pool, ws, flat, self)
-
-        def conv_bwd(rec: ConvRec, dz_, need_dg=True):
-            return self._conv_bwd(cx, rec, dz_, need_dg)
-
-        def plain_apply(dg, coef, x, relu_mask):
-            return self._plain_apply(cx, dg, coef, x, relu_mask)
 
         recs = tape.convs  # order: enc0.c1, enc0.c2, enc1.c1, ..., dec0.c1, dec0.c2, ...
         enc_recs = [(recs[2 * i], recs[2 * i + 1]) for i in range(n_levels)]
@@ -386,11 +398,11 @@ class UNet3DEngine(ConvLayers):
         # ---- decoders, last to first
         for j in range(n_dec - 1, -1, -1):
             r1, r2 = dec_recs[j]
-            dg2, coef2, _ = conv_bwd(r2, dz)
-            dz1 = plain_apply(dg2, coef2, r2.src.t0, mk)  # r2.src.t0 is r1.y (post-activation)
+            dg2, coef2, _ = self._conv_bwd(cx, r2, dz)
+            dz1 = self._plain_apply(cx, dg2, coef2, r2.src.t0, mk)  # r2.src.t0 is r1.y (post-activation)
             self._unact(dev, dz1, r2.src.t0)
             del dg2
-            dg1, coef1, coef_hi = conv_bwd(r1, dz1)
+            dg1, coef1, coef_hi = self._conv_bwd(cx, r1, dz1)
             src = tape.cats.get(j, r1.src)  # (bf16 mode: r1 ran on the materialised concat; its two halves are what the gradient splits into)
             C0, C1, Ct = src.C0, src.C1, src.C
             # skip half -> gradient of the encoder feature: its GroupNorm backward (p*dg + q*e + r on the first C0 channels)
@@ -422,17 +434,8 @@ class UNet3DEngine(ConvLayers):
                 # dzl is the gradient of the transposed convolution's (linear) output: its two gradients, with the non-linearity
                 # of the tensor it upsampled
                 up = tape.ups[j]
-                xl = up.x_low
-                Nl, D1, H1, W1, Cl = xl.shape
-                Cs = up.weight.shape[1]
-                acc = pool.take(up.weight.numel())
-                dxl = _empty_like(xl)
-                nat.call("u3d_convtr3d_bwd", dev.index, _stream(dev), _p(dzl), _p(xl), _p(up.weight.detach()), Nl, D1, H1, W1, Cl, Cs,
-                         mk, _p(dxl), _p(acc), _p(self.images.get(up.weight, Kind.CONVTR_DGRAD, dev)), flops=4.0 * 27 * Cl * Cs * Nl * D1 * H1 * W1)
-                nat.call("u3d_cvt_f64_f32", dev.index, _stream(dev), _p(acc), _p(gview(self._pindex[id(up.weight)])),
-                         up.weight.numel())
-                self._unact(dev, dxl, xl)
-                dzl = dxl
+                dzl = getattr(self, self._UP_KERNELS[up.family][1])(cx, up, dzl, mk)
+                self._unact(dev, dzl, up.x_low)
             elif self.dec_interp[j] is not None:
                 # dzl is the gradient of the interpolated (linear) tensor: the adjoint of the gather, then the non-linearity of
                 # the tensor that was upsampled
@@ -461,11 +464,11 @@ class UNet3DEngine(ConvLayers):
         pending_hi = self.n_enc_params  # upper end of the encoder gradients not yet handed to the exchange
         for i in range(n_levels - 1, -1, -1):
             r1, r2 = enc_recs[i]
-            dg2, coef2, _ = conv_bwd(r2, dz)
-            dz1 = plain_apply(dg2, coef2, r2.src.t0, mk)
+            dg2, coef2, _ = self._conv_bwd(cx, r2, dz)
+            dz1 = self._plain_apply(cx, dg2, coef2, r2.src.t0, mk)
             self._unact(dev, dz1, r2.src.t0)
             del dg2
-            dg1, coef1, _ = conv_bwd(r1, dz1, need_dg=(i > 0 or need_input_grad))
+            dg1, coef1, _ = self._conv_bwd(cx, r1, dz1, need_dg=(i > 0 or need_input_grad))
             if self.grad_sync is not None:
                 pending_hi = self._sync_encoder_level(cx, flat, i, pending_hi)  # this level's parameter gradients are final
             if i > 0:
@@ -487,20 +490,11 @@ class UNet3DEngine(ConvLayers):
                 self._unact(dev, out, e_in)
                 dz = out
             elif need_input_grad:
-                dx0 = plain_apply(dg1, coef1, tape.x0, 0)
+                dx0 = self._plain_apply(cx, dg1, coef1, tape.x0, 0)
             del dg1
 
         cx.join()
         if self.grad_sync is not None:
             self.grad_sync.finish()
 
-        dx = None
-        if dx0 is not None:
-            if Cin == 1:
-                dx = dx0.view(N, 1, D, H, W)
-            else:
-                dx = _empty((N, Cin, D, H, W), dtype=_F32, device=dev)
-                nat.call("u3d_ndhwc_to_ncdhw", dev.index, _stream(dev), _p(dx0), _p(dx), N, Cin, V)
-            if self.is2d:
-                dx = dx.view(N, Cin, H, W)
-        return flat, dx
+        return flat, self._exit_dx(dx0, tape.dims)

@@ -44,14 +44,14 @@ class _Recorder:
         return fn(*args)
 
 
-def launch_sequence(case):
+def launch_sequence(case, cases=CASES):
     """[[entry point, declared FLOPs], ...] of one training forward + backward"""
     import torch
 
     from pytorch3dunet_amd import _native as nat
     from pytorch3dunet_amd.unet3d.model import get_model
 
-    name, keys, f_maps, groups, shape = CASES[case]
+    name, keys, f_maps, groups, shape = cases[case]
     torch.manual_seed(0)
     model = get_model(dict(name=name, in_channels=1, out_channels=1, f_maps=f_maps, num_groups=groups, **keys))
     assert model.native_supported, model._native_blockers
