@@ -895,7 +895,8 @@ int u3d_conv2d_wgrad(int device, u3d_stream_t stream, const u3d_src_t* src, cons
  * 2-D twins of u3d_subpixel_conv_fwd / _dgrad_reps / _wgrad.  The upsampled half of cat(skip, F.interpolate(low, nearest))
  * (buildingblocks.py:491,:614) feeding a decoder's first Conv2d: for an output pixel of parity p the three taps per axis read only two
  * low-res pixels, so each of the 4 parity classes is a 2x2 convolution over the low-res grid with pre-summed weights — 4/9 of the
- * multiply-adds.  Requires an exact 2x upsampling on both axes (output 2*H1 x 2*W1), C1 % 4 == Cout % 4 == 0, 16-byte aligned tensors;
+ * multiply-adds.  These entry points take an exact 2x upsampling on both axes (output 2*H1 x 2*W1; the `_win` forms below: n -> 2n + 1),
+ * C1 % 4 == Cout % 4 == 0, 16-byte aligned tensors;
  * any H1, W1 >= 1.  fp32 NHWC, v_mfma_f32_32x32x2_f32.
  *   u3d_pack_subpixel2d_weights        w is the full (Cout, Cin_total, 3, 3) weight, channels [c_off, c_off + C1) are packed
  *              (u3d_subpixel2d_packed_floats(C1, Cout) floats): per axis parity 0 reads low-res offsets (-1, 0) with taps {t0}, {t1 + t2},
@@ -935,6 +936,47 @@ int u3d_pack_weights2d_slice(int device, u3d_stream_t stream, const float* w, in
                              float* packed);
 int u3d_conv2d_wgrad_strided(int device, u3d_stream_t stream, const u3d_src_t* src, const float* dz, float* dw, int dw_cin_stride, int N,
                              int H, int W, int Cout, float* workspace, size_t workspace_floats);
+/* (Added, U3D_VERSION unchanged.)  Decoder levels of a UNet2D that upsample n -> 2n + 1 along H and / or W (`native_2d_subpixel_plus:
+ * true`; the reference's 515 x 512 confocal patch pools 515 -> 257 -> 128): the 2-D twins of the round-5 entry points above.
+ * F.interpolate(nearest) to an odd size reads src = (dst - 1) >> 1 (src(0) = 0) — the exact 2x tensor shifted by one pixel with low[0]
+ * once more in front — so every output d >= 2 of such an axis sees the shifted 2x tensor under its three taps: the sub-pixel kernels
+ * run on a WINDOW (pixel u of the 2x grid is out[u + o] / dz[u + o]; same packed images, same tiles, same order of arithmetic — a
+ * window of zeros is the exact-2x entry point bit for bit) and the slab d < 2 runs on the general 3x3 kernel restricted to a box.
+ *   u3d_subpixel2d_conv_fwd_win    win = {Ho, Wo, oy, ox}: dims of `out`, o = 1 on an n -> 2n + 1 axis.  Pixels d = o of a shifted axis
+ *              are written but WRONG (they miss the extra copy of low[0]), d = 0 is not written: u3d_conv2d_box overwrites the slab
+ *   u3d_subpixel2d_conv_dgrad_win  win = {Hd, Wd, oy, ox, ly, lx}: dims of dz, shift, and the first pixel u of the 2x grid that counts
+ *              (1 on a shifted axis: the outputs d >= 2); gstats double[reps][N][C1][2] as u3d_subpixel2d_conv_dgrad_reps
+ *   u3d_subpixel2d_conv_wgrad_win  the same 6 integers; workspace as u3d_subpixel2d_conv_wgrad; atomic-free, bitwise deterministic
+ *   u3d_conv2d_box        plain 3x3 convolution of `src` (C0 may be 0: only the upsampled half; p0 must still be readable; the affine
+ *              table then has C1 channels) for the output pixels inside out_box = {y0, x0, y1, x1}; in_mask = {my, mx} or NULL: a
+ *              source pixel counts only if my && y < my || mx && x < mx (the slab's data gradient: dz outside the slab is zero);
+ *              out_win = {Ho, Wo, oy, ox} or NULL: pixel (y, x) goes to out[(y - oy, x - ox)] of an (N, Ho, Wo, Cout) tensor — a scratch
+ *              the size of the box (NULL: out is (N, H, W, Cout)).  Plain sums; pixels outside the box are not touched.  Images:
+ *              u3d_pack_weights2d_slice of the upsampled channels (mode 0 forward, mode 1 data gradient)
+ *   u3d_conv2d_wgrad_box  u3d_conv2d_wgrad over the dz pixels inside box = {y0, x0, y1, x1} only; dw (Cout, Cin, 3, 3) is written;
+ *              workspace: u3d_wgrad2d_workspace_floats() of the box dims
+ *   u3d_chan_stats_children2d / u3d_gn_bwd_apply_children2d   u3d_chan_stats_children / u3d_gn_bwd_apply_children for (N, H1, W1, C)
+ *              tensors: children = (2 + [ey && y == 0]) (2 + [ex && x == 0]) — one along the z axis a 2-D tensor does not have
+ *   u3d_nearest_childsum_add2d   dv (N, y1 - y0, x1 - x0, C): a full-resolution gradient of the pixels of box = {y0, x0, y1, x1} of the
+ *              (2 * H1 + ey) x (2 * W1 + ex) image, the box a union of whole low-res cells (cell 0 of a shifted axis owns [0, 3)); for
+ *              every cell inside it dlow[j] += sum of its children, gstats[N][C][2] += (sum, sum * x_low) of what was added */
+int u3d_subpixel2d_conv_fwd_win(int device, u3d_stream_t stream, const float* low, const float* affine, long long affine_sample_stride,
+                                const float* packed, float* out, int N, int H1, int W1, int C1, int Cout, const int* win);
+int u3d_subpixel2d_conv_dgrad_win(int device, u3d_stream_t stream, const float* dz, const float* packed, const float* x_low, float* dlow,
+                                  double* gstats, int N, int H1, int W1, int C1, int Cout, int reps, const int* win);
+int u3d_subpixel2d_conv_wgrad_win(int device, u3d_stream_t stream, const float* low, const float* affine, long long affine_sample_stride,
+                                  const float* dz, float* dw, int dw_cin_stride, int N, int H1, int W1, int C1, int Cout,
+                                  float* workspace, long long workspace_floats, const int* win);
+int u3d_conv2d_box(int device, u3d_stream_t stream, const u3d_src_t* src, const float* packed_w, float* out, int N, int H, int W,
+                   int Cout, const int* out_box, const int* in_mask, const int* out_win);
+int u3d_conv2d_wgrad_box(int device, u3d_stream_t stream, const u3d_src_t* src, const float* dz, float* dw, int N, int H, int W,
+                         int Cout, float* workspace, size_t workspace_floats, const int* box);
+int u3d_chan_stats_children2d(int device, u3d_stream_t stream, const float* x_low, int N, int H1, int W1, int C, int ey, int ex,
+                              double* stats);
+int u3d_gn_bwd_apply_children2d(int device, u3d_stream_t stream, const float* dlow, const float* x, const float* coef, int Ctot, int coff,
+                                int N, int H1, int W1, int C, int ey, int ex, int relu_mask, float* out);
+int u3d_nearest_childsum_add2d(int device, u3d_stream_t stream, const float* dv, const float* x_low, float* dlow, double* gstats, int N,
+                               int H1, int W1, int C, int ey, int ex, const int* box);
 /* (Added, U3D_VERSION unchanged.)  The first convolution of a 2-D net (`native_2d_stem: true`): the 2-D twins of
  * u3d_conv3d_small_cin_fwd_reps / u3d_conv3d_small_cin_bwd for Cin <= 4, Cout <= 32, exact fp32 (csrc/u3d_conv2d.hip).  x is a plain
  * (N,H,W,Cin) tensor, w the reference (Cout,Cin,3,3) layout — no packed image.  N <= 65535, N*H*W < 2^31.

@@ -19,6 +19,11 @@
 // Weight gradient (conv2d_wgrad_kernel): a block owns 32 output x 32 input channels x 9 taps (9 x 16 accumulator registers per wave)
 // and a contiguous range of pixel tiles; partial sums go to a workspace and are added in a fixed order (conv2d_wgrad_reduce_kernel):
 // the same inputs give a bitwise-identical dW.
+//
+// Both kernels have a BOX instantiation (u3d_conv2d_box, u3d_conv2d_wgrad_box): tiles enumerated from the origin of a box of the image,
+// only pixels inside it written (forward / data gradient) or contracted over (weight gradient) — the 2-pixel slab of a decoder level that
+// upsamples n -> 2n + 1 under `native_2d_subpixel_plus`, next to the windowed kernels of csrc/u3d_subpix2d.hip.  The other instantiations
+// are the code they were.
 #include <algorithm>
 
 #include "u3d_common.h"
@@ -140,6 +145,10 @@ struct Conv2dParams {
     int relu, has_gx, stat_reps;
     int ksplit, cps;
     long long part_stride;
+    // conv2d_mfma_kernel<.., BOX = true> (u3d_conv2d_box): tiles are enumerated from the origin of the OUTPUT BOX [b*0, b*1) and only pixels
+    // inside it are written, to out[(y - ooy, x - oox)] of an (N, oH, oW, Cout) tensor; a source pixel counts only if
+    // my && y < my || mx && x < mx (my = mx = 0: every pixel counts)
+    int by0, bx0, by1, bx1, my, mx, oH, oW, ooy, oox;
 };
 
 // one value of the (virtual) gx tensor at pixel v0 / low-res pixel v1, channel c (gx has Cout channels in data-gradient use)
@@ -189,7 +198,7 @@ __device__ __forceinline__ void c2_flush_stats(const Conv2dParams& p, float* red
     }
 }
 
-template <int NT, bool VEC, bool RES>
+template <int NT, bool VEC, bool RES, bool BOX = false>
 __global__ __launch_bounds__(256, 2) void conv2d_mfma_kernel(const Conv2dParams p) {
     using namespace c2;
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -210,7 +219,7 @@ __global__ __launch_bounds__(256, 2) void conv2d_mfma_kernel(const Conv2dParams 
     tile /= p.tx;
     const int tyi = tile % p.ty;
     const int n = tile / p.ty;
-    const int y0 = tyi * TY, x0 = txi * TX;
+    const int y0 = tyi * TY + (BOX ? p.by0 : 0), x0 = txi * TX + (BOX ? p.bx0 : 0);
     const int H = p.H, W = p.W;
     const int Ctot = p.src.C0 + p.src.C1;
 
@@ -224,7 +233,8 @@ __global__ __launch_bounds__(256, 2) void conv2d_mfma_kernel(const Conv2dParams 
         const int pix = item >> 2, q = item & 3;
         const int hy = pix / HX, hx = pix - (pix / HX) * HX;
         const int gy = y0 - 1 + hy, gxx = x0 - 1 + hx;
-        const bool ok = in && gy >= 0 && gy < H && gxx >= 0 && gxx < W;
+        bool ok = in && gy >= 0 && gy < H && gxx >= 0 && gxx < W;
+        if (BOX && (p.my | p.mx) != 0) ok = ok && ((p.my != 0 && gy < p.my) || (p.mx != 0 && gxx < p.mx));
         oks[it] = ok;
         ldsoff[it] = in ? hy * RS + hx * CS + 4 * q : -1;
         cqs[it] = 4 * q;
@@ -329,9 +339,10 @@ __global__ __launch_bounds__(256, 2) void conv2d_mfma_kernel(const Conv2dParams 
             for (int r = 0; r < 16; ++r) {
                 const int row = (r & 3) + 8 * (r >> 2) + 4 * h;
                 const int y = y0 + 4 * w + 2 * mt + (row >> 4), x = x0 + (row & 15);
-                if (y >= H || x >= W) continue;
+                if (BOX ? (y >= p.by1 || x >= p.bx1) : (y >= H || x >= W)) continue;
                 float v = acc[mt][nt][r];
-                const size_t o = ((size_t)(n * H + y) * W + x) * p.Cout + co;
+                const size_t o = BOX ? ((size_t)(n * p.oH + y - p.ooy) * p.oW + x - p.oox) * p.Cout + co
+                                     : ((size_t)(n * H + y) * W + x) * p.Cout + co;
                 if (p.ksplit > 1) {
                     outp[o] = v;
                     continue;
@@ -492,6 +503,57 @@ extern "C" int u3d_conv2d_res_reps(int device, u3d_stream_t stream, const u3d_sr
                        workspace_floats, stat_reps);
 }
 
+// The same convolution for the output pixels inside out_box = {y0, x0, y1, x1} only — the near-boundary slab of a decoder level that
+// upsamples n -> 2n + 1 (`native_2d_subpixel_plus`; the 2-D twin of u3d_conv3d_box).  src->C0 may be 0 (only the upsampled half; p0 must
+// still be readable).  in_mask = {my, mx} or NULL: a source pixel counts only if my && y < my || mx && x < mx (the slab's data gradient:
+// dz outside the slab is zero).  out_win = {Ho, Wo, oy, ox} or NULL: pixel (y, x) goes to out[(y - oy, x - ox)] of an (N, Ho, Wo, Cout)
+// tensor — a scratch the size of the box instead of the image (NULL: out is (N, H, W, Cout)).  Plain sums: no ReLU, no statistics, no
+// split-K; pixels outside the box are not touched.  A 2-pixel slab in 16 x 16 tiles wastes 7/8 of its MFMAs; it is well under 1 % of the level.
+extern "C" int u3d_conv2d_box(int device, u3d_stream_t stream, const u3d_src_t* src, const float* packed_w, float* out, int N, int H,
+                              int W, int Cout, const int* out_box, const int* in_mask, const int* out_win) {
+    U3D_ENTER(device);
+    U3D_REQUIRE(src && src->p0 && packed_w && out && out_box && N > 0 && H > 0 && W > 0 && Cout > 0 && src->C0 >= 0 && src->C1 >= 0 &&
+                    src->C0 + src->C1 > 0 && (long long)N * H * W < (1LL << 31),
+                "u3d_conv2d_box: bad argument");
+    U3D_REQUIRE(src->C1 == 0 || (src->p1 && src->ymap && src->xmap && src->D1 == 1 && src->H1 > 0 && src->W1 > 0),
+                "u3d_conv2d_box: virtual source needs p1, ymap, xmap and D1 == 1");
+    Conv2dParams p = {};
+    p.by0 = out_box[0], p.bx0 = out_box[1], p.by1 = out_box[2], p.bx1 = out_box[3];
+    U3D_REQUIRE(0 <= p.by0 && p.by0 < p.by1 && p.by1 <= H && 0 <= p.bx0 && p.bx0 < p.bx1 && p.bx1 <= W,
+                "u3d_conv2d_box: output box outside the image or empty");
+    if (in_mask) p.my = in_mask[0], p.mx = in_mask[1];
+    U3D_REQUIRE(p.my >= 0 && p.mx >= 0, "u3d_conv2d_box: negative mask");
+    p.oH = H, p.oW = W, p.ooy = p.oox = 0;
+    if (out_win) {
+        p.oH = out_win[0], p.oW = out_win[1], p.ooy = out_win[2], p.oox = out_win[3];
+        U3D_REQUIRE(p.ooy >= 0 && p.oox >= 0 && p.ooy <= p.by0 && p.oox <= p.bx0 && p.by1 - p.ooy <= p.oH && p.bx1 - p.oox <= p.oW &&
+                        (long long)N * p.oH * p.oW < (1LL << 31),
+                    "u3d_conv2d_box: the output box does not fit the output window");
+    }
+    const int Cin = src->C0 + src->C1;
+    p.src = *src;
+    p.wp = packed_w;
+    p.out = out;
+    p.N = N, p.H = H, p.W = W, p.Cout = Cout;
+    p.nchunks = (int)c2_cdiv(Cin, c2::CC), p.ntg = (int)c2_cdiv(Cout, 32);
+    p.ty = (int)c2_cdiv(p.by1 - p.by0, c2::TY), p.tx = (int)c2_cdiv(p.bx1 - p.bx0, c2::TX);
+    const int nt = p.ntg >= 2 ? 2 : 1;
+    p.ncb = (int)c2_cdiv(p.ntg, nt);
+    p.stat_reps = 1;
+    p.ksplit = 1, p.cps = p.nchunks;
+    const bool vec = c2_src_vec_ok(src);
+    const long long blocks = (long long)N * p.ty * p.tx * p.ncb;
+    U3D_REQUIRE(blocks < (1LL << 31), "u3d_conv2d_box: grid too large");
+    const size_t lds = c2::LDS_FLOATS * sizeof(float);
+    auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, p); };
+    if (nt == 2)
+        vec ? go(conv2d_mfma_kernel<2, true, false, true>) : go(conv2d_mfma_kernel<2, false, false, true>);
+    else
+        vec ? go(conv2d_mfma_kernel<1, true, false, true>) : go(conv2d_mfma_kernel<1, false, false, true>);
+    U3D_LAUNCH_CHECK();
+    return 0;
+}
+
 // =================================================================================================
 // weight gradient: dw[co][ci][tap] = sum_{n,y,x} dz[n,y,x,co] * g[n, y + dy - 1, x + dx - 1, ci], g = affine(src), zero padded.
 // MFMA: M = 32 output channels (A = dz), N = 32 input channels (B = g), K = pixels two at a time; the same A fragment feeds 9 taps.
@@ -503,9 +565,10 @@ struct Wgrad2dParams {
     int ty, tx, ncob, ncib, ntiles, tps;
     int vec_dz;
     int dst_cin;  // input channels per row of dst: Cin, or the parent's count when dw is a channel slice written directly
+    int by0, bx0, by1, bx1;  // conv2d_wgrad_kernel<.., BOX = true> (u3d_conv2d_wgrad_box): the dz pixels that take part; tiles from its origin
 };
 
-template <bool VEC>
+template <bool VEC, bool BOX = false>
 __global__ __launch_bounds__(256, 2) void conv2d_wgrad_kernel(const Wgrad2dParams p) {
     using namespace c2;
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -533,7 +596,7 @@ __global__ __launch_bounds__(256, 2) void conv2d_wgrad_kernel(const Wgrad2dParam
         tt /= p.tx;
         const int tyi = tt % p.ty;
         const int n = tt / p.ty;
-        const int y0 = tyi * TY, x0 = txi * TX;
+        const int y0 = tyi * TY + (BOX ? p.by0 : 0), x0 = txi * TX + (BOX ? p.bx0 : 0);
         // stage g (18 x 18 halo, 32 channels from ci0, affine, zero padding) and dz (16 x 16, 32 channels from co0)
         for (int item = t; item < HY * HX * (WCB / 4); item += 256) {
             const int pix = item >> 3, q = item & 7;
@@ -557,7 +620,7 @@ __global__ __launch_bounds__(256, 2) void conv2d_wgrad_kernel(const Wgrad2dParam
             const int y = y0 + (pix >> 4), x = x0 + (pix & 15);
             const int cq = co0 + 4 * q;
             f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
-            if (y < H && x < W) {
+            if (BOX ? (y < p.by1 && x < p.bx1) : (y < H && x < W)) {
                 const float* src = p.dz + ((size_t)(n * H + y) * W + x) * p.Cout;
                 if (p.vec_dz && cq + 3 < p.Cout) {
                     v = *reinterpret_cast<const f32x4*>(src + cq);
@@ -656,7 +719,7 @@ extern "C" size_t u3d_wgrad2d_workspace_floats(int N, int H, int W, int Cin, int
 }
 
 static int conv2d_wgrad_impl(int device, u3d_stream_t stream, const u3d_src_t* src, const float* dz, float* dw, int dw_cin_stride, int N,
-                             int H, int W, int Cout, float* workspace, size_t workspace_floats) {
+                             int H, int W, int Cout, float* workspace, size_t workspace_floats, const int* box = nullptr) {
     U3D_ENTER(device);
     U3D_REQUIRE(src && src->p0 && dz && dw && N > 0 && H > 0 && W > 0 && Cout > 0 && src->C0 >= 0 && src->C1 >= 0 &&
                     src->C0 + src->C1 > 0 && (long long)N * H * W < (1LL << 31),
@@ -666,7 +729,11 @@ static int conv2d_wgrad_impl(int device, u3d_stream_t stream, const u3d_src_t* s
     const int Cin = src->C0 + src->C1;
     if (dw_cin_stride == 0) dw_cin_stride = Cin;
     U3D_REQUIRE(dw_cin_stride >= Cin, "u3d_conv2d_wgrad_strided: dw_cin_stride below the source's channel count");
-    const W2Plan pl = w2_plan(device, N, H, W, Cin, Cout);
+    if (box)
+        U3D_REQUIRE(0 <= box[0] && box[0] < box[2] && box[2] <= H && 0 <= box[1] && box[1] < box[3] && box[3] <= W,
+                    "u3d_conv2d_wgrad_box: box outside the image or empty");
+    // (a box: the plan of an image of the box's size — workspace: u3d_wgrad2d_workspace_floats of the box dims)
+    const W2Plan pl = box ? w2_plan(device, N, box[2] - box[0], box[3] - box[1], Cin, Cout) : w2_plan(device, N, H, W, Cin, Cout);
     const size_t need = pl.nsplit > 1 ? (size_t)pl.nsplit * Cout * Cin * 9 : 0;
     U3D_REQUIRE(need == 0 || (workspace && workspace_floats >= need), "u3d_conv2d_wgrad: workspace too small (%zu < %zu floats)",
                 workspace_floats, need);
@@ -678,6 +745,7 @@ static int conv2d_wgrad_impl(int device, u3d_stream_t stream, const u3d_src_t* s
     p.ty = pl.ty, p.tx = pl.tx, p.ncob = pl.ncob, p.ncib = pl.ncib, p.ntiles = pl.ntiles, p.tps = pl.tps;
     p.vec_dz = (Cout % 4 == 0 && ((uintptr_t)dz & 15) == 0) ? 1 : 0;
     p.dst_cin = need ? Cin : dw_cin_stride;
+    if (box) p.by0 = box[0], p.bx0 = box[1], p.by1 = box[2], p.bx1 = box[3];
     const size_t lds = c2::WG_LDS_FLOATS * sizeof(float);
     static bool attr_set[2] = {false, false};
     if (!attr_set[0]) {
@@ -687,8 +755,20 @@ static int conv2d_wgrad_impl(int device, u3d_stream_t stream, const u3d_src_t* s
                                     (int)lds));
         attr_set[0] = true;
     }
+    if (box && !attr_set[1]) {
+        U3D_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv2d_wgrad_kernel<false, true>),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        U3D_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv2d_wgrad_kernel<true, true>),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        attr_set[1] = true;
+    }
     const long long blocks = (long long)pl.nsplit * pl.ncob * pl.ncib;
-    if (c2_src_vec_ok(src))
+    if (box) {
+        if (c2_src_vec_ok(src))
+            hipLaunchKernelGGL((conv2d_wgrad_kernel<true, true>), dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, p);
+        else
+            hipLaunchKernelGGL((conv2d_wgrad_kernel<false, true>), dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, p);
+    } else if (c2_src_vec_ok(src))
         hipLaunchKernelGGL(conv2d_wgrad_kernel<true>, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, p);
     else
         hipLaunchKernelGGL(conv2d_wgrad_kernel<false>, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, p);
@@ -718,6 +798,14 @@ extern "C" int u3d_conv2d_wgrad(int device, u3d_stream_t stream, const u3d_src_t
 extern "C" int u3d_conv2d_wgrad_strided(int device, u3d_stream_t stream, const u3d_src_t* src, const float* dz, float* dw,
                                         int dw_cin_stride, int N, int H, int W, int Cout, float* workspace, size_t workspace_floats) {
     return conv2d_wgrad_impl(device, stream, src, dz, dw, dw_cin_stride, N, H, W, Cout, workspace, workspace_floats);
+}
+
+// the same over the dz pixels inside box = {y0, x0, y1, x1} only (the slab of a level that upsamples n -> 2n + 1; the 2-D twin of
+// u3d_conv3d_wgrad_box): dw (Cout, Cin, 3, 3) is written; workspace: u3d_wgrad2d_workspace_floats() of the BOX dims
+extern "C" int u3d_conv2d_wgrad_box(int device, u3d_stream_t stream, const u3d_src_t* src, const float* dz, float* dw, int N, int H, int W,
+                                    int Cout, float* workspace, size_t workspace_floats, const int* box) {
+    U3D_REQUIRE(box != nullptr, "u3d_conv2d_wgrad_box: box is NULL");
+    return conv2d_wgrad_impl(device, stream, src, dz, dw, 0, N, H, W, Cout, workspace, workspace_floats, box);
 }
 
 // =================================================================================================

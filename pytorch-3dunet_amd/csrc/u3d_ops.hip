@@ -321,7 +321,7 @@ __global__ __launch_bounds__(256) void chan_stats_children_kernel(const float* _
             const int xi = (int)(v % W1);
             const long long r = v / W1;
             const int yi = (int)(r % H1), zi = (int)(r / H1);
-            const float wgt = (float)((2 + (ez && zi == 0)) * (2 + (ey && yi == 0)) * (2 + (ex && xi == 0)));
+            const float wgt = (float)((ez < 0 ? 1 : 2 + (ez && zi == 0)) * (2 + (ey && yi == 0)) * (2 + (ex && xi == 0)));  // (ez < 0: 2-D form)
             const f32x4 q = *reinterpret_cast<const f32x4*>(x + ((size_t)n * V + v) * C + 4 * qd);
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
@@ -348,8 +348,8 @@ __global__ __launch_bounds__(256) void chan_stats_children_kernel(const float* _
     }
 }
 
-extern "C" int u3d_chan_stats_children(int device, u3d_stream_t stream, const float* x_low, int N, int D1, int H1, int W1, int C, int ez,
-                                       int ey, int ex, double* stats) {
+static int chan_stats_children_impl(int device, u3d_stream_t stream, const float* x_low, int N, int D1, int H1, int W1, int C, int ez,
+                                    int ey, int ex, double* stats) {
     U3D_ENTER(device);
     U3D_REQUIRE(x_low && stats && N > 0 && N <= 65535 && D1 > 0 && H1 > 0 && W1 > 0 && C > 0 && C % 4 == 0 && C <= 1024 &&
                     ((uintptr_t)x_low & 15) == 0, "u3d_chan_stats_children: bad argument (C a multiple of 4, <= 1024, 16-byte aligned)");
@@ -363,6 +363,19 @@ extern "C" int u3d_chan_stats_children(int device, u3d_stream_t stream, const fl
                        (hipStream_t)stream, x_low, D1, H1, W1, C, Q, rows, ez, ey, ex, stats);
     U3D_LAUNCH_CHECK();
     return 0;
+}
+
+extern "C" int u3d_chan_stats_children(int device, u3d_stream_t stream, const float* x_low, int N, int D1, int H1, int W1, int C, int ez,
+                                       int ey, int ex, double* stats) {
+    U3D_REQUIRE(ez >= 0, "u3d_chan_stats_children: bad argument (ez)");
+    return chan_stats_children_impl(device, stream, x_low, N, D1, H1, W1, C, ez, ey, ex, stats);
+}
+
+// the 2-D form (`native_2d_subpixel_plus`): x_low (N, H1, W1, C), a low-res pixel has (2 + [ey && y == 0]) (2 + [ex && x == 0]) children —
+// ONE along the z axis a 2-D tensor does not have
+extern "C" int u3d_chan_stats_children2d(int device, u3d_stream_t stream, const float* x_low, int N, int H1, int W1, int C, int ey, int ex,
+                                         double* stats) {
+    return chan_stats_children_impl(device, stream, x_low, N, 1, H1, W1, C, -1, ey, ex, stats);
 }
 
 // =================================================================================================
@@ -758,7 +771,7 @@ __global__ void gn_bwd_apply_cnt_kernel(const float* __restrict__ dlow, const fl
         v /= H1;
         const int zz = (int)(v % D1);
         const int n = (int)(v / D1);
-        const float cnt = (float)((2 + (ez && zz == 0)) * (2 + (ey && yy == 0)) * (2 + (ex && xx == 0)));
+        const float cnt = (float)((ez < 0 ? 1 : 2 + (ez && zz == 0)) * (2 + (ey && yy == 0)) * (2 + (ex && xx == 0)));  // (ez < 0: 2-D form)
         const size_t oi = (size_t)(idx / Q) * C + c;
         const f32x4 dg = *reinterpret_cast<const f32x4*>(dlow + oi), xv = *reinterpret_cast<const f32x4*>(x + oi);
         const f32x4 pp = *reinterpret_cast<const f32x4*>(coef + ((size_t)n * 3 + 0) * Ctot + coff + c);
@@ -774,9 +787,8 @@ __global__ void gn_bwd_apply_cnt_kernel(const float* __restrict__ dlow, const fl
     }
 }
 
-extern "C" int u3d_gn_bwd_apply_children(int device, u3d_stream_t stream, const float* dlow, const float* x, const float* coef, int Ctot,
-                                         int coff, int N, int D1, int H1, int W1, int C, int ez, int ey, int ex, int relu_mask,
-                                         float* out) {
+static int gn_bwd_apply_children_impl(int device, u3d_stream_t stream, const float* dlow, const float* x, const float* coef, int Ctot,
+                                      int coff, int N, int D1, int H1, int W1, int C, int ez, int ey, int ex, int relu_mask, float* out) {
     U3D_ENTER(device);
     U3D_REQUIRE(dlow && x && coef && out && N > 0 && D1 > 0 && H1 > 0 && W1 > 0 && C > 0 && C % 4 == 0 && coff >= 0 && coff % 4 == 0 &&
                     Ctot % 4 == 0 && coff + C <= Ctot && (((uintptr_t)dlow | (uintptr_t)x | (uintptr_t)coef | (uintptr_t)out) & 15) == 0,
@@ -786,6 +798,19 @@ extern "C" int u3d_gn_bwd_apply_children(int device, u3d_stream_t stream, const 
                        N, D1, H1, W1, C, ez, ey, ex, relu_mask, out);
     U3D_LAUNCH_CHECK();
     return 0;
+}
+
+extern "C" int u3d_gn_bwd_apply_children(int device, u3d_stream_t stream, const float* dlow, const float* x, const float* coef, int Ctot,
+                                         int coff, int N, int D1, int H1, int W1, int C, int ez, int ey, int ex, int relu_mask,
+                                         float* out) {
+    U3D_REQUIRE(ez >= 0, "u3d_gn_bwd_apply_children: bad argument (ez)");
+    return gn_bwd_apply_children_impl(device, stream, dlow, x, coef, Ctot, coff, N, D1, H1, W1, C, ez, ey, ex, relu_mask, out);
+}
+
+// the 2-D form: (N, H1, W1, C) tensors, children = (2 + [ey && y == 0]) (2 + [ex && x == 0])
+extern "C" int u3d_gn_bwd_apply_children2d(int device, u3d_stream_t stream, const float* dlow, const float* x, const float* coef, int Ctot,
+                                           int coff, int N, int H1, int W1, int C, int ey, int ex, int relu_mask, float* out) {
+    return gn_bwd_apply_children_impl(device, stream, dlow, x, coef, Ctot, coff, N, 1, H1, W1, C, -1, ey, ex, relu_mask, out);
 }
 
 // Round 5, decoder levels that upsample n -> 2n + 1 (F.interpolate(nearest) to an odd skip size, buildingblocks.py:598-614): the
@@ -851,6 +876,90 @@ extern "C" int u3d_nearest_childsum_add(int device, u3d_stream_t stream, const f
     if (blocks > 256) blocks = 256;
     hipLaunchKernelGGL(nearest_childsum_add_kernel, dim3((unsigned)blocks), dim3(256), (size_t)2 * C * sizeof(double), (hipStream_t)stream,
                        dv, x_low, dlow, gstats, N, D, H, W, D1, H1, W1, C, zlo, ylo, xlo, cz, cy, cx);
+    U3D_LAUNCH_CHECK();
+    return 0;
+}
+
+// The 2-D form, on a scratch the size of the slab: dv (N, y1 - y0, x1 - x0, C) holds the full-resolution gradient of the upsampled channels
+// for the pixels of box = {y0, x0, y1, x1} of a (2 * H1 + ey) x (2 * W1 + ex) image.  The box must be a union of whole low-res cells
+// (children of cell j along an axis: [2j, 2j + 2), or with e = 1 [0, 3) for j = 0 and [2j + 1, 2j + 3) otherwise); for every cell inside
+// it dlow[j] += sum of its children, gstats[n][c] += (sum add, sum add * x_low).  A block owns a run of cells of one sample, thread
+// (row, quad) walks them; the rows are added through LDS in a fixed order, then one f64 atomic per (block, channel, quantity).
+__device__ __forceinline__ int childsum2d_first(int j, int e) { return e ? (j == 0 ? 0 : 2 * j + 1) : 2 * j; }
+__host__ __device__ __forceinline__ int childsum2d_cell(int d, int e) { return e ? (d == 0 ? 0 : (d - 1) >> 1) : d >> 1; }
+
+__global__ __launch_bounds__(256) void nearest_childsum_add2d_kernel(const float* __restrict__ dv, const float* __restrict__ xlow,
+                                                                     float* __restrict__ dlow, double* __restrict__ gstats, int H1, int W1,
+                                                                     int C, int Q, int rows, int ey, int ex, int by0, int bx0, int bh,
+                                                                     int bw, int jy0, int jx0, int nj_y, int nj_x, int per) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char childsum2d_lds[];
+    double* red = reinterpret_cast<double*>(childsum2d_lds);  // [rows][Q][8]
+    const int t = threadIdx.x, n = blockIdx.y;
+    const int row = t / Q, qd = t - row * Q;
+    const int cells = nj_y * nj_x;
+    const int cbeg = blockIdx.x * per, cend = min(cells, cbeg + per);
+    double s1[4] = {0.0, 0.0, 0.0, 0.0}, s2[4] = {0.0, 0.0, 0.0, 0.0};
+    if (row < rows) {
+        for (int cell = cbeg + row; cell < cend; cell += rows) {
+            const int jy = jy0 + cell / nj_x, jx = jx0 + cell % nj_x;
+            const int ya = childsum2d_first(jy, ey), yb = 2 * jy + 2 + ey, xa = childsum2d_first(jx, ex), xb = 2 * jx + 2 + ex;
+            f32x4 sum = {0.f, 0.f, 0.f, 0.f};
+            for (int y = ya; y < yb; ++y)
+                for (int x = xa; x < xb; ++x)
+                    sum += *reinterpret_cast<const f32x4*>(dv + (((size_t)n * bh + (y - by0)) * bw + (x - bx0)) * C + 4 * qd);
+            const size_t oi = (((size_t)n * H1 + jy) * W1 + jx) * C + 4 * qd;
+            f32x4* dst = reinterpret_cast<f32x4*>(dlow + oi);
+            *dst = *dst + sum;
+            if (gstats) {
+                const f32x4 xv = *reinterpret_cast<const f32x4*>(xlow + oi);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    s1[e] += (double)sum[e];
+                    s2[e] += (double)sum[e] * (double)xv[e];
+                }
+            }
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            red[(row * Q + qd) * 8 + e] = s1[e];
+            red[(row * Q + qd) * 8 + 4 + e] = s2[e];
+        }
+    }
+    if (gstats == nullptr) return;  // (uniform)
+    __syncthreads();
+    for (int c = t; c < C; c += 256) {
+        const int qd2 = c >> 2, e = c & 3;
+        double a = 0.0, b = 0.0;
+        for (int r = 0; r < rows; ++r) {
+            a += red[(r * Q + qd2) * 8 + e];
+            b += red[(r * Q + qd2) * 8 + 4 + e];
+        }
+        u3d_atomic_add_f64(&gstats[((size_t)n * C + c) * 2 + 0], a);
+        u3d_atomic_add_f64(&gstats[((size_t)n * C + c) * 2 + 1], b);
+    }
+}
+
+extern "C" int u3d_nearest_childsum_add2d(int device, u3d_stream_t stream, const float* dv, const float* x_low, float* dlow,
+                                          double* gstats, int N, int H1, int W1, int C, int ey, int ex, const int* box) {
+    U3D_ENTER(device);
+    U3D_REQUIRE(dv && dlow && box && N > 0 && N <= 65535 && H1 > 0 && W1 > 0 && C > 0 && C % 4 == 0 && C <= 1024 &&
+                    (ey == 0 || ey == 1) && (ex == 0 || ex == 1) && (gstats == nullptr || x_low != nullptr),
+                "u3d_nearest_childsum_add2d: bad argument (C a multiple of 4, <= 1024)");
+    U3D_REQUIRE((((uintptr_t)dv | (uintptr_t)dlow | (uintptr_t)x_low) & 15) == 0, "u3d_nearest_childsum_add2d: 16-byte alignment");
+    const int H = 2 * H1 + ey, W = 2 * W1 + ex;
+    const int y0 = box[0], x0 = box[1], y1 = box[2], x1 = box[3];
+    U3D_REQUIRE(0 <= y0 && y0 < y1 && y1 <= H && 0 <= x0 && x0 < x1 && x1 <= W, "u3d_nearest_childsum_add2d: box outside the image or empty");
+    const int jy0 = childsum2d_cell(y0, ey), jy1 = childsum2d_cell(y1 - 1, ey), jx0 = childsum2d_cell(x0, ex), jx1 = childsum2d_cell(x1 - 1, ex);
+    auto first = [](int j, int e) { return e ? (j == 0 ? 0 : 2 * j + 1) : 2 * j; };
+    U3D_REQUIRE(first(jy0, ey) == y0 && 2 * jy1 + 2 + ey == y1 && first(jx0, ex) == x0 && 2 * jx1 + 2 + ex == x1,
+                "u3d_nearest_childsum_add2d: the box is not a union of whole low-res cells");
+    const int Q = C / 4, rows = 256 / Q;
+    const int nj_y = jy1 - jy0 + 1, nj_x = jx1 - jx0 + 1;
+    const int cells = nj_y * nj_x;
+    const int per = rows * 8;  // cells per block
+    hipLaunchKernelGGL(nearest_childsum_add2d_kernel, dim3((unsigned)((cells + per - 1) / per), (unsigned)N), dim3(256),
+                       (size_t)rows * Q * 8 * sizeof(double), (hipStream_t)stream, dv, x_low, dlow, gstats, H1, W1, C, Q, rows, ey, ex, y0,
+                       x0, y1 - y0, x1 - x0, jy0, jx0, nj_y, nj_x, per);
     U3D_LAUNCH_CHECK();
     return 0;
 }

@@ -12,6 +12,12 @@
 // kernels of u3d_conv2d.hip (halo of a 16-channel chunk through LDS, two buffers, one barrier per chunk, B fragments streamed from a
 // packed global image one k-step ahead).
 //
+// A level that upsamples n -> 2n + 1 along an axis (`native_2d_subpixel_plus`; F.interpolate(nearest) to an odd size reads
+// src = (dst - 1) >> 1, src(0) = 0) is the same 2x tensor shifted by one pixel with low[0] once more in front: the `_win` entry points run
+// the SAME three kernels with pixel u of the 2x grid at out[u + o] / dz[u + o] (and, for the gradients, counted only if u >= l) — offsets and
+// predicate live in the staging descriptors and the epilogue addresses, the k-loops and the LDS layout do not know about them; the exact
+// entry points pass o = l = 0.  The slab d < 2 of a shifted axis belongs to u3d_conv2d_box / u3d_conv2d_wgrad_box (csrc/u3d_conv2d.hip).
+//
 // Layout choices (why):
 //   forward   a block of 4 waves owns a 16(y) x 8(x) LOW-RES tile (= 32 x 16 output pixels) and 32 output channels; wave w owns the
 //             low-res rows 4w .. 4w + 3 as ONE 32-row M-tile and keeps the accumulators of all FOUR parity classes (4 x 16 registers).
@@ -194,6 +200,7 @@ struct Sp2FwdParams {
     float* out;  // (N, 2 * H1, 2 * W1, Cout)
     int N, H1, W1, C1, Cout;
     int ty, tx, nchunks, ntg, avec;
+    int Ho, Wo, oy, ox;  // u3d_subpixel2d_conv_fwd_win: pixel u of the 2x grid is written to out[u + o] of an (Ho, Wo) image (exact: 2*H1, 2*W1, 0, 0)
 };
 
 __global__ __launch_bounds__(256, 2) void subpixel2d_fwd_kernel(const Sp2FwdParams p) {
@@ -312,7 +319,7 @@ __global__ __launch_bounds__(256, 2) void subpixel2d_fwd_kernel(const Sp2FwdPara
     // ---- epilogue: lane column = output channel, register r = M row (r & 3) + 8 (r >> 2) + 4h = low-res pixel (row >> 3, row & 7)
     const int co = cb * 32 + i32;
     if (co >= p.Cout) return;
-    const int H = 2 * H1, W = 2 * W1;
+    const int H = p.Ho, W = p.Wo;
 #pragma unroll
     for (int cls = 0; cls < 4; ++cls)
 #pragma unroll
@@ -320,17 +327,14 @@ __global__ __launch_bounds__(256, 2) void subpixel2d_fwd_kernel(const Sp2FwdPara
             const int row = (r & 3) + 8 * (r >> 2) + 4 * h;
             const int ly = y0 + 4 * w + (row >> 3), lx = x0 + (row & 7);
             if (ly >= H1 || lx >= W1) continue;
-            const int y = 2 * ly + (cls >> 1), x = 2 * lx + (cls & 1);
+            const int y = 2 * ly + (cls >> 1) + p.oy, x = 2 * lx + (cls & 1) + p.ox;  // (2 * H1 + oy <= Ho: inside the image)
             p.out[(((size_t)n * H + y) * W + x) * p.Cout + co] = acc[cls][r];
         }
 }
 
-extern "C" int u3d_subpixel2d_conv_fwd(int device, u3d_stream_t stream, const float* low, const float* affine,
-                                       long long affine_sample_stride, const float* packed, float* out, int N, int H1, int W1, int C1,
-                                       int Cout, float* workspace, long long workspace_floats) {
+static int s2_fwd_impl(int device, u3d_stream_t stream, const float* low, const float* affine, long long affine_sample_stride,
+                       const float* packed, float* out, int N, int H1, int W1, int C1, int Cout, const int* win) {
     U3D_ENTER(device);
-    (void)workspace;  // no split-K form: small grids run on few blocks
-    (void)workspace_floats;
     U3D_REQUIRE(low && packed && out && N > 0 && H1 > 0 && W1 > 0 && C1 > 0 && Cout > 0 && C1 % 4 == 0 && Cout % 4 == 0 &&
                     4LL * N * H1 * W1 < (1LL << 31) && ((uintptr_t)low & 15) == 0 && ((uintptr_t)packed & 15) == 0,
                 "u3d_subpixel2d_conv_fwd: bad argument (C1 %% 4 == Cout %% 4 == 0, 16-byte aligned tensors)");
@@ -340,11 +344,36 @@ extern "C" int u3d_subpixel2d_conv_fwd(int device, u3d_stream_t stream, const fl
     p.ty = (int)s2_cdiv(H1, s2::FLY), p.tx = (int)s2_cdiv(W1, s2::FLX);
     p.nchunks = (int)s2_cdiv(C1, s2::CC), p.ntg = (int)s2_cdiv(Cout, 32);
     p.avec = s2_affine_vec(affine, affine_sample_stride) ? 1 : 0;
+    p.Ho = 2 * H1, p.Wo = 2 * W1, p.oy = p.ox = 0;
+    if (win) {
+        p.Ho = win[0], p.Wo = win[1], p.oy = win[2], p.ox = win[3];
+        U3D_REQUIRE(p.oy >= 0 && p.ox >= 0 && 2 * H1 + p.oy <= p.Ho && 2 * W1 + p.ox <= p.Wo && (long long)N * p.Ho * p.Wo < (1LL << 31),
+                    "u3d_subpixel2d_conv_fwd_win: the shifted 2x grid does not fit the output");
+    }
     const long long blocks = (long long)N * p.ty * p.tx * p.ntg;
     U3D_REQUIRE(blocks < (1LL << 31), "u3d_subpixel2d_conv_fwd: grid too large");
     hipLaunchKernelGGL(subpixel2d_fwd_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p);
     U3D_LAUNCH_CHECK();
     return 0;
+}
+
+extern "C" int u3d_subpixel2d_conv_fwd(int device, u3d_stream_t stream, const float* low, const float* affine,
+                                       long long affine_sample_stride, const float* packed, float* out, int N, int H1, int W1, int C1,
+                                       int Cout, float* workspace, long long workspace_floats) {
+    (void)workspace;  // no split-K form: small grids run on few blocks
+    (void)workspace_floats;
+    return s2_fwd_impl(device, stream, low, affine, affine_sample_stride, packed, out, N, H1, W1, C1, Cout, nullptr);
+}
+
+// ... on a WINDOW, for a decoder level that upsamples n -> 2n + 1 along some axes (F.interpolate(nearest) to an odd skip size reads
+// src = (dst - 1) >> 1: the exact 2x tensor shifted by one pixel with low[0] once more in front): win = {Ho, Wo, oy, ox}, pixel u of the
+// 2x grid is written to out[u + o] of an (N, Ho, Wo, Cout) tensor.  Every output d >= 2 of a shifted axis is right; d = o is written but
+// WRONG (it misses the extra copy of low[0]) and d = 0 is not written: u3d_conv2d_box overwrites the slab d < 2 on the same stream.
+extern "C" int u3d_subpixel2d_conv_fwd_win(int device, u3d_stream_t stream, const float* low, const float* affine,
+                                           long long affine_sample_stride, const float* packed, float* out, int N, int H1, int W1,
+                                           int C1, int Cout, const int* win) {
+    U3D_REQUIRE(win != nullptr, "u3d_subpixel2d_conv_fwd_win: win is NULL");
+    return s2_fwd_impl(device, stream, low, affine, affine_sample_stride, packed, out, N, H1, W1, C1, Cout, win);
 }
 
 // =================================================================================================
@@ -357,6 +386,8 @@ struct Sp2DgradParams {
     double* gstats;     // optional [reps][N][C1][2]
     int N, H1, W1, C1, Cout;
     int ty, tx, nchunks, ntg, ncb, reps;
+    // u3d_subpixel2d_conv_dgrad_win: pixel u of the 2x grid is dz[u + o] of an (Hd, Wd) image and counts only if u >= l
+    int Hd, Wd, oy, ox, ly, lx;
 };
 
 template <int NT>
@@ -391,11 +422,11 @@ __global__ __launch_bounds__(256, 2) void subpixel2d_dgrad_kernel(const Sp2Dgrad
         const int rr = r % DPY;
         const int plane = r / DPY;
         const int gy = 2 * (y0 + rr) + (plane >> 1) - 1, gx = 2 * (x0 + cc) + (plane & 1) - 1;
-        const bool ok = in && gy >= 0 && gy < H && gx >= 0 && gx < W;
+        const bool ok = in && gy >= p.ly && gy < H && gx >= p.lx && gx < W;  // (l >= 0)
         oks[it] = ok;
         ldsoff[it] = in ? plane * DPLANE + rr * RS + cc * CS + 4 * q : -1;
         cqs[it] = 4 * q;
-        goff[it] = ok ? (((size_t)n * H + gy) * W + gx) * Cout : 0;
+        goff[it] = ok ? (((size_t)n * p.Hd + gy + p.oy) * p.Wd + gx + p.ox) * Cout : 0;
     }
     f32x4 raw[DNIT];
     auto load_chunk = [&](int c) {
@@ -500,8 +531,8 @@ __global__ __launch_bounds__(256, 2) void subpixel2d_dgrad_kernel(const Sp2Dgrad
     }
 }
 
-extern "C" int u3d_subpixel2d_conv_dgrad_reps(int device, u3d_stream_t stream, const float* dz, const float* packed, const float* x_low,
-                                              float* dlow, double* gstats, int N, int H1, int W1, int C1, int Cout, int reps) {
+static int s2_dgrad_impl(int device, u3d_stream_t stream, const float* dz, const float* packed, const float* x_low, float* dlow,
+                         double* gstats, int N, int H1, int W1, int C1, int Cout, int reps, const int* win) {
     U3D_ENTER(device);
     U3D_REQUIRE(dz && packed && dlow && N > 0 && H1 > 0 && W1 > 0 && C1 > 0 && Cout > 0 && C1 % 4 == 0 && Cout % 4 == 0 && reps >= 1 &&
                     4LL * N * H1 * W1 < (1LL << 31) && ((uintptr_t)dz & 15) == 0 && ((uintptr_t)packed & 15) == 0 && (!gstats || x_low),
@@ -512,6 +543,13 @@ extern "C" int u3d_subpixel2d_conv_dgrad_reps(int device, u3d_stream_t stream, c
     p.ty = (int)s2_cdiv(H1, s2::DLY), p.tx = (int)s2_cdiv(W1, s2::DLX);
     p.nchunks = (int)s2_cdiv(Cout, s2::CC), p.ntg = (int)s2_cdiv(C1, 32);
     p.reps = reps;
+    p.Hd = 2 * H1, p.Wd = 2 * W1, p.oy = p.ox = p.ly = p.lx = 0;
+    if (win) {
+        p.Hd = win[0], p.Wd = win[1], p.oy = win[2], p.ox = win[3], p.ly = win[4], p.lx = win[5];
+        U3D_REQUIRE(p.oy >= 0 && p.ox >= 0 && 2 * H1 + p.oy <= p.Hd && 2 * W1 + p.ox <= p.Wd && p.ly >= 0 && p.lx >= 0 &&
+                        (long long)N * p.Hd * p.Wd < (1LL << 31),
+                    "u3d_subpixel2d_conv_dgrad_win: bad window");
+    }
     const int nt = p.ntg > 2 ? 2 : 1;  // a block produces 64 * nt channels
     p.ncb = (int)s2_cdiv(p.ntg, 2 * nt);
     const long long blocks = (long long)N * p.ty * p.tx * p.ncb;
@@ -524,6 +562,21 @@ extern "C" int u3d_subpixel2d_conv_dgrad_reps(int device, u3d_stream_t stream, c
     return 0;
 }
 
+extern "C" int u3d_subpixel2d_conv_dgrad_reps(int device, u3d_stream_t stream, const float* dz, const float* packed, const float* x_low,
+                                              float* dlow, double* gstats, int N, int H1, int W1, int C1, int Cout, int reps) {
+    return s2_dgrad_impl(device, stream, dz, packed, x_low, dlow, gstats, N, H1, W1, C1, Cout, reps, nullptr);
+}
+
+// ... reading dz through the window of u3d_subpixel2d_conv_fwd_win: win = {Hd, Wd, oy, ox, ly, lx} — dz is (N, Hd, Wd, Cout), pixel u of
+// the 2x grid is dz[u + o] and counts only if u >= l (l = 1 on a shifted axis: the outputs d >= 2; the slab's share of the gradient
+// comes from u3d_conv2d_box + u3d_nearest_childsum_add2d).  dlow is written, gstats as u3d_subpixel2d_conv_dgrad_reps.
+extern "C" int u3d_subpixel2d_conv_dgrad_win(int device, u3d_stream_t stream, const float* dz, const float* packed, const float* x_low,
+                                             float* dlow, double* gstats, int N, int H1, int W1, int C1, int Cout, int reps,
+                                             const int* win) {
+    U3D_REQUIRE(win != nullptr, "u3d_subpixel2d_conv_dgrad_win: win is NULL");
+    return s2_dgrad_impl(device, stream, dz, packed, x_low, dlow, gstats, N, H1, W1, C1, Cout, reps, win);
+}
+
 // =================================================================================================
 // weight gradient of the upsampled channels
 struct Sp2WgradParams {
@@ -534,6 +587,7 @@ struct Sp2WgradParams {
     float* dst;  // workspace [nsplit][Cout][C1][9]
     int N, H1, W1, C1, Cout;
     int ty, tx, ncob, ncib, ntiles, tps, avec;
+    int Hd, Wd, oy, ox, ly, lx;  // the dz window of Sp2DgradParams
 };
 
 __global__ __launch_bounds__(256, 2) void subpixel2d_wgrad_kernel(const Sp2WgradParams p) {
@@ -548,7 +602,6 @@ __global__ __launch_bounds__(256, 2) void subpixel2d_wgrad_kernel(const Sp2Wgrad
     const int ci0 = cib * WCB, co0 = cob * WCB;
     const int tile0 = split * p.tps, tile1 = min(p.ntiles, tile0 + p.tps);
     const int H1 = p.H1, W1 = p.W1, C1 = p.C1, Cout = p.Cout;
-    const int H = 2 * H1, W = 2 * W1;
     float* const gl = lds + WG_G;
     float* const dzl = lds + WG_DZ;
     const int py = w >> 1, px = w & 1;  // wave w owns parity class w
@@ -590,8 +643,9 @@ __global__ __launch_bounds__(256, 2) void subpixel2d_wgrad_kernel(const Sp2Wgrad
             const int ly = y0 + (pp >> 3), lx = x0 + (pp & 7);
             const int cq = co0 + 4 * q;
             f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
-            if (ly < H1 && lx < W1 && cq < Cout)
-                v = *reinterpret_cast<const f32x4*>(p.dz + (((size_t)n * H + 2 * ly + (cls >> 1)) * W + 2 * lx + (cls & 1)) * Cout + cq);
+            const int uy = 2 * ly + (cls >> 1), ux = 2 * lx + (cls & 1);  // pixel of the 2x grid
+            if (ly < H1 && lx < W1 && cq < Cout && uy >= p.ly && ux >= p.lx)
+                v = *reinterpret_cast<const f32x4*>(p.dz + (((size_t)n * p.Hd + uy + p.oy) * p.Wd + ux + p.ox) * Cout + cq);
             *reinterpret_cast<f32x4*>(dzl + idx * WCB + 4 * q) = v;
         }
         __syncthreads();
@@ -682,9 +736,9 @@ extern "C" long long u3d_subpixel2d_wgrad_workspace_floats(int N, int H1, int W1
     return (long long)pl.nsplit * Cout * C1 * 9;  // (always: the block results go through the workspace, also with one split)
 }
 
-extern "C" int u3d_subpixel2d_conv_wgrad(int device, u3d_stream_t stream, const float* low, const float* affine,
-                                         long long affine_sample_stride, const float* dz, float* dw, int dw_cin_stride, int N, int H1,
-                                         int W1, int C1, int Cout, float* workspace, long long workspace_floats) {
+static int s2_wgrad_impl(int device, u3d_stream_t stream, const float* low, const float* affine, long long affine_sample_stride,
+                         const float* dz, float* dw, int dw_cin_stride, int N, int H1, int W1, int C1, int Cout, float* workspace,
+                         long long workspace_floats, const int* win) {
     U3D_ENTER(device);
     U3D_REQUIRE(low && dz && dw && N > 0 && H1 > 0 && W1 > 0 && C1 > 0 && Cout > 0 && C1 % 4 == 0 && Cout % 4 == 0 &&
                     dw_cin_stride >= C1 && 4LL * N * H1 * W1 < (1LL << 31) && ((uintptr_t)low & 15) == 0 && ((uintptr_t)dz & 15) == 0,
@@ -698,6 +752,13 @@ extern "C" int u3d_subpixel2d_conv_wgrad(int device, u3d_stream_t stream, const 
     p.N = N, p.H1 = H1, p.W1 = W1, p.C1 = C1, p.Cout = Cout;
     p.ty = pl.ty, p.tx = pl.tx, p.ncob = pl.ncob, p.ncib = pl.ncib, p.ntiles = pl.ntiles, p.tps = pl.tps;
     p.avec = s2_affine_vec(affine, affine_sample_stride) ? 1 : 0;
+    p.Hd = 2 * H1, p.Wd = 2 * W1, p.oy = p.ox = p.ly = p.lx = 0;
+    if (win) {
+        p.Hd = win[0], p.Wd = win[1], p.oy = win[2], p.ox = win[3], p.ly = win[4], p.lx = win[5];
+        U3D_REQUIRE(p.oy >= 0 && p.ox >= 0 && 2 * H1 + p.oy <= p.Hd && 2 * W1 + p.ox <= p.Wd && p.ly >= 0 && p.lx >= 0 &&
+                        (long long)N * p.Hd * p.Wd < (1LL << 31),
+                    "u3d_subpixel2d_conv_wgrad_win: bad window");
+    }
     const size_t lds = s2::WG_LDS_FLOATS * sizeof(float);
     static bool attr_set = false;
     if (!attr_set) {
@@ -715,4 +776,21 @@ extern "C" int u3d_subpixel2d_conv_wgrad(int device, u3d_stream_t stream, const 
                        C1 * 9, dw_cin_stride * 9, dw);
     U3D_LAUNCH_CHECK();
     return 0;
+}
+
+extern "C" int u3d_subpixel2d_conv_wgrad(int device, u3d_stream_t stream, const float* low, const float* affine,
+                                         long long affine_sample_stride, const float* dz, float* dw, int dw_cin_stride, int N, int H1,
+                                         int W1, int C1, int Cout, float* workspace, long long workspace_floats) {
+    return s2_wgrad_impl(device, stream, low, affine, affine_sample_stride, dz, dw, dw_cin_stride, N, H1, W1, C1, Cout, workspace,
+                         workspace_floats, nullptr);
+}
+
+// ... with dz read through the window of u3d_subpixel2d_conv_dgrad_win (the same 6 integers): the weight gradient of the outputs d >= 2
+// of a level that upsamples n -> 2n + 1; the slab's share comes from u3d_conv2d_wgrad_box.  Same plan, same fixed-order fold and reduce.
+extern "C" int u3d_subpixel2d_conv_wgrad_win(int device, u3d_stream_t stream, const float* low, const float* affine,
+                                             long long affine_sample_stride, const float* dz, float* dw, int dw_cin_stride, int N, int H1,
+                                             int W1, int C1, int Cout, float* workspace, long long workspace_floats, const int* win) {
+    U3D_REQUIRE(win != nullptr, "u3d_subpixel2d_conv_wgrad_win: win is NULL");
+    return s2_wgrad_impl(device, stream, low, affine, affine_sample_stride, dz, dw, dw_cin_stride, N, H1, W1, C1, Cout, workspace,
+                         workspace_floats, win);
 }

@@ -116,8 +116,14 @@ class ConvLayers:
         return t
 
     def _src_plus(self, src: VSrc):
-        """`src.plus` of a sub-pixel layer's source; a 2-D net's sub-pixel levels are exact 2x on H and W (D = D1 = 1 is no axis)"""
-        return (0, 0, 0) if self.is2d else src.plus
+        """`src.plus` of a sub-pixel layer's source; a 2-D net (D = D1 = 1 is no axis): (0, py, px) under `native_2d_subpixel_plus`, whose
+        sub-pixel levels may upsample n -> 2n + 1 along H and W; without it they are exact 2x"""
+        if not self.is2d:
+            return src.plus
+        if not self.subpixel2d_plus or src.t1 is None:
+            return (0, 0, 0)
+        e = (0, src.H - 2 * src.H1, src.W - 2 * src.W1)
+        return e if all(v in (0, 1) for v in e) else (0, 0, 0)
 
     def _subpixel_layers(self, size):
         """decoder first convs whose low-res input is upsampled by exactly 2 — or, round 5, from n to 2n + 1 voxels — in every dimension at
@@ -140,8 +146,8 @@ class ConvLayers:
             # every axis upsampled by exactly 2, or n -> 2n + 1 (the pooled size of an odd level; round 5: the sub-pixel kernels on a
             # shifted window + the general kernels on the near-boundary slab, _fwd_subpixel / _dgrad_subpixel / _wgrad_subpixel)
             ratio = [a - 2 * b for a, b in zip(dims[skip_lvl], dims[low_lvl])]
-            # (2-D: exact 2x only — the windowed / slab form of an n -> 2n + 1 level is 3-D only, such a level keeps its virtual concat)
-            if (all(r in (0, 1) for r in ratio) and ((self.subpixel_plus and not is2d) or not any(ratio)) and C0 > 0 and C1 > 0 and C0 % 4 == 0
+            # (2-D: exact 2x only unless `native_2d_subpixel_plus` is set — without it an n -> 2n + 1 level keeps its virtual concat)
+            if (all(r in (0, 1) for r in ratio) and ((self.subpixel2d_plus if is2d else self.subpixel_plus) or not any(ratio)) and C0 > 0 and C1 > 0 and C0 % 4 == 0
                     and C1 % 4 == 0 and c1.conv.out_channels % 4 == 0):
                 out[id(c1.conv.weight)] = (C0, C1)
                 if any(ratio):
@@ -165,13 +171,17 @@ class ConvLayers:
                 and src.H == 2 * src.H1 and src.W == 2 * src.W1):
             # `native_2d_subpixel`, an exact-2x level of a 2-D net: every low-res pixel is replicated exactly 4x
             return st0, dataclasses.replace(st1, scale=4.0)
-        plus = src.plus
+        plus = self._src_plus(src) if self.is2d else src.plus
         if st0 is not None and plus is not None and any(plus) and self.fused_stats and src.C1 % 4 == 0 and src.t1.dtype == _F32:
             # n -> 2n + 1 along some axes: the first low-res cell of such an axis has three children, every other cell two — the sums of
             # the upsampled half as a weighted pass over the LOW-RES tensor (round 6), the skip half from its producer
             st1w = pool.table(src.N, src.C1)
-            nat.call("u3d_chan_stats_children", dev.index, _stream(dev), _p(src.t1), src.N, src.D1, src.H1, src.W1, src.C1, *plus,
-                     _p(st1w.t))
+            if self.is2d:  # (`native_2d_subpixel_plus`: a low-res pixel has one child along z)
+                nat.call("u3d_chan_stats_children2d", dev.index, _stream(dev), _p(src.t1), src.N, src.H1, src.W1, src.C1, *plus[1:],
+                         _p(st1w.t))
+            else:
+                nat.call("u3d_chan_stats_children", dev.index, _stream(dev), _p(src.t1), src.N, src.D1, src.H1, src.W1, src.C1, *plus,
+                         _p(st1w.t))
             return st0, st1w
         st = pool.table(src.N, src.C, self.stat_reps)
         s = src.struct()
@@ -487,9 +497,11 @@ class ConvLayers:
         """weight gradient + the data gradient's split-K scratch (roles swapped)"""
         lib = nat.get_lib()
         if sub is not None:  # (`native_2d_subpixel`: skip slice on the conv2d kernels + the sub-pixel slice's block slots)
+            boxes = slab_boxes((1, H, W), (0, H % 2, W % 2), 2)  # (`native_2d_subpixel_plus`: the slab's weight-gradient launches)
             return max(lib.u3d_wgrad2d_workspace_floats(N, H, W, sub[0], Cout),
                        lib.u3d_subpixel2d_wgrad_workspace_floats(N, H // 2, W // 2, sub[1], Cout),
-                       lib.u3d_conv2d_workspace_floats(N, H, W, Cout, sub[0]))
+                       lib.u3d_conv2d_workspace_floats(N, H, W, Cout, sub[0]),
+                       *(lib.u3d_wgrad2d_workspace_floats(N, b[4] - b[1], b[5] - b[2], sub[1], Cout) for b in boxes))
         if not small and self._bf16_routed_weight(Cin, Cout, virtual):  # (the bf16 kernels' plans, csrc/u3d_conv2d_bf16.hip)
             sfx = "_c16" if self._c16(Cin, Cout) else ""
             return max(getattr(lib, f"u3d_wgrad2d_bf16{sfx}_workspace_floats")(N, H, W, Cin, Cout),
@@ -548,7 +560,8 @@ class ConvLayers:
             nat.call("u3d_subpixel_conv_fwd_win", dev.index, _stream(dev), _p(src.t1), _p(c.affine.view(-1)[2 * C0:]), c.Ctot * 2,
                      _p(self.images.get(conv.weight, Kind.UP_FWD, dev, pair)), _p(part), N, D1, H1, W1, C1, Cout, win,
                      flops=128.0 * C1 * Cout * N * D1 * H1 * W1)
-            s_up = src.up_only_struct(c.affine_hi if c.affine_hi is not None else c.affine[:, C0:].contiguous())
+            a_hi = c.affine_hi if c.affine_hi is not None else c.affine[:, C0:].contiguous()  # (held: the struct keeps only its pointer)
+            s_up = src.up_only_struct(a_hi)
             wp1 = self.images.get(conv.weight, Kind.SLAB_FWD, dev, pair)  # 27-tap forward image of the upsampled channels (slab launches)
             for box in slab_boxes((D, H, W), plus, 2):
                 nat.call("u3d_conv3d_box", dev.index, _stream(dev), ctypes.byref(s_up), _p(wp1), _p(part), N, D, H, W, Cout,
@@ -577,13 +590,28 @@ class ConvLayers:
         # `native_2d_subpixel`: the upsampled half as 4 parity-class 2x2 convolutions over the low-res tensor (4/9 of the multiply-adds,
         # csrc/u3d_subpix2d.hip), then the skip half, whose epilogue adds the partial sums before ReLU / statistics (u3d_conv2d_res_reps)
         dev, conv, src, N, H, W, Cout = c.dev, c.conv, c.src, c.N, c.H, c.W, c.Cout
-        assert c.D == 1 and H == 2 * src.H1 and W == 2 * src.W1
+        plus = self._src_plus(src)
+        assert c.D == 1 and H == 2 * src.H1 + plus[1] and W == 2 * src.W1 + plus[2]
         pair = C0, C1 = c.sub[id(conv.weight)]
         ystats = c.take_stats(self.stat_reps)
         part = _empty((N, 1, H, W, Cout), dtype=_F32, device=dev)
-        nat.call("u3d_subpixel2d_conv_fwd", dev.index, _stream(dev), _p(src.t1), _p(c.affine.view(-1)[2 * C0:]), c.Ctot * 2,
-                 _p(self.images.get(conv.weight, Kind.UP_FWD2D, dev, pair)), _p(part), N, src.H1, src.W1, C1, Cout, None, 0,
-                 flops=32.0 * C1 * Cout * N * src.H1 * src.W1)
+        if any(plus):
+            # `native_2d_subpixel_plus`, n -> 2n + 1 along the axes with plus = 1: the sub-pixel kernel writes the window d = u + plus, the 3x3
+            # kernel the slab d < 2 of those axes (overwriting the window's first row / column, which misses the extra copy of low[0])
+            nat.call("u3d_subpixel2d_conv_fwd_win", dev.index, _stream(dev), _p(src.t1), _p(c.affine.view(-1)[2 * C0:]), c.Ctot * 2,
+                     _p(self.images.get(conv.weight, Kind.UP_FWD2D, dev, pair)), _p(part), N, src.H1, src.W1, C1, Cout,
+                     (ctypes.c_int * 4)(H, W, *plus[1:]), flops=32.0 * C1 * Cout * N * src.H1 * src.W1)
+            a_hi = c.affine_hi if c.affine_hi is not None else c.affine[:, C0:].contiguous()  # (held: the struct keeps only its pointer)
+            s_up = src.up_only_struct(a_hi)
+            wp1 = self.images.get(conv.weight, Kind.SLAB_FWD2D, dev, pair)
+            for box in slab_boxes((1, H, W), plus, 2):
+                nat.call("u3d_conv2d_box", dev.index, _stream(dev), ctypes.byref(s_up), _p(wp1), _p(part), N, H, W, Cout,
+                         (ctypes.c_int * 4)(box[1], box[2], box[4], box[5]), None, None,
+                         flops=18.0 * C1 * Cout * N * (box[4] - box[1]) * (box[5] - box[2]))
+        else:
+            nat.call("u3d_subpixel2d_conv_fwd", dev.index, _stream(dev), _p(src.t1), _p(c.affine.view(-1)[2 * C0:]), c.Ctot * 2,
+                     _p(self.images.get(conv.weight, Kind.UP_FWD2D, dev, pair)), _p(part), N, src.H1, src.W1, C1, Cout, None, 0,
+                     flops=32.0 * C1 * Cout * N * src.H1 * src.W1)
         a0 = c.affine_lo if c.affine_lo is not None else c.affine[:, :C0].contiguous()
         s0 = VSrc(src.t0).struct(a0)
         need = nat.get_lib().u3d_conv2d_workspace_floats(N, H, W, C0, Cout)  # split-K scratch on small grids
@@ -870,7 +898,8 @@ class ConvLayers:
             nat.call("u3d_subpixel_conv_wgrad_win", dev.index, _stream(dev), _p(src.t1), _p(rec.affine.view(-1)[2 * C0:]), Ct * 2,
                      _p(c.dz), _p(dwv[C0 * 27:]), Ct, c.N, src.D1, src.H1, src.W1, C1, c.Cout, _p(ws), ws.numel(), win,
                      flops=128.0 * C1 * c.Cout * c.N * src.D1 * src.H1 * src.W1)
-            s_up = src.up_only_struct(rec.affine_hi if rec.affine_hi is not None else rec.affine[:, C0:].contiguous())
+            a_hi = rec.affine_hi if rec.affine_hi is not None else rec.affine[:, C0:].contiguous()  # (held across the loop, as above)
+            s_up = src.up_only_struct(a_hi)
             slice_view = dwv.view(c.Cout, Ct, 27)[:, C0:, :]
             for box in slab_boxes((c.D, c.H, c.W), plus, 2):
                 tmp = _empty((c.Cout, C1, 27), dtype=_F32, device=dev)
@@ -1011,8 +1040,28 @@ class ConvLayers:
         C0, C1 = rec.sub
         Ct = src.C
         dwv = cx.gview(rec.idx_w)
-        nat.call("u3d_subpixel2d_conv_wgrad", dev.index, _stream(dev), _p(src.t1), _p(rec.affine.view(-1)[2 * C0:]), Ct * 2, _p(c.dz),
-                 _p(dwv[C0 * 9:]), Ct, c.N, src.H1, src.W1, C1, c.Cout, _p(ws), ws.numel(), flops=32.0 * C1 * c.Cout * c.N * src.H1 * src.W1)
+        plus = self._src_plus(src)
+        if any(plus):
+            # `native_2d_subpixel_plus`: outputs d >= 2 of the shifted axes through the windowed sub-pixel kernel, the slab d < 2 through the
+            # 3x3 kernel on disjoint boxes of dz (each into scratch, added to the same channel slice)
+            win = (ctypes.c_int * 6)(c.H, c.W, *plus[1:], *plus[1:])
+            nat.call("u3d_subpixel2d_conv_wgrad_win", dev.index, _stream(dev), _p(src.t1), _p(rec.affine.view(-1)[2 * C0:]), Ct * 2,
+                     _p(c.dz), _p(dwv[C0 * 9:]), Ct, c.N, src.H1, src.W1, C1, c.Cout, _p(ws), ws.numel(), win,
+                     flops=32.0 * C1 * c.Cout * c.N * src.H1 * src.W1)
+            # (a_hi is held across the loop: the struct keeps only its pointer, and `tmp` below must not be carved out of a freed copy)
+            a_hi = rec.affine_hi if rec.affine_hi is not None else rec.affine[:, C0:].contiguous()
+            s_up = src.up_only_struct(a_hi)
+            slice_view = dwv.view(c.Cout, Ct, 9)[:, C0:, :]
+            for box in slab_boxes((1, c.H, c.W), plus, 2):
+                tmp = _empty((c.Cout, C1, 9), dtype=_F32, device=dev)
+                nat.call("u3d_conv2d_wgrad_box", dev.index, _stream(dev), ctypes.byref(s_up), _p(c.dz), _p(tmp), c.N, c.H, c.W, c.Cout,
+                         _p(ws), ws.numel(), (ctypes.c_int * 4)(box[1], box[2], box[4], box[5]),
+                         flops=18.0 * C1 * c.Cout * c.N * (box[4] - box[1]) * (box[5] - box[2]))
+                slice_view += tmp
+        else:
+            nat.call("u3d_subpixel2d_conv_wgrad", dev.index, _stream(dev), _p(src.t1), _p(rec.affine.view(-1)[2 * C0:]), Ct * 2, _p(c.dz),
+                     _p(dwv[C0 * 9:]), Ct, c.N, src.H1, src.W1, C1, c.Cout, _p(ws), ws.numel(),
+                     flops=32.0 * C1 * c.Cout * c.N * src.H1 * src.W1)
         a0 = rec.affine_lo if rec.affine_lo is not None else rec.affine[:, :C0].contiguous()
         s0 = VSrc(src.t0).struct(a0)
         nat.call("u3d_conv2d_wgrad_strided", dev.index, _stream(dev), ctypes.byref(s0), _p(c.dz), _p(dwv), Ct, c.N, c.H, c.W, c.Cout,
@@ -1033,9 +1082,31 @@ class ConvLayers:
         nat.call("u3d_conv2d_ex_reps", dev.index, _stream(dev), ctypes.byref(s_dz), _p(self.images.get(w, Kind.SKIP_DGRAD2D, dev, pair)), _p(dg0),
                  c.N, c.H, c.W, C0, 0, None, ctypes.byref(s_x0), _p(gst0.t), _p(ws), ws.numel(), gst0.reps,
                  flops=18.0 * C0 * c.Cout * c.N * c.H * c.W)
-        nat.call("u3d_subpixel2d_conv_dgrad_reps", dev.index, _stream(dev), _p(c.dz), _p(self.images.get(w, Kind.UP_DGRAD2D, dev, pair)),
-                 _p(src.t1), _p(dlow), _p(gst1.t), c.N, src.H1, src.W1, C1, c.Cout, gst1.reps,
-                 flops=32.0 * C1 * c.Cout * c.N * src.H1 * src.W1)
+        plus = self._src_plus(src)
+        if any(plus):
+            # `native_2d_subpixel_plus`: the share of the outputs d >= 2 from the windowed sub-pixel kernel; the slab's share as a
+            # full-resolution gradient of the upsampled channels on the three rows / columns it reaches (3x3 kernel on dz masked to the
+            # slab, into a scratch the size of each box — never a full-resolution tensor), folded into the first low-res cells of the
+            # shifted axes together with its part of the GroupNorm-backward sums (replica row 0)
+            win = (ctypes.c_int * 6)(c.H, c.W, *plus[1:], *plus[1:])
+            nat.call("u3d_subpixel2d_conv_dgrad_win", dev.index, _stream(dev), _p(c.dz), _p(self.images.get(w, Kind.UP_DGRAD2D, dev, pair)),
+                     _p(src.t1), _p(dlow), _p(gst1.t), c.N, src.H1, src.W1, C1, c.Cout, gst1.reps, win,
+                     flops=32.0 * C1 * c.Cout * c.N * src.H1 * src.W1)
+            wpd1 = self.images.get(w, Kind.SLAB_DGRAD2D, dev, pair)
+            mask = (ctypes.c_int * 2)(2 * plus[1], 2 * plus[2])
+            for box in slab_boxes((1, c.H, c.W), plus, 3):
+                y0, x0, y1, x1 = box[1], box[2], box[4], box[5]
+                dv = _empty((c.N, y1 - y0, x1 - x0, C1), dtype=_F32, device=dev)
+                nat.call("u3d_conv2d_box", dev.index, _stream(dev), ctypes.byref(s_dz), _p(wpd1), _p(dv), c.N, c.H, c.W, C1,
+                         (ctypes.c_int * 4)(y0, x0, y1, x1), mask, (ctypes.c_int * 4)(y1 - y0, x1 - x0, y0, x0),
+                         flops=18.0 * C1 * c.Cout * c.N * (y1 - y0) * (x1 - x0))
+                nat.call("u3d_nearest_childsum_add2d", dev.index, _stream(dev), _p(dv), _p(src.t1), _p(dlow), _p(gst1.t), c.N, src.H1,
+                         src.W1, C1, *plus[1:], (ctypes.c_int * 4)(y0, x0, y1, x1))
+                del dv
+        else:
+            nat.call("u3d_subpixel2d_conv_dgrad_reps", dev.index, _stream(dev), _p(c.dz), _p(self.images.get(w, Kind.UP_DGRAD2D, dev, pair)),
+                     _p(src.t1), _p(dlow), _p(gst1.t), c.N, src.H1, src.W1, C1, c.Cout, gst1.reps,
+                     flops=32.0 * C1 * c.Cout * c.N * src.H1 * src.W1)
         return (dg0, dlow), (gst0, gst1)
 
     def _wgrad_conv2d_bf16(self, c: "_BwdCall"):

@@ -37,6 +37,7 @@ class UNet3DEngine(ConvLayers):
         self.is2d = keys.native_2d  # (N,C,H,W) runs as (N,C,1,H,W): 3x3 convolutions on the `conv2d` families, 2x2 pooling
         self.stem = keys.native_2d_stem  # the first layer on the small-Cin 2-D kernels (`_small2d`)
         self.subpixel2d = keys.native_2d_subpixel  # exact-2x decoder levels on csrc/u3d_subpix2d.hip
+        self.subpixel2d_plus = keys.native_2d_subpixel_plus  # ... and the n -> 2n + 1 levels on a shifted window + the slab's box launches
         self.vcat = keys.native_2d_bf16_vcat  # a decoder's first conv reads its concat inside the bf16 kernels (`_bf16_vcat`)
         self.bf16_deconv = keys.native_2d_residual_bf16_deconv  # the decoders' ConvTranspose2d on the bf16 matrix pipe (`_bf16_convtr2d`)
         self.children = 4.0 if self.is2d else 8.0  # full-res voxels a low-res voxel of an exact-2x level stands for
@@ -414,8 +415,12 @@ class UNet3DEngine(ConvLayers):
                 skip_grad[lvl] = (dg0, C0, coef1, Ct)
                 if any(self._src_plus(src)):
                     # n -> 2n + 1 along some axes: the first low-res cell of such an axis has three children
-                    nat.call("u3d_gn_bwd_apply_children", dev.index, _stream(dev), _p(dlow), _p(src.t1), _p(coef1), Ct, C0, src.N, src.D1,
-                             src.H1, src.W1, C1, *src.plus, mk, _p(dzl))
+                    if self.is2d:  # (`native_2d_subpixel_plus`: one child along the z axis a 2-D tensor does not have)
+                        nat.call("u3d_gn_bwd_apply_children2d", dev.index, _stream(dev), _p(dlow), _p(src.t1), _p(coef1), Ct, C0, src.N,
+                                 src.H1, src.W1, C1, *self._src_plus(src)[1:], mk, _p(dzl))
+                    else:
+                        nat.call("u3d_gn_bwd_apply_children", dev.index, _stream(dev), _p(dlow), _p(src.t1), _p(coef1), Ct, C0, src.N,
+                                 src.D1, src.H1, src.W1, C1, *src.plus, mk, _p(dzl))
                 else:
                     # dlow already holds the children sums: (p*dlow + 8*(q*x + r)) * (x > 0) on the low-res producer (2-D: 4 children)
                     coef_up = coef_hi if coef_hi is not None else coef1[:, :, C0:] * self._up_scale(dev)

@@ -54,6 +54,8 @@ class Kind(enum.IntEnum):
     SKIP_DGRAD2D = enum.auto()
     UP_FWD2D = enum.auto()      # ... the pre-summed parity-class images of the remaining C1 (upsampled) channels
     UP_DGRAD2D = enum.auto()
+    SLAB_FWD2D = enum.auto()    # ... the plain 3x3 images of those C1 channels: slab launches of an n -> 2n + 1 level (`native_2d_subpixel_plus`)
+    SLAB_DGRAD2D = enum.auto()
 
 
 @dataclass(frozen=True)
@@ -115,6 +117,8 @@ _KINDS = {
                          half=1, up2d=True),
     Kind.UP_DGRAD2D: _Spec(lambda lib, ci, co, m: lib.u3d_subpixel2d_dgrad_packed_floats(co, ci), _F32,
                            "u3d_pack_subpixel2d_dgrad_weights", None, half=1, up2d=True),
+    Kind.SLAB_FWD2D: _Spec(_2d, _F32, "u3d_pack_weights2d_slice", 0, half=1),
+    Kind.SLAB_DGRAD2D: _Spec(_2d, _F32, "u3d_pack_weights2d_slice", 1, half=1),
 }
 _BF16_BOTH = 6  # batch row that writes BF16_FWD and, right behind it in one buffer, BF16_DGRAD from one read of the weight
 
@@ -239,7 +243,10 @@ class WeightImages:
         for w in self._each:  # 2-D images: one small launch per weight and image (u3d_pack_weights2d)
             pair = sub.get(id(w)) if sub else None
             if pair is not None:  # (`native_2d_subpixel`: the images of the two input-channel halves instead)
-                for kind in (Kind.SKIP_FWD2D, Kind.SKIP_DGRAD2D)[:nd] + (Kind.UP_FWD2D, Kind.UP_DGRAD2D)[:nd]:
+                kinds = (Kind.SKIP_FWD2D, Kind.SKIP_DGRAD2D)[:nd] + (Kind.UP_FWD2D, Kind.UP_DGRAD2D)[:nd]
+                if id(w) in plus:
+                    kinds += (Kind.SLAB_FWD2D, Kind.SLAB_DGRAD2D)[:nd]
+                for kind in kinds:
                     self.get(w, kind, dev, pair)
                 continue
             for kind in (Kind.FWD2D, Kind.DGRAD2D)[:nd]:

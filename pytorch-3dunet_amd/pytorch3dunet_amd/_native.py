@@ -488,6 +488,22 @@ _PROTOS = {
     "u3d_subpixel2d_wgrad_workspace_floats": (c_int64, [c_int, c_int, c_int, c_int, c_int]),
     "u3d_subpixel2d_conv_wgrad": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                                           c_int, c_int, c_void_p, c_int64]),
+    # ... on a shifted window + the slab launches of a level that upsamples n -> 2n + 1 (`native_2d_subpixel_plus`; win / box: int arrays)
+    "u3d_subpixel2d_conv_fwd_win": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                                            c_int, c_void_p]),
+    "u3d_subpixel2d_conv_dgrad_win": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                              c_int, c_int, c_int, c_void_p]),
+    "u3d_subpixel2d_conv_wgrad_win": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                                              c_int, c_int, c_void_p, c_int64, c_void_p]),
+    "u3d_conv2d_box": (c_int, [c_int, c_void_p, POINTER(U3DSrc), c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                               c_void_p]),
+    "u3d_conv2d_wgrad_box": (c_int, [c_int, c_void_p, POINTER(U3DSrc), c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t,
+                                     c_void_p]),
+    "u3d_chan_stats_children2d": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "u3d_gn_bwd_apply_children2d": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                            c_int, c_int, c_void_p]),
+    "u3d_nearest_childsum_add2d": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                           c_int, c_void_p]),
     # small-Cin first layer of a 2-D net (`native_2d_stem`; csrc/u3d_conv2d.hip)
     "u3d_conv2d_small_cin_fwd_variant": (c_int, [c_int, c_int, c_int, c_int, c_int]),
     "u3d_conv2d_small_cin_fwd_reps": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,

@@ -39,6 +39,8 @@ KEYS = (
         "the single-source 3x3 layers with both channel counts % 32 take bf16 MFMA operands; everything else stays fp32"),
     Key("native_2d_stem", "U3D_NATIVE_2D_STEM", DoubleConv, "native_2d", None, None, "u3d_conv2d.hip",
         "the first layer (Cin <= 4, Cout <= 32) on the small-Cin kernels, exact fp32; next to native_2d_bf16 also the % 16 layers (`_c16`)"),
+    Key("native_2d_subpixel_plus", "U3D_NATIVE_2D_SUBPIXEL_PLUS", DoubleConv, "native_2d_subpixel", None, None, "u3d_subpix2d.hip, u3d_conv2d.hip",
+        "also the levels that upsample n -> 2n + 1 along H and / or W: the same kernels on a shifted window + 3x3 box launches on the 2-pixel slab"),
     Key("native_2d_subpixel", "U3D_NATIVE_2D_SUBPIXEL", DoubleConv, "native_2d", None, ("native_2d_bf16", "the fp32 sub-pixel decoder path"),
         "u3d_subpix2d.hip", "the upsampled half of a decoder's first convolution at an exact-2x level as four 2x2 convolutions; no bf16 form"),
     Key("native_2d", "U3D_NATIVE_2D", None, None, None, None, "u3d_conv2d.hip",
@@ -82,6 +84,7 @@ def resolve(values: dict, is3d: bool, basic_module: type, compute_dtype):
                                  f"the two keys ({fp32}: true is the fp32 2-D path)")
             compute_dtype = k.precision
         if k.refuses is not None and _BY_NAME[k.refuses[0]] in on:
-            other = next(o.name for o in on if k.refuses[0] in (c.name for c in _chain(o)))  # (the most derived one)
-            raise ValueError(f"u3d: {k.name} is {k.refuses[1]}; {other} contradicts it — drop one of the two keys")
+            other = next(o.name for o in on if k.refuses[0] in (c.name for c in _chain(o)))  # (the most derived one ...
+            mine = next(o.name for o in on if k in _chain(o))  # ... on either side: a key inherits the refusal of the key it implies)
+            raise ValueError(f"u3d: {mine} is {k.refuses[1]}; {other} contradicts it — drop one of the two keys")
     return Native2D(**{k.name: True for k in on}), compute_dtype

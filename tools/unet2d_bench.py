@@ -43,7 +43,13 @@ its ms per step, its speed-up over the `native_2d` arm of the same run and the v
 than 5 % faster), the decoder levels it took, the 3x3 FLOPs per image it executes (16 instead of 36 multiply-adds per low-res pixel for
 the upsampled half of those levels) and the per-entry-point times of its convolution launches.
 
-  python tools/unet2d_bench.py [--configs confocal,dsb2018] [--batch N] [--steps 10] [--warmup 3] [--bf16] [--stem] [--vcat] [--subpixel]   (--batch: every config's own default)"""
+With --subpixel-plus (UNet2D configurations, next to --subpixel) the alternation gains the arm `native_2d_subpixel_plus: true` (also the
+levels that upsample n -> 2n + 1 along H and / or W — two of the three levels of the 515 x 512 confocal patch — on the same kernels through a
+shifted window, the 2-pixel slab on box launches of csrc/u3d_conv2d.hip).  The record adds its ms per step, its speed-up over the
+`native_2d_subpixel` arm of the same run and the verdict against the same bar (more than 5 % faster than that arm), the levels it took, the
+FLOPs it executes, its convolution launches by entry point and torch.cuda.max_memory_allocated over one step of every fp32 arm.
+
+  python tools/unet2d_bench.py [--configs confocal,dsb2018] [--batch N] [--steps 10] [--warmup 3] [--bf16] [--stem] [--vcat] [--subpixel] [--subpixel-plus]   (--batch: every config's own default)"""
 import argparse
 import json
 import os
@@ -100,7 +106,8 @@ def layer_flops_per_image(cfg, hw):
 def conv_flops_per_image(cfg, hw, subpixel=False):
     """18 * Cin * Cout * pixels summed over the 3x3 layers (one direction), counted from the module tree.  `subpixel`: the FLOPs the
     `native_2d_subpixel` arm EXECUTES — at a decoder level that upsamples by exactly 2 (C0, C1, Cout multiples of 4) the C1 upsampled
-    input channels of the first convolution cost 2 * 16 * C1 * Cout per LOW-RES pixel = 8 * C1 * Cout per output pixel instead of 18"""
+    input channels of the first convolution cost 2 * 16 * C1 * Cout per LOW-RES pixel = 8 * C1 * Cout per output pixel instead of 18;
+    `subpixel="plus"`: the `native_2d_subpixel_plus` arm — an n -> 2n + 1 level too, whose 2-pixel slab stays at 18 per output pixel"""
     from pytorch3dunet_amd.unet3d.model import get_model
 
     m = get_model(dict(cfg))
@@ -122,8 +129,11 @@ def conv_flops_per_image(cfg, hw, subpixel=False):
         for i, sc in enumerate((dec.basic_module.SingleConv1, dec.basic_module.SingleConv2)):
             ci, co = sc.conv.in_channels, sc.conv.out_channels
             c1 = (ci - co) if i == 0 else 0  # (a DoubleConv decoder's first conv: C0 = Cout skip channels, C1 = Cin - C0 upsampled)
-            if subpixel and i == 0 and h == 2 * h1 and w == 2 * w1 and c1 > 0 and c1 % 4 == 0 and (ci - c1) % 4 == 0 and co % 4 == 0:
-                tot += (18.0 * (ci - c1) + 8.0 * c1) * co * h * w
+            py, px = h - 2 * h1, w - 2 * w1
+            fits = (py, px) == (0, 0) or (subpixel == "plus" and py in (0, 1) and px in (0, 1))
+            if subpixel and i == 0 and fits and c1 > 0 and c1 % 4 == 0 and (ci - c1) % 4 == 0 and co % 4 == 0:
+                slab = h * w - (h - 2 * py) * (w - 2 * px)  # output pixels d < 2 of the shifted axes: the plain 3x3 kernel
+                tot += (18.0 * (ci - c1) * h * w + 8.0 * c1 * 4 * h1 * w1 + 18.0 * c1 * slab) * co
             else:
                 tot += 18.0 * ci * co * h * w
     return tot
@@ -137,6 +147,8 @@ def make(cfg, native, dev):
     extra = {}
     if native == "subpixel":
         extra, native = dict(native_2d_subpixel=True), True
+    elif native == "subpixel_plus":
+        extra, native = dict(native_2d_subpixel_plus=True), True
     elif native == "bf16_stem_vcat":
         extra, native = dict(native_2d_stem=True, native_2d_bf16_vcat=True), "bf16"
     elif native in ("stem", "bf16_stem"):
@@ -182,6 +194,7 @@ def main():
     ap.add_argument("--stem", action="store_true", help="also time the UNet2D step with native_2d_stem next to native_2d (and, with --bf16, next to native_2d_bf16)")
     ap.add_argument("--vcat", action="store_true", help="with --bf16 --stem: also time the UNet2D step with native_2d_bf16_vcat on top of them")
     ap.add_argument("--subpixel", action="store_true", help="also time the UNet2D step with native_2d_subpixel next to native_2d")
+    ap.add_argument("--subpixel-plus", action="store_true", help="also time the UNet2D step with native_2d_subpixel_plus (next to --subpixel)")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "unet2d_bench measures on the GPU"
     from pytorch3dunet_amd import _native as nat
@@ -207,6 +220,8 @@ def main():
                 paths.insert(paths.index("bf16") + 1, "bf16_stem")
                 if a.vcat:
                     paths.insert(paths.index("bf16_stem") + 1, "bf16_stem_vcat")
+        if a.subpixel_plus and not _residual(cfg):
+            paths.insert(1, "subpixel_plus")
         if a.subpixel and not _residual(cfg):
             paths.insert(1, "subpixel")
         runs = {p: make(cfg, p, dev) for p in paths}
@@ -285,6 +300,33 @@ def main():
                        subpixel_conv2d_gflop_fwd_per_image_executed=round(conv_flops_per_image(cfg, hw, subpixel=True) / 1e9, 2),
                        subpixel_conv_family_ms_per_step=round(sum(v["ms"] for v in spconv.values()), 3),
                        subpixel_conv_calls=calls(spconv))
+        if "subpixel_plus" in ms:
+            # the plus arm against the native_2d_subpixel arm of the same run (against native_2d without --subpixel); peak memory of one
+            # step per fp32 arm: a full-resolution slab scratch would show up here
+            def peak_bytes(path):
+                torch.cuda.synchronize()
+                torch.cuda.reset_peak_memory_stats(dev)
+                step(*runs[path], x, target, loss_fn)
+                torch.cuda.synchronize()
+                return torch.cuda.max_memory_allocated(dev)
+
+            base = "subpixel" if "subpixel" in ms else True
+            ppfam = family_step("subpixel_plus")
+            ppconv = {k: v for k, v in ppfam.items() if "conv2d" in k or "subpixel2d" in k}
+            eng = runs["subpixel_plus"][0]._get_engine()
+            taken = eng._subpixel_layers((1,) + tuple(hw))
+            ratio = best[base] / best["subpixel_plus"]
+            rec.update(subpixel_plus_ms_per_step=[round(v, 3) for v in ms["subpixel_plus"]],
+                       subpixel_plus_images_per_s=round(batch * 1000.0 / best["subpixel_plus"], 2),
+                       subpixel_plus_speedup_over_subpixel=round(ratio, 4) if base == "subpixel" else None,
+                       subpixel_plus_speedup_over_native_fp32=round(best[True] / best["subpixel_plus"], 4),
+                       subpixel_plus_bar="more than 1.05x the native_2d_subpixel arm of the same run",
+                       subpixel_plus_meets_bar=bool(ratio > 1.05) if base == "subpixel" else None,
+                       subpixel_plus_decoder_levels_taken=f"{len(taken)} of {len(eng.dec)} ({len(taken.plus)} of them n -> 2n + 1)",
+                       subpixel_plus_conv2d_gflop_fwd_per_image_executed=round(conv_flops_per_image(cfg, hw, subpixel="plus") / 1e9, 2),
+                       subpixel_plus_conv_family_ms_per_step=round(sum(v["ms"] for v in ppconv.values()), 3),
+                       subpixel_plus_conv_calls=calls(ppconv),
+                       subpixel_plus_peak_memory_bytes={str(p): peak_bytes(p) for p in paths if p in (True, "subpixel", "subpixel_plus")})
         if "bf16" in ms:
             bfam = family_step("bf16")
             bconv = {k: v for k, v in bfam.items() if "conv2d" in k}
