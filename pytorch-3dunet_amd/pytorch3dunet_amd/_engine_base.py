@@ -413,8 +413,10 @@ class ConvRec:
     idx_gw: int = -1  # indices into the flat parameter list
     idx_gb: int = -1
     idx_w: int = -1
-    small: bool = False  # ran through the small-Cin (first layer) kernels
+    family: str = "fp32"  # the `ConvLayers._FWD_KERNELS` row forward chose: what backward (`_bwd_families`) and the scratch sizing dispatch on
     sub: Optional[tuple] = None  # (C0, C1): the upsampled half ran as a sub-pixel convolution (csrc/u3d_subpix.hip)
+    plus: tuple = (0, 0, 0)      # a sub-pixel layer: per axis 1 where its level upsamples n -> 2n + 1 (`ConvLayers._src_plus`)
+    c16: bool = False            # a `conv2d_bf16` layer on the `_c16` entry points and `*_C16` images (`ConvLayers._c16`)
     pre_norm: bool = True        # GroupNorm on the conv input ('gc…'); False: `affine` is the identity table
     post: Optional[tuple] = None  # post-norm order ('cg…'): (z = [f_inner](conv output), its GroupNorm affine table, f_inner, slope); y = f(a*z + b)
     norm: Optional[str] = "g"    # 'g' GroupNorm, 'b' BatchNorm3d (mean_rstd is (C,2)), None: conv bias (idx_gb = its index)
@@ -424,6 +426,10 @@ class ConvRec:
     # GroupNorm finalize itself (u3d_gn_finalize_split) — the kernels that read ONE half as a plain tensor take these
     affine_lo: Optional[torch.Tensor] = None
     affine_hi: Optional[torch.Tensor] = None
+
+    @property
+    def small(self) -> bool:  # ran through the small-Cin (first layer) kernels
+        return self.family in ("small", "small2d")
 
 
 @dataclass

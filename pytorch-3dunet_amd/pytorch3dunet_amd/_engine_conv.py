@@ -1,7 +1,10 @@
 """One SingleConv / ResNetBlock convolution (reference buildingblocks.py:99-135) forward and backward on the native kernels: which
 kernel FAMILY runs a layer (first-layer small-Cin, sub-pixel decoder, split-fp32, bf16 operands / bf16 storage, fp32 MFMA) is decided
-in ONE place per direction (`_fwd_family` / `_bwd_family`) and dispatched through a table — a new family is a new entry, not a
-new flag inside the layer code.  Mixin of `engine.UNet3DEngine`."""
+ONCE, in forward (`_fwd_family`), and kept in the layer's record: `ConvRec.family`, with `sub`, `plus` and `c16` beside it.  Backward maps
+the recorded family to its (data-gradient, weight-gradient) families in one place (`_BWD_FAMILY`; `_bwd_families` holds the few
+decisions that are backward's own), the shared scratch is sized from the same record (`_family_ws_floats`), and every launcher reads the
+record instead of asking the routing rules again — a new family is a new entry in the tables, not a new flag inside the layer code.
+Mixin of `engine.UNet3DEngine`."""
 from __future__ import annotations
 
 import copy
@@ -51,6 +54,8 @@ class _ConvCall:
     b16: bool                            # bf16 activation storage
     affine_lo: Optional[torch.Tensor] = None  # sub-pixel layers: compact rows of `affine` for the skip / upsampled channels
     affine_hi: Optional[torch.Tensor] = None
+    plus: tuple = (0, 0, 0)              # `_src_plus` of a sub-pixel layer's source
+    c16: bool = False                    # a `conv2d_bf16` layer on the `_c16` envelope
 
     def take_stats(self, reps: int = 1) -> Optional[StatTable]:
         return self.pool.table(self.N, self.Cout, reps) if self.stats else None
@@ -72,7 +77,6 @@ class _BwdCall:
     H: int
     W: int
     Cout: int
-    bf16: bool   # both directions of this layer run on the bf16-operand kernels
     b16: bool    # bf16 activation storage
     job: object = None  # U3DGnBwdJob for the weight-gradient reduce launch to carry (the family that takes it sets it back to None)
     greps: int = 1      # replica rows requested for the GroupNorm-backward sums the fp32 data-gradient kernel writes (u3d_conv3d_ex_reps)
@@ -117,7 +121,8 @@ class ConvLayers:
 
     def _src_plus(self, src: VSrc):
         """`src.plus` of a sub-pixel layer's source; a 2-D net (D = D1 = 1 is no axis): (0, py, px) under `native_2d_subpixel_plus`, whose
-        sub-pixel levels may upsample n -> 2n + 1 along H and W; without it they are exact 2x"""
+        sub-pixel levels may upsample n -> 2n + 1 along H and W; without it they are exact 2x.  Asked by `_single_conv_fwd`, which records
+        the answer (`ConvRec.plus`, `_ConvCall.plus`: what every launcher and backward read), and by `_stats_of`, which runs before it"""
         if not self.is2d:
             return src.plus
         if not self.subpixel2d_plus or src.t1 is None:
@@ -164,14 +169,12 @@ class ConvLayers:
                 s = src.struct()
                 nat.call("u3d_chan_stats_reps", dev.index, _stream(dev), ctypes.byref(s), src.N, src.D, src.H, src.W, *_tab(st0))
             return st0, None
-        if st0 is not None and st1 is not None and src.exact2x and self.fused_stats:
-            # every low-res voxel is replicated exactly 8x: reuse the producer's sums
-            return st0, dataclasses.replace(st1, scale=8.0)
-        if (st0 is not None and st1 is not None and self.subpixel2d and self.fused_stats and src.D == 1
-                and src.H == 2 * src.H1 and src.W == 2 * src.W1):
-            # `native_2d_subpixel`, an exact-2x level of a 2-D net: every low-res pixel is replicated exactly 4x
-            return st0, dataclasses.replace(st1, scale=4.0)
-        plus = self._src_plus(src) if self.is2d else src.plus
+        # (a 2-D net, D = D1 = 1: H and W, and only under `native_2d_subpixel`)
+        exact2x = (self.subpixel2d and src.H == 2 * src.H1 and src.W == 2 * src.W1) if self.is2d else src.exact2x
+        if st0 is not None and st1 is not None and exact2x and self.fused_stats:
+            # every low-res voxel is replicated exactly 8x (2-D: every pixel 4x): reuse the producer's sums
+            return st0, dataclasses.replace(st1, scale=self.children)
+        plus = self._src_plus(src)
         if st0 is not None and plus is not None and any(plus) and self.fused_stats and src.C1 % 4 == 0 and src.t1.dtype == _F32:
             # n -> 2n + 1 along some axes: the first low-res cell of such an axis has three children, every other cell two — the sums of
             # the upsampled half as a weighted pass over the LOW-RES tensor (round 6), the skip half from its producer
@@ -243,7 +246,7 @@ class ConvLayers:
         coef_hi = None
         job.gstats_lo, job.C0, job.reps_lo = _p(lo.t), lo.C, lo.reps
         if hi is not None:
-            coef_hi = _empty((N, 3, hi.C), dtype=_F32, device=dev) if not any(self._src_plus(rec.src)) else None
+            coef_hi = _empty((N, 3, hi.C), dtype=_F32, device=dev) if not any(rec.plus) else None
             job.gstats_hi, job.C1, job.hi_scale, job.reps_hi, job.coef_hi = (_p(hi.t), hi.C, self.children, hi.reps,
                                                                              _p(coef_hi))
         else:
@@ -266,7 +269,7 @@ class ConvLayers:
             C = lo.C + hi.C
             if rec.norm == "g" and nat.get_lib().u3d_gn_bwd_finalize_split_supported(N, C, rec.G) == 1:
                 # ... and the low-res apply pass of an exact-2x level wants the upper channels' (p, 8q, 8r) as a compact table
-                coef_hi = _empty((N, 3, hi.C), dtype=_F32, device=dev) if not any(self._src_plus(rec.src)) else None
+                coef_hi = _empty((N, 3, hi.C), dtype=_F32, device=dev) if not any(rec.plus) else None
                 nat.call("u3d_gn_bwd_finalize_split", dev.index, _stream(dev), _p(lo.t), lo.C, _p(hi.t), hi.C, _p(rec.mean_rstd),
                          _p(rec.gn_w.detach()), N, rec.G, count, _p(gview(rec.idx_gw)), _p(gview(rec.idx_gb)), _p(coef),
                          self.children, _p(coef_hi))
@@ -289,8 +292,9 @@ class ConvLayers:
         """THE rule for a 2-D net in bf16 (`native_2d_bf16`, `native_2d_residual_bf16`), stated once: a 3x3 layer runs forward, data
         gradient and weight gradient on the `conv2d_bf16` family when it reads ONE real tensor (`virtual`: its input is a virtual concat)
         and `_bf16_layer` holds — with or without a residual in its epilogue (u3d_conv2d_bf16_res).  Asked in this form by
-        `_weight_images` (which weights get BF16_FWD2D / BF16_DGRAD2D images) and `_layer_ws_floats` (scratch), and through
-        `_bf16_routed` by `_fwd_family` and `_conv_bwd`, and by `_cat_bf16` for a decoder's written-out concat.  Under `native_2d_stem`
+        `_weight_images` (which weights get BF16_FWD2D / BF16_DGRAD2D images) and `_layer_ws_floats` (scratch of a layer not yet recorded),
+        and through `_bf16_routed` by `_fwd_family` (backward reads its answer from the record), and by `_cat_bf16` for a decoder's
+        written-out concat.  Under `native_2d_stem`
         the rule widens to both channel counts % 16 (the net's 16-channel stem layers); a layer only inside the wider rule runs on the
         `_c16` entry points with the `*_C16` images (`_c16`), a layer inside the old one keeps today's."""
         if virtual:
@@ -475,9 +479,10 @@ class ConvLayers:
         "conv2d_bf16": "_fwd_conv2d_bf16",  # u3d_conv2d_bf16.hip: ... except, in bf16, the single-source layers that fit (`_bf16_routed`)
         "small2d": "_fwd_small2d",    # u3d_conv2d.hip: ... and, under `native_2d_stem`, the first layer, Cin <= 4 (the 3-D `small` rule)
         "subpixel2d": "_fwd_subpixel2d",  # u3d_subpix2d.hip + u3d_conv2d.hip: `native_2d_subpixel`, cat(skip, nearest2x(low)), 4/9 of the MACs
+        "conv2d_bf16_src": "_fwd_conv2d_bf16_src",  # u3d_conv2d_bf16.hip: `native_2d_bf16_vcat`, a decoder's virtual concat read in place
     }
 
-    # ---- a 2-D net (`is2d`): small2d -> subpixel2d -> conv2d_bf16 | conv2d, stated once per direction --------------------------------
+    # ---- a 2-D net (`is2d`): small2d -> subpixel2d -> conv2d_bf16 | conv2d_bf16_src | conv2d ----------------------------------------
     def _fwd_family_2d(self, c: "_ConvCall", residual) -> str:
         if self._small2d(c.Ctot, c.Cout, c.src.t1 is not None) and residual is None:
             return "small2d"
@@ -485,30 +490,9 @@ class ConvLayers:
             return "subpixel2d"
         # (a decoder's first conv reaches here on its materialised concat when it fits: `_cat_bf16`; forward and data gradient
         # are covered together by the one channel rule; a residual rides in either family's epilogue)
-        return "conv2d_bf16" if self._bf16_routed(c.src, c.Cout) else "conv2d"
-
-    def _bwd_family_2d(self, c: "_BwdCall") -> str:
-        """data gradient and weight gradient alike (a small2d layer that needs a data gradient arrives with `c.bf16` False: `_conv_bwd`)"""
-        if c.rec.sub is not None:
-            return "subpixel2d"
-        return "conv2d_bf16" if c.bf16 else "conv2d"
-
-    def _layer_ws_floats_2d(self, N, H, W, Cin, Cout, sub, small, virtual):
-        """weight gradient + the data gradient's split-K scratch (roles swapped)"""
-        lib = nat.get_lib()
-        if sub is not None:  # (`native_2d_subpixel`: skip slice on the conv2d kernels + the sub-pixel slice's block slots)
-            boxes = slab_boxes((1, H, W), (0, H % 2, W % 2), 2)  # (`native_2d_subpixel_plus`: the slab's weight-gradient launches)
-            return max(lib.u3d_wgrad2d_workspace_floats(N, H, W, sub[0], Cout),
-                       lib.u3d_subpixel2d_wgrad_workspace_floats(N, H // 2, W // 2, sub[1], Cout),
-                       lib.u3d_conv2d_workspace_floats(N, H, W, Cout, sub[0]),
-                       *(lib.u3d_wgrad2d_workspace_floats(N, b[4] - b[1], b[5] - b[2], sub[1], Cout) for b in boxes))
-        if not small and self._bf16_routed_weight(Cin, Cout, virtual):  # (the bf16 kernels' plans, csrc/u3d_conv2d_bf16.hip)
-            sfx = "_c16" if self._c16(Cin, Cout) else ""
-            return max(getattr(lib, f"u3d_wgrad2d_bf16{sfx}_workspace_floats")(N, H, W, Cin, Cout),
-                       getattr(lib, f"u3d_conv2d_bf16{sfx}_workspace_floats")(N, H, W, Cout, Cin))
-        need = max(lib.u3d_wgrad2d_workspace_floats(N, H, W, Cin, Cout), lib.u3d_conv2d_workspace_floats(N, H, W, Cout, Cin))
-        # (a small layer: the one-pass backward, or — when a data gradient is needed — the fall-through to the fp32 family)
-        return max(need, lib.u3d_small_cin2d_bwd_workspace_floats(N, H, W, Cin, Cout)) if small else need
+        if not self._bf16_routed(c.src, c.Cout):
+            return "conv2d"
+        return "conv2d_bf16" if c.src.t1 is None else "conv2d_bf16_src"  # (`_bf16_vcat`: the `_src` entry points)
 
     def _fwd_family(self, c: "_ConvCall", residual) -> str:
         if self.is2d:
@@ -532,8 +516,8 @@ class ConvLayers:
 
     def _small2d(self, Cin: int, Cout: int, virtual: bool) -> bool:
         """THE rule for the small-Cin family of a 2-D net under `native_2d_stem`, the 3-D `small` rule: a single real source with
-        Cin <= 4 and Cout <= 32 (no residual: DoubleConv nets have none).  Asked by `_fwd_family`, `_weight_images` (such a layer gets no
-        packed image up front) and `_layer_ws_floats`."""
+        Cin <= 4 and Cout <= 32 (no residual: DoubleConv nets have none).  Asked by `_fwd_family` and `_weight_images` (such a layer gets no
+        packed image up front)."""
         return self.stem and self.small_cin and not virtual and Cin <= 4 and Cout <= 32
 
     def _fwd_small2d(self, c: "_ConvCall"):
@@ -552,7 +536,7 @@ class ConvLayers:
         ystats = c.take_stats(1 if self._split_fwd(C0, Cout) else self.stat_reps)
         part = _empty((N, D, H, W, Cout), dtype=_F32, device=dev)
         D1, H1, W1 = src.D1, src.H1, src.W1
-        plus = src.plus
+        plus = c.plus
         if any(plus):
             # n -> 2n + 1 along the axes with plus = 1: the sub-pixel kernel writes the window d = u + plus, the general kernel the slab
             # d < 2 of those axes (overwriting the window's first plane, which misses the extra copy of low[0])
@@ -590,7 +574,7 @@ class ConvLayers:
         # `native_2d_subpixel`: the upsampled half as 4 parity-class 2x2 convolutions over the low-res tensor (4/9 of the multiply-adds,
         # csrc/u3d_subpix2d.hip), then the skip half, whose epilogue adds the partial sums before ReLU / statistics (u3d_conv2d_res_reps)
         dev, conv, src, N, H, W, Cout = c.dev, c.conv, c.src, c.N, c.H, c.W, c.Cout
-        plus = self._src_plus(src)
+        plus = c.plus
         assert c.D == 1 and H == 2 * src.H1 + plus[1] and W == 2 * src.W1 + plus[2]
         pair = C0, C1 = c.sub[id(conv.weight)]
         ystats = c.take_stats(self.stat_reps)
@@ -664,20 +648,8 @@ class ConvLayers:
         # bf16 MFMA operands, fp32 accumulation / epilogue on the D = 1 tensors (csrc/u3d_conv2d_bf16.hip): fused affine (rounded once
         # after it), ReLU and statistics as the fp32 kernel; with a residual (ResidualUNet2D's conv3 in a pre-norm order): out =
         # [relu](conv + residual), the fp32 residual added to the fp32 sum in the epilogue (u3d_conv2d_bf16_res)
-        assert c.D == 1
-        if c.src.t1 is not None:  # a decoder's virtual concat (`_bf16_vcat`): same plan, image and scratch, `_src` entry point
-            assert c.residual is None and not self._c16(c.Ctot, c.Cout)
-            wp = self.images.get(c.conv.weight, Kind.BF16_FWD2D, c.dev)
-            ystats = c.take_stats(self.stat_reps)
-            need = nat.get_lib().u3d_conv2d_bf16_workspace_floats(c.N, c.H, c.W, c.Ctot, c.Cout)
-            kws = _empty(need, dtype=_F32, device=c.dev) if need > 0 else None
-            yp, yr = _tab(ystats)
-            s = c.src.struct(c.affine)
-            nat.call("u3d_conv2d_bf16_src", c.dev.index, _stream(c.dev), ctypes.byref(s), _p(wp), _p(c.y), c.N, c.H, c.W, c.Cout, c.relu,
-                     yp, _p(kws), need, yr, flops=18.0 * c.Ctot * c.Cout * c.N * c.H * c.W)
-            return ystats
-        c16 = self._c16(c.Ctot, c.Cout)  # (a 16-channel stem layer under `native_2d_stem`: same kernels, `_c16` envelope)
-        assert not (c16 and c.residual is not None)
+        c16 = c.c16  # (a 16-channel stem layer under `native_2d_stem`: same kernels, `_c16` envelope)
+        assert c.D == 1 and c.src.t1 is None and not (c16 and c.residual is not None)
         wp = self.images.get(c.conv.weight, Kind.BF16_FWD2D_C16 if c16 else Kind.BF16_FWD2D, c.dev)
         ystats = c.take_stats(self.stat_reps)
         lib = nat.get_lib()
@@ -691,6 +663,19 @@ class ConvLayers:
             args.append(_p(c.residual))
         nat.call("u3d_conv2d_bf16_res" if c.residual is not None else ("u3d_conv2d_bf16_c16" if c16 else "u3d_conv2d_bf16"), *args,
                  flops=18.0 * c.Ctot * c.Cout * c.N * c.H * c.W)
+        return ystats
+
+    def _fwd_conv2d_bf16_src(self, c: "_ConvCall"):
+        # ... on a decoder's virtual concat (`_bf16_vcat`): same plan, image and scratch, `_src` entry point
+        assert c.D == 1 and c.residual is None and not c.c16
+        wp = self.images.get(c.conv.weight, Kind.BF16_FWD2D, c.dev)
+        ystats = c.take_stats(self.stat_reps)
+        need = nat.get_lib().u3d_conv2d_bf16_workspace_floats(c.N, c.H, c.W, c.Ctot, c.Cout)
+        kws = _empty(need, dtype=_F32, device=c.dev) if need > 0 else None
+        yp, yr = _tab(ystats)
+        s = c.src.struct(c.affine)
+        nat.call("u3d_conv2d_bf16_src", c.dev.index, _stream(c.dev), ctypes.byref(s), _p(wp), _p(c.y), c.N, c.H, c.W, c.Cout, c.relu,
+                 yp, _p(kws), need, yr, flops=18.0 * c.Ctot * c.Cout * c.N * c.H * c.W)
         return ystats
 
     def _fwd_fp32(self, c: "_ConvCall"):
@@ -734,15 +719,17 @@ class ConvLayers:
         # BatchNorm3d without running estimates normalises with batch statistics in eval mode too (_norm_finalize)
         bn_training = (bool(gn.training) or gn.running_mean is None) if spec.norm == "b" else True
         split = None  # sub-pixel layers: compact (N,C0,2) / (N,C1,2) copies of the affine rows, written by the finalize launch
+        pair = sub.get(id(conv.weight)) if (sub and src.t1 is not None and residual is None) else None  # (C0, C1) of a sub-pixel layer
+        plus = self._src_plus(src) if pair is not None else (0, 0, 0)
         if post:
             affine, mean_rstd = self._identity_affine(N, Ctot, dev), None
         else:
             affine = _empty((N, Ctot, 2), dtype=_F32, device=dev)
-            if spec.norm == "g" and src.t1 is not None and residual is None and sub and id(conv.weight) in sub:
+            if spec.norm == "g" and pair is not None:
                 # sub-pixel layer: its two halves are read by different kernels as plain tensors
-                Cs0, Cs1 = sub[id(conv.weight)]
+                Cs0, Cs1 = pair
                 split = (Cs0, _empty((N, Cs0, 2), dtype=_F32, device=dev),
-                         _empty((N, Cs1, 2), dtype=_F32, device=dev) if any(self._src_plus(src)) else None)
+                         _empty((N, Cs1, 2), dtype=_F32, device=dev) if any(plus) else None)
             mean_rstd = self._norm_finalize(spec.norm, gn, *st_in, G, float(D * H * W), affine, dev, split)
         # y_out: recomputation under activation checkpointing rewrites the (still alive) block output in place with the
         # bit-identical values instead of allocating a second copy
@@ -753,25 +740,24 @@ class ConvLayers:
         y = y_out if (y_out is not None and not post) else _empty((N, D, H, W, Cout), dtype=src.t0.dtype if b16 else _F32, device=dev)
         # ---- the convolution itself: ONE decision (which kernel family), then the family's launcher from the table
         call = _ConvCall(dev, conv, src, affine, y, N, D, H, W, Ctot, Cout, relu, bool(want_stats and self.fused_stats), pool, conv_res,
-                         sub, b16, *(split[1:] if split is not None else (None, None)))
+                         sub, b16, *(split[1:] if split is not None else (None, None)), plus)
         family = self._fwd_family(call, residual)
-        small = family in ("small", "small2d")
+        call.c16 = family == "conv2d_bf16" and self._c16(Ctot, Cout)
         dmod = getattr(sc, "dropout", None) if spec.drop == "d" else (getattr(sc, "dropout2d", None) if spec.drop == "D" else None)
+        rec = None
+        if tape is not None:
+            # (the routing above included; the normal path completes it at the end: a post-norm layer's output and statistics, the dropout)
+            rec = ConvRec(name=name, src=src, affine=affine, mean_rstd=mean_rstd, y=y, gn_w=gn.weight if gn is not None else None,
+                          conv_w=conv.weight, G=G, idx_gw=self._pindex[id(gn.weight)] if gn is not None else -1,
+                          idx_gb=self._pindex[id(gn.bias)] if gn is not None else self._pindex[id(conv.bias)],
+                          idx_w=self._pindex[id(conv.weight)], family=family, sub=pair, plus=plus, c16=call.c16, pre_norm=not post,
+                          norm=spec.norm, bn_training=bn_training, affine_lo=call.affine_lo, affine_hi=call.affine_hi)
+            tape.convs.append(rec)
         # record_only (recomputation under activation checkpointing, the block's LAST convolution): y_out still holds this layer's final
         # output — the block output the forward pass kept — so only what backward needs beside it is rebuilt (the GroupNorm tables of
         # the layer's input, above): no convolution launch, no in-place activation pass.  Not for post-norm orders (backward wants the
         # pre-norm tensor z) and not under dropout (its mask belongs to the record).
         if record_only and y_out is not None and not post and not (dmod is not None and dmod.training and dmod.p > 0.0):
-            if tape is not None:
-                nw = gn.weight if gn is not None else None
-                tape.convs.append(
-                    ConvRec(name, src, affine, mean_rstd, y, nw, conv.weight, G,
-                            self._pindex[id(gn.weight)] if gn is not None else -1,
-                            self._pindex[id(gn.bias)] if gn is not None else self._pindex[id(conv.bias)],
-                            self._pindex[id(conv.weight)], small,
-                            sub.get(id(conv.weight)) if (sub and src.t1 is not None and residual is None) else None,
-                            not post, None, spec.norm, bn_training, None, call.affine_lo, call.affine_hi)
-                )
             return y, None
         ystats = getattr(self, self._FWD_KERNELS[family])(call)
         post_rec = None
@@ -815,16 +801,8 @@ class ConvLayers:
                 nat.call("u3d_affine_act_fwd", dev.index, _stream(dev), _p(y), _p(table), N, D * H * W, Cout, ACT_NONE, 0.0, _p(y))
                 drop_rec = ("D", table)
             ystats = None  # the epilogue's sums describe the tensor before the dropout
-        if tape is not None:
-            nw = gn.weight if gn is not None else None
-            tape.convs.append(
-                ConvRec(name, src, affine, mean_rstd, y, nw, conv.weight, G,
-                        self._pindex[id(gn.weight)] if gn is not None else -1,
-                        self._pindex[id(gn.bias)] if gn is not None else self._pindex[id(conv.bias)],
-                        self._pindex[id(conv.weight)], small,
-                        sub.get(id(conv.weight)) if (sub and src.t1 is not None and residual is None) else None,
-                        not post, post_rec, spec.norm, bn_training, drop_rec, call.affine_lo, call.affine_hi)
-            )
+        if rec is not None:
+            rec.mean_rstd, rec.y, rec.post, rec.drop = mean_rstd, y, post_rec, drop_rec
         return y, ystats
 
     # ---- backward kernel families ---------------------------------------------------------------------------------------------------
@@ -847,25 +825,24 @@ class ConvLayers:
         "subpixel2d": "_dgrad_subpixel2d",  # u3d_conv2d.hip (skip half) + u3d_subpix2d.hip (upsampled half at LOW resolution)
     }
 
-    def _wgrad_family(self, c: "_BwdCall") -> str:
-        if self.is2d:
-            return self._bwd_family_2d(c)
-        if c.bf16 and c.Cout % 32 == 0:  # (Cout % 64 == 32 since round 4: 64-column blocks with a zero upper half)
-            return "bf16"
-        if c.rec.sub is not None:
-            return "subpixel"
-        if self.overlap_small_wgrad and c.N * c.D * c.H * c.W <= c.cx.SIDE_MAX_VOXELS and self.debug is None:
-            return "fp32_side"
-        return "fp32"
+    # the family forward recorded (`ConvRec.family`, a row of _FWD_KERNELS) -> the family of its two gradients, where the name differs: the
+    # small families when a data gradient is needed, the split forward, the `_src` entry points (which the `conv2d_bf16` launchers call)
+    _BWD_FAMILY = {"small": "fp32", "f32s": "fp32", "small2d": "conv2d", "conv2d_bf16_src": "conv2d_bf16"}
 
-    def _dgrad_family(self, c: "_BwdCall") -> str:
-        if self.is2d:
-            return self._bwd_family_2d(c)
-        if c.rec.sub is not None:
-            return "subpixel"
-        if c.src.t1 is None and not c.rec.small and self._split_dgrad(c.src.C, c.Cout):
-            return "f32s"
-        return "bf16" if c.bf16 else "fp32"
+    def _bwd_families(self, cx, rec: ConvRec, need_dg=True):
+        """(data-gradient family, weight-gradient family) of a recorded layer: the table's answer, but for the decisions that are backward's
+        own.  (None, None): the small families' one-pass backward (dw and the GroupNorm-backward sums, no data gradient)."""
+        if rec.small and not need_dg:
+            return None, None
+        dgrad = wgrad = self._BWD_FAMILY.get(rec.family, rec.family)
+        src, Cout = rec.src, rec.y.shape[-1]
+        if rec.family in ("f32s", "fp32") and src.t1 is None and self._split_dgrad(src.C, Cout):
+            dgrad = "f32s"  # (the forward's channel rule with the roles swapped: 16 -> 32 is split forward only, 32 -> 16 backward only)
+        if wgrad == "bf16" and Cout % 32 != 0:  # (Cout % 64 == 32 since round 4: 64-column blocks with a zero upper half)
+            wgrad = "fp32"
+        if wgrad == "fp32" and self.overlap_small_wgrad and src.N * src.D * src.H * src.W <= cx.SIDE_MAX_VOXELS and self.debug is None:
+            wgrad = "fp32_side"  # (U3D_SIDE_VOXELS, off by default)
+        return dgrad, wgrad
 
     def _wgrad_bf16(self, c: "_BwdCall"):
         cx, dev, src, rec = c.cx, c.cx.dev, c.src, c.rec
@@ -890,7 +867,7 @@ class ConvLayers:
         C0, C1 = rec.sub
         Ct = src.C
         dwv = cx.gview(rec.idx_w)
-        plus = src.plus
+        plus = rec.plus
         if any(plus):
             # n -> 2n + 1: outputs d >= 2 of the shifted axes through the windowed sub-pixel kernel, the slab d < 2 through the general
             # kernel on disjoint boxes of dz (each into scratch, added to the same channel slice)
@@ -949,7 +926,7 @@ class ConvLayers:
         dg0 = _empty((Nn, Dd, Hh, Ww, C0), dtype=_F32, device=dev)
         dlow = _empty_like(src.t1)
         split0 = self._split_dgrad(C0, Cout)
-        plus = src.plus
+        plus = rec.plus
         gst0 = pool.table(Nn, C0, 1 if split0 else c.greps)
         gst1 = pool.table(Nn, C1, 1 if any(plus) else c.greps)  # (the windowed form of an n -> 2n + 1 level keeps one row)
         if split0:
@@ -964,7 +941,6 @@ class ConvLayers:
             nat.call("u3d_conv3d_ex_reps", dev.index, _stream(dev), ctypes.byref(s_dz), _p(self.images.get(w, Kind.SKIP_DGRAD, dev, pair)), _p(dg0),
                      Nn, Dd, Hh, Ww, C0, 0, None, ctypes.byref(s_x0), _p(gst0.t), None, _p(ws), ws.numel(), gst0.reps,
                      flops=54.0 * C0 * Cout * Nn * Dd * Hh * Ww)
-        plus = src.plus
         if any(plus):
             # n -> 2n + 1: the share of the outputs d >= 2 from the windowed sub-pixel kernel; the slab's share as a full-resolution
             # gradient of the upsampled channels inside the slab's dilation (general kernel on dz masked to the slab), folded into the
@@ -1040,7 +1016,7 @@ class ConvLayers:
         C0, C1 = rec.sub
         Ct = src.C
         dwv = cx.gview(rec.idx_w)
-        plus = self._src_plus(src)
+        plus = rec.plus
         if any(plus):
             # `native_2d_subpixel_plus`: outputs d >= 2 of the shifted axes through the windowed sub-pixel kernel, the slab d < 2 through the
             # 3x3 kernel on disjoint boxes of dz (each into scratch, added to the same channel slice)
@@ -1082,7 +1058,7 @@ class ConvLayers:
         nat.call("u3d_conv2d_ex_reps", dev.index, _stream(dev), ctypes.byref(s_dz), _p(self.images.get(w, Kind.SKIP_DGRAD2D, dev, pair)), _p(dg0),
                  c.N, c.H, c.W, C0, 0, None, ctypes.byref(s_x0), _p(gst0.t), _p(ws), ws.numel(), gst0.reps,
                  flops=18.0 * C0 * c.Cout * c.N * c.H * c.W)
-        plus = self._src_plus(src)
+        plus = rec.plus
         if any(plus):
             # `native_2d_subpixel_plus`: the share of the outputs d >= 2 from the windowed sub-pixel kernel; the slab's share as a
             # full-resolution gradient of the upsampled channels on the three rows / columns it reaches (3x3 kernel on dz masked to the
@@ -1113,10 +1089,10 @@ class ConvLayers:
         # both operands rounded to bf16 while staged (g = a*x + b and dz), fp32 sums added in a fixed order; takes no GroupNorm-backward
         # job, like the fp32 2-D kernel
         cx, dev, src, rec = c.cx, c.cx.dev, c.src, c.rec
-        sfx = "_c16" if self._c16(src.C, c.Cout) else ""
+        sfx = "_c16" if rec.c16 else ""
         need = getattr(nat.get_lib(), f"u3d_wgrad2d_bf16{sfx}_workspace_floats")(c.N, c.H, c.W, src.C, c.Cout)
         ws = cx.ensure_ws(need)
-        if src.t1 is not None:  # (`_bf16_vcat`: the same plan on the virtual concat)
+        if rec.family == "conv2d_bf16_src":  # (`_bf16_vcat`: the same plan on the virtual concat)
             s = src.struct(rec.affine)
             nat.call("u3d_conv2d_wgrad_bf16_src", dev.index, _stream(dev), ctypes.byref(s), _p(c.dz), _p(cx.gview(rec.idx_w)), c.N, c.H,
                      c.W, c.Cout, _p(ws), ws.numel(), flops=18.0 * src.C * c.Cout * c.N * c.H * c.W)
@@ -1126,14 +1102,13 @@ class ConvLayers:
 
     def _dgrad_conv2d_bf16(self, c: "_BwdCall"):
         cx, dev, src, rec = c.cx, c.cx.dev, c.src, c.rec
-        c16 = self._c16(src.C, c.Cout)
-        sfx = "_c16" if c16 else ""
-        wpd = self.images.get(rec.conv_w, Kind.BF16_DGRAD2D_C16 if c16 else Kind.BF16_DGRAD2D, dev)
+        sfx = "_c16" if rec.c16 else ""
+        wpd = self.images.get(rec.conv_w, Kind.BF16_DGRAD2D_C16 if rec.c16 else Kind.BF16_DGRAD2D, dev)
         dg = _empty((c.N, c.D, c.H, c.W, src.C), dtype=_F32, device=dev)
         gst = cx.pool.table(c.N, src.C, c.greps)
         need = getattr(nat.get_lib(), f"u3d_conv2d_bf16{sfx}_workspace_floats")(c.N, c.H, c.W, c.Cout, src.C)  # roles swapped
         kws = cx.ensure_ws(need) if need > 0 else None
-        if src.t1 is not None:  # (`_bf16_vcat`: gx is the virtual concat; dz and dg are plain tensors of the full width)
+        if rec.family == "conv2d_bf16_src":  # (`_bf16_vcat`: gx is the virtual concat; dz and dg are plain tensors of the full width)
             s = src.struct()
             nat.call("u3d_conv2d_bf16_dgrad_src", dev.index, _stream(dev), _p(c.dz), _p(wpd), _p(dg), c.N, c.H, c.W, c.Cout,
                      ctypes.byref(s), _p(gst.t), _p(kws), need, gst.reps, flops=18.0 * src.C * c.Cout * c.N * c.H * c.W)
@@ -1188,7 +1163,9 @@ class ConvLayers:
                     nat.call("u3d_act_bwd", dev.index, _stream(dev), _p(dz_), _p(z), dz_.numel(), inner, islope, _p(dz_))
         if self.debug is not None:
             self.debug[rec.name + ".dz"] = dz_.clone()
-        if rec.small and not need_dg:
+        # ---- ONE decision, read off the record: the (data-gradient, weight-gradient) families
+        dgrad, wgrad = self._bwd_families(cx, rec, need_dg)
+        if wgrad is None:
             # one pass gives dw and the GroupNorm-backward sums; no data gradient needed (csrc/u3d_smallc.hip)
             gst = pool.table(Nn, src.C)
             if self.is2d:  # (D = 1: the 2-D twin, csrc/u3d_conv2d.hip)
@@ -1203,17 +1180,16 @@ class ConvLayers:
                 return None, self._identity_coef(Nn, src.C, dev), None
             coef = _empty((Nn, 3, src.C), dtype=_F32, device=dev)
             return None, coef, self._norm_bwd_finalize(cx, rec, (gst, None), float(Dd * Hh * Ww), coef)
-        bf16 = rec.sub is None and not rec.small and self._bf16_routed(src, Cout)  # (the forward's decision, `_fwd_family`)
         b16 = src.t0.dtype == torch.bfloat16  # bf16 activation storage
-        assert not b16 or (bf16 and Cout % 64 == 0 and dz_.dtype == torch.bfloat16)
-        call = _BwdCall(cx, rec, dz_, src, Nn, Dd, Hh, Ww, Cout, bf16, b16)
-        # ---- data gradient (+ the GroupNorm-backward sums of the conv input), then weight gradient: one family decision each.  The
-        # one-block reduction of those sums rides in the weight gradient's reduce launch where the family takes a job (round 6)
+        assert not b16 or (rec.family == "bf16" and Cout % 64 == 0 and dz_.dtype == torch.bfloat16)
+        call = _BwdCall(cx, rec, dz_, src, Nn, Dd, Hh, Ww, Cout, b16)
+        # ---- data gradient (+ the GroupNorm-backward sums of the conv input), then weight gradient.  The one-block reduction of those
+        # sums rides in the weight gradient's reduce launch where the family takes a job (round 6)
         # (replica rows for the sums only where the weight-gradient launch will take the reduction as a job: it reads them in that form)
-        if (self.stat_reps > 1 and rec.pre_norm and rec.norm == "g" and self._wgrad_family(call) in ("fp32", "subpixel")
+        if (self.stat_reps > 1 and rec.pre_norm and rec.norm == "g" and wgrad in ("fp32", "subpixel")
                 and nat.get_lib().u3d_conv3d_wgrad_job_supported(Nn, src.C, rec.G) == 1):
             call.greps = self.stat_reps
-        dg, gst = getattr(self, self._DGRAD_KERNELS[self._dgrad_family(call)])(call)
+        dg, gst = getattr(self, self._DGRAD_KERNELS[dgrad])(call)
         if self.debug is not None and rec.sub is None:
             self.debug[rec.name + ".dg"] = dg.clone()
         coef = coef_hi = None
@@ -1221,7 +1197,7 @@ class ConvLayers:
             coef = _empty((Nn, 3, src.C), dtype=_F32, device=dev)
             call.job, coef_hi = self._norm_bwd_job(cx, rec, gst, float(Dd * Hh * Ww), coef)
         had_job = call.job is not None
-        getattr(self, self._WGRAD_KERNELS[self._wgrad_family(call)])(call)
+        getattr(self, self._WGRAD_KERNELS[wgrad])(call)
         if not rec.pre_norm:
             return dg, self._identity_coef(Nn, src.C, dev), None  # no GroupNorm on the conv input: dx = dg
         if not had_job or call.job is not None:  # (no job, or a weight-gradient family without a reduce launch to carry it)
@@ -1249,31 +1225,48 @@ class ConvLayers:
     def _wgrad_workspace(self, tape, dev):
         return _empty(max(self._wgrad_workspace_floats(tape.convs), 4), dtype=_F32, device=dev)
 
-    def _layer_ws_floats(self, N, D, H, W, Cin, Cout, sub=None, small=False, virtual=False):
-        """scratch floats one 3x3x3 layer's backward needs from the shared buffer, for the kernels it will actually run"""
-        if self.is2d:
-            return self._layer_ws_floats_2d(N, H, W, Cin, Cout, sub, small, virtual)
+    def _family_ws_floats(self, family, N, D, H, W, Cin, Cout, sub=None, plus=(0, 0, 0), c16=False):
+        """scratch floats the backward of one layer of forward family `family` needs from the shared buffer: its weight gradient + its
+        data gradient's split-K scratch (roles swapped); `sub`, `plus`, `c16` as the layer's record holds them"""
         lib = nat.get_lib()
-        if small:
+        if family == "small":
             return lib.u3d_small_cin_bwd_workspace_floats(N, D, H, W, Cin, Cout)
-        if sub is not None:  # skip slice (fp32 kernels) + sub-pixel slice + the slab boxes of an n -> 2n + 1 level
-            # (a sub-pixel level's odd axes are its n -> 2n + 1 axes)
-            boxes = slab_boxes((D, H, W), (D % 2, H % 2, W % 2), 2)
+        if family == "subpixel":  # skip slice (fp32 kernels) + sub-pixel slice + the slab boxes of an n -> 2n + 1 level
+            boxes = slab_boxes((D, H, W), plus, 2)
             return max([lib.u3d_wgrad_workspace_floats(N, D, H, W, sub[0], Cout),
                         lib.u3d_subpixel_wgrad_workspace_floats(N, D // 2, H // 2, W // 2, sub[1], Cout),
                         lib.u3d_conv3d_workspace_floats(N, D, H, W, Cout, sub[0])] +
                        [lib.u3d_wgrad_workspace_floats(N, b[3] - b[0], b[4] - b[1], b[5] - b[2], sub[1], Cout) for b in boxes])
-        if not virtual and self._bf16_layer(Cin, Cout):
-            need = lib.u3d_conv3d_bf16_workspace_floats(N, D, H, W, Cout, Cin)  # data gradient: roles swapped
-            wg = lib.u3d_wgrad_bf16_workspace_floats(N, D, H, W, Cin, Cout)
-            return max(need, wg)
-        return max(lib.u3d_wgrad_workspace_floats(N, D, H, W, Cin, Cout), lib.u3d_conv3d_workspace_floats(N, D, H, W, Cout, Cin))
+        if family == "bf16":
+            return max(lib.u3d_conv3d_bf16_workspace_floats(N, D, H, W, Cout, Cin), lib.u3d_wgrad_bf16_workspace_floats(N, D, H, W, Cin, Cout))
+        if family in ("fp32", "f32s"):  # (the split data gradient grows the buffer itself, `_BwdCtx.ensure_ws`)
+            return max(lib.u3d_wgrad_workspace_floats(N, D, H, W, Cin, Cout), lib.u3d_conv3d_workspace_floats(N, D, H, W, Cout, Cin))
+        if family == "subpixel2d":  # (`native_2d_subpixel`: skip slice on the conv2d kernels + the sub-pixel slice's block slots)
+            boxes = slab_boxes((1, H, W), plus, 2)  # (`native_2d_subpixel_plus`: the slab's weight-gradient launches)
+            return max(lib.u3d_wgrad2d_workspace_floats(N, H, W, sub[0], Cout),
+                       lib.u3d_subpixel2d_wgrad_workspace_floats(N, H // 2, W // 2, sub[1], Cout),
+                       lib.u3d_conv2d_workspace_floats(N, H, W, Cout, sub[0]),
+                       *(lib.u3d_wgrad2d_workspace_floats(N, b[4] - b[1], b[5] - b[2], sub[1], Cout) for b in boxes))
+        if family in ("conv2d_bf16", "conv2d_bf16_src"):  # (the bf16 kernels' plans, csrc/u3d_conv2d_bf16.hip)
+            sfx = "_c16" if c16 else ""
+            return max(getattr(lib, f"u3d_wgrad2d_bf16{sfx}_workspace_floats")(N, H, W, Cin, Cout),
+                       getattr(lib, f"u3d_conv2d_bf16{sfx}_workspace_floats")(N, H, W, Cout, Cin))
+        need = max(lib.u3d_wgrad2d_workspace_floats(N, H, W, Cin, Cout), lib.u3d_conv2d_workspace_floats(N, H, W, Cout, Cin))
+        if family == "small2d":  # (the one-pass backward, or — when a data gradient is needed — the fall-through to the fp32 family)
+            return max(need, lib.u3d_small_cin2d_bwd_workspace_floats(N, H, W, Cin, Cout))
+        assert family == "conv2d", family
+        return need
+
+    def _layer_ws_floats(self, N, D, H, W, Cin, Cout, small=False):
+        """... by shape, of a single-source (Cin -> Cout) layer no forward has recorded yet (a checkpointed block that backward will
+        recompute): the family it will take, from the rules forward asks"""
+        if self.is2d:
+            family = "small2d" if small else ("conv2d_bf16" if self._bf16_routed_weight(Cin, Cout, False) else "conv2d")
+        else:
+            family = "small" if small else ("bf16" if self._bf16_layer(Cin, Cout) else "fp32")
+        return self._family_ws_floats(family, N, D, H, W, Cin, Cout, c16=family == "conv2d_bf16" and self._c16(Cin, Cout))
 
     def _wgrad_workspace_floats(self, convs):
         """scratch floats the backward kernels of these recorded layers need (one shared buffer, sized once per backward)"""
-        need = 0
-        for r in convs:
-            # (a virtual concat the bf16 kernels read in place, `_bf16_vcat`, takes their plans like a single-source layer)
-            need = max(need, self._layer_ws_floats(r.src.N, r.src.D, r.src.H, r.src.W, r.src.C, r.y.shape[-1], r.sub, r.small,
-                                                   r.src.t1 is not None and not self._bf16_vcat(r.src, r.y.shape[-1])))
-        return int(need)
+        return int(max((self._family_ws_floats(r.family, r.src.N, r.src.D, r.src.H, r.src.W, r.src.C, r.y.shape[-1], r.sub, r.plus, r.c16)
+                        for r in convs), default=0))

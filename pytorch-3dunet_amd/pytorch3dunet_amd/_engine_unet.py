@@ -413,14 +413,14 @@ class UNet3DEngine(ConvLayers):
             if r1.sub is not None:
                 dg0, dlow = dg1
                 skip_grad[lvl] = (dg0, C0, coef1, Ct)
-                if any(self._src_plus(src)):
+                if any(r1.plus):
                     # n -> 2n + 1 along some axes: the first low-res cell of such an axis has three children
                     if self.is2d:  # (`native_2d_subpixel_plus`: one child along the z axis a 2-D tensor does not have)
                         nat.call("u3d_gn_bwd_apply_children2d", dev.index, _stream(dev), _p(dlow), _p(src.t1), _p(coef1), Ct, C0, src.N,
-                                 src.H1, src.W1, C1, *self._src_plus(src)[1:], mk, _p(dzl))
+                                 src.H1, src.W1, C1, *r1.plus[1:], mk, _p(dzl))
                     else:
                         nat.call("u3d_gn_bwd_apply_children", dev.index, _stream(dev), _p(dlow), _p(src.t1), _p(coef1), Ct, C0, src.N,
-                                 src.D1, src.H1, src.W1, C1, *src.plus, mk, _p(dzl))
+                                 src.D1, src.H1, src.W1, C1, *r1.plus, mk, _p(dzl))
                 else:
                     # dlow already holds the children sums: (p*dlow + 8*(q*x + r)) * (x > 0) on the low-res producer (2-D: 4 children)
                     coef_up = coef_hi if coef_hi is not None else coef1[:, :, C0:] * self._up_scale(dev)
