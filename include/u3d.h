@@ -1183,6 +1183,56 @@ int u3d_convtr2d_wgrad_bf16_variant(int N, int H1, int W1, int Cin, int Cout, lo
 int u3d_convtr2d_wgrad_bf16(int device, u3d_stream_t stream, const float* x, const float* dt, float* dw, int N, int H1, int W1, int Cin,
                             int Cout, int accumulate, float* workspace, long long workspace_floats);
 
+/* ---- (Added, U3D_VERSION unchanged.)  Sub-pixel decoder convolutions of a UNet2D on the bf16 MFMA (`native_2d_bf16_subpixel: true`;
+ * csrc/u3d_conv2d_bf16.hip) ------
+ * The bf16 twins of u3d_subpixel2d_conv_fwd / _dgrad_reps / _wgrad on v_mfma_f32_32x32x16_bf16: the upsampled half of cat(skip,
+ * F.interpolate(low, nearest)) (buildingblocks.py:491,:614) under a decoder's first Conv2d at a level that upsamples by exactly 2 on both
+ * axes, as four parity-class 2x2 convolutions over the low-res grid — 4/9 of the multiply-adds in all three directions, the data gradient
+ * at low resolution with the children sum folded in.  Tensors in HBM are fp32 NHWC, accumulation is fp32.
+ * Rounding points: WEIGHTS — the pre-summed taps are added in fp32 from the fp32 master weight (ascending (ty, tx) order) and rounded ONCE
+ * to bf16, nearest even, by the pack kernel; ACTIVATIONS and dz — rounded once while staged to LDS, after the fp32 affine fmaf(x, a, b);
+ * zero padding applies after the affine and stays exactly 0.  Forward and data gradient are therefore not bit-equal to the 9-tap bf16
+ * kernels on a written-out concat (which round every tap); the weight gradient multiplies the same bf16 operands.
+ * Envelope: C1 % 32 == 0, Cout % 32 == 0, 16-byte aligned pointers (affine_sample_stride % 4 == 0), any H1, W1 >= 1, N * 2H1 * 2W1 <
+ * 2^31; outside it every entry point returns U3D_EINVAL (u3d_last_error) without launching anything.
+ *   u3d_pack_subpixel2d_weights_bf16  channels [c_off, c_off + C1) of the full (Cout, Cin_total, 3, 3) weight -> an image of
+ *              u3d_subpixel2d_bf16_packed_elems(C1, Cout, dgrad) 2-byte elements in the B-operand lane layout of u3d_pack_weights2d_bf16,
+ *              [K / 16 chunk][16][n-tile][64 lanes][8].  dgrad = 0 (forward, K = C1): entry (2a + b) * 4 + 2u + v = parity class (a, b), tap
+ *              half (u, v); per axis parity 0 reads low-res offsets (-1, 0) with taps {t0}, {t1 + t2}, parity 1 reads (0, +1) with
+ *              {t0 + t1}, {t2}.  dgrad = 1 (K = Cout): entry 4 ry + rx of the 4 x 4 stride-2 gather; per axis dz[2j - 1 .. 2j + 2] carry
+ *              t2, t1 + t2, t0 + t1, t0
+ *   u3d_subpixel2d_conv_fwd_bf16      the contract of u3d_subpixel2d_conv_fwd: low (N,H1,W1,C1), affine optional (sample n at affine + n *
+ *              affine_sample_stride floats), out (N,2*H1,2*W1,Cout) receives the plain partial sums (no ReLU, no statistics): add the skip
+ *              half with u3d_conv2d_bf16_res(skip, sliced image, residual = out).  One staged low-res halo of a 16-channel chunk serves all
+ *              four classes: nine A-fragment positions, sixteen MFMAs per M-tile and n-tile
+ *   u3d_subpixel2d_conv_dgrad_bf16    dlow (N,H1,W1,C1) from dz (N,2*H1,2*W1,Cout), de-interleaved into its four parity planes while
+ *              staged; optional gstats double[reps][N][C1][2] += (sum dlow, sum dlow * x_low), zeroed by the caller (needs x_low)
+ *   u3d_subpixel2d_conv_wgrad_bf16    the sixteen (class, tap half) 32 x 32 matrices over the low-res grid, written per block to its slot
+ *              of `workspace` (u3d_subpixel2d_wgrad_bf16_workspace_floats() floats, always needed) and folded into the nine taps by a
+ *              second kernel that adds the slots in slot order: no atomics, the same inputs give the same bits.  dw points at the first
+ *              upsampled input channel inside the (Cout, dw_cin_stride, 3, 3) gradient; only channels [dw, dw + C1) are written
+ *   u3d_pack_weights2d_bf16_slice     u3d_pack_weights2d_bf16 of the input channels [c_off, c_off + Cin) of a (Cout, cin_stride, 3, 3)
+ *              weight; c_off = 0, cin_stride = Cin writes the image of u3d_pack_weights2d_bf16 bit for bit
+ *   u3d_conv2d_wgrad_bf16_strided     u3d_conv2d_wgrad_bf16 writing a CHANNEL SLICE of a wider gradient: dw points at the slice's first
+ *              input channel inside (Cout, dw_cin_stride, 3, 3); dw_cin_stride = Cin writes u3d_conv2d_wgrad_bf16's dw bit for bit
+ * The skip half's forward and data gradient are u3d_conv2d_bf16_res / u3d_conv2d_bf16 on sliced images, unchanged. */
+long long u3d_subpixel2d_bf16_packed_elems(int C1, int Cout, int dgrad);
+int u3d_pack_subpixel2d_weights_bf16(int device, u3d_stream_t stream, const float* w, int Cout, int Cin_total, int c_off, int C1,
+                                     int dgrad, void* packed);
+int u3d_subpixel2d_conv_fwd_bf16(int device, u3d_stream_t stream, const float* low, const float* affine, long long affine_sample_stride,
+                                 const void* packed, float* out, int N, int H1, int W1, int C1, int Cout);
+int u3d_subpixel2d_conv_dgrad_bf16(int device, u3d_stream_t stream, const float* dz, const void* packed, const float* x_low, float* dlow,
+                                   double* gstats, int N, int H1, int W1, int C1, int Cout, int reps);
+long long u3d_subpixel2d_wgrad_bf16_workspace_floats(int N, int H1, int W1, int C1, int Cout);
+int u3d_subpixel2d_conv_wgrad_bf16(int device, u3d_stream_t stream, const float* low, const float* affine, long long affine_sample_stride,
+                                   const float* dz, float* dw, int dw_cin_stride, int N, int H1, int W1, int C1, int Cout,
+                                   float* workspace, long long workspace_floats);
+int u3d_pack_weights2d_bf16_slice(int device, u3d_stream_t stream, const float* w, int Cout, int Cin, int mode, int cin_stride, int c_off,
+                                  void* packed);
+int u3d_conv2d_wgrad_bf16_strided(int device, u3d_stream_t stream, const float* x, const float* affine, const float* dz, float* dw,
+                                  int dw_cin_stride, int N, int H, int W, int Cin, int Cout, float* workspace,
+                                  long long workspace_floats);
+
 /* ---- layout: NCDHW <-> NDHWC for multi-channel model inputs ------------------------------------ */
 int u3d_ncdhw_to_ndhwc(int device, u3d_stream_t stream, const float* src, float* dst, int N, int C, int64_t V);
 int u3d_ndhwc_to_ncdhw(int device, u3d_stream_t stream, const float* src, float* dst, int N, int C, int64_t V);

@@ -32,6 +32,13 @@
 // kernels (template parameter V / VC and a parameter struct with the second base): with both halves % 32 channels a staged 16-channel
 // chunk, a 32-channel weight-gradient block and a 32-channel n-tile of the data gradient's gx lie wholly in one source, so the choice
 // is a uniform branch; the affine, the rounding and the zero padding stay in c2b_stage8.  The single-source instantiations are unchanged.
+//
+// Sub-pixel decoder convolutions (`native_2d_bf16_subpixel`, the u3d_subpixel2d_*_bf16 entry points at the end of this file): the upsampled
+// half of a decoder's first convolution at an exact-2x level as four parity-class 2x2 convolutions over the low-res tensor.  Rounding
+// points: WEIGHTS — the pre-summed taps are added in fp32 from the fp32 master weight and rounded once to bf16, nearest even, by
+// pack_subpix2d_bf16_kernel; ACTIVATIONS and dz — once while staged to LDS, after the fp32 affine fmaf(x, a, b), through the same
+// c2b_stage8 (zero padding applies after the affine and stays exactly 0).  The skip half runs the kernels above on channel-sliced images
+// (u3d_pack_weights2d_bf16_slice, u3d_conv2d_wgrad_bf16_strided: the same kernels with a row stride, bit-identical at stride = Cin).
 #include <algorithm>
 
 #include "u3d_common.h"
@@ -105,8 +112,9 @@ __device__ __forceinline__ c2b_bf16x8 c2b_stage8(const f32x4& lo, const f32x4& h
 // weight packing: image [chunk][tap][ntile][lane][8] of B[k][n]: lane l holds k = 16 * chunk + 8 * (l >> 5) + j, column n = 32 * ntile +
 // (l & 31) — the B operand of v_mfma_f32_32x32x16_bf16; the A fragment of the same lane half is the 8 channels of its ds_read_b128.
 //   mode 0 (forward): B[k = ci][n = co] = w[co][ci][tap]           mode 1 (data gradient): B[k = co][n = ci] = w[co][ci][8 - tap]
+// (cs, coff: the input channels [coff, coff + Cin) of a (Cout, cs, 3, 3) weight — u3d_pack_weights2d_bf16_slice; cs = Cin, coff = 0: the whole)
 __global__ void pack_weights2d_bf16_kernel(const float* __restrict__ w, int Cout, int Cin, int mode, int K, int Nn, int ntg,
-                                           long long total, __bf16* __restrict__ packed) {
+                                           long long total, __bf16* __restrict__ packed, int cs, int coff) {
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
         const int j = (int)(i & 7);
         const int lane = (int)((i >> 3) & 63);
@@ -119,7 +127,7 @@ __global__ void pack_weights2d_bf16_kernel(const float* __restrict__ w, int Cout
         const int nn = nt * 32 + (lane & 31);
         float v = 0.f;
         if (k < K && nn < Nn)
-            v = mode == 0 ? w[((size_t)nn * Cin + k) * 9 + tap] : w[((size_t)k * Cin + nn) * 9 + (8 - tap)];
+            v = mode == 0 ? w[((size_t)nn * cs + coff + k) * 9 + tap] : w[((size_t)k * cs + coff + nn) * 9 + (8 - tap)];
         packed[i] = (__bf16)v;
     }
 }
@@ -469,6 +477,7 @@ struct Wgrad2dBf16Params {
     float* dst;  // nsplit == 1: dw; else workspace [nsplit][Cout][Cin][9]
     int N, H, W, Cin, Cout;
     int ty, tx, ncob, ncib, ntiles, tps;
+    int dstride;  // input channels per output channel of dst: Cin, or dw_cin_stride of u3d_conv2d_wgrad_bf16_strided writing dw directly
 };
 
 // ... of u3d_conv2d_wgrad_bf16_src: x is the skip half (N,H,W,C0), channels [C0, C0 + C1) of the virtual concat come from v1 (N,H1,W1,C1)
@@ -618,18 +627,19 @@ __global__ __launch_bounds__(256, 2) void conv2d_wgrad_bf16_kernel(const P p) {
             const float v = ((red[(0 * 32 + row) * 32 + col] + red[(1 * 32 + row) * 32 + col]) + red[(2 * 32 + row) * 32 + col]) +
                             red[(3 * 32 + row) * 32 + col];
             const int co = co0 + row, ci = ci0 + col;
-            if (co < Cout && ci < Cin) p.dst[(size_t)split * Cout * Cin * 9 + ((size_t)co * Cin + ci) * 9 + tap] = v;
+            if (co < Cout && ci < Cin) p.dst[(size_t)split * Cout * Cin * 9 + ((size_t)co * p.dstride + ci) * 9 + tap] = v;
         }
         __syncthreads();
     }
 }
 
-// dw[i] = sum over splits in split order (bitwise-reproducible)
-__global__ void conv2d_wgrad_bf16_reduce_kernel(const float* __restrict__ ws, int nsplit, long long total, float* __restrict__ dw) {
+// dw[i] = sum over splits in split order (bitwise-reproducible); row = 9 * Cin elements per output channel, drow = 9 * dw_cin_stride
+__global__ void conv2d_wgrad_bf16_reduce_kernel(const float* __restrict__ ws, int nsplit, long long total, float* __restrict__ dw, int row,
+                                                int drow) {
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
         float v = 0.f;
         for (int s = 0; s < nsplit; ++s) v += ws[(size_t)s * total + i];
-        dw[i] = v;
+        dw[row == drow ? i : (i / row) * drow + i % row] = v;
     }
 }
 
@@ -682,9 +692,13 @@ long long c2b_packed_elems(int Cin, int Cout, int mode, bool c16) {
     return (long long)(K / c2b::CC) * 9 * c2b_cdiv(Nn, 32) * 64 * 8;  // (a half n-tile is stored whole, its upper columns zero)
 }
 
-int c2b_pack_launch(const char* who, int device, u3d_stream_t stream, const float* w, int Cout, int Cin, int mode, void* packed, bool c16) {
+int c2b_pack_launch(const char* who, int device, u3d_stream_t stream, const float* w, int Cout, int Cin, int mode, void* packed, bool c16,
+                    int cin_stride = 0, int c_off = 0) {
     U3D_ENTER(device);
     U3D_REQUIRE(w && packed && Cout > 0 && Cin > 0 && (mode == 0 || mode == 1), "%s: bad argument", who);
+    if (cin_stride == 0) cin_stride = Cin;
+    U3D_REQUIRE(c_off >= 0 && c_off + Cin <= cin_stride, "%s: channels [%d, %d) do not lie inside a weight of %d input channels", who, c_off,
+                c_off + Cin, cin_stride);
     int K, Nn;
     c2b_dims(Cin, Cout, mode, K, Nn);
     U3D_REQUIRE(c2b_env_fwd(K, Nn, c16), "%s: mode %d of a (%d -> %d) weight is outside the bf16 envelope (contraction %% 16, "
@@ -694,7 +708,7 @@ int c2b_pack_launch(const char* who, int device, u3d_stream_t stream, const floa
     long long blocks = c2b_cdiv(total, 256);
     if (blocks > 4096) blocks = 4096;
     hipLaunchKernelGGL(pack_weights2d_bf16_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, w, Cout, Cin, mode, K, Nn,
-                       (int)c2b_cdiv(Nn, 32), total, reinterpret_cast<__bf16*>(packed));
+                       (int)c2b_cdiv(Nn, 32), total, reinterpret_cast<__bf16*>(packed), cin_stride, c_off);
     U3D_LAUNCH_CHECK();
     return 0;
 }
@@ -707,6 +721,14 @@ extern "C" long long u3d_packed_weight2d_bf16_c16_elems(int Cin, int Cout, int m
 
 extern "C" int u3d_pack_weights2d_bf16(int device, u3d_stream_t stream, const float* w, int Cout, int Cin, int mode, void* packed) {
     return c2b_pack_launch("u3d_pack_weights2d_bf16", device, stream, w, Cout, Cin, mode, packed, false);
+}
+
+// ... of the input channels [c_off, c_off + Cin) of a (Cout, cin_stride, 3, 3) weight (the skip half of a sub-pixel decoder layer): the
+// image of a (Cout, Cin, 3, 3) weight holding those channels; c_off = 0, cin_stride = Cin is u3d_pack_weights2d_bf16 bit for bit
+extern "C" int u3d_pack_weights2d_bf16_slice(int device, u3d_stream_t stream, const float* w, int Cout, int Cin, int mode, int cin_stride,
+                                             int c_off, void* packed) {
+    U3D_REQUIRE(cin_stride > 0, "u3d_pack_weights2d_bf16_slice: bad argument");
+    return c2b_pack_launch("u3d_pack_weights2d_bf16_slice", device, stream, w, Cout, Cin, mode, packed, false, cin_stride, c_off);
 }
 
 // ... of a layer with both channel counts % 16: the same fragment layout (for produced channels % 32 the same image bit for bit)
@@ -896,8 +918,10 @@ int c2b_wgrad_variant(int N, int H, int W, int Cin, int Cout, bool c16) {
 
 int c2b_wgrad_launch(const char* who, int device, u3d_stream_t stream, const float* x, const float* affine, const float* dz, float* dw,
                      int N, int H, int W, int Cin, int Cout, float* workspace, long long workspace_floats, bool c16,
-                     const u3d_src_t* vsrc = nullptr) {
+                     const u3d_src_t* vsrc = nullptr, int dw_cin_stride = 0) {
     U3D_ENTER(device);
+    if (dw_cin_stride == 0) dw_cin_stride = Cin;
+    U3D_REQUIRE(dw_cin_stride >= Cin, "%s: dw_cin_stride %d is smaller than Cin %d", who, dw_cin_stride, Cin);
     U3D_REQUIRE(c2b_env_wgrad(Cin, Cout, c16), "%s: (%d -> %d) channels are outside the bf16 envelope (both %% %d)", who, Cin, Cout,
                 c16 ? 16 : 32);
     U3D_REQUIRE(x && dz && dw && N > 0 && H > 0 && W > 0 && (long long)N * H * W < (1LL << 31), "%s: bad argument", who);
@@ -913,6 +937,7 @@ int c2b_wgrad_launch(const char* who, int device, u3d_stream_t stream, const flo
     p.dst = need ? workspace : dw;
     p.N = N, p.H = H, p.W = W, p.Cin = Cin, p.Cout = Cout;
     p.ty = pl.ty, p.tx = pl.tx, p.ncob = pl.ncob, p.ncib = pl.ncib, p.ntiles = pl.ntiles, p.tps = pl.tps;
+    p.dstride = need ? Cin : dw_cin_stride;
     const long long blocks = (long long)pl.nsplit * pl.ncob * pl.ncib;
     U3D_REQUIRE(blocks < (1LL << 31), "%s: grid too large", who);
     if (vsrc == nullptr) {
@@ -932,7 +957,7 @@ int c2b_wgrad_launch(const char* who, int device, u3d_stream_t stream, const flo
         long long rb = c2b_cdiv(total, 256);
         if (rb > 4096) rb = 4096;
         hipLaunchKernelGGL(conv2d_wgrad_bf16_reduce_kernel, dim3((unsigned)rb), dim3(256), 0, (hipStream_t)stream, workspace, pl.nsplit, total,
-                           dw);
+                           dw, 9 * Cin, 9 * dw_cin_stride);
         U3D_LAUNCH_CHECK();
     }
     return 0;
@@ -957,6 +982,16 @@ extern "C" int u3d_conv2d_wgrad_bf16_c16_variant(int N, int H, int W, int Cin, i
 extern "C" int u3d_conv2d_wgrad_bf16(int device, u3d_stream_t stream, const float* x, const float* affine, const float* dz, float* dw,
                                      int N, int H, int W, int Cin, int Cout, float* workspace, long long workspace_floats) {
     return c2b_wgrad_launch("u3d_conv2d_wgrad_bf16", device, stream, x, affine, dz, dw, N, H, W, Cin, Cout, workspace, workspace_floats, false);
+}
+
+// ... writing a CHANNEL SLICE of a wider gradient (the skip half of a sub-pixel decoder layer): dw points at the slice's first input channel
+// inside (Cout, dw_cin_stride, 3, 3); same plan, same sums in the same order — dw_cin_stride = Cin is u3d_conv2d_wgrad_bf16 bit for bit
+extern "C" int u3d_conv2d_wgrad_bf16_strided(int device, u3d_stream_t stream, const float* x, const float* affine, const float* dz, float* dw,
+                                             int dw_cin_stride, int N, int H, int W, int Cin, int Cout, float* workspace,
+                                             long long workspace_floats) {
+    U3D_REQUIRE(dw_cin_stride > 0, "u3d_conv2d_wgrad_bf16_strided: bad argument");
+    return c2b_wgrad_launch("u3d_conv2d_wgrad_bf16_strided", device, stream, x, affine, dz, dw, N, H, W, Cin, Cout, workspace,
+                            workspace_floats, false, nullptr, dw_cin_stride);
 }
 
 // ... of a layer with both channel counts % 16: a 16-channel cell stages zeros for its two missing channel octets, dw stores are masked
@@ -1574,6 +1609,655 @@ extern "C" int u3d_convtr2d_wgrad_bf16(int device, u3d_stream_t stream, const fl
     if (rb > 4096) rb = 4096;
     hipLaunchKernelGGL(convtr2d_wgrad_bf16_reduce_kernel, dim3((unsigned)rb), dim3(256), 0, (hipStream_t)stream, workspace, pl.nsplit, total,
                        accumulate ? 1 : 0, dw);
+    U3D_LAUNCH_CHECK();
+    return 0;
+}
+
+// =================================================================================================
+// Sub-pixel decoder convolutions of a UNet2D in bf16 (`native_2d_bf16_subpixel: true`): the bf16 twins of u3d_subpixel2d_conv_fwd /
+// _dgrad_reps / _wgrad of csrc/u3d_subpix2d.hip on v_mfma_f32_32x32x16_bf16.  The upsampled half of cat(skip, nearest2x(low)) under a 3x3
+// convolution: an output pixel of parity p reads, per axis, only the two low-res pixels j + p - 1 + e (e = 0, 1) — p = 0: {t0}, {t1 + t2};
+// p = 1: {t0 + t1}, {t2} — so each of the 4 parity classes is a 2x2 convolution over the low-res grid, 4/9 of the multiply-adds, and the data
+// gradient lands at low resolution with the children sum folded in.  Tensors in HBM are fp32 NHWC, accumulation is fp32.
+// Rounding points: the pre-summed taps are added in fp32 from the fp32 master weight (in ascending (ty, tx) order) and rounded ONCE to
+// bf16, nearest even, by the pack kernel; activations and dz are rounded once while staged to LDS, after the fp32 affine fmaf(x, a, b);
+// zero padding applies after the affine and stays exactly 0 (c2b_stage8).  Not bit-equal to the 9-tap bf16 kernels on the written-out
+// concat in forward and data gradient (those round every tap); the weight gradient multiplies the same bf16 operands.
+//
+// Forward (subpix2d_fwd_bf16_kernel): the 3x3 kernel's block — 16 x 16 LOW-RES pixels, 18 x 18 halo [hy][hx][16 bf16] with 37 slots per row,
+// double-buffered over 16-channel chunks — serving all four classes from one staged halo: nine A-fragment positions, sixteen MFMAs per
+// M-tile (class (a, b) takes halo offsets (a + u, b + v)); 2 M-tiles x 4 classes = 128 accumulator registers, so a block owns 32 output
+// channels.  out (N, 2H1, 2W1, Cout) receives the plain partial sums: the skip half joins through u3d_conv2d_bf16_res(residual = out).
+//
+// Data gradient (subpix2d_dgrad_bf16_kernel): dlow[i] = sum over the 4 x 4 stride-2 gather dz[2i - 1 + r], per axis r = 0..3 carrying t2,
+// t1 + t2, t0 + t1, t0.  The 34 x 34 dz region of a 16 x 16 dlow tile is staged DE-INTERLEAVED into its four parity planes (17 x 17 each,
+// 35 slots per row): tap r reads plane (r + 1) & 1 at offset r >> 1, unit-stride A-fragment reads with the forward's conflict-free pattern.
+// One 38 KB buffer, the next chunk in flight in registers (convtr2d_dgrad_bf16_kernel's schedule).  The epilogue adds (sum dlow, sum dlow *
+// x_low) per block into gstats, replica row block % reps.
+//
+// Weight gradient (subpix2d_wgrad_bf16_kernel): the sixteen (class, tap half) 32 x 32 matrices M[a, b, u, v][co][ci] = sum_{i, j} dz[2i + a,
+// 2j + b, co] * g[i + a - 1 + u, j + b - 1 + v, ci] over 8 x 16 low-res tiles; wave w owns class w (4 accumulators), its dz plane and the
+// shared low-res halo sit in LDS as [pixel][32 channels] and are fetched with ds_read_b64_tr_b16 (8-byte aligned addresses: 64-byte pixels,
+// lane offsets multiples of 8).  Every block writes its 16 matrices to its workspace slot; subpix2d_wgrad_bf16_fold_kernel folds them into
+// the nine taps (4 matrices per tap) and adds the slots in slot order: no atomics, the same inputs give the same bits.
+namespace {
+
+namespace sp2b {
+constexpr int T = 16;                       // low-res tile edge
+constexpr int PS = 32;                      // bytes per staged pixel (16 bf16)
+// forward: the 3x3 kernel's halo
+constexpr int FH = T + 2;                   // 18
+constexpr int FRS = FH * PS + 16;           // 592 bytes per row: 37 slots
+constexpr int FBUF = FH * FRS;              // 10656
+constexpr int FITEMS = FH * FH * 2;         // 648 (pixel, channel octet) items per chunk
+constexpr int FNIT = (FITEMS + 255) / 256;  // 3
+constexpr int F_LDS_BYTES = 2 * FBUF;       // 21312 (double-buffered)
+// data gradient: four parity planes
+constexpr int DP = T + 1;                   // 17 rows / columns per plane
+constexpr int DRS = DP * PS + 16;           // 560 bytes per row: 35 slots
+constexpr int DPL = DP * DRS;               // 9520 bytes per plane
+constexpr int DITEMS = 4 * DP * DP * 2;     // 2312
+constexpr int DNIT = (DITEMS + 255) / 256;  // 10
+constexpr int D_LDS_BYTES = 4 * DPL;        // 38080 (the final [4][32][2] float reduction reuses the first 1024)
+// weight gradient
+constexpr int WTY = 8;                      // tile rows (x 16 columns) of the low-res grid
+constexpr int WHY = WTY + 2, WHX = T + 2;   // 10 x 18 low-res halo
+constexpr int WPP = 64;                     // bytes per staged pixel (32 bf16)
+constexpr int W_G = 0;                      // [10 * 18][32] bf16
+constexpr int W_DZ = WHY * WHX * WPP;       // 11520: [4 planes][8 * 16][32] bf16
+constexpr int W_LDS_BYTES = W_DZ + 4 * WTY * T * WPP;  // 44288
+constexpr int W_GIT = (WHY * WHX * 4 + 255) / 256;     // 3 halo items (pixel, octet) per thread
+constexpr int W_DIT = 4 * WTY * T * 4 / 256;           // 8 dz items per thread
+constexpr int W_DB = 4;                                // dz items staged per batch
+
+// the sixteen (class, tap half) products of one chunk in halo-position order: q = (2a + b) * 4 + 2u + v reads halo offset (a + u, b + v)
+struct Seq {
+    int q[16], pos[16];
+};
+constexpr Seq make_seq() {
+    Seq s{};
+    int n = 0;
+    for (int dy = 0; dy < 3; ++dy)
+        for (int dx = 0; dx < 3; ++dx)
+            for (int a = 0; a < 2; ++a)
+                for (int b = 0; b < 2; ++b) {
+                    const int u = dy - a, v = dx - b;
+                    if (u < 0 || u > 1 || v < 0 || v > 1) continue;
+                    s.q[n] = (2 * a + b) * 4 + 2 * u + v;
+                    s.pos[n] = dy * 3 + dx;
+                    ++n;
+                }
+    return s;
+}
+}  // namespace sp2b
+
+inline bool sp2b_ok(int C1, int Cout) { return C1 > 0 && Cout > 0 && C1 % 32 == 0 && Cout % 32 == 0; }
+inline bool sp2b_dims_ok(int N, int H1, int W1, int C1, int Cout) {
+    return N > 0 && H1 > 0 && W1 > 0 && (long long)N * 4 * H1 * W1 < (1ll << 31) && (long long)16 * C1 * Cout < (1ll << 31);
+}
+
+// the taps of the 3-tap axis summed into tap half e of parity p (forward, index 2p + e) and into gather row r (data gradient)
+__device__ __forceinline__ void sp2b_taps_fwd(int p, int e, int& t0, int& t1) {
+    t0 = (p == 0) ? (e == 0 ? 0 : 1) : (e == 0 ? 0 : 2);
+    t1 = (p == 0) ? (e == 0 ? 0 : 2) : (e == 0 ? 1 : 2);
+}
+__device__ __forceinline__ void sp2b_taps_dgrad(int r, int& t0, int& t1) {
+    t0 = r == 0 ? 2 : (r == 1 ? 1 : 0);
+    t1 = r == 0 ? 2 : (r == 1 ? 2 : (r == 2 ? 1 : 0));
+}
+
+// images [K / 16 chunk][16][n-tile][lane][8] of B[k][n], the fragment layout of pack_weights2d_bf16_kernel; w (Cout, cs, 3, 3), channels
+// from coff.  dgrad == 0: entry q = (2a + b) * 4 + 2u + v, B[k = ci][n = co]; dgrad == 1: entry 4 ry + rx, B[k = co][n = ci].  The taps
+// are added in fp32 in ascending (ty, tx) order, then rounded once.
+__global__ void pack_subpix2d_bf16_kernel(const float* __restrict__ w, int cs, int coff, int dgrad, int ntg, long long total,
+                                          __bf16* __restrict__ packed) {
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const int j = (int)(i & 7);
+        const int lane = (int)((i >> 3) & 63);
+        long long r = i >> 9;
+        const int nt = (int)(r % ntg);
+        r /= ntg;
+        const int q = (int)(r % 16);
+        const int chunk = (int)(r / 16);
+        const int k = chunk * 16 + 8 * (lane >> 5) + j;
+        const int nn = nt * 32 + (lane & 31);
+        int y0, y1, x0, x1;
+        if (dgrad == 0) {
+            sp2b_taps_fwd(q >> 3, (q >> 1) & 1, y0, y1);
+            sp2b_taps_fwd((q >> 2) & 1, q & 1, x0, x1);
+        } else {
+            sp2b_taps_dgrad(q >> 2, y0, y1);
+            sp2b_taps_dgrad(q & 3, x0, x1);
+        }
+        const float* base = dgrad == 0 ? w + ((size_t)nn * cs + coff + k) * 9 : w + ((size_t)k * cs + coff + nn) * 9;
+        float v = 0.f;
+        for (int ty = y0; ty <= y1; ty += (y1 > y0 ? y1 - y0 : 1))
+            for (int tx = x0; tx <= x1; tx += (x1 > x0 ? x1 - x0 : 1)) v += base[ty * 3 + tx];
+        packed[i] = (__bf16)v;
+    }
+}
+
+struct Subpix2dBf16Params {
+    const float* src;     // forward: low (N,H1,W1,C1); data gradient: dz (N,2H1,2W1,Cout)
+    const float* affine;  // forward: (a, b) rows of the C1 channels, sample n at affine + n * astride; or null
+    long long astride;
+    const c2b_bf16x8* wp;
+    const float* x_low;   // data gradient: (N,H1,W1,C1) for gstats, or null
+    float* out;           // forward: out (N,2H1,2W1,Cout); data gradient: dlow (N,H1,W1,C1)
+    double* gstats;
+    int N, H1, W1, C1, Cout;
+    int nchunks, ntg, ty, tx, reps;
+};
+
+__global__ __launch_bounds__(256, 2) void subpix2d_fwd_bf16_kernel(const Subpix2dBf16Params p) {
+    using namespace sp2b;
+    extern __shared__ __attribute__((aligned(16))) char lds_sp2f[];
+    char* const lds = lds_sp2f;
+    const int t = threadIdx.x;
+    const int l = t & 63, w = t >> 6, h = l >> 5, i32 = l & 31;
+    int tile = blockIdx.x;
+    const int cb = tile % p.ntg;
+    tile /= p.ntg;
+    const int txi = tile % p.tx;
+    tile /= p.tx;
+    const int tyi = tile % p.ty;
+    const int n = tile / p.ty;
+    const int y0 = tyi * T, x0 = txi * T;
+    const int H1 = p.H1, W1 = p.W1, C1 = p.C1;
+
+    int ldsoff[FNIT], gpix[FNIT];  // gpix < 0: outside the image (stays exactly 0)
+#pragma unroll
+    for (int it = 0; it < FNIT; ++it) {
+        const int item = t + 256 * it;
+        const bool in = item < FITEMS;
+        const int pix = item >> 1, q = item & 1;
+        const int hy = pix / FH, hx = pix - (pix / FH) * FH;
+        const int gy = y0 - 1 + hy, gxx = x0 - 1 + hx;
+        const bool ok = in && gy >= 0 && gy < H1 && gxx >= 0 && gxx < W1;
+        ldsoff[it] = in ? hy * FRS + hx * PS + 16 * q : -1;
+        gpix[it] = ok ? (n * H1 + gy) * W1 + gxx : -1;
+    }
+    const float* const aff_n = p.affine != nullptr ? p.affine + (size_t)n * p.astride : nullptr;
+    f32x4 raw[FNIT][2];
+    auto load_chunk = [&](int c) {
+#pragma unroll
+        for (int it = 0; it < FNIT; ++it) {
+            raw[it][0] = raw[it][1] = f32x4{0.f, 0.f, 0.f, 0.f};
+            if (gpix[it] >= 0) {
+                const float* src = p.src + (size_t)gpix[it] * C1 + c * 16 + 8 * ((t + 256 * it) & 1);
+                raw[it][0] = u3d_ldq(src);
+                raw[it][1] = u3d_ldq(src + 4);
+            }
+        }
+    };
+    auto store_chunk = [&](int c, char* buf) {
+#pragma unroll
+        for (int it = 0; it < FNIT; ++it) {
+            if (ldsoff[it] < 0) continue;
+            const bool ok = gpix[it] >= 0;
+            const float* aff = (aff_n != nullptr && ok) ? aff_n + (c * 16 + 8 * ((t + 256 * it) & 1)) * 2 : nullptr;
+            *reinterpret_cast<c2b_bf16x8*>(buf + ldsoff[it]) = c2b_stage8(raw[it][0], raw[it][1], aff, ok);
+        }
+    };
+
+    f32x16 acc[2][4];  // [M-tile][parity class 2a + b]
+#pragma unroll
+    for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+        for (int cls = 0; cls < 4; ++cls)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[mt][cls][r] = 0.f;
+
+    // A-fragment base: lane (i32, h) of M-tile mt owns low-res pixel (4w + 2mt + (i32 >> 4), i32 & 15), channels 8h .. 8h + 7; halo offset
+    // (dy, dx) of it is halo pixel (+dy, +dx)
+    const int abase = (4 * w + (i32 >> 4)) * FRS + (i32 & 15) * PS + 16 * h;
+    auto bidx = [&](int c, int q) -> long long { return ((long long)(c * 16 + q) * p.ntg + cb) * 64 + l; };
+    constexpr Seq SQ = make_seq();
+
+    load_chunk(0);
+    store_chunk(0, lds);
+    __syncthreads();
+    for (int c = 0; c < p.nchunks; ++c) {
+        const char* cur = lds + (c & 1) * FBUF;
+        if (c + 1 < p.nchunks) load_chunk(c + 1);  // in flight during the MFMAs
+        c2b_bf16x8 bq = p.wp[bidx(c, SQ.q[0])], bn = bq;
+        c2b_bf16x8 a[2];
+#pragma unroll
+        for (int s = 0; s < 16; ++s) {
+            if (s + 1 < 16) bn = p.wp[bidx(c, SQ.q[s + 1])];
+            if (s == 0 || SQ.pos[s] != SQ.pos[s - 1]) {
+                const int dy = SQ.pos[s] / 3, dx = SQ.pos[s] - (SQ.pos[s] / 3) * 3;
+#pragma unroll
+                for (int mt = 0; mt < 2; ++mt) a[mt] = *reinterpret_cast<const c2b_bf16x8*>(cur + abase + (2 * mt + dy) * FRS + dx * PS);
+            }
+#pragma unroll
+            for (int mt = 0; mt < 2; ++mt)
+                acc[mt][SQ.q[s] >> 2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[mt], bq, acc[mt][SQ.q[s] >> 2], 0, 0, 0);
+            bq = bn;
+        }
+        if (c + 1 < p.nchunks) store_chunk(c + 1, lds + ((c + 1) & 1) * FBUF);  // (that buffer was last read in chunk c - 1)
+        __syncthreads();
+    }
+
+    // ---- lane column = output channel, register r = M row (r & 3) + 8 (r >> 2) + 4h; class (a, b) of low-res (i, j) is out[2i + a][2j + b]
+    const int co = cb * 32 + i32;
+    const int Ho = 2 * H1, Wo = 2 * W1;
+#pragma unroll
+    for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+        for (int cls = 0; cls < 4; ++cls)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int row = (r & 3) + 8 * (r >> 2) + 4 * h;
+                const int i = y0 + 4 * w + 2 * mt + (row >> 4), j = x0 + (row & 15);
+                if (i >= H1 || j >= W1) continue;
+                p.out[((size_t)(n * Ho + 2 * i + (cls >> 1)) * Wo + 2 * j + (cls & 1)) * p.Cout + co] = acc[mt][cls][r];
+            }
+}
+
+__global__ __launch_bounds__(256, 2) void subpix2d_dgrad_bf16_kernel(const Subpix2dBf16Params p) {
+    using namespace sp2b;
+    extern __shared__ __attribute__((aligned(16))) char lds_sp2d[];
+    char* const lds = lds_sp2d;
+    const int t = threadIdx.x;
+    const int l = t & 63, w = t >> 6, h = l >> 5, i32 = l & 31;
+    int tile = blockIdx.x;
+    const int cb = tile % p.ntg;
+    tile /= p.ntg;
+    const int txi = tile % p.tx;
+    tile /= p.tx;
+    const int tyi = tile % p.ty;
+    const int n = tile / p.ty;
+    const int y0 = tyi * T, x0 = txi * T;
+    const int H1 = p.H1, W1 = p.W1, Hd = 2 * p.H1, Wd = 2 * p.W1, K = p.Cout;  // the contraction runs over the layer's Cout
+
+    // item = (plane 2pa + pb, plane row py, plane column px, channel octet q): dz pixel (2 (y0 + py) - pa, 2 (x0 + px) - pb)
+    int ldsoff[DNIT], gpix[DNIT];  // gpix < 0: outside dz (zero)
+#pragma unroll
+    for (int it = 0; it < DNIT; ++it) {
+        const int item = t + 256 * it;
+        const bool in = item < DITEMS;
+        const int q = item & 1;
+        int pix = item >> 1;
+        const int px = pix % DP;
+        pix /= DP;
+        const int py = pix % DP;
+        const int pl = pix / DP;
+        const int gy = 2 * (y0 + py) - (pl >> 1), gxx = 2 * (x0 + px) - (pl & 1);
+        const bool ok = in && gy >= 0 && gy < Hd && gxx >= 0 && gxx < Wd;
+        ldsoff[it] = in ? pl * DPL + py * DRS + px * PS + 16 * q : -1;
+        gpix[it] = ok ? (n * Hd + gy) * Wd + gxx : -1;
+    }
+    f32x4 raw[DNIT][2];
+    auto load_chunk = [&](int c) {
+#pragma unroll
+        for (int it = 0; it < DNIT; ++it) {
+            raw[it][0] = raw[it][1] = f32x4{0.f, 0.f, 0.f, 0.f};
+            if (gpix[it] >= 0) {
+                const float* src = p.src + (size_t)gpix[it] * K + c * 16 + 8 * ((t + 256 * it) & 1);
+                raw[it][0] = u3d_ldq(src);
+                raw[it][1] = u3d_ldq(src + 4);
+            }
+        }
+    };
+    auto store_chunk = [&]() {
+#pragma unroll
+        for (int it = 0; it < DNIT; ++it)
+            if (ldsoff[it] >= 0)
+                *reinterpret_cast<c2b_bf16x8*>(lds + ldsoff[it]) = c2b_stage8(raw[it][0], raw[it][1], nullptr, gpix[it] >= 0);
+    };
+
+    f32x16 acc[2];
+#pragma unroll
+    for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[mt][r] = 0.f;
+
+    // lane (i32, h) of M-tile mt owns dlow pixel (ii, jj) = (4w + 2mt + (i32 >> 4), i32 & 15); gather row ry reads dz row 2 (y0 + ii) - 1 + ry:
+    // plane pa = (ry + 1) & 1, plane row ii + (ry >> 1); columns alike
+    const int abase = (4 * w + (i32 >> 4)) * DRS + (i32 & 15) * PS + 16 * h;
+    auto bidx = [&](int c, int q) -> long long { return ((long long)(c * 16 + q) * p.ntg + cb) * 64 + l; };
+
+    load_chunk(0);
+    store_chunk();
+    __syncthreads();
+    for (int c = 0; c < p.nchunks; ++c) {
+        if (c + 1 < p.nchunks) load_chunk(c + 1);  // in flight during the MFMAs
+        c2b_bf16x8 bq = p.wp[bidx(c, 0)], bn = bq;
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+            const int ry = q >> 2, rx = q & 3;
+            if (q + 1 < 16) bn = p.wp[bidx(c, q + 1)];
+            const int toff = (2 * ((ry + 1) & 1) + ((rx + 1) & 1)) * DPL + (ry >> 1) * DRS + (rx >> 1) * PS;
+            c2b_bf16x8 a[2];
+#pragma unroll
+            for (int mt = 0; mt < 2; ++mt) a[mt] = *reinterpret_cast<const c2b_bf16x8*>(lds + abase + toff + 2 * mt * DRS);
+#pragma unroll
+            for (int mt = 0; mt < 2; ++mt) acc[mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[mt], bq, acc[mt], 0, 0, 0);
+            bq = bn;
+        }
+        __syncthreads();  // every wave is done reading the one buffer
+        if (c + 1 < p.nchunks) {
+            store_chunk();
+            __syncthreads();
+        }
+    }
+
+    const int ci = cb * 32 + i32;
+    float s0 = 0.f, s1 = 0.f;
+#pragma unroll
+    for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int row = (r & 3) + 8 * (r >> 2) + 4 * h;
+            const int y = y0 + 4 * w + 2 * mt + (row >> 4), x = x0 + (row & 15);
+            if (y >= H1 || x >= W1) continue;
+            const size_t o = ((size_t)(n * H1 + y) * W1 + x) * p.C1 + ci;
+            const float v = acc[mt][r];
+            p.out[o] = v;
+            if (p.gstats != nullptr) {
+                s0 += v;
+                s1 += v * p.x_low[o];
+            }
+        }
+    if (p.gstats != nullptr) {  // (uniform over the grid) lane halves, then the 4 waves in a fixed order, one f64 atomic per quantity
+        float* red = reinterpret_cast<float*>(lds);  // [4][32][2]; the last barrier of the chunk loop freed the buffer
+        s0 += __shfl_xor(s0, 32);
+        s1 += __shfl_xor(s1, 32);
+        if (l < 32) {
+            red[(w * 32 + l) * 2] = s0;
+            red[(w * 32 + l) * 2 + 1] = s1;
+        }
+        __syncthreads();
+        if (t < 32) {
+            const float a0 = ((red[t * 2] + red[(32 + t) * 2]) + red[(64 + t) * 2]) + red[(96 + t) * 2];
+            const float a1 = ((red[t * 2 + 1] + red[(32 + t) * 2 + 1]) + red[(64 + t) * 2 + 1]) + red[(96 + t) * 2 + 1];
+            double* o = p.gstats + ((size_t)(blockIdx.x % p.reps) * p.N * p.C1 + (size_t)n * p.C1 + cb * 32 + t) * 2;
+            u3d_atomic_add_f64(o, (double)a0);
+            u3d_atomic_add_f64(o + 1, (double)a1);
+        }
+    }
+}
+
+struct Subpix2dWgradBf16Params {
+    const float* low;     // (N,H1,W1,C1)
+    const float* affine;  // rows of the C1 channels, sample n at affine + n * astride; or null
+    long long astride;
+    const float* dz;      // (N,2H1,2W1,Cout)
+    float* ws;            // [nsplit][16][Cout][C1]
+    int N, H1, W1, C1, Cout;
+    int ty, tx, ncob, ncib, ntiles, tps;
+};
+
+__global__ __launch_bounds__(256, 2) void subpix2d_wgrad_bf16_kernel(const Subpix2dWgradBf16Params p) {
+    using namespace sp2b;
+    extern __shared__ __attribute__((aligned(16))) char lds_sp2w[];
+    char* const lds = lds_sp2w;
+    const int t = threadIdx.x, l = t & 63, w = t >> 6, h = l >> 5, i32 = l & 31;
+    int b = blockIdx.x;
+    const int cib = b % p.ncib;
+    b /= p.ncib;
+    const int cob = b % p.ncob;
+    const int split = b / p.ncob;
+    const int ci0 = cib * 32, co0 = cob * 32;
+    const int tile0 = split * p.tps, tile1 = min(p.ntiles, tile0 + p.tps);
+    const int H1 = p.H1, W1 = p.W1, Hd = 2 * p.H1, Wd = 2 * p.W1, C1 = p.C1, Cout = p.Cout;
+    char* const gl = lds + W_G;
+    char* const dzl = lds + W_DZ;
+    const int pa = w >> 1, pb = w & 1;  // this wave's parity class
+
+    f32x16 acc[4];  // [tap half 2u + v]
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[k][r] = 0.f;
+
+    // transposed-read lane offset, as conv2d_wgrad_bf16_kernel: lane l receives channel (l & 31) of the 8 pixels 8 * (l >> 5) .. + 7
+    const int g4 = l >> 4, sidx = l & 15;
+    const int lane_off = (8 * (g4 >> 1) + (sidx >> 2)) * WPP + (16 * (g4 & 1) + 4 * (sidx & 3)) * 2;
+
+    for (int tile = tile0; tile < tile1; ++tile) {
+        int tt = tile;
+        const int txi = tt % p.tx;
+        tt /= p.tx;
+        const int tyi = tt % p.ty;
+        const int n = tt / p.ty;
+        const int y0 = tyi * WTY, x0 = txi * T;
+        const float* const aff_n = p.affine != nullptr ? p.affine + (size_t)n * p.astride : nullptr;
+        // stage g (10 x 18 low-res halo from (y0 - 1, x0 - 1), 32 channels from ci0, affine, zero padding) ...
+        {
+            f32x4 rg[W_GIT][2];
+            bool okg[W_GIT];
+#pragma unroll
+            for (int k = 0; k < W_GIT; ++k) {
+                const int item = t + 256 * k;
+                const int pix = item >> 2, q = item & 3;
+                const int hy = pix / WHX, hx = pix - (pix / WHX) * WHX;
+                const int gy = y0 - 1 + hy, gxx = x0 - 1 + hx;
+                okg[k] = item < WHY * WHX * 4 && gy >= 0 && gy < H1 && gxx >= 0 && gxx < W1;
+                rg[k][0] = rg[k][1] = f32x4{0.f, 0.f, 0.f, 0.f};
+                if (okg[k]) {
+                    const float* src = p.low + ((size_t)(n * H1 + gy) * W1 + gxx) * C1 + ci0 + 8 * q;
+                    rg[k][0] = u3d_ldq(src);
+                    rg[k][1] = u3d_ldq(src + 4);
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < W_GIT; ++k) {
+                const int item = t + 256 * k;
+                if (item >= WHY * WHX * 4) continue;
+                const float* aff = (aff_n != nullptr && okg[k]) ? aff_n + (ci0 + 8 * (item & 3)) * 2 : nullptr;
+                *reinterpret_cast<c2b_bf16x8*>(gl + (item >> 2) * WPP + 16 * (item & 3)) = c2b_stage8(rg[k][0], rg[k][1], aff, okg[k]);
+            }
+        }
+        // ... and dz de-interleaved into its four parity planes (8 x 16 pixels each, 32 channels from co0): plane (a, b), pixel (py, px) is
+        // dz[2 (y0 + py) + a][2 (x0 + px) + b]
+        auto stage_dz = [&](int it0) {
+            f32x4 rd[W_DB][2];
+            bool okd[W_DB];
+#pragma unroll
+            for (int k = 0; k < W_DB; ++k) {
+                const int item = t + 256 * (it0 + k);
+                const int q = item & 3, pix = (item >> 2) & (WTY * T - 1), pl = item >> 9;
+                const int i = y0 + (pix >> 4), j = x0 + (pix & 15);
+                okd[k] = i < H1 && j < W1;
+                rd[k][0] = rd[k][1] = f32x4{0.f, 0.f, 0.f, 0.f};
+                if (okd[k]) {
+                    const float* src = p.dz + ((size_t)(n * Hd + 2 * i + (pl >> 1)) * Wd + 2 * j + (pl & 1)) * Cout + co0 + 8 * q;
+                    rd[k][0] = u3d_ldq(src);
+                    rd[k][1] = u3d_ldq(src + 4);
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < W_DB; ++k) {
+                const int item = t + 256 * (it0 + k);
+                *reinterpret_cast<c2b_bf16x8*>(dzl + (item >> 2) * WPP + 16 * (item & 3)) = c2b_stage8(rd[k][0], rd[k][1], nullptr, okd[k]);
+            }
+        };
+        for (int it0 = 0; it0 < W_DIT; it0 += W_DB) stage_dz(it0);
+        __syncthreads();
+        // wave w = class (pa, pb): all 8 rows of its dz plane, one 16-pixel row per k-step; tap half (u, v) pairs dz plane pixel (py, jj) with
+        // low-res halo pixel (py + pa + u, jj + pb + v)
+#pragma unroll 2
+        for (int py = 0; py < WTY; ++py) {
+            const c2b_bf16x8 a = c2b_tr_frag(dzl + (w * WTY * T + py * T) * WPP + lane_off);
+#pragma unroll
+            for (int u = 0; u < 2; ++u)
+#pragma unroll
+                for (int v = 0; v < 2; ++v) {
+                    const c2b_bf16x8 g = c2b_tr_frag(gl + ((py + pa + u) * WHX + pb + v) * WPP + lane_off);
+                    acc[2 * u + v] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, g, acc[2 * u + v], 0, 0, 0);
+                }
+        }
+        __syncthreads();
+    }
+
+    // ---- this block's slot: matrix q = 4w + 2u + v, [co][ci]; register r = output channel (r & 3) + 8 (r >> 2) + 4h, lane column = ci
+    float* const dst = p.ws + ((size_t)split * 16 + 4 * w) * Cout * C1;
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int row = (r & 3) + 8 * (r >> 2) + 4 * h;
+            dst[((size_t)k * Cout + co0 + row) * C1 + ci0 + i32] = acc[k][r];
+        }
+}
+
+// dw[co][ci][ky][kx] = sum over slots in slot order of the 4 matrices that carry the tap: per axis tap 0 <- (p, e) = (0, 0), (1, 0); tap 1 <-
+// (0, 1), (1, 0); tap 2 <- (0, 1), (1, 1).  drow = 9 * dw_cin_stride elements per output channel of dw.
+__global__ void subpix2d_wgrad_bf16_fold_kernel(const float* __restrict__ ws, int nsplit, int Cout, int C1, float* __restrict__ dw,
+                                                long long drow) {
+    const long long total = (long long)Cout * C1 * 9;
+    const size_t mat = (size_t)Cout * C1;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const int tap = (int)(i % 9);
+        const long long cc = i / 9;  // co * C1 + ci
+        const int ky = tap / 3, kx = tap - ky * 3;
+        // (parity, tap half) pairs of the two contributions per axis
+        const int ay0 = 0, uy0 = ky == 0 ? 0 : 1, ay1 = 1, uy1 = ky == 2 ? 1 : 0;
+        const int ax0 = 0, ux0 = kx == 0 ? 0 : 1, ax1 = 1, ux1 = kx == 2 ? 1 : 0;
+        const int q00 = (2 * ay0 + ax0) * 4 + 2 * uy0 + ux0, q01 = (2 * ay0 + ax1) * 4 + 2 * uy0 + ux1;
+        const int q10 = (2 * ay1 + ax0) * 4 + 2 * uy1 + ux0, q11 = (2 * ay1 + ax1) * 4 + 2 * uy1 + ux1;
+        float v = 0.f;
+        for (int s = 0; s < nsplit; ++s) {
+            const float* m = ws + (size_t)s * 16 * mat + cc;
+            v += ((m[q00 * mat] + m[q01 * mat]) + m[q10 * mat]) + m[q11 * mat];
+        }
+        dw[(cc / C1) * drow + (cc % C1) * 9 + tap] = v;
+    }
+}
+
+struct Sp2bWPlan {
+    int ty, tx, ncob, ncib, ntiles, tps, nsplit;
+};
+
+// ~4 blocks per CU over the launch; ONE function for the launcher and the workspace size
+Sp2bWPlan sp2b_wplan(int device, int N, int H1, int W1, int C1, int Cout) {
+    Sp2bWPlan pl;
+    pl.ty = (int)c2b_cdiv(H1, sp2b::WTY);
+    pl.tx = (int)c2b_cdiv(W1, sp2b::T);
+    pl.ncob = Cout / 32;
+    pl.ncib = C1 / 32;
+    pl.ntiles = N * pl.ty * pl.tx;
+    const long long cells = (long long)pl.ncob * pl.ncib;
+    const long long target = 4LL * c2b_cu_count(device);
+    const long long ns = std::max<long long>(1, std::min<long long>(pl.ntiles, c2b_cdiv(target, cells)));
+    pl.tps = (int)c2b_cdiv(pl.ntiles, ns);
+    pl.nsplit = (int)c2b_cdiv(pl.ntiles, pl.tps);
+    return pl;
+}
+
+}  // namespace
+
+extern "C" long long u3d_subpixel2d_bf16_packed_elems(int C1, int Cout, int dgrad) {
+    if ((dgrad != 0 && dgrad != 1) || !sp2b_ok(C1, Cout) || (long long)16 * C1 * Cout >= (1ll << 31)) return 0;
+    return (long long)16 * C1 * Cout;  // [K / 16][16][Nn / 32][64][8]
+}
+
+extern "C" int u3d_pack_subpixel2d_weights_bf16(int device, u3d_stream_t stream, const float* w, int Cout, int Cin_total, int c_off, int C1,
+                                                int dgrad, void* packed) {
+    U3D_ENTER(device);
+    U3D_REQUIRE(w && packed && (dgrad == 0 || dgrad == 1), "u3d_pack_subpixel2d_weights_bf16: bad argument");
+    U3D_REQUIRE(sp2b_ok(C1, Cout) && (long long)16 * C1 * Cout < (1ll << 31),
+                "u3d_pack_subpixel2d_weights_bf16: (%d -> %d) channels are outside the bf16 sub-pixel envelope (both %% 32)", C1, Cout);
+    U3D_REQUIRE(c_off >= 0 && c_off + C1 <= Cin_total, "u3d_pack_subpixel2d_weights_bf16: channels [%d, %d) do not lie inside a weight of %d "
+                "input channels", c_off, c_off + C1, Cin_total);
+    U3D_REQUIRE(c2b_aligned(packed), "u3d_pack_subpixel2d_weights_bf16: the image must be 16-byte aligned");
+    const long long total = (long long)16 * C1 * Cout;
+    long long blocks = c2b_cdiv(total, 256);
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(pack_subpix2d_bf16_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, w, Cin_total, c_off, dgrad,
+                       (dgrad == 0 ? Cout : C1) / 32, total, reinterpret_cast<__bf16*>(packed));
+    U3D_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int u3d_subpixel2d_conv_fwd_bf16(int device, u3d_stream_t stream, const float* low, const float* affine,
+                                            long long affine_sample_stride, const void* packed, float* out, int N, int H1, int W1, int C1,
+                                            int Cout) {
+    U3D_ENTER(device);
+    U3D_REQUIRE(sp2b_ok(C1, Cout), "u3d_subpixel2d_conv_fwd_bf16: (%d -> %d) channels are outside the bf16 sub-pixel envelope (both %% 32)", C1,
+                Cout);
+    U3D_REQUIRE(low && packed && out, "u3d_subpixel2d_conv_fwd_bf16: bad argument");
+    U3D_REQUIRE(sp2b_dims_ok(N, H1, W1, C1, Cout), "u3d_subpixel2d_conv_fwd_bf16: bad sizes (the output pixel count must be < 2^31)");
+    U3D_REQUIRE(c2b_aligned(low) && c2b_aligned(affine) && c2b_aligned(packed) && c2b_aligned(out) && affine_sample_stride % 4 == 0,
+                "u3d_subpixel2d_conv_fwd_bf16: pointers must be 16-byte aligned");
+    Subpix2dBf16Params p = {};
+    p.src = low;
+    p.affine = affine;
+    p.astride = affine_sample_stride;
+    p.wp = reinterpret_cast<const c2b_bf16x8*>(packed);
+    p.out = out;
+    p.N = N, p.H1 = H1, p.W1 = W1, p.C1 = C1, p.Cout = Cout;
+    p.nchunks = C1 / 16, p.ntg = Cout / 32, p.reps = 1;
+    p.ty = (int)c2b_cdiv(H1, sp2b::T), p.tx = (int)c2b_cdiv(W1, sp2b::T);
+    const long long blocks = (long long)N * p.ty * p.tx * p.ntg;
+    U3D_REQUIRE(blocks < (1LL << 31), "u3d_subpixel2d_conv_fwd_bf16: grid too large");
+    hipLaunchKernelGGL(subpix2d_fwd_bf16_kernel, dim3((unsigned)blocks), dim3(256), sp2b::F_LDS_BYTES, (hipStream_t)stream, p);
+    U3D_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int u3d_subpixel2d_conv_dgrad_bf16(int device, u3d_stream_t stream, const float* dz, const void* packed, const float* x_low,
+                                              float* dlow, double* gstats, int N, int H1, int W1, int C1, int Cout, int reps) {
+    U3D_ENTER(device);
+    U3D_REQUIRE(sp2b_ok(C1, Cout), "u3d_subpixel2d_conv_dgrad_bf16: (%d -> %d) channels are outside the bf16 sub-pixel envelope (both %% 32)",
+                C1, Cout);
+    U3D_REQUIRE(dz && packed && dlow && reps >= 1 && (!gstats || x_low), "u3d_subpixel2d_conv_dgrad_bf16: bad argument (gstats needs x_low)");
+    U3D_REQUIRE(sp2b_dims_ok(N, H1, W1, C1, Cout), "u3d_subpixel2d_conv_dgrad_bf16: bad sizes (the dz pixel count must be < 2^31)");
+    U3D_REQUIRE(c2b_aligned(dz) && c2b_aligned(packed) && c2b_aligned(dlow) && c2b_aligned(x_low),
+                "u3d_subpixel2d_conv_dgrad_bf16: pointers must be 16-byte aligned");
+    Subpix2dBf16Params p = {};
+    p.src = dz;
+    p.wp = reinterpret_cast<const c2b_bf16x8*>(packed);
+    p.x_low = x_low;
+    p.out = dlow;
+    p.gstats = gstats;
+    p.N = N, p.H1 = H1, p.W1 = W1, p.C1 = C1, p.Cout = Cout;
+    p.nchunks = Cout / 16, p.ntg = C1 / 32, p.reps = reps;
+    p.ty = (int)c2b_cdiv(H1, sp2b::T), p.tx = (int)c2b_cdiv(W1, sp2b::T);
+    const long long blocks = (long long)N * p.ty * p.tx * p.ntg;
+    U3D_REQUIRE(blocks < (1LL << 31), "u3d_subpixel2d_conv_dgrad_bf16: grid too large");
+    hipLaunchKernelGGL(subpix2d_dgrad_bf16_kernel, dim3((unsigned)blocks), dim3(256), sp2b::D_LDS_BYTES, (hipStream_t)stream, p);
+    U3D_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" long long u3d_subpixel2d_wgrad_bf16_workspace_floats(int N, int H1, int W1, int C1, int Cout) {
+    if (!sp2b_ok(C1, Cout) || !sp2b_dims_ok(N, H1, W1, C1, Cout)) return 0;
+    return (long long)sp2b_wplan(c2b_current_device(), N, H1, W1, C1, Cout).nsplit * 16 * C1 * Cout;
+}
+
+extern "C" int u3d_subpixel2d_conv_wgrad_bf16(int device, u3d_stream_t stream, const float* low, const float* affine,
+                                              long long affine_sample_stride, const float* dz, float* dw, int dw_cin_stride, int N, int H1,
+                                              int W1, int C1, int Cout, float* workspace, long long workspace_floats) {
+    U3D_ENTER(device);
+    U3D_REQUIRE(sp2b_ok(C1, Cout), "u3d_subpixel2d_conv_wgrad_bf16: (%d -> %d) channels are outside the bf16 sub-pixel envelope (both %% 32)",
+                C1, Cout);
+    U3D_REQUIRE(low && dz && dw && workspace && dw_cin_stride >= C1, "u3d_subpixel2d_conv_wgrad_bf16: bad argument");
+    U3D_REQUIRE(sp2b_dims_ok(N, H1, W1, C1, Cout), "u3d_subpixel2d_conv_wgrad_bf16: bad sizes (the dz pixel count must be < 2^31)");
+    U3D_REQUIRE(c2b_aligned(low) && c2b_aligned(affine) && c2b_aligned(dz) && c2b_aligned(workspace) && affine_sample_stride % 4 == 0,
+                "u3d_subpixel2d_conv_wgrad_bf16: pointers must be 16-byte aligned");
+    const Sp2bWPlan pl = sp2b_wplan(device, N, H1, W1, C1, Cout);
+    const long long need = (long long)pl.nsplit * 16 * C1 * Cout;
+    U3D_REQUIRE(workspace_floats >= need, "u3d_subpixel2d_conv_wgrad_bf16: workspace too small (%lld < %lld floats)", workspace_floats, need);
+    Subpix2dWgradBf16Params p = {};
+    p.low = low;
+    p.affine = affine;
+    p.astride = affine_sample_stride;
+    p.dz = dz;
+    p.ws = workspace;
+    p.N = N, p.H1 = H1, p.W1 = W1, p.C1 = C1, p.Cout = Cout;
+    p.ty = pl.ty, p.tx = pl.tx, p.ncob = pl.ncob, p.ncib = pl.ncib, p.ntiles = pl.ntiles, p.tps = pl.tps;
+    const long long blocks = (long long)pl.nsplit * pl.ncob * pl.ncib;
+    U3D_REQUIRE(blocks < (1LL << 31), "u3d_subpixel2d_conv_wgrad_bf16: grid too large");
+    hipLaunchKernelGGL(subpix2d_wgrad_bf16_kernel, dim3((unsigned)blocks), dim3(256), sp2b::W_LDS_BYTES, (hipStream_t)stream, p);
+    U3D_LAUNCH_CHECK();
+    const long long total = (long long)9 * C1 * Cout;
+    long long rb = c2b_cdiv(total, 256);
+    if (rb > 4096) rb = 4096;
+    hipLaunchKernelGGL(subpix2d_wgrad_bf16_fold_kernel, dim3((unsigned)rb), dim3(256), 0, (hipStream_t)stream, workspace, pl.nsplit, Cout, C1,
+                       dw, (long long)9 * dw_cin_stride);
     U3D_LAUNCH_CHECK();
     return 0;
 }

@@ -134,7 +134,8 @@ class ConvLayers:
         """decoder first convs whose low-res input is upsampled by exactly 2 — or, round 5, from n to 2n + 1 voxels — in every dimension at
         this input size: {id(weight): (C0, C1)} (+ `.plus`: the ids with an n -> 2n + 1 axis) — per-call state, handed down as `sub`"""
         is2d = self.is2d
-        if not self.subpixel or any(ct is not None for ct in self.dec_up) or any(self.dec_interp):
+        bf16_sub = is2d and self.subpixel2d_bf16  # (`native_2d_bf16_subpixel`: the levels `_bf16_subpixel` accepts, on the bf16 kernels)
+        if not (self.subpixel or bf16_sub) or any(ct is not None for ct in self.dec_up) or any(self.dec_interp):
             return _SubLayers()  # (a transposed convolution yields 2n-1 voxels, resized to the skip: never an exact 2x replication)
         dims = [tuple(size)[1:] if is2d else tuple(size)]  # (2-D, `native_2d_subpixel`: H and W only)
         for has_pool, _, _ in self.enc:
@@ -144,10 +145,16 @@ class ConvLayers:
         L = len(self.enc)
         for j, (c1, _) in enumerate(self.dec):
             skip_lvl, low_lvl = L - 2 - j, L - 1 - j
-            if skip_lvl < 0 or low_lvl >= len(dims) or self._cat_bf16(c1):  # (bf16 mode: the concat is materialised, an ordinary layer)
+            if skip_lvl < 0 or low_lvl >= len(dims):
                 continue
             C0 = self.enc[skip_lvl][2].conv.out_channels
             C1 = c1.conv.in_channels - C0
+            if self._cat_bf16(c1):  # (bf16 mode: the concat is materialised or read in place, an ordinary layer — but for `_bf16_subpixel`)
+                if bf16_sub and self._bf16_subpixel(c1, C0, C1, dims[skip_lvl], dims[low_lvl]):
+                    out[id(c1.conv.weight)] = (C0, C1)
+                continue
+            if not self.subpixel:  # (`native_2d_bf16_subpixel` alone: a layer outside `_cat_bf16` keeps its fp32 virtual concat)
+                continue
             # every axis upsampled by exactly 2, or n -> 2n + 1 (the pooled size of an odd level; round 5: the sub-pixel kernels on a
             # shifted window + the general kernels on the near-boundary slab, _fwd_subpixel / _dgrad_subpixel / _wgrad_subpixel)
             ratio = [a - 2 * b for a, b in zip(dims[skip_lvl], dims[low_lvl])]
@@ -160,9 +167,10 @@ class ConvLayers:
         out.plus = frozenset(plus)  # the layers of this call whose packed set includes the slab images (WeightImages.repack)
         return out
 
-    def _stats_of(self, src: VSrc, st0: Optional[StatTable], st1: Optional[StatTable], pool: _StatPool, dev):
+    def _stats_of(self, src: VSrc, st0: Optional[StatTable], st1: Optional[StatTable], pool: _StatPool, dev, sub2d_bf16: bool = False):
         """(lo, hi) tables of the per-channel sums of a (virtual) tensor: `hi` holds the upsampled half's when it has a table of its
-        own, else None (`lo` covers every channel).  st0 / st1: the producers' tables of the two halves, if they wrote any."""
+        own, else None (`lo` covers every channel).  st0 / st1: the producers' tables of the two halves, if they wrote any.
+        sub2d_bf16: the layer is a sub-pixel one under `native_2d_bf16_subpixel` (an exact-2x level by `_bf16_subpixel`)."""
         if src.t1 is None:
             if st0 is None:
                 st0 = pool.table(src.N, src.C0, self.stat_reps)
@@ -170,7 +178,7 @@ class ConvLayers:
                 nat.call("u3d_chan_stats_reps", dev.index, _stream(dev), ctypes.byref(s), src.N, src.D, src.H, src.W, *_tab(st0))
             return st0, None
         # (a 2-D net, D = D1 = 1: H and W, and only under `native_2d_subpixel`)
-        exact2x = (self.subpixel2d and src.H == 2 * src.H1 and src.W == 2 * src.W1) if self.is2d else src.exact2x
+        exact2x = ((self.subpixel2d or sub2d_bf16) and src.H == 2 * src.H1 and src.W == 2 * src.W1) if self.is2d else src.exact2x
         if st0 is not None and st1 is not None and exact2x and self.fused_stats:
             # every low-res voxel is replicated exactly 8x (2-D: every pixel 4x): reuse the producer's sums
             return st0, dataclasses.replace(st1, scale=self.children)
@@ -310,6 +318,18 @@ class ConvLayers:
         return (self.vcat and not self.post_norm and src.t1 is not None and src.C0 > 0 and src.C1 > 0
                 and src.C0 % 32 == 0 and src.C1 % 32 == 0 and self._bf16_layer(src.C, Cout)
                 and src.t0.dtype == _F32 and src.t1.dtype == _F32 and os.environ.get("U3D_BF16_CAT", "1") != "0")
+
+    def _bf16_subpixel(self, c1, C0: int, C1: int, dims_skip, dims_low) -> bool:
+        """THE rule for a decoder's first conv under `native_2d_bf16_subpixel`, stated once: the key is on; the layer is one `_cat_bf16`
+        accepts (bf16, a pre-norm order); its level upsamples by exactly 2 on both axes (H == 2 * H1 and W == 2 * W1); C0 % 32 == C1 % 32
+        == Cout % 32 == 0 (the envelope of the sub-pixel bf16 kernels and of the skip half's sliced images); both halves are fp32 tensors
+        (every activation of a 2-D net is); the upsampling is nearest (`_subpixel_layers` returns before asking when a decoder has a
+        transposed convolution or an interpolation).  Asked by `_subpixel_layers` alone: forward, `_stats_of` and the image cache read its
+        answer from the `sub` table of the call, backward from the record.  A level outside it — n -> 2n + 1, 16-channel halves under
+        `native_2d_stem` — keeps its written-out concat (`_cat_bf16`) or the `_src` entry points (`_bf16_vcat`)."""
+        return (self.subpixel2d_bf16 and self._cat_bf16(c1) and not self.post_norm and not self.act_bf16
+                and all(a == 2 * b for a, b in zip(dims_skip, dims_low))
+                and C0 > 0 and C1 > 0 and C0 % 32 == 0 and C1 % 32 == 0 and c1.conv.out_channels % 32 == 0)
 
     def _c16(self, Cin: int, Cout: int) -> bool:
         """a layer `_bf16_routed_weight` accepts lies outside today's envelope: the `_c16` entry points and `*_C16` images are its"""
@@ -478,7 +498,9 @@ class ConvLayers:
         "conv2d": "_fwd_conv2d",      # u3d_conv2d.hip: 3x3 convolutions of a 2-D net (native_2d), every layer and only those ...
         "conv2d_bf16": "_fwd_conv2d_bf16",  # u3d_conv2d_bf16.hip: ... except, in bf16, the single-source layers that fit (`_bf16_routed`)
         "small2d": "_fwd_small2d",    # u3d_conv2d.hip: ... and, under `native_2d_stem`, the first layer, Cin <= 4 (the 3-D `small` rule)
-        "subpixel2d": "_fwd_subpixel2d",  # u3d_subpix2d.hip + u3d_conv2d.hip: `native_2d_subpixel`, cat(skip, nearest2x(low)), 4/9 of the MACs
+        # u3d_subpix2d.hip + u3d_conv2d.hip: `native_2d_subpixel`, cat(skip, nearest2x(low)), 4/9 of the MACs; under `native_2d_bf16_subpixel`
+        # (the two keys refuse each other) the family's three launchers run their bf16 twins of u3d_conv2d_bf16.hip (`_*_subpixel2d_bf16`)
+        "subpixel2d": "_fwd_subpixel2d",
         "conv2d_bf16_src": "_fwd_conv2d_bf16_src",  # u3d_conv2d_bf16.hip: `native_2d_bf16_vcat`, a decoder's virtual concat read in place
     }
 
@@ -573,6 +595,8 @@ class ConvLayers:
     def _fwd_subpixel2d(self, c: "_ConvCall"):
         # `native_2d_subpixel`: the upsampled half as 4 parity-class 2x2 convolutions over the low-res tensor (4/9 of the multiply-adds,
         # csrc/u3d_subpix2d.hip), then the skip half, whose epilogue adds the partial sums before ReLU / statistics (u3d_conv2d_res_reps)
+        if self.subpixel2d_bf16:  # (the two are never on together: `native_2d_subpixel` refuses the bf16 keys)
+            return self._fwd_subpixel2d_bf16(c)
         dev, conv, src, N, H, W, Cout = c.dev, c.conv, c.src, c.N, c.H, c.W, c.Cout
         plus = c.plus
         assert c.D == 1 and H == 2 * src.H1 + plus[1] and W == 2 * src.W1 + plus[2]
@@ -603,6 +627,26 @@ class ConvLayers:
         yp, yr = _tab(ystats)
         nat.call("u3d_conv2d_res_reps", dev.index, _stream(dev), ctypes.byref(s0), _p(self.images.get(conv.weight, Kind.SKIP_FWD2D, dev, pair)),
                  _p(c.y), N, H, W, Cout, c.relu, yp, None, None, _p(kws), need, yr, _p(part), flops=18.0 * C0 * Cout * N * H * W)
+        return ystats
+
+    def _fwd_subpixel2d_bf16(self, c: "_ConvCall"):
+        # `native_2d_bf16_subpixel`: the same two launches on the bf16 MFMA (csrc/u3d_conv2d_bf16.hip) — the upsampled half as 4 parity-class
+        # 2x2 convolutions with taps pre-summed in fp32 and rounded once, then the skip half on its sliced image, whose epilogue adds the fp32
+        # partial sums before ReLU / statistics (u3d_conv2d_bf16_res).  The concat is never written.
+        dev, conv, src, N, H, W, Cout = c.dev, c.conv, c.src, c.N, c.H, c.W, c.Cout
+        assert c.D == 1 and H == 2 * src.H1 and W == 2 * src.W1 and not any(c.plus)
+        pair = C0, C1 = c.sub[id(conv.weight)]
+        ystats = c.take_stats(self.stat_reps)
+        part = _empty((N, 1, H, W, Cout), dtype=_F32, device=dev)
+        nat.call("u3d_subpixel2d_conv_fwd_bf16", dev.index, _stream(dev), _p(src.t1), _p(c.affine.view(-1)[2 * C0:]), c.Ctot * 2,
+                 _p(self.images.get(conv.weight, Kind.UP_BF16_FWD2D, dev, pair)), _p(part), N, src.H1, src.W1, C1, Cout,
+                 flops=32.0 * C1 * Cout * N * src.H1 * src.W1)
+        a0 = c.affine_lo if c.affine_lo is not None else c.affine[:, :C0].contiguous()
+        need = nat.get_lib().u3d_conv2d_bf16_workspace_floats(N, H, W, C0, Cout)  # split-K scratch on small grids
+        kws = _empty(need, dtype=_F32, device=dev) if need > 0 else None
+        yp, yr = _tab(ystats)
+        nat.call("u3d_conv2d_bf16_res", dev.index, _stream(dev), _p(src.t0), _p(a0), _p(self.images.get(conv.weight, Kind.SKIP_BF16_FWD2D, dev, pair)),
+                 _p(c.y), N, H, W, C0, Cout, c.relu, yp, None, None, _p(kws), need, yr, _p(part), flops=18.0 * C0 * Cout * N * H * W)
         return ystats
 
     def _fwd_f32s(self, c: "_ConvCall"):
@@ -1012,6 +1056,8 @@ class ConvLayers:
     def _wgrad_subpixel2d(self, c: "_BwdCall"):
         # `native_2d_subpixel`: the weight gradient in two channel slices of the same (Cout, Ctot, 9) buffer — upsampled channels from the
         # 16 (parity class, tap half) matrices over the low-res grid, skip channels from the standard kernel (takes no job, as `conv2d`)
+        if self.subpixel2d_bf16:
+            return self._wgrad_subpixel2d_bf16(c)
         cx, dev, src, rec, ws = c.cx, c.cx.dev, c.src, c.rec, c.cx.ws
         C0, C1 = rec.sub
         Ct = src.C
@@ -1043,9 +1089,47 @@ class ConvLayers:
         nat.call("u3d_conv2d_wgrad_strided", dev.index, _stream(dev), ctypes.byref(s0), _p(c.dz), _p(dwv), Ct, c.N, c.H, c.W, c.Cout,
                  _p(ws), ws.numel(), flops=18.0 * C0 * c.Cout * c.N * c.H * c.W)
 
+    def _wgrad_subpixel2d_bf16(self, c: "_BwdCall"):
+        # `native_2d_bf16_subpixel`: the two slices of the same (Cout, Ctot, 9) buffer on the bf16 MFMA — both operands rounded once while
+        # staged, fp32 sums added in a fixed order (takes no job, as `conv2d_bf16`)
+        cx, dev, src, rec = c.cx, c.cx.dev, c.src, c.rec
+        C0, C1 = rec.sub
+        Ct = src.C
+        lib = nat.get_lib()
+        ws = cx.ensure_ws(max(lib.u3d_subpixel2d_wgrad_bf16_workspace_floats(c.N, src.H1, src.W1, C1, c.Cout),
+                              lib.u3d_wgrad2d_bf16_workspace_floats(c.N, c.H, c.W, C0, c.Cout)))
+        dwv = cx.gview(rec.idx_w)
+        nat.call("u3d_subpixel2d_conv_wgrad_bf16", dev.index, _stream(dev), _p(src.t1), _p(rec.affine.view(-1)[2 * C0:]), Ct * 2, _p(c.dz),
+                 _p(dwv[C0 * 9:]), Ct, c.N, src.H1, src.W1, C1, c.Cout, _p(ws), ws.numel(), flops=32.0 * C1 * c.Cout * c.N * src.H1 * src.W1)
+        a0 = rec.affine_lo if rec.affine_lo is not None else rec.affine[:, :C0].contiguous()
+        nat.call("u3d_conv2d_wgrad_bf16_strided", dev.index, _stream(dev), _p(src.t0), _p(a0), _p(c.dz), _p(dwv), Ct, c.N, c.H, c.W, C0, c.Cout,
+                 _p(ws), ws.numel(), flops=18.0 * C0 * c.Cout * c.N * c.H * c.W)
+
+    def _dgrad_subpixel2d_bf16(self, c: "_BwdCall"):
+        # `native_2d_bf16_subpixel`: the skip half at full resolution (u3d_conv2d_bf16 on dz with the mode-1 image of channels [0, C0), gx =
+        # skip); the upsampled half directly at LOW resolution.  dg = (dg_skip, dlow) and two statistics tables, as `_dgrad_subpixel2d`
+        cx, dev, src, rec, pool = c.cx, c.cx.dev, c.src, c.rec, c.cx.pool
+        C0, C1 = rec.sub
+        w, pair = rec.conv_w, tuple(rec.sub)
+        dg0 = _empty((c.N, 1, c.H, c.W, C0), dtype=_F32, device=dev)
+        dlow = _empty_like(src.t1)
+        gst0 = pool.table(c.N, C0, c.greps)
+        gst1 = pool.table(c.N, C1, c.greps)
+        need = nat.get_lib().u3d_conv2d_bf16_workspace_floats(c.N, c.H, c.W, c.Cout, C0)  # roles swapped
+        kws = cx.ensure_ws(need) if need > 0 else None
+        nat.call("u3d_conv2d_bf16", dev.index, _stream(dev), _p(c.dz), None, _p(self.images.get(w, Kind.SKIP_BF16_DGRAD2D, dev, pair)), _p(dg0),
+                 c.N, c.H, c.W, c.Cout, C0, 0, None, _p(src.t0), _p(gst0.t), _p(kws), need, gst0.reps,
+                 flops=18.0 * C0 * c.Cout * c.N * c.H * c.W)
+        nat.call("u3d_subpixel2d_conv_dgrad_bf16", dev.index, _stream(dev), _p(c.dz), _p(self.images.get(w, Kind.UP_BF16_DGRAD2D, dev, pair)),
+                 _p(src.t1), _p(dlow), _p(gst1.t), c.N, src.H1, src.W1, C1, c.Cout, gst1.reps,
+                 flops=32.0 * C1 * c.Cout * c.N * src.H1 * src.W1)
+        return (dg0, dlow), (gst0, gst1)
+
     def _dgrad_subpixel2d(self, c: "_BwdCall"):
         # skip half at full resolution (mode-1 image of channels [0, C0)); upsampled half directly at LOW resolution, the children sum
         # of the nearest upsampling folded into the 4x4-tap stride-2 gather.  dg = (dg_skip, dlow)
+        if self.subpixel2d_bf16:
+            return self._dgrad_subpixel2d_bf16(c)
         cx, dev, src, rec, ws, pool = c.cx, c.cx.dev, c.src, c.rec, c.cx.ws, c.cx.pool
         C0, C1 = rec.sub
         w, pair = rec.conv_w, tuple(rec.sub)
@@ -1241,6 +1325,10 @@ class ConvLayers:
             return max(lib.u3d_conv3d_bf16_workspace_floats(N, D, H, W, Cout, Cin), lib.u3d_wgrad_bf16_workspace_floats(N, D, H, W, Cin, Cout))
         if family in ("fp32", "f32s"):  # (the split data gradient grows the buffer itself, `_BwdCtx.ensure_ws`)
             return max(lib.u3d_wgrad_workspace_floats(N, D, H, W, Cin, Cout), lib.u3d_conv3d_workspace_floats(N, D, H, W, Cout, Cin))
+        if family == "subpixel2d" and self.subpixel2d_bf16:  # (`native_2d_bf16_subpixel`: the same three on the bf16 kernels' plans)
+            return max(lib.u3d_wgrad2d_bf16_workspace_floats(N, H, W, sub[0], Cout),
+                       lib.u3d_subpixel2d_wgrad_bf16_workspace_floats(N, H // 2, W // 2, sub[1], Cout),
+                       lib.u3d_conv2d_bf16_workspace_floats(N, H, W, Cout, sub[0]))
         if family == "subpixel2d":  # (`native_2d_subpixel`: skip slice on the conv2d kernels + the sub-pixel slice's block slots)
             boxes = slab_boxes((1, H, W), plus, 2)  # (`native_2d_subpixel_plus`: the slab's weight-gradient launches)
             return max(lib.u3d_wgrad2d_workspace_floats(N, H, W, sub[0], Cout),

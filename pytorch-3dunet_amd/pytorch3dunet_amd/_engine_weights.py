@@ -56,6 +56,10 @@ class Kind(enum.IntEnum):
     UP_DGRAD2D = enum.auto()
     SLAB_FWD2D = enum.auto()    # ... the plain 3x3 images of those C1 channels: slab launches of an n -> 2n + 1 level (`native_2d_subpixel_plus`)
     SLAB_DGRAD2D = enum.auto()
+    SKIP_BF16_FWD2D = enum.auto()    # sub-pixel layer of a 2-D net in bf16 (`native_2d_bf16_subpixel`): the first C0 (skip) input channels ...
+    SKIP_BF16_DGRAD2D = enum.auto()
+    UP_BF16_FWD2D = enum.auto()      # ... the parity-class images of the remaining C1 channels: taps pre-summed in fp32, rounded once
+    UP_BF16_DGRAD2D = enum.auto()
 
 
 @dataclass(frozen=True)
@@ -67,7 +71,7 @@ class _Spec:
     batch: Optional[int] = None   # C-ABI mode of the image's row in the per-step batch launch of its dtype (None: packed on demand)
     half: Optional[int] = None    # the image may be / is of one half of a sub-pixel pair (C0, C1): 0 = skip, 1 = upsampled channels
     transposed: bool = False      # ConvTranspose weight (Cin, Cout, ...): the entry point takes (Cin, Cout), else (Cout, Cin)
-    up2d: bool = False            # u3d_pack_subpixel2d_*: the entry point takes (Cout, Cin_total, c_off, C1)
+    up2d: bool = False            # u3d_pack_subpixel2d_*: the entry point takes (Cout, Cin_total, c_off, C1[, mode])
 
 
 _f32 = lambda lib, ci, co, m: lib.u3d_packed_weight_floats(ci, co, m)  # noqa: E731
@@ -80,6 +84,7 @@ _tr2d = lambda lib, ci, co, m: lib.u3d_convtr2d_packed_floats(ci, co)  # noqa: E
 _2db = lambda lib, ci, co, m: lib.u3d_packed_weight2d_bf16_elems(ci, co, m)  # noqa: E731
 _2db16 = lambda lib, ci, co, m: lib.u3d_packed_weight2d_bf16_c16_elems(ci, co, m)  # noqa: E731
 _tr2db = lambda lib, ci, co, m: lib.u3d_packed_convtr2d_bf16_elems(ci, co, m)  # noqa: E731
+_up2db = lambda lib, ci, co, m: lib.u3d_subpixel2d_bf16_packed_elems(ci, co, m)  # noqa: E731
 
 # the C-ABI mode numbers of include/u3d.h live in this table (and `_BF16_BOTH`) and nowhere else in the package
 _KINDS = {
@@ -119,6 +124,10 @@ _KINDS = {
                            "u3d_pack_subpixel2d_dgrad_weights", None, half=1, up2d=True),
     Kind.SLAB_FWD2D: _Spec(_2d, _F32, "u3d_pack_weights2d_slice", 0, half=1),
     Kind.SLAB_DGRAD2D: _Spec(_2d, _F32, "u3d_pack_weights2d_slice", 1, half=1),
+    Kind.SKIP_BF16_FWD2D: _Spec(_2db, _BF16, "u3d_pack_weights2d_bf16_slice", 0, half=0),
+    Kind.SKIP_BF16_DGRAD2D: _Spec(_2db, _BF16, "u3d_pack_weights2d_bf16_slice", 1, half=0),
+    Kind.UP_BF16_FWD2D: _Spec(_up2db, _BF16, "u3d_pack_subpixel2d_weights_bf16", 0, half=1, up2d=True),
+    Kind.UP_BF16_DGRAD2D: _Spec(_up2db, _BF16, "u3d_pack_subpixel2d_weights_bf16", 1, half=1, up2d=True),
 }
 _BF16_BOTH = 6  # batch row that writes BF16_FWD and, right behind it in one buffer, BF16_DGRAD from one read of the weight
 
@@ -199,7 +208,7 @@ class WeightImages:
             args += () if spec.mode is None else (spec.mode,)
             args += (ld, off) if spec.half is not None else ()
             if spec.up2d:
-                args = (co, ld, off, ci)
+                args = (co, ld, off, ci) + (() if spec.mode is None else (spec.mode,))
             nat.call(spec.entry, dev.index, _stream(dev), _p(w.detach()), *args, _p(out))
         self._images[key] = (ver, out)
         return out
@@ -252,6 +261,11 @@ class WeightImages:
             for kind in (Kind.FWD2D, Kind.DGRAD2D)[:nd]:
                 self.get(w, kind, dev)
         for w in self._each_bf16:  # ... and of the 2-D layers on the bf16 kernels (u3d_pack_weights2d_bf16)
+            pair = sub.get(id(w)) if sub else None
+            if pair is not None:  # (`native_2d_bf16_subpixel`: the images of the two input-channel halves instead)
+                for kind in (Kind.SKIP_BF16_FWD2D, Kind.SKIP_BF16_DGRAD2D)[:nd] + (Kind.UP_BF16_FWD2D, Kind.UP_BF16_DGRAD2D)[:nd]:
+                    self.get(w, kind, dev, pair)
+                continue
             for kind in (Kind.BF16_FWD2D, Kind.BF16_DGRAD2D)[:nd]:
                 self.get(w, kind, dev)
         for w in self._each_bf16_c16:  # ... and of its 16-channel stem layers (u3d_pack_weights2d_bf16_c16)

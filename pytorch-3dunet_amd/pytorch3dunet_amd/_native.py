@@ -557,6 +557,19 @@ _PROTOS = {
     "u3d_convtr2d_wgrad_bf16_variant": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int64]),
     "u3d_convtr2d_wgrad_bf16": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
                                         c_int64]),
+    # sub-pixel decoder convolutions of a 2-D net on the bf16 MFMA (`native_2d_bf16_subpixel`; csrc/u3d_conv2d_bf16.hip)
+    "u3d_subpixel2d_bf16_packed_elems": (c_int64, [c_int, c_int, c_int]),
+    "u3d_pack_subpixel2d_weights_bf16": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "u3d_subpixel2d_conv_fwd_bf16": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                                             c_int]),
+    "u3d_subpixel2d_conv_dgrad_bf16": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                               c_int, c_int, c_int]),
+    "u3d_subpixel2d_wgrad_bf16_workspace_floats": (c_int64, [c_int, c_int, c_int, c_int, c_int]),
+    "u3d_subpixel2d_conv_wgrad_bf16": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                                               c_int, c_int, c_void_p, c_int64]),
+    "u3d_pack_weights2d_bf16_slice": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "u3d_conv2d_wgrad_bf16_strided": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                              c_int, c_void_p, c_int64]),
     "u3d_maxpool2d_fwd": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "u3d_maxpool2d_bwd_merge": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                                         c_int, c_int, c_void_p]),

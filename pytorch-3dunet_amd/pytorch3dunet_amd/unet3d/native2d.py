@@ -35,6 +35,8 @@ KEYS = (
         "a fp32 ResidualUNet2D on the residual executor at D = 1; native_2d alone leaves it on the warning path"),
     Key("native_2d_bf16_vcat", "U3D_NATIVE_2D_BF16_VCAT", DoubleConv, "native_2d_bf16", "bf16", None, "u3d_conv2d_bf16.hip",
         "the decoders' first convolutions read cat(skip, interpolate(x)) in place (`_src` entry points) when both halves are % 32 channels"),
+    Key("native_2d_bf16_subpixel", "U3D_NATIVE_2D_BF16_SUBPIXEL", DoubleConv, "native_2d_bf16", "bf16", None, "u3d_conv2d_bf16.hip",
+        "the decoders' first convolutions at exact-2x levels with all channel counts % 32 as four 2x2 bf16 convolutions (4/9 of the MACs)"),
     Key("native_2d_bf16", "U3D_NATIVE_2D_BF16", DoubleConv, "native_2d", "bf16", None, "u3d_conv2d_bf16.hip",
         "the single-source 3x3 layers with both channel counts % 32 take bf16 MFMA operands; everything else stays fp32"),
     Key("native_2d_stem", "U3D_NATIVE_2D_STEM", DoubleConv, "native_2d", None, None, "u3d_conv2d.hip",

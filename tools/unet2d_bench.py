@@ -37,6 +37,11 @@ u3d_nearest_cat_fwd calls they replace and of the single-source bf16 calls of bo
 on has the decoders' first convolutions among them, so the comparison is on the difference of the totals), and
 torch.cuda.max_memory_allocated over one step of every arm.
 
+With --bf16-subpixel (next to --bf16 --stem --vcat) the alternation gains the arm `native_2d_bf16` + `native_2d_stem` + `native_2d_bf16_vcat` +
+`native_2d_bf16_subpixel: true` (the decoders' first convolutions at exact-2x levels on the sub-pixel bf16 kernels).  The record adds its
+ms per step, its speed-up over the vcat arm of the same run and the verdict against the project's bar for a speed mode (more than 5 %
+faster than that arm), the levels it took, the per-call ms of the new entry points and of the `_src` calls they replace, and peak memory.
+
 With --subpixel (UNet2D configurations) the alternation gains the arm `native_2d` + `native_2d_subpixel: true` (the upsampled half of the
 decoders' first convolutions on the sub-pixel kernels of csrc/u3d_subpix2d.hip at the levels that upsample by exactly 2).  The record adds
 its ms per step, its speed-up over the `native_2d` arm of the same run and the verdict against the project's bar for a speed mode (more
@@ -49,7 +54,7 @@ shifted window, the 2-pixel slab on box launches of csrc/u3d_conv2d.hip).  The r
 `native_2d_subpixel` arm of the same run and the verdict against the same bar (more than 5 % faster than that arm), the levels it took, the
 FLOPs it executes, its convolution launches by entry point and torch.cuda.max_memory_allocated over one step of every fp32 arm.
 
-  python tools/unet2d_bench.py [--configs confocal,dsb2018] [--batch N] [--steps 10] [--warmup 3] [--bf16] [--stem] [--vcat] [--subpixel] [--subpixel-plus]   (--batch: every config's own default)"""
+  python tools/unet2d_bench.py [--configs confocal,dsb2018] [--batch N] [--steps 10] [--warmup 3] [--bf16] [--stem] [--vcat] [--bf16-subpixel] [--subpixel] [--subpixel-plus]   (--batch: every config's own default)"""
 import argparse
 import json
 import os
@@ -151,6 +156,8 @@ def make(cfg, native, dev):
         extra, native = dict(native_2d_subpixel_plus=True), True
     elif native == "bf16_stem_vcat":
         extra, native = dict(native_2d_stem=True, native_2d_bf16_vcat=True), "bf16"
+    elif native == "bf16_stem_vcat_subpixel":
+        extra, native = dict(native_2d_stem=True, native_2d_bf16_vcat=True, native_2d_bf16_subpixel=True), "bf16"
     elif native in ("stem", "bf16_stem"):
         extra, native = dict(native_2d_stem=True), ("bf16" if native == "bf16_stem" else True)
     if native == "bf16_deconv":
@@ -193,6 +200,7 @@ def main():
     ap.add_argument("--bf16", action="store_true", help="also time the step with native_2d_bf16 / native_2d_residual_bf16, alternated with the others")
     ap.add_argument("--stem", action="store_true", help="also time the UNet2D step with native_2d_stem next to native_2d (and, with --bf16, next to native_2d_bf16)")
     ap.add_argument("--vcat", action="store_true", help="with --bf16 --stem: also time the UNet2D step with native_2d_bf16_vcat on top of them")
+    ap.add_argument("--bf16-subpixel", action="store_true", help="with --bf16 --stem --vcat: also time the UNet2D step with native_2d_bf16_subpixel on top of them")
     ap.add_argument("--subpixel", action="store_true", help="also time the UNet2D step with native_2d_subpixel next to native_2d")
     ap.add_argument("--subpixel-plus", action="store_true", help="also time the UNet2D step with native_2d_subpixel_plus (next to --subpixel)")
     a = ap.parse_args()
@@ -220,6 +228,8 @@ def main():
                 paths.insert(paths.index("bf16") + 1, "bf16_stem")
                 if a.vcat:
                     paths.insert(paths.index("bf16_stem") + 1, "bf16_stem_vcat")
+                    if a.bf16_subpixel:
+                        paths.insert(paths.index("bf16_stem_vcat") + 1, "bf16_stem_vcat_subpixel")
         if a.subpixel_plus and not _residual(cfg):
             paths.insert(1, "subpixel_plus")
         if a.subpixel and not _residual(cfg):
@@ -420,6 +430,41 @@ def main():
                        vcat_replaced_calls_ms=round(base.get("u3d_nearest_cat_fwd", {"ms": 0.0})["ms"] +
                                                     sum(base[k]["ms"] - vc.get(k, {"ms": 0.0})["ms"] for k in single if k in base), 3),
                        peak_memory_bytes={str(p): peak_bytes(p) for p in paths if p is not False})
+        if "bf16_stem_vcat_subpixel" in ms:
+            # the sub-pixel bf16 arm against the vcat arm of the same run: the new entry points and the skip half's launches, the `_src` calls
+            # of the vcat arm they replace, bracketed by name; peak memory of one step per arm
+            snames = ("u3d_subpixel2d_conv_fwd_bf16", "u3d_subpixel2d_conv_dgrad_bf16", "u3d_subpixel2d_conv_wgrad_bf16", "u3d_conv2d_bf16_res",
+                      "u3d_conv2d_wgrad_bf16_strided", "u3d_conv2d_bf16", "u3d_conv2d_wgrad_bf16", "u3d_conv2d_bf16_src",
+                      "u3d_conv2d_bf16_dgrad_src", "u3d_conv2d_wgrad_bf16_src", "u3d_gn_bwd_apply", "u3d_gn_bwd_apply_up")
+
+            def snamed_step(path):
+                prof = nat.EventProfiler(only=snames, prealloc=512)
+                nat.profiler = prof
+                step(*runs[path], x, target, loss_fn)
+                torch.cuda.synchronize()
+                nat.profiler = None
+                return {k: {"calls": v["calls"], "ms": round(v["ms"], 3), "ms_per_call": round(v["ms"] / v["calls"], 4)}
+                        for k, v in prof.summary().items()}
+
+            def speak_bytes(path):
+                torch.cuda.synchronize()
+                torch.cuda.reset_peak_memory_stats(dev)
+                step(*runs[path], x, target, loss_fn)
+                torch.cuda.synchronize()
+                return torch.cuda.max_memory_allocated(dev)
+
+            vcb, spb = snamed_step("bf16_stem_vcat"), snamed_step("bf16_stem_vcat_subpixel")
+            eng = runs["bf16_stem_vcat_subpixel"][0]._get_engine()
+            taken = eng._subpixel_layers((1,) + tuple(hw))
+            ratio = best["bf16_stem_vcat"] / best["bf16_stem_vcat_subpixel"]
+            rec.update(bf16_subpixel_ms_per_step=[round(v, 3) for v in ms["bf16_stem_vcat_subpixel"]],
+                       bf16_subpixel_images_per_s=round(batch * 1000.0 / best["bf16_stem_vcat_subpixel"], 2),
+                       bf16_subpixel_speedup_over_vcat=round(ratio, 4),
+                       bf16_subpixel_bar="more than 1.05x the native_2d_bf16_vcat arm of the same run",
+                       bf16_subpixel_meets_bar=bool(ratio > 1.05),
+                       bf16_subpixel_decoder_levels_taken=f"{len(taken)} of {len(eng.dec)}",
+                       bf16_subpixel_vcat_arm_calls=vcb, bf16_subpixel_arm_calls=spb,
+                       bf16_subpixel_peak_memory_bytes={p: speak_bytes(p) for p in ("bf16_stem_vcat", "bf16_stem_vcat_subpixel")})
         if not a.native_only:
             rec.update(stock_ms_per_step=[round(v, 3) for v in ms[False]], stock_images_per_s=round(batch * 1000.0 / best[False], 2),
                        native_speedup=round(best[False] / best[True], 3))
