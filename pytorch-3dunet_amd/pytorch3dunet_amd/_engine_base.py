@@ -413,8 +413,8 @@ class ConvRec:
     idx_gw: int = -1  # indices into the flat parameter list
     idx_gb: int = -1
     idx_w: int = -1
-    family: str = "fp32"  # the `ConvLayers._FWD_KERNELS` row forward chose: what backward (`_bwd_families`) and the scratch sizing dispatch on
-    sub: Optional[tuple] = None  # (C0, C1): the upsampled half ran as a sub-pixel convolution (csrc/u3d_subpix.hip)
+    family: str = "fp32"  # the `ConvLayers._FWD_KERNELS` row forward chose: ALL that backward (`_bwd_families`) and the scratch sizing dispatch on
+    sub: Optional[tuple] = None  # (C0, C1): the upsampled half ran as a sub-pixel convolution (the `subpixel`, `subpixel2d`, `subpixel2d_bf16` rows)
     plus: tuple = (0, 0, 0)      # a sub-pixel layer: per axis 1 where its level upsamples n -> 2n + 1 (`ConvLayers._src_plus`)
     c16: bool = False            # a `conv2d_bf16` layer on the `_c16` entry points and `*_C16` images (`ConvLayers._c16`)
     pre_norm: bool = True        # GroupNorm on the conv input ('gc…'); False: `affine` is the identity table

@@ -1,6 +1,6 @@
 """One SingleConv / ResNetBlock convolution (reference buildingblocks.py:99-135) forward and backward on the native kernels: which
-kernel FAMILY runs a layer (first-layer small-Cin, sub-pixel decoder, split-fp32, bf16 operands / bf16 storage, fp32 MFMA) is decided
-ONCE, in forward (`_fwd_family`), and kept in the layer's record: `ConvRec.family`, with `sub`, `plus` and `c16` beside it.  Backward maps
+kernel FAMILY runs a layer (first-layer small-Cin, sub-pixel decoder in fp32 or bf16, split-fp32, bf16 operands / bf16 storage, fp32 MFMA)
+is decided ONCE, in forward (`_fwd_family`), and kept in the layer's record: `ConvRec.family`, with `sub`, `plus`, `c16` beside it.  Backward maps
 the recorded family to its (data-gradient, weight-gradient) families in one place (`_BWD_FAMILY`; `_bwd_families` holds the few
 decisions that are backward's own), the shared scratch is sized from the same record (`_family_ws_floats`), and every launcher reads the
 record instead of asking the routing rules again — a new family is a new entry in the tables, not a new flag inside the layer code.
@@ -27,9 +27,10 @@ from ._engine_weights import Kind
 
 class _SubLayers(dict):
     """{id(conv weight): (C0, C1)} of the decoder first convs that take the sub-pixel path at one input size; `plus` = the ids whose level
-    upsamples n -> 2n + 1 along some axis"""
+    upsamples n -> 2n + 1 along some axis; `family` = the one `_FWD_KERNELS` row every entry runs on (`_subpixel_layers` chooses it)"""
 
     plus = frozenset()
+    family = None
 
 
 @dataclass
@@ -50,7 +51,7 @@ class _ConvCall:
     stats: bool                          # the epilogue accumulates (sum, sum of squares) of the written values
     pool: _StatPool
     residual: Optional[torch.Tensor]     # added before the ReLU inside the conv epilogue (pre-norm residual blocks)
-    sub: dict                            # sub-pixel layers of this forward: id(weight) -> (C0, C1)
+    sub: dict                            # sub-pixel layers of this forward (`_SubLayers`): id(weight) -> (C0, C1), and their family
     b16: bool                            # bf16 activation storage
     affine_lo: Optional[torch.Tensor] = None  # sub-pixel layers: compact rows of `affine` for the skip / upsampled channels
     affine_hi: Optional[torch.Tensor] = None
@@ -132,9 +133,11 @@ class ConvLayers:
 
     def _subpixel_layers(self, size):
         """decoder first convs whose low-res input is upsampled by exactly 2 — or, round 5, from n to 2n + 1 voxels — in every dimension at
-        this input size: {id(weight): (C0, C1)} (+ `.plus`: the ids with an n -> 2n + 1 axis) — per-call state, handed down as `sub`"""
+        this input size: {id(weight): (C0, C1)} (+ `.plus`: the ids with an n -> 2n + 1 axis, `.family`: the kernel family of them all) —
+        per-call state, handed down as `sub`: forward, `_stats_of` and the image cache read the join of a decoder from it"""
         is2d = self.is2d
         bf16_sub = is2d and self.subpixel2d_bf16  # (`native_2d_bf16_subpixel`: the levels `_bf16_subpixel` accepts, on the bf16 kernels)
+        assert not (bf16_sub and self.subpixel)  # (`native_2d_subpixel` refuses the bf16 keys: one family per table)
         if not (self.subpixel or bf16_sub) or any(ct is not None for ct in self.dec_up) or any(self.dec_interp):
             return _SubLayers()  # (a transposed convolution yields 2n-1 voxels, resized to the skip: never an exact 2x replication)
         dims = [tuple(size)[1:] if is2d else tuple(size)]  # (2-D, `native_2d_subpixel`: H and W only)
@@ -142,6 +145,7 @@ class ConvLayers:
             if has_pool:
                 dims.append(tuple(d // 2 for d in dims[-1]))
         out, plus = _SubLayers(), set()
+        out.family = "subpixel2d_bf16" if bf16_sub else ("subpixel2d" if is2d else "subpixel")
         L = len(self.enc)
         for j, (c1, _) in enumerate(self.dec):
             skip_lvl, low_lvl = L - 2 - j, L - 1 - j
@@ -149,11 +153,11 @@ class ConvLayers:
                 continue
             C0 = self.enc[skip_lvl][2].conv.out_channels
             C1 = c1.conv.in_channels - C0
-            if self._cat_bf16(c1):  # (bf16 mode: the concat is materialised or read in place, an ordinary layer — but for `_bf16_subpixel`)
+            # (bf16 mode: the concat is materialised or read in place, an ordinary layer — but for `_bf16_subpixel`, which asks `_cat_bf16`
+            # itself: under `native_2d_bf16_subpixel` a layer outside it keeps its fp32 virtual concat)
+            if bf16_sub or self._cat_bf16(c1):
                 if bf16_sub and self._bf16_subpixel(c1, C0, C1, dims[skip_lvl], dims[low_lvl]):
                     out[id(c1.conv.weight)] = (C0, C1)
-                continue
-            if not self.subpixel:  # (`native_2d_bf16_subpixel` alone: a layer outside `_cat_bf16` keeps its fp32 virtual concat)
                 continue
             # every axis upsampled by exactly 2, or n -> 2n + 1 (the pooled size of an odd level; round 5: the sub-pixel kernels on a
             # shifted window + the general kernels on the near-boundary slab, _fwd_subpixel / _dgrad_subpixel / _wgrad_subpixel)
@@ -498,18 +502,17 @@ class ConvLayers:
         "conv2d": "_fwd_conv2d",      # u3d_conv2d.hip: 3x3 convolutions of a 2-D net (native_2d), every layer and only those ...
         "conv2d_bf16": "_fwd_conv2d_bf16",  # u3d_conv2d_bf16.hip: ... except, in bf16, the single-source layers that fit (`_bf16_routed`)
         "small2d": "_fwd_small2d",    # u3d_conv2d.hip: ... and, under `native_2d_stem`, the first layer, Cin <= 4 (the 3-D `small` rule)
-        # u3d_subpix2d.hip + u3d_conv2d.hip: `native_2d_subpixel`, cat(skip, nearest2x(low)), 4/9 of the MACs; under `native_2d_bf16_subpixel`
-        # (the two keys refuse each other) the family's three launchers run their bf16 twins of u3d_conv2d_bf16.hip (`_*_subpixel2d_bf16`)
-        "subpixel2d": "_fwd_subpixel2d",
+        "subpixel2d": "_fwd_subpixel2d",  # u3d_subpix2d.hip + u3d_conv2d.hip: `native_2d_subpixel`, cat(skip, nearest2x(low)), 4/9 of the MACs
+        "subpixel2d_bf16": "_fwd_subpixel2d_bf16",  # u3d_conv2d_bf16.hip: `native_2d_bf16_subpixel`, the same on bf16 MFMA (`_bf16_subpixel`)
         "conv2d_bf16_src": "_fwd_conv2d_bf16_src",  # u3d_conv2d_bf16.hip: `native_2d_bf16_vcat`, a decoder's virtual concat read in place
     }
 
-    # ---- a 2-D net (`is2d`): small2d -> subpixel2d -> conv2d_bf16 | conv2d_bf16_src | conv2d ----------------------------------------
+    # ---- a 2-D net (`is2d`): small2d -> subpixel2d | subpixel2d_bf16 (the table's) -> conv2d_bf16 | conv2d_bf16_src | conv2d ----------
     def _fwd_family_2d(self, c: "_ConvCall", residual) -> str:
         if self._small2d(c.Ctot, c.Cout, c.src.t1 is not None) and residual is None:
             return "small2d"
         if c.src.t1 is not None and residual is None and id(c.conv.weight) in c.sub:
-            return "subpixel2d"
+            return c.sub.family
         # (a decoder's first conv reaches here on its materialised concat when it fits: `_cat_bf16`; forward and data gradient
         # are covered together by the one channel rule; a residual rides in either family's epilogue)
         if not self._bf16_routed(c.src, c.Cout):
@@ -522,7 +525,7 @@ class ConvLayers:
         if self.small_cin and c.src.t1 is None and c.Ctot <= 4 and c.Cout <= 32 and residual is None and not c.b16:
             return "small"
         if c.src.t1 is not None and residual is None and id(c.conv.weight) in c.sub:
-            return "subpixel"
+            return c.sub.family
         if c.src.t1 is None and self._split_fwd(c.Ctot, c.Cout):
             return "f32s"
         if c.src.t1 is None and self._bf16_layer(c.Ctot, c.Cout):
@@ -595,8 +598,6 @@ class ConvLayers:
     def _fwd_subpixel2d(self, c: "_ConvCall"):
         # `native_2d_subpixel`: the upsampled half as 4 parity-class 2x2 convolutions over the low-res tensor (4/9 of the multiply-adds,
         # csrc/u3d_subpix2d.hip), then the skip half, whose epilogue adds the partial sums before ReLU / statistics (u3d_conv2d_res_reps)
-        if self.subpixel2d_bf16:  # (the two are never on together: `native_2d_subpixel` refuses the bf16 keys)
-            return self._fwd_subpixel2d_bf16(c)
         dev, conv, src, N, H, W, Cout = c.dev, c.conv, c.src, c.N, c.H, c.W, c.Cout
         plus = c.plus
         assert c.D == 1 and H == 2 * src.H1 + plus[1] and W == 2 * src.W1 + plus[2]
@@ -858,6 +859,7 @@ class ConvLayers:
         "conv2d": "_wgrad_conv2d",      # u3d_conv2d.hip (2-D nets)
         "conv2d_bf16": "_wgrad_conv2d_bf16",  # u3d_conv2d_bf16.hip (2-D nets in bf16: every layer the bf16 forward covers)
         "subpixel2d": "_wgrad_subpixel2d",  # u3d_subpix2d.hip (upsampled channels) + u3d_conv2d.hip strided (skip channels)
+        "subpixel2d_bf16": "_wgrad_subpixel2d_bf16",  # u3d_conv2d_bf16.hip: both channel slices on bf16 MFMA
     }
     _DGRAD_KERNELS = {
         "subpixel": "_dgrad_subpixel",  # skip half at full resolution + upsampled half directly at LOW resolution
@@ -867,6 +869,7 @@ class ConvLayers:
         "conv2d": "_dgrad_conv2d",  # u3d_conv2d.hip (2-D nets)
         "conv2d_bf16": "_dgrad_conv2d_bf16",  # u3d_conv2d_bf16.hip
         "subpixel2d": "_dgrad_subpixel2d",  # u3d_conv2d.hip (skip half) + u3d_subpix2d.hip (upsampled half at LOW resolution)
+        "subpixel2d_bf16": "_dgrad_subpixel2d_bf16",  # u3d_conv2d_bf16.hip: both halves on bf16 MFMA
     }
 
     # the family forward recorded (`ConvRec.family`, a row of _FWD_KERNELS) -> the family of its two gradients, where the name differs: the
@@ -1056,8 +1059,6 @@ class ConvLayers:
     def _wgrad_subpixel2d(self, c: "_BwdCall"):
         # `native_2d_subpixel`: the weight gradient in two channel slices of the same (Cout, Ctot, 9) buffer — upsampled channels from the
         # 16 (parity class, tap half) matrices over the low-res grid, skip channels from the standard kernel (takes no job, as `conv2d`)
-        if self.subpixel2d_bf16:
-            return self._wgrad_subpixel2d_bf16(c)
         cx, dev, src, rec, ws = c.cx, c.cx.dev, c.src, c.rec, c.cx.ws
         C0, C1 = rec.sub
         Ct = src.C
@@ -1128,8 +1129,6 @@ class ConvLayers:
     def _dgrad_subpixel2d(self, c: "_BwdCall"):
         # skip half at full resolution (mode-1 image of channels [0, C0)); upsampled half directly at LOW resolution, the children sum
         # of the nearest upsampling folded into the 4x4-tap stride-2 gather.  dg = (dg_skip, dlow)
-        if self.subpixel2d_bf16:
-            return self._dgrad_subpixel2d_bf16(c)
         cx, dev, src, rec, ws, pool = c.cx, c.cx.dev, c.src, c.rec, c.cx.ws, c.cx.pool
         C0, C1 = rec.sub
         w, pair = rec.conv_w, tuple(rec.sub)
@@ -1325,7 +1324,7 @@ class ConvLayers:
             return max(lib.u3d_conv3d_bf16_workspace_floats(N, D, H, W, Cout, Cin), lib.u3d_wgrad_bf16_workspace_floats(N, D, H, W, Cin, Cout))
         if family in ("fp32", "f32s"):  # (the split data gradient grows the buffer itself, `_BwdCtx.ensure_ws`)
             return max(lib.u3d_wgrad_workspace_floats(N, D, H, W, Cin, Cout), lib.u3d_conv3d_workspace_floats(N, D, H, W, Cout, Cin))
-        if family == "subpixel2d" and self.subpixel2d_bf16:  # (`native_2d_bf16_subpixel`: the same three on the bf16 kernels' plans)
+        if family == "subpixel2d_bf16":  # (`native_2d_bf16_subpixel`: the three of `subpixel2d` below on the bf16 kernels' plans)
             return max(lib.u3d_wgrad2d_bf16_workspace_floats(N, H, W, sub[0], Cout),
                        lib.u3d_subpixel2d_wgrad_bf16_workspace_floats(N, H // 2, W // 2, sub[1], Cout),
                        lib.u3d_conv2d_bf16_workspace_floats(N, H, W, Cout, sub[0]))

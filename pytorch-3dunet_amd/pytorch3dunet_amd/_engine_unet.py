@@ -267,7 +267,7 @@ class UNet3DEngine(ConvLayers):
         x0, dims, tape = self._enter(x, save)
         N, _, D, H, W = dims
         sub = self._subpixel_layers((D, H, W))
-        self.images.repack(dev, save, sub, sub.plus)
+        self.images.repack(dev, save, sub)
         # stat doubles: every conv output + every GN input computed standalone; generous upper bound
         tot = 0
         R = self.stat_reps
@@ -333,18 +333,12 @@ class UNet3DEngine(ConvLayers):
                     tape.ups.append(UpRec(cur, None, tabs, (Ds, Hs, Ws), self.dec_interp[j]))
                 cur, cur_st = up, None
             src = VSrc(sk, cur)  # skip channels first (buildingblocks.py:491)
-            sub_bf16 = self._cat_bf16(c1) and id(c1.conv.weight) in sub  # (`native_2d_bf16_subpixel`: `_bf16_subpixel` accepted this level)
-            st_in = stats_of(src, sk_st, cur_st, pool, dev, sub_bf16)
-            if sub_bf16:
-                # the two halves run as plain tensors on the sub-pixel bf16 kernels: the concat is never written and nothing of it is kept
-                y1, s1 = self._single_conv_fwd(c1, f"dec{j}.c1", src, st_in, pool, tape, sub=sub)
-            elif self._cat_bf16(c1) and self._bf16_routed(src, c1.conv.out_channels):
-                # `native_2d_bf16_vcat`: the bf16 kernels read the two halves in place (`_bf16_vcat`) — no copy, and the tape keeps the
-                # virtual source itself (no `tape.cats` entry)
-                y1, s1 = self._single_conv_fwd(c1, f"dec{j}.c1", src, st_in, pool, tape)
-            elif self._cat_bf16(c1):
-                # bf16 mode: the concat is written out once and the layer is an ordinary single-source bf16 layer (`_cat_bf16`); the
-                # per-channel sums of the virtual tensor describe the materialised one exactly
+            in_sub = id(c1.conv.weight) in sub  # (a sub-pixel level of this forward: its two halves run as plain tensors)
+            st_in = stats_of(src, sk_st, cur_st, pool, dev, in_sub and sub.family == "subpixel2d_bf16")
+            # ONE question per decoder: is the concat written out?  bf16 mode, a layer that fits the bf16 kernels (`_cat_bf16`) and is neither
+            # a sub-pixel level nor read in place by the `_src` entry points (`native_2d_bf16_vcat`, `_bf16_vcat`) — it then runs as an
+            # ordinary single-source bf16 layer; the per-channel sums of the virtual tensor describe the materialised one exactly
+            if self._cat_bf16(c1) and not in_sub and not self._bf16_routed(src, c1.conv.out_channels):
                 cat = _empty((src.N, src.D, src.H, src.W, src.C), dtype=_F32, device=dev)
                 nat.call("u3d_nearest_cat_fwd", dev.index, _stream(dev), _p(sk), _p(cur), _p(src.maps[0]), _p(src.maps[1]), _p(src.maps[2]),
                          src.N, src.D, src.H, src.W, src.D1, src.H1, src.W1, src.C0, src.C1, _p(cat))
@@ -352,7 +346,7 @@ class UNet3DEngine(ConvLayers):
                     tape.cats[j] = src
                 y1, s1 = self._single_conv_fwd(c1, f"dec{j}.c1", VSrc(cat), st_in, pool, tape)
                 del cat
-            else:
+            else:  # (every other join keeps the virtual source, on the tape too; `sub` changes nothing for a level outside it)
                 y1, s1 = self._single_conv_fwd(c1, f"dec{j}.c1", src, st_in, pool, tape, sub=sub)
             src2 = VSrc(y1)
             y2, s2 = self._single_conv_fwd(c2, f"dec{j}.c2", src2, stats_of(src2, s1, None, pool, dev), pool, tape)

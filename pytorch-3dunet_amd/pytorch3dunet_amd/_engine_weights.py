@@ -21,7 +21,8 @@ _BF16 = torch.bfloat16
 
 class Kind(enum.IntEnum):
     """every image a kernel reads; `_KINDS` says how each one is sized and packed.  A decoder first conv on the sub-pixel path has the
-    SKIP_* / UP_* images (and SLAB_* at a level that upsamples n -> 2n + 1) of its two input-channel halves instead of FWD / DGRAD."""
+    SKIP_* / UP_* images (and SLAB_* at a level that upsamples n -> 2n + 1) of its two input-channel halves instead of the whole-weight
+    pair of its family: `_SUB_KINDS` says which."""
 
     FWD = enum.auto()           # fp32 3x3x3 forward ...
     DGRAD = enum.auto()         # ... and data gradient (flipped taps, swapped roles)
@@ -128,6 +129,13 @@ _KINDS = {
     Kind.SKIP_BF16_DGRAD2D: _Spec(_2db, _BF16, "u3d_pack_weights2d_bf16_slice", 1, half=0),
     Kind.UP_BF16_FWD2D: _Spec(_up2db, _BF16, "u3d_pack_subpixel2d_weights_bf16", 0, half=1, up2d=True),
     Kind.UP_BF16_DGRAD2D: _Spec(_up2db, _BF16, "u3d_pack_subpixel2d_weights_bf16", 1, half=1, up2d=True),
+}
+# the images a sub-pixel layer reads, stated once: (forward, data-gradient) pair of the whole weight in a `repack` list -> the pairs of its
+# skip half, its upsampled half and — an n -> 2n + 1 level — the slab (None: the family takes exact-2x levels only)
+_SUB_KINDS = {
+    (Kind.FWD, Kind.DGRAD): ((Kind.SKIP_FWD, Kind.SKIP_DGRAD), (Kind.UP_FWD, Kind.UP_DGRAD), (Kind.SLAB_FWD, Kind.SLAB_DGRAD)),
+    (Kind.FWD2D, Kind.DGRAD2D): ((Kind.SKIP_FWD2D, Kind.SKIP_DGRAD2D), (Kind.UP_FWD2D, Kind.UP_DGRAD2D), (Kind.SLAB_FWD2D, Kind.SLAB_DGRAD2D)),
+    (Kind.BF16_FWD2D, Kind.BF16_DGRAD2D): ((Kind.SKIP_BF16_FWD2D, Kind.SKIP_BF16_DGRAD2D), (Kind.UP_BF16_FWD2D, Kind.UP_BF16_DGRAD2D), None),
 }
 _BF16_BOTH = 6  # batch row that writes BF16_FWD and, right behind it in one buffer, BF16_DGRAD from one read of the weight
 
@@ -243,31 +251,30 @@ class WeightImages:
             hit = self._tables[launch] = (key, build())
         return hit[1]
 
-    def repack(self, dev, grads: bool, sub=None, plus=()):
+    @staticmethod
+    def _layer_kinds(w, nd, whole, sub):
+        """(pair, kinds) of one weight of a `repack` list: the first `nd` of its `whole`-weight images, or — a layer of `sub` — of each
+        pair `_SUB_KINDS` names, with its (C0, C1)"""
+        pair = sub.get(id(w)) if sub else None
+        if pair is None:
+            return None, whole[:nd]
+        skip, up, slab = _SUB_KINDS[whole]
+        return pair, skip[:nd] + up[:nd] + (slab[:nd] if id(w) in sub.plus else ())
+
+    def repack(self, dev, grads: bool, sub=None):
         """(Re)pack the images of ALL conv weights whose parameter changed since the last pack — one launch for the whole model
         (u3d_pack_weights_batch_cells; bf16 mode: u3d_pack_weights_bf16_batch) instead of one per layer and image; the buffers and the
         device descriptor tables are allocated once and reused (stable pointers).  `grads`: the data-gradient images too.  `sub`:
-        {id(weight): (C0, C1)} of the layers on the sub-pixel path in this forward, `plus` the ids among them with slab images."""
+        the `_SubLayers` of this forward, {id(weight): (C0, C1)} of the layers on the sub-pixel path, `sub.plus` the ids with slab images."""
         nd = 2 if grads else 1
         for w in self._each:  # 2-D images: one small launch per weight and image (u3d_pack_weights2d)
-            pair = sub.get(id(w)) if sub else None
-            if pair is not None:  # (`native_2d_subpixel`: the images of the two input-channel halves instead)
-                kinds = (Kind.SKIP_FWD2D, Kind.SKIP_DGRAD2D)[:nd] + (Kind.UP_FWD2D, Kind.UP_DGRAD2D)[:nd]
-                if id(w) in plus:
-                    kinds += (Kind.SLAB_FWD2D, Kind.SLAB_DGRAD2D)[:nd]
-                for kind in kinds:
-                    self.get(w, kind, dev, pair)
-                continue
-            for kind in (Kind.FWD2D, Kind.DGRAD2D)[:nd]:
-                self.get(w, kind, dev)
+            pair, kinds = self._layer_kinds(w, nd, (Kind.FWD2D, Kind.DGRAD2D), sub)  # (`native_2d_subpixel`: the two halves instead)
+            for kind in kinds:
+                self.get(w, kind, dev, pair)
         for w in self._each_bf16:  # ... and of the 2-D layers on the bf16 kernels (u3d_pack_weights2d_bf16)
-            pair = sub.get(id(w)) if sub else None
-            if pair is not None:  # (`native_2d_bf16_subpixel`: the images of the two input-channel halves instead)
-                for kind in (Kind.SKIP_BF16_FWD2D, Kind.SKIP_BF16_DGRAD2D)[:nd] + (Kind.UP_BF16_FWD2D, Kind.UP_BF16_DGRAD2D)[:nd]:
-                    self.get(w, kind, dev, pair)
-                continue
-            for kind in (Kind.BF16_FWD2D, Kind.BF16_DGRAD2D)[:nd]:
-                self.get(w, kind, dev)
+            pair, kinds = self._layer_kinds(w, nd, (Kind.BF16_FWD2D, Kind.BF16_DGRAD2D), sub)  # (`native_2d_bf16_subpixel`: likewise)
+            for kind in kinds:
+                self.get(w, kind, dev, pair)
         for w in self._each_bf16_c16:  # ... and of its 16-channel stem layers (u3d_pack_weights2d_bf16_c16)
             for kind in (Kind.BF16_FWD2D_C16, Kind.BF16_DGRAD2D_C16)[:nd]:
                 self.get(w, kind, dev)
@@ -275,12 +282,7 @@ class WeightImages:
             self._repack_bf16(dev, nd)
         refs = []
         for w in self._f32:
-            pair = sub.get(id(w)) if sub else None
-            kinds = (Kind.FWD, Kind.DGRAD)[:nd]
-            if pair is not None:
-                kinds = (Kind.SKIP_FWD, Kind.SKIP_DGRAD)[:nd] + (Kind.UP_FWD, Kind.UP_DGRAD)[:nd]
-                if id(w) in plus:
-                    kinds += (Kind.SLAB_FWD, Kind.SLAB_DGRAD)[:nd]
+            pair, kinds = self._layer_kinds(w, nd, (Kind.FWD, Kind.DGRAD), sub)
             refs += [(w, kind, pair) for kind in kinds]
         stale = self._stale(refs)
         if not stale:

@@ -10,7 +10,7 @@ import torch
 
 from pytorch3dunet_amd import _native as nat
 from pytorch3dunet_amd._engine_base import ConvRec, VSrc, slab_boxes
-from pytorch3dunet_amd._engine_conv import ConvLayers, _ConvCall
+from pytorch3dunet_amd._engine_conv import ConvLayers, _ConvCall, _SubLayers
 
 CHANNELS = (1, 4, 8, 16, 32, 48, 64)
 ENGINES = {  # name: (class, model keys)
@@ -25,6 +25,8 @@ ENGINES = {  # name: (class, model keys)
     "unet2d_bf16_stem": ("UNet2D", dict(native_2d_bf16=True, native_2d_stem=True)),
     "unet2d_bf16_vcat": ("UNet2D", dict(native_2d_bf16_vcat=True)),
     "unet2d_bf16_vcat_stem": ("UNet2D", dict(native_2d_bf16_vcat=True, native_2d_stem=True)),
+    "unet2d_bf16_subpixel": ("UNet2D", dict(native_2d_bf16_subpixel=True)),
+    "unet2d_bf16_subpixel_vcat": ("UNet2D", dict(native_2d_bf16_subpixel=True, native_2d_bf16_vcat=True)),
     "resunet2d": ("ResidualUNet2D", dict(native_2d_residual=True)),
     "resunet2d_bf16": ("ResidualUNet2D", dict(native_2d_residual_bf16=True)),
 }
@@ -36,15 +38,15 @@ def _frozen_bf16(eng, src, Cout, sub, small):
     return sub is None and not small and eng._bf16_routed(src, Cout)  # (`_conv_bwd`: "the forward's decision")
 
 
-def _frozen_bwd_family_2d(sub, bf16):
-    if sub is not None:
-        return "subpixel2d"
+def _frozen_bwd_family_2d(eng, sub, bf16):
+    if sub is not None:  # (the parent's `_*_subpixel2d` launchers began with `if self.subpixel2d_bf16: return self._*_subpixel2d_bf16(c)`)
+        return "subpixel2d_bf16" if eng.subpixel2d_bf16 else "subpixel2d"
     return "conv2d_bf16" if bf16 else "conv2d"
 
 
 def _frozen_wgrad_family(eng, src, Cout, sub, bf16, side_max_voxels):
     if eng.is2d:
-        return _frozen_bwd_family_2d(sub, bf16)
+        return _frozen_bwd_family_2d(eng, sub, bf16)
     if bf16 and Cout % 32 == 0:
         return "bf16"
     if sub is not None:
@@ -56,7 +58,7 @@ def _frozen_wgrad_family(eng, src, Cout, sub, bf16, side_max_voxels):
 
 def _frozen_dgrad_family(eng, src, Cout, sub, small, bf16):
     if eng.is2d:
-        return _frozen_bwd_family_2d(sub, bf16)
+        return _frozen_bwd_family_2d(eng, sub, bf16)
     if sub is not None:
         return "subpixel"
     if src.t1 is None and not small and eng._split_dgrad(src.C, Cout):
@@ -74,6 +76,10 @@ def _frozen_families(eng, src, Cout, sub, small, need_dg, side_max_voxels):
 def _frozen_layer_ws_floats(eng, N, D, H, W, Cin, Cout, sub, small, virtual):
     lib = nat.get_lib()
     if eng.is2d:
+        if sub is not None and eng.subpixel2d_bf16:  # (`_family_ws_floats`: `family == "subpixel2d" and self.subpixel2d_bf16`)
+            return max(lib.u3d_wgrad2d_bf16_workspace_floats(N, H, W, sub[0], Cout),
+                       lib.u3d_subpixel2d_wgrad_bf16_workspace_floats(N, H // 2, W // 2, sub[1], Cout),
+                       lib.u3d_conv2d_bf16_workspace_floats(N, H, W, Cout, sub[0]))
         if sub is not None:
             boxes = slab_boxes((1, H, W), (0, H % 2, W % 2), 2)
             return max(lib.u3d_wgrad2d_workspace_floats(N, H, W, sub[0], Cout),
@@ -114,7 +120,8 @@ def _source(is2d, C, virtual, plus):
 
 def _layers(eng):
     """(src, Cout, sub) of every layer of the grid this engine could meet: single and virtual sources, the latter with and without a
-    sub-pixel entry where `_subpixel_layers` could make one (channel counts % 4; an n -> 2n + 1 level only where the engine takes them)"""
+    sub-pixel entry where `_subpixel_layers` could make one (channel counts % 4; an n -> 2n + 1 level only where the engine takes them;
+    under `native_2d_bf16_subpixel` what `_bf16_subpixel` accepts: the exact-2x source with all channel counts % 32)"""
     takes_plus = eng.subpixel2d_plus if eng.is2d else eng.subpixel_plus
     for C, Cout in itertools.product(CHANNELS, repeat=2):
         yield _source(eng.is2d, C, False, False), Cout, None
@@ -123,16 +130,19 @@ def _layers(eng):
             yield src, Cout, None
             if eng.subpixel and C % 4 == 0 and Cout % 4 == 0 and (takes_plus or not plus):
                 yield src, Cout, (C, C)
+            if eng.subpixel2d_bf16 and C % 32 == 0 and Cout % 32 == 0 and not plus:
+                yield src, Cout, (C, C)
 
 
 def _record(eng, src, Cout, pair):
     """the routing part of the record, as `_single_conv_fwd` fills it"""
     conv = types.SimpleNamespace(weight=object())
-    sub = {id(conv.weight): pair} if pair is not None else {}
+    sub = _SubLayers({id(conv.weight): pair} if pair is not None else {})  # (the family: as `_subpixel_layers` names it)
+    sub.family = "subpixel2d_bf16" if eng.subpixel2d_bf16 else ("subpixel2d" if eng.is2d else "subpixel")
     call = _ConvCall(dev=None, conv=conv, src=src, affine=None, y=None, N=src.N, D=src.D, H=src.H, W=src.W, Ctot=src.C, Cout=Cout, relu=0,
                      stats=False, pool=None, residual=None, sub=sub, b16=False)
     family = eng._fwd_family(call, None)
-    assert (family in ("subpixel", "subpixel2d")) == (pair is not None)
+    assert (family in ("subpixel", "subpixel2d", "subpixel2d_bf16")) == (pair is not None)
     return ConvRec(name="layer", src=src, affine=None, mean_rstd=None, y=torch.empty(0, Cout), gn_w=None, conv_w=None, G=1, family=family,
                    sub=pair, plus=eng._src_plus(src) if pair is not None else (0, 0, 0),
                    c16=family == "conv2d_bf16" and eng._c16(src.C, Cout))
@@ -186,6 +196,17 @@ def test_scratch_sized_from_the_record_is_the_old_by_shape_answer(engines):
             sizes.add((rec.family, want > 0))
     assert {f for f, nonzero in sizes if nonzero} == set(ConvLayers._FWD_KERNELS)  # (no family's comparison is 0 == 0 throughout)
     assert engines["unet3d"]._wgrad_workspace_floats([]) == 0
+
+
+def test_subpixel_table_names_the_family_of_its_layers(engines):
+    seen = {}
+    for name, eng in engines.items():
+        sub = eng._subpixel_layers((1, 8, 8) if eng.is2d else (8, 8, 8))  # (f_maps 32, 64: one decoder, 32 + 64 -> 32 at exact 2x)
+        assert len(sub) <= 1 and (not sub or sub.family in ConvLayers._FWD_KERNELS)
+        if sub:
+            seen[name] = sub.family
+    assert seen == dict(unet3d="subpixel", unet3d_f32s="subpixel", unet2d_subpixel="subpixel2d", unet2d_subpixel_plus="subpixel2d",
+                        unet2d_bf16_subpixel="subpixel2d_bf16", unet2d_bf16_subpixel_vcat="subpixel2d_bf16")
 
 
 def test_tables_name_launchers_of_the_mixin():

@@ -1,6 +1,7 @@
 """Which entry points one training step launches around the 3x3(x3) convolutions, in order, with the FLOPs each call declares — held
 against the sequence the commit before a layer's kernel family was recorded once (`ConvRec.family`, `ConvLayers._bwd_families`) launched
-on the MI355X (tests/golden/launch_sequences_conv.json; recorded twice there, identical).  The cases are the conv-family outcomes the two
+on the MI355X (tests/golden/launch_sequences_conv.json; recorded twice there, identical; the two `unet2d_bf16_subpixel*` cases likewise at
+the commit before `subpixel2d_bf16` became a recorded family of its own and a decoder's join one decision).  The cases are the conv-family outcomes the two
 older fixtures do not reach, each at about the smallest shape that takes the branch; the recorder and the comparison are
 test_gpu_launch_sequence_2d.py's.  (That recorder asks for no input gradient, so a stem layer on the bf16 kernels whose small-family
 first layer needs a data gradient has no case here; `unet2d_stem` of the older fixture holds the small family's fall-through.)
@@ -26,7 +27,12 @@ CASES = {  # name: (class, model keys, f_maps, num_groups, input shape)
     "unet3d_bf16": ("UNet3D", dict(compute_dtype="bf16"), [32, 64, 128], 8, (1, 1, 9, 16, 16)),  # written-out concat; 16 -> 32 stays fp32
     # post-norm order: `_bf16_vcat` and `_cat_bf16` both refuse, the decoder's first conv runs fp32 on the virtual source
     "unet2d_bf16_vcat_cgr": ("UNet2D", dict(native_2d_bf16_vcat=True, layer_order="cgr"), [32, 64], 8, (2, 1, 35, 45)),
+    # the top decoder is exact 2x (`subpixel2d_bf16`), the bottom one goes 10 -> 21: its concat is written out ...
+    "unet2d_bf16_subpixel": ("UNet2D", dict(native_2d_bf16_subpixel=True), [32, 64, 128], 8, (2, 1, 36, 42)),
+    # ... or, with the `_src` entry points beside the sub-pixel family, read in place: no concat is written at either level
+    "unet2d_bf16_subpixel_vcat": ("UNet2D", dict(native_2d_bf16_subpixel=True, native_2d_bf16_vcat=True), [32, 64, 128], 8, (2, 1, 36, 42)),
 }
+_SUB_BF16 = ("u3d_subpixel2d_conv_fwd_bf16", "u3d_subpixel2d_conv_dgrad_bf16", "u3d_subpixel2d_conv_wgrad_bf16")
 REACHES = {  # entry points a case's sequence must contain (asserted when recording and by the test)
     "unet2d_subpixel_plus": ("u3d_subpixel2d_conv_fwd_win", "u3d_conv2d_box", "u3d_subpixel2d_conv_fwd", "u3d_conv2d_wgrad_box",
                              "u3d_nearest_childsum_add2d", "u3d_gn_bwd_apply_children2d", "u3d_chan_stats_children2d"),
@@ -37,7 +43,11 @@ REACHES = {  # entry points a case's sequence must contain (asserted when record
     "unet3d_bf16": ("u3d_nearest_cat_fwd", "u3d_conv3d_bf16_ex", "u3d_conv3d_wgrad_bf16_job", "u3d_conv3d_ex_reps",
                     "u3d_conv3d_wgrad_job"),
     "unet2d_bf16_vcat_cgr": ("u3d_conv2d_ex_reps", "u3d_conv2d_bf16", "u3d_conv2d_wgrad", "u3d_conv2d_wgrad_bf16"),
+    "unet2d_bf16_subpixel": _SUB_BF16 + ("u3d_conv2d_bf16_res", "u3d_conv2d_wgrad_bf16_strided", "u3d_pack_subpixel2d_weights_bf16",
+                                         "u3d_pack_weights2d_bf16_slice", "u3d_nearest_cat_fwd"),
+    "unet2d_bf16_subpixel_vcat": _SUB_BF16 + ("u3d_conv2d_bf16_src", "u3d_conv2d_bf16_dgrad_src", "u3d_conv2d_wgrad_bf16_src"),
 }
+ABSENT = {"unet2d_bf16_subpixel_vcat": ("u3d_nearest_cat_fwd",)}  # entry points a case's sequence must not contain
 assert set(REACHES) == set(CASES)
 
 
@@ -53,6 +63,7 @@ def test_launch_sequence(case):
         want = json.load(fh)[case]
     got = launch_sequence(case, CASES)
     assert not _missing(case, got), _missing(case, got)
+    assert not {name for name, _ in got} & set(ABSENT.get(case, ())), case
     diff = next((i for i, (a, b) in enumerate(zip(got, want)) if a != b), min(len(got), len(want)))
     assert got == want, f"{len(got)} launches against {len(want)}; first difference at {diff}: {got[diff:diff + 2]} / {want[diff:diff + 2]}"
 
