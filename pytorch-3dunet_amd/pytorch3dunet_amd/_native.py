@@ -1,4 +1,10 @@
-"""ctypes binding of the C-ABI in include/u3d.h (libu3d_hip.so, gfx950 HIP kernels).
+"""ctypes binding of libu3d_hip.so (gfx950 HIP kernels), derived from include/u3d.h at import.
+
+The header is the only statement of the C-ABI: `parse_header` reads its declarations, the four `typedef struct`s and the `U3D_*`
+constants, and this module keeps no second copy of any of them.  One type rule: scalars map through `_SCALARS`; EVERY pointer argument
+and struct field is `c_void_p` (struct pointers too: two of the four structs travel as device arrays through `data_ptr()`, so a typed
+pointer cannot be the rule), which takes `ctypes.byref(struct)`, `(c_int * n)(...)`, an integer address and None alike; a
+`const char*` return is `c_char_p`.  The reader is strict: whatever it does not understand raises `U3DError`, nothing is skipped.
 
 The product path has NO fallback: if the shared library is missing or a call fails, a RuntimeError is raised.
 """
@@ -6,588 +12,104 @@ from __future__ import annotations
 
 import ctypes
 import os
+import re
 import threading
-from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_size_t, c_void_p
+from ctypes import c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_size_t, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # (U3D_LIB_PATH: another build of the same library — same-box A/B runs of compile-time kernel experiments, tools/ab_libs.sh)
 LIB_PATH = os.environ.get("U3D_LIB_PATH") or os.path.join(_HERE, "lib", "libu3d_hip.so")
-
-U3D_OK = 0
-
-
-class U3DSrc(ctypes.Structure):
-    """mirror of u3d_src_t (include/u3d.h)"""
-
-    _fields_ = [
-        ("p0", c_void_p),
-        ("p1", c_void_p),
-        ("zmap", c_void_p),
-        ("ymap", c_void_p),
-        ("xmap", c_void_p),
-        ("affine", c_void_p),
-        ("C0", c_int32),
-        ("C1", c_int32),
-        ("D1", c_int32),
-        ("H1", c_int32),
-        ("W1", c_int32),
-    ]
-
-
-class U3DAdamDesc(ctypes.Structure):
-    """mirror of u3d_adam_desc_t (include/u3d.h)"""
-
-    _fields_ = [("p", c_void_p), ("g", c_void_p), ("m", c_void_p), ("v", c_void_p), ("first", c_int64), ("numel", c_int64)]
-
-
-class U3DGnBwdJob(ctypes.Structure):
-    """mirror of u3d_gn_bwd_job_t (include/u3d.h)"""
-
-    _fields_ = [("gstats_lo", c_void_p), ("gstats_hi", c_void_p), ("mean_rstd", c_void_p), ("gamma", c_void_p), ("dgamma", c_void_p),
-                ("dbeta", c_void_p), ("coef", c_void_p), ("coef_hi", c_void_p), ("count", ctypes.c_double), ("C0", c_int32),
-                ("C1", c_int32), ("N", c_int32), ("G", c_int32), ("hi_scale", ctypes.c_float), ("reps_lo", c_int32), ("reps_hi", c_int32), ("reserved", c_int32)]
-
-
-class U3DPackDesc(ctypes.Structure):
-    """mirror of u3d_pack_desc_t (include/u3d.h)"""
-
-    _fields_ = [("w", c_void_p), ("packed", c_void_p), ("first", c_int64), ("Cout", c_int32), ("Cin", c_int32),
-                ("mode", c_int32), ("cin_stride", c_int32)]
-
-
-_PROTOS = {
-    # name: (restype, argtypes)
-    "u3d_version": (c_int, []),
-    "u3d_debug_stream_pass": (c_int, [c_int, c_void_p, c_void_p, c_int64, c_int, c_int, c_double]),
-    "u3d_debug_mfma_f32_rate": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, POINTER(c_double)]),
-    "u3d_last_error": (c_char_p, []),
-    "u3d_check_device": (c_int, [c_int]),
-    "u3d_set_tuning": (c_int, [c_int, c_int]),
-    "u3d_set_profile_buffer": (c_int, [c_void_p, c_size_t]),
-    "u3d_packed_weight_floats": (c_size_t, [c_int, c_int, c_int]),
-    "u3d_pack_weights": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
-    "u3d_pack_weights_batch": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int64]),
-    "u3d_pack_weights_cells_blocks": (c_int64, [c_void_p, c_int, c_int, c_int, c_int]),
-    "u3d_pack_weights_batch_cells": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int64]),
-    "u3d_conv3d": (
-        c_int,
-        [c_int, c_void_p, POINTER(U3DSrc), c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
-         POINTER(U3DSrc), c_void_p],
-    ),
-    "u3d_wgrad_workspace_floats": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
-    "u3d_conv3d_variant": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
-    "u3d_conv3d_wgrad_variant": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
-    "u3d_conv3d_wgrad": (
-        c_int,
-        [c_int, c_void_p, POINTER(U3DSrc), c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t],
-    ),
-    "u3d_conv3d_small_cin_fwd": (
-        c_int,
-        [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
-    ),
-    "u3d_conv3d_small_cin_fwd_reps": (
-        c_int,
-        [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int],
-    ),
-    "u3d_small_cin_bwd_workspace_floats": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
-    "u3d_conv3d_small_cin_bwd": (
-        c_int,
-        [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
-         c_int, c_void_p, c_size_t],
-    ),
-    "u3d_conv3d_naive": (
-        c_int,
-        [c_int, c_void_p, POINTER(U3DSrc), c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int],
-    ),
-    "u3d_chan_stats": (c_int, [c_int, c_void_p, POINTER(U3DSrc), c_int, c_int, c_int, c_int, c_void_p]),
-    "u3d_chan_stats_reps": (c_int, [c_int, c_void_p, POINTER(U3DSrc), c_int, c_int, c_int, c_int, c_void_p, c_int]),
-    "u3d_gn_finalize": (
-        c_int,
-        [c_int, c_void_p, c_void_p, c_int, c_double, c_void_p, c_int, c_double, c_int, c_int, c_double, c_void_p,
-         c_void_p, c_float, c_void_p, c_void_p],
-    ),
-    "u3d_gn_bwd_finalize": (
-        c_int,
-        [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_void_p, c_void_p, c_void_p],
-    ),
-    "u3d_gn_finalize_split": (
-        c_int,
-        [c_int, c_void_p, c_void_p, c_int, c_double, c_void_p, c_int, c_double, c_int, c_int, c_double, c_void_p,
-         c_void_p, c_float, c_void_p, c_void_p, c_int, c_void_p, c_void_p],
-    ),
-    "u3d_gn_bwd_finalize_split_supported": (c_int, [c_int, c_int, c_int]),
-    "u3d_chan_stats_children": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
-    "u3d_adam_step": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int64, c_double, c_double, c_double, c_double, c_double, c_int64]),
-    "u3d_gn_bwd_finalize_split": (
-        c_int,
-        [c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_double, c_void_p, c_void_p,
-         c_void_p, c_float, c_void_p],
-    ),
-    "u3d_gn_bwd_apply": (
-        c_int,
-        [c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int64, c_int, c_int, c_void_p],
-    ),
-    "u3d_gn_bwd_apply_up": (
-        c_int,
-        [c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
-         c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p],
-    ),
-    "u3d_maxpool2_fwd": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
-    "u3d_maxpool2_bwd_merge": (
-        c_int,
-        [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
-         c_int, c_void_p],
-    ),
-    "u3d_maxpool2_bwd_merge_gn": (
-        c_int,
-        [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int,
-         c_int, c_int, c_int, c_int, c_void_p],
-    ),
-    "u3d_conv1x1_head_fwd": (
-        c_int,
-        [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_int, c_void_p, c_void_p],
-    ),
-    "u3d_conv1x1_head_bwd": (
-        c_int,
-        [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_int, c_void_p, c_void_p],
-    ),
-    "u3d_conv1x1_head_bwd_reps": (
-        c_int,
-        [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_int],
-    ),
-    "u3d_conv3d_wgrad_strided": (
-        c_int,
-        [c_int, c_void_p, POINTER(U3DSrc), c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t],
-    ),
-    "u3d_conv3d_ex_reps": (
-        c_int,
-        [c_int, c_void_p, POINTER(U3DSrc), c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, POINTER(U3DSrc),
-         c_void_p, c_void_p, c_void_p, c_int64, c_int],
-    ),
-    "u3d_gn_finalize_reps": (
-        c_int,
-        [c_int, c_void_p, c_void_p, c_int, c_double, c_int, c_void_p, c_int, c_double, c_int, c_int, c_int, c_double, c_void_p, c_void_p,
-         c_float, c_void_p, c_void_p, c_int, c_void_p, c_void_p],
-    ),
-    "u3d_conv3d_wgrad_job_supported": (c_int, [c_int, c_int, c_int]),
-    "u3d_conv3d_wgrad_job": (
-        c_int,
-        [c_int, c_void_p, POINTER(U3DSrc), c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t,
-         POINTER(U3DGnBwdJob)],
-    ),
-    "u3d_subpixel_wgrad_workspace_floats": (c_int64, [c_int, c_int, c_int, c_int, c_int, c_int]),
-    "u3d_subpixel_conv_wgrad": (
-        c_int,
-        [c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
-         c_void_p, c_int64],
-    ),
-    "u3d_convtr3d_subpixel_packed_floats": (c_int64, [c_int, c_int]),
-    "u3d_pack_convtr3d_subpixel": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_void_p]),
-    "u3d_convtr3d_fwd_subpixel": (
-        c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int],
-    ),
-    "u3d_subpixel_packed_floats": (c_int64, [c_int, c_int]),
-    "u3d_subpixel_dgrad_packed_floats": (c_int64, [c_int, c_int]),
-    "u3d_pack_subpixel_dgrad_weights": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
-    "u3d_subpixel_conv_dgrad": (
-        c_int,
-        [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int],
-    ),
-    "u3d_subpixel_conv_dgrad_reps": (
-        c_int,
-        [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int],
-    ),
-    "u3d_pack_subpixel_weights": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
-    # round 5: decoder levels that upsample n -> 2n + 1 (sub-pixel kernels on a window + the general kernels on the boundary slab)
-    "u3d_subpixel_conv_fwd_win": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
-                                          c_int, c_int, POINTER(c_int)]),
-    "u3d_subpixel_conv_dgrad_win": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
-                                            c_int, c_int, POINTER(c_int)]),
-    "u3d_subpixel_conv_wgrad_win": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
-                                            c_int, c_int, c_int, c_void_p, c_int64, POINTER(c_int)]),
-    "u3d_conv3d_box": (c_int, [c_int, c_void_p, POINTER(U3DSrc), c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, POINTER(c_int),
-                               POINTER(c_int)]),
-    "u3d_conv3d_wgrad_box": (c_int, [c_int, c_void_p, POINTER(U3DSrc), c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p,
-                                     c_size_t, POINTER(c_int)]),
-    "u3d_gn_bwd_apply_children": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
-                                          c_int, c_int, c_int, c_int, c_void_p]),
-    "u3d_nearest_childsum_add": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
-                                         c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int]),
-    "u3d_subpixel_fwd_workspace_floats": (c_int64, [c_int, c_int, c_int, c_int, c_int, c_int]),
-    "u3d_subpixel_conv_fwd": (
-        c_int,
-        [c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
-         c_void_p, c_int64],
-    ),
-    "u3d_conv3d_workspace_floats": (c_int64, [c_int, c_int, c_int, c_int, c_int, c_int]),
-    "u3d_conv3d_ex": (
-        c_int,
-        [c_int, c_void_p, POINTER(U3DSrc), c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
-         POINTER(U3DSrc), c_void_p, c_void_p, c_void_p, c_int64],
-    ),
-    "u3d_conv3d_residual": (
-        c_int,
-        [c_int, c_void_p, POINTER(U3DSrc), c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p],
-    ),
-    "u3d_gn_bwd_apply_add": (
-        c_int,
-        [c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p],
-    ),
-    "u3d_conv1x1_fwd": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p]),
-    "u3d_conv1x1_bwd": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p]),
-    "u3d_pack_convtr_weights": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
-    "u3d_convtr3d_fwd": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
-    "u3d_convtr3d_bwd": (
-        c_int,
-        [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
-         c_void_p],
-    ),
-    "u3d_nearest_add_fwd": (
-        c_int,
-        [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
-         c_int, c_void_p, c_void_p],
-    ),
-    "u3d_nearest_sum_bwd": (
-        c_int,
-        [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
-         c_void_p],
-    ),
-    "u3d_se_gate_fwd": (
-        c_int,
-        [c_int, c_void_p, c_void_p, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
-         c_void_p],
-    ),
-    "u3d_se_apply_fwd": (
-        c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p]),
-    "u3d_se_bwd_reduce": (
-        c_int,
-        [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p,
-         c_void_p],
-    ),
-    "u3d_se_gate_bwd": (
-        c_int,
-        [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_void_p,
-         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
-    ),
-    "u3d_se_bwd_apply": (
-        c_int,
-        [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int,
-         c_int, c_void_p],
-    ),
-    "u3d_se_apply_fwd_b16": (
-        c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p]),
-    "u3d_se_bwd_reduce_b16": (
-        c_int,
-        [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p,
-         c_void_p],
-    ),
-    "u3d_se_bwd_apply_b16": (
-        c_int,
-        [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int,
-         c_int, c_void_p],
-    ),
-    "u3d_bce_dice_scratch_doubles": (c_int64, [c_int, c_int, c_int64]),
-    "u3d_bce_dice_fwd": (
-        c_int,
-        [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_float, c_float, c_float, c_void_p, c_void_p,
-         c_void_p],
-    ),
-    "u3d_bce_dice_bwd": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_void_p]),
-    "u3d_softmax_ce_scratch_doubles": (c_int64, [c_int, c_int, c_int64]),
-    "u3d_softmax_ce_fwd": (
-        c_int,
-        [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p],
-    ),
-    "u3d_softmax_ce_bwd": (
-        c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_int64, c_void_p]),
-    "u3d_dice_scratch_doubles": (c_int64, [c_int, c_int, c_int64]),
-    "u3d_dice_fwd": (
-        c_int,
-        [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_int, c_int, c_float, c_void_p, c_void_p,
-         c_void_p],
-    ),
-    "u3d_dice_bwd": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_int, c_void_p]),
-    "u3d_bce_dice_fwd_ex": (
-        c_int,
-        [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_float, c_float, c_float, c_int64, c_int, c_float,
-         c_float, c_void_p, c_void_p, c_void_p],
-    ),
-    "u3d_bce_dice_bwd_ex": (
-        c_int,
-        [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_int64, c_int, c_float, c_float, c_void_p],
-    ),
-    "u3d_softmax_ce_fwd_ex": (
-        c_int,
-        [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_int64, c_int, c_int64, c_void_p, c_void_p,
-         c_void_p],
-    ),
-    "u3d_softmax_ce_bwd_ex": (
-        c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_int64, c_int64, c_void_p]),
-    "u3d_dice_fwd_ex": (
-        c_int,
-        [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_int, c_int, c_float, c_int64, c_int, c_float,
-         c_void_p, c_void_p, c_void_p],
-    ),
-    "u3d_dice_bwd_ex": (
-        c_int,
-        [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_int, c_int64, c_int, c_float, c_void_p],
-    ),
-    "u3d_reg_loss_scratch_doubles": (c_int64, [c_int, c_int, c_int64]),
-    "u3d_reg_loss_fwd": (
-        c_int,
-        [c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_int64, c_int, c_float, c_float, c_float, c_int, c_int,
-         c_float, c_void_p, c_void_p],
-    ),
-    "u3d_reg_loss_bwd": (
-        c_int,
-        [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_int64, c_int, c_float, c_float, c_float, c_int,
-         c_int, c_float, c_void_p],
-    ),
-    "u3d_conv3d_bf16_supported": (c_int, [c_int, c_int]),
-    "u3d_packed_weight_bf16_elems": (c_int64, [c_int, c_int, c_int]),
-    "u3d_packed_weight_f32s_elems": (c_int64, [c_int, c_int, c_int]),
-    "u3d_pack_weights_f32s": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
-    "u3d_conv3d_f32s": (
-        c_int,
-        [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 7 + [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                                                                 c_int64],
-    ),
-    "u3d_pack_weights_bf16": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
-    # bf16 activation storage (include/u3d.h, "_b16" entry points)
-    "u3d_conv3d_bf16_ex_b16": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
-                                       c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64]),
-    "u3d_conv3d_wgrad_bf16_b16": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
-                                          c_int, c_void_p, c_int64]),
-    "u3d_convtr3d_fwd_t8_b16": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int]),
-    "u3d_convtr3d_dgrad_t8_b16": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
-                                          c_int]),
-    "u3d_convtr3d_wgrad_t8_b16": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
-                                          c_void_p, c_int64]),
-    "u3d_conv1x1_fwd_b16": (c_int, [c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int,
-                                    c_void_p]),
-    "u3d_conv1x1_mfma_b16_supported": (c_int, [c_int, c_int]),
-    "u3d_conv1x1_fwd_mfma_b16": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int,
-                                         c_void_p]),
-    "u3d_conv1x1_bwd_mfma_b16_workspace_floats": (c_int64, [c_int, c_int, c_int, c_int, c_int, c_int]),
-    "u3d_conv1x1_bwd_mfma_b16": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
-                                         c_void_p, c_void_p, c_void_p, c_void_p, c_int64]),
-    "u3d_conv1x1_bwd_b16": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int64, c_int, c_int, c_void_p,
-                                    c_void_p]),
-    "u3d_maxpool2_fwd_b16": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
-    "u3d_maxpool2_bwd_merge_b16": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
-                                           c_int, c_int, c_int, c_int, c_void_p]),
-    "u3d_nearest_add_fwd_t8_b16": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
-                                           c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
-    "u3d_nearest_sum_bwd_t8_b16": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
-                                           c_int, c_int, c_int, c_void_p]),
-    "u3d_gn_bwd_apply_b16": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int64, c_int, c_int,
-                                     c_void_p, c_void_p]),
-    "u3d_conv1x1_head_fwd_b16": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_int, c_void_p,
-                                         c_void_p]),
-    "u3d_conv1x1_head_bwd_b16": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_int, c_void_p,
-                                         c_void_p]),
-    "u3d_pack_weights_bf16_blocks": (c_int64, [c_int, c_int, c_int]),
-    "u3d_pack_weights_bf16_batch": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int64]),
-    "u3d_conv3d_bf16": (
-        c_int,
-        [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
-         c_void_p, c_void_p, c_void_p],
-    ),
-    "u3d_conv3d_bf16_workspace_floats": (c_int64, [c_int, c_int, c_int, c_int, c_int, c_int]),
-    "u3d_conv3d_bf16_tile_variant": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
-    "u3d_conv3d_wgrad_bf16_b16_variant": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int]),
-    "u3d_conv3d_wgrad_bf16_job_supported": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int]),
-    "u3d_conv3d_wgrad_bf16_job": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
-                                          c_int, c_void_p, c_int64, POINTER(U3DGnBwdJob)]),
-    "u3d_conv3d_wgrad_bf16_b16_job": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
-                                              c_int, c_void_p, c_int64, POINTER(U3DGnBwdJob)]),
-    "u3d_conv3d_bf16_ex": (
-        c_int,
-        [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
-         c_void_p, c_void_p, c_void_p, c_void_p, c_int64],
-    ),
-    "u3d_conv3d_wgrad_bf16_supported": (c_int, [c_int, c_int]),
-    "u3d_wgrad_bf16_workspace_floats": (c_int64, [c_int, c_int, c_int, c_int, c_int, c_int]),
-    "u3d_conv3d_wgrad_bf16": (
-        c_int,
-        [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int64],
-    ),
-    "u3d_convtr3d_t8_supported": (c_int, [c_int, c_int]),
-    "u3d_convtr3d_t8_packed_elems": (c_int64, [c_int, c_int, c_int]),
-    "u3d_pack_convtr3d_t8": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
-    "u3d_convtr3d_fwd_t8": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int]),
-    "u3d_convtr3d_dgrad_t8": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int]),
-    "u3d_convtr3d_dgrad_t8_workspace_floats": (c_int64, [c_int, c_int, c_int, c_int, c_int, c_int]),
-    "u3d_convtr3d_fwd_t8_workspace_floats": (c_int64, [c_int, c_int, c_int, c_int, c_int, c_int]),
-    "u3d_convtr3d_fwd_t8_b16_ex": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
-                                           c_void_p, c_int64]),
-    "u3d_convtr3d_dgrad_t8_ex": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
-                                         c_void_p, c_int64]),
-    "u3d_convtr3d_dgrad_t8_b16_ex": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
-                                             c_void_p, c_int64]),
-    "u3d_convtr3d_wgrad_t8_workspace_floats": (c_int64, [c_int, c_int, c_int, c_int, c_int, c_int]),
-    "u3d_convtr3d_wgrad_t8": (
-        c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int64]),
-    "u3d_nearest_add_fwd_t8": (
-        c_int,
-        [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
-         c_int, c_void_p, c_void_p],
-    ),
-    "u3d_nearest_sum_bwd_t8": (
-        c_int,
-        [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
-         c_void_p],
-    ),
-    "u3d_act_fwd": (c_int, [c_int, c_void_p, c_void_p, c_int64, c_int, c_float, c_void_p]),
-    "u3d_act_bwd": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_float, c_void_p]),
-    "u3d_affine_act_fwd": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_float, c_void_p]),
-    "u3d_affine_add_act_fwd": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_float, c_void_p]),
-    "u3d_resample2_fwd": (c_int, [c_int, c_void_p] + [c_void_p] * 7 + [c_int] * 8 + [c_void_p]),
-    "u3d_resample2_bwd": (c_int, [c_int, c_void_p] + [c_void_p] * 10 + [c_int] * 8 + [c_void_p]),
-    "u3d_nearest_cat_fwd": (c_int, [c_int, c_void_p] + [c_void_p] * 5 + [c_int] * 9 + [c_void_p]),
-    "u3d_split_channels": (c_int, [c_int, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p]),
-    "u3d_bn_finalize": (c_int, [c_int, c_void_p, c_void_p, c_int, c_double, c_void_p, c_int, c_double, c_int, c_double, c_void_p,
-                                c_void_p, c_float, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "u3d_bn_bwd_finalize": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_double, c_int, c_void_p, c_void_p,
-                                    c_void_p]),
-    "u3d_bias_table": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_void_p]),
-    "u3d_bias_grad": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_void_p]),
-    "u3d_mul": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
-    "u3d_pair_stats": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p]),
-    "u3d_cvt_f64_f32": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int64]),
-    "u3d_cvt_f64_f32_sum": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int64, c_int]),
-    # 2-D path (csrc/u3d_conv2d.hip)
-    "u3d_packed_weight2d_floats": (c_size_t, [c_int, c_int, c_int]),
-    "u3d_pack_weights2d": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
-    "u3d_conv2d_workspace_floats": (c_int64, [c_int, c_int, c_int, c_int, c_int]),
-    "u3d_conv2d_ex_reps": (c_int, [c_int, c_void_p, POINTER(U3DSrc), c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p,
-                                   POINTER(U3DSrc), c_void_p, c_void_p, c_int64, c_int]),
-    "u3d_conv2d_res_reps": (c_int, [c_int, c_void_p, POINTER(U3DSrc), c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p,
-                                    POINTER(U3DSrc), c_void_p, c_void_p, c_int64, c_int, c_void_p]),
-    "u3d_convtr2d_packed_floats": (c_size_t, [c_int, c_int]),
-    "u3d_convtr2d_wgrad_workspace_doubles": (c_size_t, [c_int, c_int]),
-    "u3d_pack_convtr2d": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
-    "u3d_convtr2d_fwd": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int]),
-    "u3d_convtr2d_dgrad": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int]),
-    "u3d_convtr2d_wgrad": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
-                                   c_size_t]),
-    "u3d_wgrad2d_workspace_floats": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
-    "u3d_conv2d_wgrad": (c_int, [c_int, c_void_p, POINTER(U3DSrc), c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t]),
-    "u3d_pack_weights2d_slice": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
-    "u3d_conv2d_wgrad_strided": (c_int, [c_int, c_void_p, POINTER(U3DSrc), c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p,
-                                         c_size_t]),
-    # sub-pixel decoder convolutions of a 2-D net (`native_2d_subpixel`; csrc/u3d_subpix2d.hip)
-    "u3d_subpixel2d_packed_floats": (c_int64, [c_int, c_int]),
-    "u3d_subpixel2d_dgrad_packed_floats": (c_int64, [c_int, c_int]),
-    "u3d_pack_subpixel2d_weights": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
-    "u3d_pack_subpixel2d_dgrad_weights": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
-    "u3d_subpixel2d_conv_fwd": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
-                                        c_int, c_void_p, c_int64]),
-    "u3d_subpixel2d_conv_dgrad_reps": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
-                                               c_int, c_int, c_int]),
-    "u3d_subpixel2d_wgrad_workspace_floats": (c_int64, [c_int, c_int, c_int, c_int, c_int]),
-    "u3d_subpixel2d_conv_wgrad": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
-                                          c_int, c_int, c_void_p, c_int64]),
-    # ... on a shifted window + the slab launches of a level that upsamples n -> 2n + 1 (`native_2d_subpixel_plus`; win / box: int arrays)
-    "u3d_subpixel2d_conv_fwd_win": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
-                                            c_int, c_void_p]),
-    "u3d_subpixel2d_conv_dgrad_win": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
-                                              c_int, c_int, c_int, c_void_p]),
-    "u3d_subpixel2d_conv_wgrad_win": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
-                                              c_int, c_int, c_void_p, c_int64, c_void_p]),
-    "u3d_conv2d_box": (c_int, [c_int, c_void_p, POINTER(U3DSrc), c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
-                               c_void_p]),
-    "u3d_conv2d_wgrad_box": (c_int, [c_int, c_void_p, POINTER(U3DSrc), c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t,
-                                     c_void_p]),
-    "u3d_chan_stats_children2d": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
-    "u3d_gn_bwd_apply_children2d": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
-                                            c_int, c_int, c_void_p]),
-    "u3d_nearest_childsum_add2d": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
-                                           c_int, c_void_p]),
-    # small-Cin first layer of a 2-D net (`native_2d_stem`; csrc/u3d_conv2d.hip)
-    "u3d_conv2d_small_cin_fwd_variant": (c_int, [c_int, c_int, c_int, c_int, c_int]),
-    "u3d_conv2d_small_cin_fwd_reps": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
-                                              c_int, c_void_p, c_int]),
-    "u3d_small_cin2d_bwd_workspace_floats": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
-    "u3d_conv2d_small_cin_bwd_variant": (c_int, [c_int, c_int, c_int, c_int, c_int]),
-    "u3d_conv2d_small_cin_bwd": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
-                                         c_int, c_int, c_void_p, c_size_t]),
-    # bf16-operand 2-D convolutions (csrc/u3d_conv2d_bf16.hip)
-    "u3d_conv2d_bf16_supported": (c_int, [c_int, c_int]),
-    "u3d_conv2d_wgrad_bf16_supported": (c_int, [c_int, c_int]),
-    "u3d_packed_weight2d_bf16_elems": (c_int64, [c_int, c_int, c_int]),
-    "u3d_pack_weights2d_bf16": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
-    "u3d_conv2d_bf16_workspace_floats": (c_int64, [c_int, c_int, c_int, c_int, c_int]),
-    "u3d_conv2d_bf16_variant": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int]),
-    "u3d_conv2d_bf16": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
-                                c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int]),
-    "u3d_conv2d_bf16_res": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
-                                    c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p]),
-    "u3d_wgrad2d_bf16_workspace_floats": (c_int64, [c_int, c_int, c_int, c_int, c_int]),
-    "u3d_conv2d_wgrad_bf16_variant": (c_int, [c_int, c_int, c_int, c_int, c_int]),
-    "u3d_conv2d_wgrad_bf16": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
-                                      c_void_p, c_int64]),
-    # ... their `_c16` twins: both channel counts % 16 (`native_2d_stem` next to `native_2d_bf16`)
-    "u3d_conv2d_bf16_c16_supported": (c_int, [c_int, c_int]),
-    "u3d_conv2d_wgrad_bf16_c16_supported": (c_int, [c_int, c_int]),
-    "u3d_packed_weight2d_bf16_c16_elems": (c_int64, [c_int, c_int, c_int]),
-    "u3d_pack_weights2d_bf16_c16": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
-    "u3d_conv2d_bf16_c16_workspace_floats": (c_int64, [c_int, c_int, c_int, c_int, c_int]),
-    "u3d_conv2d_bf16_c16_variant": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int]),
-    "u3d_conv2d_bf16_c16": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
-                                    c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int]),
-    "u3d_wgrad2d_bf16_c16_workspace_floats": (c_int64, [c_int, c_int, c_int, c_int, c_int]),
-    "u3d_conv2d_wgrad_bf16_c16_variant": (c_int, [c_int, c_int, c_int, c_int, c_int]),
-    "u3d_conv2d_wgrad_bf16_c16": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
-                                          c_void_p, c_int64]),
-    # ... on a decoder's virtual concat (`native_2d_bf16_vcat`): u3d_src_t* where the entry points above take x / gx
-    "u3d_conv2d_bf16_src": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
-                                    c_int64, c_int]),
-    "u3d_conv2d_bf16_dgrad_src": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
-                                          c_void_p, c_int64, c_int]),
-    "u3d_conv2d_wgrad_bf16_src": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int64]),
-    # bf16-operand ConvTranspose2d (csrc/u3d_conv2d_bf16.hip)
-    "u3d_convtr2d_bf16_supported": (c_int, [c_int, c_int]),
-    "u3d_packed_convtr2d_bf16_elems": (c_int64, [c_int, c_int, c_int]),
-    "u3d_pack_convtr2d_bf16": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
-    "u3d_convtr2d_fwd_bf16": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int]),
-    "u3d_convtr2d_dgrad_bf16_variant": (c_int, [c_int, c_int, c_int, c_int, c_int]),
-    "u3d_convtr2d_dgrad_bf16": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int]),
-    "u3d_convtr2d_wgrad_bf16_workspace_floats": (c_int64, [c_int, c_int, c_int, c_int, c_int]),
-    "u3d_convtr2d_wgrad_bf16_variant": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int64]),
-    "u3d_convtr2d_wgrad_bf16": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
-                                        c_int64]),
-    # sub-pixel decoder convolutions of a 2-D net on the bf16 MFMA (`native_2d_bf16_subpixel`; csrc/u3d_conv2d_bf16.hip)
-    "u3d_subpixel2d_bf16_packed_elems": (c_int64, [c_int, c_int, c_int]),
-    "u3d_pack_subpixel2d_weights_bf16": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
-    "u3d_subpixel2d_conv_fwd_bf16": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
-                                             c_int]),
-    "u3d_subpixel2d_conv_dgrad_bf16": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
-                                               c_int, c_int, c_int]),
-    "u3d_subpixel2d_wgrad_bf16_workspace_floats": (c_int64, [c_int, c_int, c_int, c_int, c_int]),
-    "u3d_subpixel2d_conv_wgrad_bf16": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
-                                               c_int, c_int, c_void_p, c_int64]),
-    "u3d_pack_weights2d_bf16_slice": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
-    "u3d_conv2d_wgrad_bf16_strided": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
-                                              c_int, c_void_p, c_int64]),
-    "u3d_maxpool2d_fwd": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
-    "u3d_maxpool2d_bwd_merge": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
-                                        c_int, c_int, c_void_p]),
-    "u3d_maxpool2d_bwd_merge_gn": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int,
-                                           c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
-    "u3d_ncdhw_to_ndhwc": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64]),
-    "u3d_ndhwc_to_ncdhw": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64]),
-}
-
-EXPORTED_SYMBOLS = tuple(_PROTOS.keys())
-
-_lib = None
-_lock = threading.Lock()
-launch_count = 0  # number of native calls issued (tests assert the HIP path really ran)
+HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "include", "u3d.h"))
 
 
 class U3DError(RuntimeError):
     pass
+
+
+_SCALARS = {"int": c_int, "long long": c_int64, "int64_t": c_int64, "int32_t": c_int32, "size_t": c_size_t, "float": c_float,
+            "double": c_double, "u3d_stream_t": c_void_p}
+_POINTEES = set(_SCALARS) - {"u3d_stream_t"} | {"void", "uint8_t", "char"}  # + the header's own structs
+_STRUCT_NAMES = {"u3d_src_t": "U3DSrc", "u3d_adam_desc_t": "U3DAdamDesc", "u3d_gn_bwd_job_t": "U3DGnBwdJob", "u3d_pack_desc_t": "U3DPackDesc"}
+_CONSTANTS = ("U3D_VERSION", "U3D_OK", "U3D_EINVAL", "U3D_EHIP", "U3D_EARCH", "U3D_EWORKSPACE")
+
+_STRUCT = re.compile(r"typedef\s+struct\s*\w*\s*\{([^{}]*)\}\s*(\w+)\s*;")  # (the tag, if any, is not used)
+_FUNC = re.compile(r"([\w\s*]+?)\b(u3d_[a-z0-9_]+)\s*\(([^(){};]*)\)\s*;")
+_STREAM = re.compile(r"typedef\s+void\s*\*\s*u3d_stream_t\s*;")
+
+
+def _ctype(decl, pointees, where):
+    """`[const] base [*] name` -> (ctype, name)"""
+    toks = decl.replace("*", " * ").split()
+    toks = toks[1:] if toks[:1] == ["const"] else toks
+    star = toks[-2:-1] == ["*"]
+    base, name = " ".join(toks[:-2 if star else -1]), "".join(toks[-1:])
+    if not name.isidentifier() or (base not in pointees if star else base not in _SCALARS):
+        raise U3DError(f"u3d.h: unknown type {base + '*' * star!r} of {name!r} in {where}")
+    return (c_void_p if star else _SCALARS[base]), name
+
+
+def parse_header(text):
+    """(prototypes {name: (restype, [argtypes])}, structs {C name: [(field, ctype)]}, constants {name: int}) of a u3d.h text, all in
+    header order.  Raises U3DError on anything that is not a declaration it understands."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    consts = {}
+    for line in re.findall(r"^[ \t]*#[ \t]*(.*?)[ \t]*$", text, flags=re.M):
+        m = re.fullmatch(r"define[ \t]+(U3D_\w+)(?:[ \t]+(-?\d+|\(-?\d+\)))?", line)  # (no value: the include guard)
+        if m and m.group(2) and m.group(1) not in consts:
+            consts[m.group(1)] = int(m.group(2).strip("()"))
+        elif (m and m.group(2)) or not (m or re.fullmatch(r"ifndef[ \t]+U3D_H|ifdef[ \t]+__cplusplus|endif|include[ \t]*<\w+\.h>", line)):
+            raise U3DError(f"u3d.h: #{line}: not the guard, the C++ wrapper, an #include or one integer constant U3D_* defined once")
+    text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)
+    m = re.fullmatch(r'\s*extern\s+"C"\s*\{(.*)\}\s*', text, flags=re.S)
+    text = _STREAM.sub("", m.group(1) if m else text, count=1)
+    structs = {}
+    for body, cname in _STRUCT.findall(text):
+        if cname in structs:
+            raise U3DError(f"u3d.h: struct {cname} is declared twice")
+        fields = structs[cname] = []
+        for field in filter(None, (f.strip() for f in body.split(";"))):
+            first, *more = field.split(",")
+            ctype, name = _ctype(first, _POINTEES | set(structs), f"struct {cname}")
+            if more and ("*" in first or not all(n.strip().isidentifier() for n in more)):
+                raise U3DError(f"u3d.h: cannot parse field {field!r} of struct {cname}")
+            fields += [(n.strip(), ctype) for n in (name, *more)]
+    text = _STRUCT.sub("", text)
+    pointees, protos = _POINTEES | set(structs), {}
+    for ret, name, args in _FUNC.findall(text):
+        if name in protos:
+            raise U3DError(f"u3d.h: {name} is declared twice")
+        ret, args = " ".join(ret.split()), args.strip()
+        if ret != "const char*" and ret not in _SCALARS:
+            raise U3DError(f"u3d.h: unknown return type {ret!r} of {name}")
+        argtypes = [] if args in ("", "void") else [_ctype(a, pointees, name)[0] for a in args.split(",")]
+        protos[name] = (c_char_p if ret == "const char*" else _SCALARS[ret], argtypes)
+    rest = _FUNC.sub("", text).strip()
+    if rest:
+        m = re.search(r"u3d_[a-z0-9_]+\s*\(", rest)
+        raise U3DError(f"u3d.h: not a declaration this reader understands: {(m.group(0) if m else rest[:60])!r}")
+    return protos, structs, consts
+
+
+def read_header(path):
+    if not os.path.exists(path):
+        raise U3DError(f"C-ABI header {path} not found: the binding is derived from include/u3d.h of the source tree "
+                       "(looked for it relative to the package, <package>/../../include/u3d.h).")
+    with open(path) as fh:
+        protos, structs, consts = parse_header(fh.read())
+    if set(structs) != set(_STRUCT_NAMES) or not set(_CONSTANTS) <= set(consts):
+        raise U3DError(f"{path}: structs {sorted(structs)} / constants {sorted(consts)} are not the ones this module names")
+    return protos, structs, consts
+
+
+_PROTOS, _structs, _consts = read_header(HEADER_PATH)  # name: (restype, argtypes), in header order
+EXPORTED_SYMBOLS = tuple(_PROTOS)
+U3D_VERSION, U3D_OK, U3D_EINVAL, U3D_EHIP, U3D_EARCH, U3D_EWORKSPACE = (_consts[k] for k in _CONSTANTS)
+U3DSrc, U3DAdamDesc, U3DGnBwdJob, U3DPackDesc = (
+    type(py, (ctypes.Structure,), {"_fields_": _structs[c], "__doc__": f"{c} of include/u3d.h"}) for c, py in _STRUCT_NAMES.items())
+
+_lib = None
+_lock = threading.Lock()
+launch_count = 0  # number of native calls issued (tests assert the HIP path really ran)
 
 
 def lib_available() -> bool:
@@ -617,7 +139,7 @@ def get_lib():
             fn = getattr(lib, name)  # AttributeError if a declared symbol is missing
             fn.restype = res
             fn.argtypes = args
-        if lib.u3d_version() < 128:
+        if lib.u3d_version() < U3D_VERSION:
             raise U3DError("libu3d_hip.so is older than the Python host code")
         for kv in os.environ.get("U3D_TUNE", "").split(","):  # A/B knobs of u3d_set_tuning, e.g. U3D_TUNE=8:256,9:1 (results never change)
             if ":" in kv:

@@ -31,6 +31,7 @@ def test_header_symbols_exported():
     declared = set(re.findall(r"\b(u3d_[a-z0-9_]+)\s*\(", hdr)) - {"u3d_stream_t", "u3d_src_t"}
     assert declared, "no declarations parsed"
     assert declared == set(nat.EXPORTED_SYMBOLS)
+    assert len(nat.EXPORTED_SYMBOLS) == 250  # (the table is read from the same header: not an empty parse on both sides)
     if not nat.lib_available():
         pytest.fail(f"{nat.LIB_PATH} missing: run __graft_entry__.build()")
     lib = ctypes.CDLL(nat.LIB_PATH)
