@@ -1233,6 +1233,12 @@ int u3d_conv2d_wgrad_bf16_strided(int device, u3d_stream_t stream, const float* 
                                   int dw_cin_stride, int N, int H, int W, int Cin, int Cout, float* workspace,
                                   long long workspace_floats);
 
+/* ---- (Added, U3D_VERSION unchanged.)  Sub-pixel decoder convolutions of a UNet3D on the bf16 MFMA (`bf16_subpixel: true`): the eight
+ * entry points of csrc/u3d_subpix_bf16.hip and the two slice helpers of csrc/u3d_bf16.hip are declared, with their contracts, in
+ * include/u3d_subpix_bf16.h — part of this header: included here, inside the extern "C" block, and read by the ctypes binding as its second
+ * table. */
+#include <u3d_subpix_bf16.h>
+
 /* ---- layout: NCDHW <-> NDHWC for multi-channel model inputs ------------------------------------ */
 int u3d_ncdhw_to_ndhwc(int device, u3d_stream_t stream, const float* src, float* dst, int N, int C, int64_t V);
 int u3d_ndhwc_to_ncdhw(int device, u3d_stream_t stream, const float* src, float* dst, int N, int C, int64_t V);

@@ -721,8 +721,9 @@ __global__ __launch_bounds__(256) void splitk_bf16_reduce_kernel(const bf16_conv
 // mode 0 (forward):       B[k = input channel ][col = output channel] = w[col][k][tap]
 // mode 1 (data gradient): B[k = output channel][col = input channel ] = w[k][col][26 - tap]   (taps flipped, roles swapped)
 // lane l of a fragment holds column (l & 31) of n-tile `nt` and the 8 consecutive k = chunk*16 + 8*(l >> 5) + 0..7.
+// (cs, coff: the input channels [coff, coff + Cin) of a (Cout, cs, 3,3,3) weight — u3d_pack_weights_bf16_slice; cs = Cin, coff = 0: the whole)
 __global__ void pack_weights_bf16_kernel(const float* __restrict__ w, int Cout, int Cin, int mode, __bf16* __restrict__ out,
-                                         long long total) {
+                                         long long total, int cs, int coff) {
     const int Kc = mode == 0 ? Cin : Cout;   // contraction channels
     const int Nc = mode == 0 ? Cout : Cin;   // produced channels
     const int ntiles = Nc >> 5;
@@ -739,9 +740,9 @@ __global__ void pack_weights_bf16_kernel(const float* __restrict__ w, int Cout, 
         float v = 0.f;
         if (k < Kc && col < Nc) {
             if (mode == 0)
-                v = w[((size_t)col * Cin + k) * 27 + tap];
+                v = w[((size_t)col * cs + coff + k) * 27 + tap];
             else
-                v = w[((size_t)k * Cin + col) * 27 + (26 - tap)];
+                v = w[((size_t)k * cs + coff + col) * 27 + (26 - tap)];
         }
         out[i] = (__bf16)v;
     }
@@ -989,7 +990,26 @@ extern "C" int u3d_pack_weights_bf16(int device, u3d_stream_t stream, const floa
     long long blocks = (total + 255) / 256;
     if (blocks > 4096) blocks = 4096;
     hipLaunchKernelGGL(pack_weights_bf16_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, w, Cout, Cin, mode,
-                       reinterpret_cast<__bf16*>(packed), total);
+                       reinterpret_cast<__bf16*>(packed), total, Cin, 0);
+    U3D_LAUNCH_CHECK();
+    return 0;
+}
+
+// the image of the input channels [c_off, c_off + Cin) of a (Cout, cin_stride, 3,3,3) weight (the skip half of a `bf16_subpixel` layer): the
+// same kernel reading at a channel stride; c_off = 0, cin_stride = Cin is u3d_pack_weights_bf16 bit for bit
+extern "C" int u3d_pack_weights_bf16_slice(int device, u3d_stream_t stream, const float* w, int Cout, int Cin, int mode, int cin_stride,
+                                           int c_off, void* packed) {
+    U3D_ENTER(device);
+    const long long total = u3d_packed_weight_bf16_elems(Cin, Cout, mode);
+    U3D_REQUIRE(w && packed && (mode == 0 || mode == 1) && total > 0 && Cin % 32 == 0 && Cout % 32 == 0,
+                "u3d_pack_weights_bf16_slice: needs Cin %% 32 == 0 and Cout %% 32 == 0 (Cin %d, Cout %d)", Cin, Cout);
+    U3D_REQUIRE(c_off >= 0 && c_off + Cin <= cin_stride, "u3d_pack_weights_bf16_slice: channels [%d, %d) do not lie inside a weight of %d "
+                "input channels", c_off, c_off + Cin, cin_stride);
+    U3D_REQUIRE(((uintptr_t)packed & 15) == 0, "u3d_pack_weights_bf16_slice: the image must be 16-byte aligned");
+    long long blocks = (total + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(pack_weights_bf16_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, w, Cout, Cin, mode,
+                       reinterpret_cast<__bf16*>(packed), total, cin_stride, c_off);
     U3D_LAUNCH_CHECK();
     return 0;
 }
@@ -2091,8 +2111,9 @@ __device__ __forceinline__ f64x4s u3d_sum_splits4(const float* __restrict__ p, s
 // costs more than the GEMM at 1024 channels.
 // (has_job, round 6: the grid carries ONE extra block — block 0 — that runs the GroupNorm-backward reduction of the layer's input, as in
 // wgrad_reduce_kernel of csrc/u3d_conv.hip: u3d_conv3d_wgrad_bf16_job)
+// (dcs: input channels per output channel of the buffer dw points into — u3d_conv3d_wgrad_bf16_strided; dcs = C: the whole gradient)
 __global__ __launch_bounds__(256) void wgrad_bf16_reduce_kernel(const float* __restrict__ ws, int S, int C, int K, float* __restrict__ dw,
-                                                                int has_job, u3d_gn_bwd_job_t job) {
+                                                                int has_job, u3d_gn_bwd_job_t job, int dcs) {
     __shared__ float tile[64][28];
     if (has_job && blockIdx.x == 0) {
         extern __shared__ double shb[];
@@ -2118,14 +2139,14 @@ __global__ __launch_bounds__(256) void wgrad_bf16_reduce_kernel(const float* __r
     const int ci = cib * 32 + cil;
     for (int i = t; i < 27 * 64; i += 256) {
         const int co = i / 27, tap = i - co * 27;
-        if (cob * 64 + co < K) dw[((size_t)(cob * 64 + co) * C + ci) * 27 + tap] = tile[co][tap];
+        if (cob * 64 + co < K) dw[((size_t)(cob * 64 + co) * dcs + ci) * 27 + tap] = tile[co][tap];
     }
 }
 
 // few (pair, channel) rows but many splits (64-channel layers at full resolution): one thread per output element instead, so
 // that the sum over hundreds of splits is spread over the whole chip (the scattered 4-byte writes are few there)
 __global__ __launch_bounds__(256) void wgrad_bf16_reduce_flat_kernel(const float* __restrict__ ws, int S, int C, int K, float* __restrict__ dw,
-                                                                     int has_job, u3d_gn_bwd_job_t job) {
+                                                                     int has_job, u3d_gn_bwd_job_t job, int dcs) {
     if (has_job && blockIdx.x == 0) {
         extern __shared__ double shb[];
         u3d_gn_bwd_finalize_body(job.gstats_lo, job.mean_rstd, job.gamma, job.N, job.C0 + job.C1, job.G, job.count, 1, 1, job.dgamma,
@@ -2145,7 +2166,7 @@ __global__ __launch_bounds__(256) void wgrad_bf16_reduce_flat_kernel(const float
         const size_t off = ((size_t)pair * 27 + tap) * 2048 + (ci & 31) * 64 + (co & 63);
         const f64x4s sum = u3d_sum_splits4(ws + off, (size_t)P * 27 * 2048, S);
 #pragma unroll
-        for (int e = 0; e < 4; ++e) dw[((size_t)(co + e) * C + ci) * 27 + tap] = (float)sum.v[e];
+        for (int e = 0; e < 4; ++e) dw[((size_t)(co + e) * dcs + ci) * 27 + tap] = (float)sum.v[e];
     }
 }
 
@@ -2201,7 +2222,7 @@ extern "C" int u3d_conv3d_wgrad_bf16_b16_variant(int N, int D, int H, int W, int
 
 static int conv3d_wgrad_bf16_impl(int device, u3d_stream_t stream, const float* x, const float* affine, const float* dz, float* dw,
                                   int N, int D, int H, int W, int C, int K, float* workspace, long long workspace_floats, int b16,
-                                  const u3d_gn_bwd_job_t* job = nullptr);
+                                  const u3d_gn_bwd_job_t* job = nullptr, int dw_cin_stride = 0);
 // does the launch that writes dw for this shape have a reduce pass (one split: the round-4 kernels write dw themselves)?
 static bool wgrad_bf16_has_reduce(int N, int D, int H, int W, int C, int K, int b16, const float* dw) {
     const int variant = b16 ? wgrad_b16_variant(N, D, H, W, C, K) : 0;
@@ -2240,6 +2261,17 @@ extern "C" int u3d_conv3d_wgrad_bf16(int device, u3d_stream_t stream, const floa
     return conv3d_wgrad_bf16_impl(device, stream, x, affine, dz, dw, N, D, H, W, C, K, workspace, workspace_floats, 0);
 }
 
+// u3d_conv3d_wgrad_bf16 writing a CHANNEL SLICE of a wider gradient (the skip half of a `bf16_subpixel` layer): dw points at the slice's
+// first input channel inside (Cout, dw_cin_stride, 3,3,3).  The fp32-storage launch always reduces its splits in a second kernel, and only
+// that kernel's store addresses carry the stride: dw_cin_stride = Cin is u3d_conv3d_wgrad_bf16 bit for bit.
+extern "C" int u3d_conv3d_wgrad_bf16_strided(int device, u3d_stream_t stream, const float* x, const float* affine, const float* dz, float* dw,
+                                             int dw_cin_stride, int N, int D, int H, int W, int Cin, int Cout, float* workspace,
+                                             long long workspace_floats) {
+    if (dw_cin_stride < Cin) return u3d_set_err(U3D_EINVAL, "u3d_conv3d_wgrad_bf16_strided: dw_cin_stride %d < Cin %d", dw_cin_stride, Cin);
+    return conv3d_wgrad_bf16_impl(device, stream, x, affine, dz, dw, N, D, H, W, Cin, Cout, workspace, workspace_floats, 0, nullptr,
+                                  dw_cin_stride);
+}
+
 // bf16 activation storage: x and dz are bf16 tensors (half the bytes of a kernel whose operand re-reads make it HBM-bound)
 extern "C" int u3d_conv3d_wgrad_bf16_b16(int device, u3d_stream_t stream, const void* x, const float* affine, const void* dz, float* dw,
                                          int N, int D, int H, int W, int C, int K, float* workspace, long long workspace_floats) {
@@ -2249,8 +2281,9 @@ extern "C" int u3d_conv3d_wgrad_bf16_b16(int device, u3d_stream_t stream, const 
 
 static int conv3d_wgrad_bf16_impl(int device, u3d_stream_t stream, const float* x, const float* affine, const float* dz, float* dw,
                                   int N, int D, int H, int W, int C, int K, float* workspace, long long workspace_floats, int b16,
-                                  const u3d_gn_bwd_job_t* job) {
+                                  const u3d_gn_bwd_job_t* job, int dw_cin_stride) {
     U3D_ENTER(device);
+    const int dcs = dw_cin_stride > 0 ? dw_cin_stride : C;
     if (job) {
         U3D_REQUIRE(job->gstats_lo && job->mean_rstd && job->gamma && job->dgamma && job->dbeta && job->coef && job->C0 > 0 &&
                         job->C1 >= 0 && (job->C1 == 0) == (job->gstats_hi == nullptr) && (job->coef_hi == nullptr || job->C1 > 0) &&
@@ -2311,12 +2344,12 @@ static int conv3d_wgrad_bf16_impl(int device, u3d_stream_t stream, const float* 
     const unsigned jx = job ? 1u : 0u;
     if (q.P * 32 >= 1024) {
         hipLaunchKernelGGL(wgrad_bf16_reduce_kernel, dim3((unsigned)(q.P * 32) + jx), dim3(256), job_lds, (hipStream_t)stream, workspace, q.S, C,
-                           K, dw, (int)jx, jb);
+                           K, dw, (int)jx, jb, dcs);
     } else {
         long long rb = ((long long)C * (K / 4) * 27 + 255) / 256;  // one thread per (tap, input channel, quad of output channels)
         if (rb > 8192) rb = 8192;
         hipLaunchKernelGGL(wgrad_bf16_reduce_flat_kernel, dim3((unsigned)rb + jx), dim3(256), job_lds, (hipStream_t)stream, workspace, q.S, C, K,
-                           dw, (int)jx, jb);
+                           dw, (int)jx, jb, dcs);
     }
     U3D_LAUNCH_CHECK();
     return 0;

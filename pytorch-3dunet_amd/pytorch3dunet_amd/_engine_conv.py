@@ -27,10 +27,16 @@ from ._engine_weights import Kind
 
 class _SubLayers(dict):
     """{id(conv weight): (C0, C1)} of the decoder first convs that take the sub-pixel path at one input size; `plus` = the ids whose level
-    upsamples n -> 2n + 1 along some axis; `family` = the one `_FWD_KERNELS` row every entry runs on (`_subpixel_layers` chooses it)"""
+    upsamples n -> 2n + 1 along some axis; `family` = the `_FWD_KERNELS` row the entries run on (`_subpixel_layers` chooses it) but for
+    those of `bf16_ids`, a UNet3D's levels under `bf16_subpixel`, whose row is `subpixel_bf16` (the other entries of such a table are the
+    layers outside `_cat_bf16`, on the fp32 sub-pixel kernels as without the key): ask `family_of`"""
 
     plus = frozenset()
     family = None
+    bf16_ids = frozenset()
+
+    def family_of(self, wid):
+        return "subpixel_bf16" if wid in self.bf16_ids else self.family
 
 
 @dataclass
@@ -138,13 +144,14 @@ class ConvLayers:
         is2d = self.is2d
         bf16_sub = is2d and self.subpixel2d_bf16  # (`native_2d_bf16_subpixel`: the levels `_bf16_subpixel` accepts, on the bf16 kernels)
         assert not (bf16_sub and self.subpixel)  # (`native_2d_subpixel` refuses the bf16 keys: one family per table)
-        if not (self.subpixel or bf16_sub) or any(ct is not None for ct in self.dec_up) or any(self.dec_interp):
+        bf16_sub3d = not is2d and self.subpixel_bf16  # (`bf16_subpixel`: the levels `_bf16_subpixel3d` accepts, listed in `bf16_ids`)
+        if not (self.subpixel or bf16_sub or bf16_sub3d) or any(ct is not None for ct in self.dec_up) or any(self.dec_interp):
             return _SubLayers()  # (a transposed convolution yields 2n-1 voxels, resized to the skip: never an exact 2x replication)
         dims = [tuple(size)[1:] if is2d else tuple(size)]  # (2-D, `native_2d_subpixel`: H and W only)
         for has_pool, _, _ in self.enc:
             if has_pool:
                 dims.append(tuple(d // 2 for d in dims[-1]))
-        out, plus = _SubLayers(), set()
+        out, plus, bf16_ids = _SubLayers(), set(), set()
         out.family = "subpixel2d_bf16" if bf16_sub else ("subpixel2d" if is2d else "subpixel")
         L = len(self.enc)
         for j, (c1, _) in enumerate(self.dec):
@@ -158,6 +165,11 @@ class ConvLayers:
             if bf16_sub or self._cat_bf16(c1):
                 if bf16_sub and self._bf16_subpixel(c1, C0, C1, dims[skip_lvl], dims[low_lvl]):
                     out[id(c1.conv.weight)] = (C0, C1)
+                if bf16_sub3d and self._bf16_subpixel3d(c1, C0, C1, dims[skip_lvl], dims[low_lvl]):
+                    out[id(c1.conv.weight)] = (C0, C1)
+                    bf16_ids.add(id(c1.conv.weight))
+                continue
+            if not self.subpixel:  # (U3D_SUBPIXEL=0 next to `bf16_subpixel`: no fp32 sub-pixel level)
                 continue
             # every axis upsampled by exactly 2, or n -> 2n + 1 (the pooled size of an odd level; round 5: the sub-pixel kernels on a
             # shifted window + the general kernels on the near-boundary slab, _fwd_subpixel / _dgrad_subpixel / _wgrad_subpixel)
@@ -168,6 +180,7 @@ class ConvLayers:
                 out[id(c1.conv.weight)] = (C0, C1)
                 if any(ratio):
                     plus.add(id(c1.conv.weight))
+        out.bf16_ids = frozenset(bf16_ids)
         out.plus = frozenset(plus)  # the layers of this call whose packed set includes the slab images (WeightImages.repack)
         return out
 
@@ -333,6 +346,19 @@ class ConvLayers:
         `native_2d_stem` — keeps its written-out concat (`_cat_bf16`) or the `_src` entry points (`_bf16_vcat`)."""
         return (self.subpixel2d_bf16 and self._cat_bf16(c1) and not self.post_norm and not self.act_bf16
                 and all(a == 2 * b for a, b in zip(dims_skip, dims_low))
+                and C0 > 0 and C1 > 0 and C0 % 32 == 0 and C1 % 32 == 0 and c1.conv.out_channels % 32 == 0)
+
+    def _bf16_subpixel3d(self, c1, C0: int, C1: int, dims_skip, dims_low) -> bool:
+        """THE rule for a decoder's first conv of a UNet3D under `bf16_subpixel`, stated once: the key is on; the layer is one `_cat_bf16`
+        accepts (bf16, a pre-norm order, channel counts the bf16 kernels take); the layer order is pre-norm; bf16 activation storage is
+        off; its level upsamples by exactly 2 on all three axes at this input size (the upsampling is nearest: `_subpixel_layers` returns
+        before asking when a decoder has a transposed convolution or an interpolation); C0 % 32 == C1 % 32 == Cout % 32 == 0 (the envelope
+        of the sub-pixel bf16 kernels and of the skip half's sliced images).  Asked by `_subpixel_layers` alone: forward and the image
+        cache read its answer from the `sub` table of the call (`family_of`), backward from the record.  A level outside it — n -> 2n + 1
+        on some axis, other channel counts, a post-norm order — keeps its written-out concat (`_cat_bf16`) or, where `_cat_bf16` is
+        false, the fp32 virtual-concat kernels, as without the key."""
+        return (self.subpixel_bf16 and self._cat_bf16(c1) and not self.post_norm and not self.act_bf16
+                and len(dims_skip) == 3 and all(a == 2 * b for a, b in zip(dims_skip, dims_low))
                 and C0 > 0 and C1 > 0 and C0 % 32 == 0 and C1 % 32 == 0 and c1.conv.out_channels % 32 == 0)
 
     def _c16(self, Cin: int, Cout: int) -> bool:
@@ -525,7 +551,7 @@ class ConvLayers:
         if self.small_cin and c.src.t1 is None and c.Ctot <= 4 and c.Cout <= 32 and residual is None and not c.b16:
             return "small"
         if c.src.t1 is not None and residual is None and id(c.conv.weight) in c.sub:
-            return c.sub.family
+            return c.sub.family_of(id(c.conv.weight))
         if c.src.t1 is None and self._split_fwd(c.Ctot, c.Cout):
             return "f32s"
         if c.src.t1 is None and self._bf16_layer(c.Ctot, c.Cout):
@@ -593,6 +619,26 @@ class ConvLayers:
             nat.call("u3d_conv3d_ex_reps", dev.index, _stream(dev), ctypes.byref(s0), _p(self.images.get(conv.weight, Kind.SKIP_FWD, dev, pair)),
                      _p(c.y), N, D, H, W, Cout, c.relu, yp, None, None, _p(part), None, 0, yr,
                      flops=54.0 * C0 * Cout * N * D * H * W)
+        return ystats
+
+    def _fwd_subpixel_bf16(self, c: "_ConvCall"):
+        # `bf16_subpixel`: the same two launches on the bf16 MFMA — the upsampled half as 8 parity-class 2x2x2 convolutions with taps
+        # pre-summed in fp32 and rounded once (csrc/u3d_subpix_bf16.hip), then the skip half on its sliced 27-tap image, whose epilogue adds
+        # the fp32 partial sums before ReLU / statistics (u3d_conv3d_bf16_ex, residual = part).  The concat is never written.
+        dev, conv, src, N, D, H, W, Cout = c.dev, c.conv, c.src, c.N, c.D, c.H, c.W, c.Cout
+        assert D == 2 * src.D1 and H == 2 * src.H1 and W == 2 * src.W1 and not any(c.plus) and not c.b16
+        pair = C0, C1 = c.sub[id(conv.weight)]
+        ystats = c.take_stats()
+        part = _empty((N, D, H, W, Cout), dtype=_F32, device=dev)
+        nat.call("u3d_subpixel_conv_fwd_bf16", dev.index, _stream(dev), _p(src.t1), _p(c.affine.view(-1)[2 * C0:]), c.Ctot * 2,
+                 _p(self.images.get(conv.weight, Kind.UP_BF16_FWD, dev, pair)), _p(part), N, src.D1, src.H1, src.W1, C1, Cout,
+                 flops=128.0 * C1 * Cout * N * src.D1 * src.H1 * src.W1)
+        a0 = c.affine_lo if c.affine_lo is not None else c.affine[:, :C0].contiguous()
+        need = nat.get_lib().u3d_conv3d_bf16_workspace_floats(N, D, H, W, C0, Cout)  # split-K scratch on small grids
+        kws = _empty(need, dtype=_F32, device=dev) if need > 0 else None
+        nat.call("u3d_conv3d_bf16_ex", dev.index, _stream(dev), _p(src.t0), _p(a0), _p(self.images.get(conv.weight, Kind.SKIP_BF16_FWD, dev, pair)),
+                 _p(c.y), N, D, H, W, C0, Cout, c.relu, _tab(ystats)[0], None, None, _p(part), _p(kws), need,
+                 flops=54.0 * C0 * Cout * N * D * H * W)
         return ystats
 
     def _fwd_subpixel2d(self, c: "_ConvCall"):
@@ -804,7 +850,7 @@ class ConvLayers:
         # pre-norm tensor z) and not under dropout (its mask belongs to the record).
         if record_only and y_out is not None and not post and not (dmod is not None and dmod.training and dmod.p > 0.0):
             return y, None
-        ystats = getattr(self, self._FWD_KERNELS[family])(call)
+        ystats = self._launcher(0, family)(call)
         post_rec = None
         if post:
             # GroupNorm over the conv output z (statistics from the conv epilogue), then the non-linearity: y = f(a*z + b);
@@ -871,6 +917,20 @@ class ConvLayers:
         "subpixel2d": "_dgrad_subpixel2d",  # u3d_conv2d.hip (skip half) + u3d_subpix2d.hip (upsampled half at LOW resolution)
         "subpixel2d_bf16": "_dgrad_subpixel2d_bf16",  # u3d_conv2d_bf16.hip: both halves on bf16 MFMA
     }
+
+    # `bf16_subpixel` (a UNet3D's levels `_bf16_subpixel3d` accepts): the family `subpixel_bf16`, its three launchers in a table of its own.
+    # The three tables above hold the families that replaced a by-shape ladder of backward, and each of their rows is held against that
+    # ladder; this family was never chosen by shape — only `_subpixel_layers` names it, forward records it, backward reads the record.
+    _RECORDED_ONLY = {
+        "subpixel_bf16": ("_fwd_subpixel_bf16",    # u3d_subpix_bf16.hip + u3d_bf16.hip: the upsampled half on the low-res grid, then the skip half
+                          "_dgrad_subpixel_bf16",  # u3d_bf16.hip (skip half) + u3d_subpix_bf16.hip (upsampled half at LOW resolution)
+                          "_wgrad_subpixel_bf16"),  # u3d_subpix_bf16.hip + u3d_bf16.hip strided: both channel slices on bf16 MFMA
+    }
+
+    def _launcher(self, which: int, family: str):
+        """the bound launcher of `family`: which = 0 forward (`_FWD_KERNELS`), 1 data gradient, 2 weight gradient; or its `_RECORDED_ONLY` row"""
+        table = (self._FWD_KERNELS, self._DGRAD_KERNELS, self._WGRAD_KERNELS)[which]
+        return getattr(self, table[family] if family in table else self._RECORDED_ONLY[family][which])
 
     # the family forward recorded (`ConvRec.family`, a row of _FWD_KERNELS) -> the family of its two gradients, where the name differs: the
     # small families when a data gradient is needed, the split forward, the `_src` entry points (which the `conv2d_bf16` launchers call)
@@ -1106,6 +1166,44 @@ class ConvLayers:
         nat.call("u3d_conv2d_wgrad_bf16_strided", dev.index, _stream(dev), _p(src.t0), _p(a0), _p(c.dz), _p(dwv), Ct, c.N, c.H, c.W, C0, c.Cout,
                  _p(ws), ws.numel(), flops=18.0 * C0 * c.Cout * c.N * c.H * c.W)
 
+    def _wgrad_subpixel_bf16(self, c: "_BwdCall"):
+        # `bf16_subpixel`: the two slices of the same (Cout, Ctot, 27) buffer on the bf16 MFMA — both operands rounded once while staged,
+        # fp32 sums added in a fixed order.  Takes no job: the GroupNorm-backward reduction of the layer's input stays the separate
+        # u3d_gn_bwd_finalize_split launch (`_conv_bwd` runs it when c.job comes back set; same bits by the header's contract)
+        cx, dev, src, rec = c.cx, c.cx.dev, c.src, c.rec
+        C0, C1 = rec.sub
+        Ct = src.C
+        lib = nat.get_lib()
+        ws = cx.ensure_ws(max(lib.u3d_subpixel_wgrad_bf16_workspace_floats(c.N, src.D1, src.H1, src.W1, C1, c.Cout),
+                              lib.u3d_wgrad_bf16_workspace_floats(c.N, c.D, c.H, c.W, C0, c.Cout)))
+        dwv = cx.gview(rec.idx_w)
+        nat.call("u3d_subpixel_conv_wgrad_bf16", dev.index, _stream(dev), _p(src.t1), _p(rec.affine.view(-1)[2 * C0:]), Ct * 2, _p(c.dz),
+                 _p(dwv[C0 * 27:]), Ct, c.N, src.D1, src.H1, src.W1, C1, c.Cout, _p(ws), ws.numel(),
+                 flops=128.0 * C1 * c.Cout * c.N * src.D1 * src.H1 * src.W1)
+        a0 = rec.affine_lo if rec.affine_lo is not None else rec.affine[:, :C0].contiguous()
+        nat.call("u3d_conv3d_wgrad_bf16_strided", dev.index, _stream(dev), _p(src.t0), _p(a0), _p(c.dz), _p(dwv), Ct, c.N, c.D, c.H, c.W, C0,
+                 c.Cout, _p(ws), ws.numel(), flops=54.0 * C0 * c.Cout * c.N * c.D * c.H * c.W)
+
+    def _dgrad_subpixel_bf16(self, c: "_BwdCall"):
+        # `bf16_subpixel`: the skip half at full resolution (u3d_conv3d_bf16_ex on dz with the mode-1 image of channels [0, C0), gx = skip);
+        # the upsampled half directly at LOW resolution.  dg = (dg_skip, dlow) and two statistics tables, as `_dgrad_subpixel`
+        cx, dev, src, rec, pool = c.cx, c.cx.dev, c.src, c.rec, c.cx.pool
+        C0, C1 = rec.sub
+        w, pair = rec.conv_w, tuple(rec.sub)
+        dg0 = _empty((c.N, c.D, c.H, c.W, C0), dtype=_F32, device=dev)
+        dlow = _empty_like(src.t1)
+        gst0 = pool.table(c.N, C0)
+        gst1 = pool.table(c.N, C1, c.greps)
+        need = nat.get_lib().u3d_conv3d_bf16_workspace_floats(c.N, c.D, c.H, c.W, c.Cout, C0)  # roles swapped
+        kws = cx.ensure_ws(need) if need > 0 else None
+        nat.call("u3d_conv3d_bf16_ex", dev.index, _stream(dev), _p(c.dz), None, _p(self.images.get(w, Kind.SKIP_BF16_DGRAD, dev, pair)), _p(dg0),
+                 c.N, c.D, c.H, c.W, c.Cout, C0, 0, None, _p(src.t0), _p(gst0.t), None, _p(kws), need,
+                 flops=54.0 * C0 * c.Cout * c.N * c.D * c.H * c.W)
+        nat.call("u3d_subpixel_conv_dgrad_bf16", dev.index, _stream(dev), _p(c.dz), _p(self.images.get(w, Kind.UP_BF16_DGRAD, dev, pair)),
+                 _p(src.t1), _p(dlow), _p(gst1.t), c.N, src.D1, src.H1, src.W1, C1, c.Cout, gst1.reps,
+                 flops=128.0 * C1 * c.Cout * c.N * src.D1 * src.H1 * src.W1)
+        return (dg0, dlow), (gst0, gst1)
+
     def _dgrad_subpixel2d_bf16(self, c: "_BwdCall"):
         # `native_2d_bf16_subpixel`: the skip half at full resolution (u3d_conv2d_bf16 on dz with the mode-1 image of channels [0, C0), gx =
         # skip); the upsampled half directly at LOW resolution.  dg = (dg_skip, dlow) and two statistics tables, as `_dgrad_subpixel2d`
@@ -1272,7 +1370,7 @@ class ConvLayers:
         if (self.stat_reps > 1 and rec.pre_norm and rec.norm == "g" and wgrad in ("fp32", "subpixel")
                 and nat.get_lib().u3d_conv3d_wgrad_job_supported(Nn, src.C, rec.G) == 1):
             call.greps = self.stat_reps
-        dg, gst = getattr(self, self._DGRAD_KERNELS[dgrad])(call)
+        dg, gst = self._launcher(1, dgrad)(call)
         if self.debug is not None and rec.sub is None:
             self.debug[rec.name + ".dg"] = dg.clone()
         coef = coef_hi = None
@@ -1280,7 +1378,7 @@ class ConvLayers:
             coef = _empty((Nn, 3, src.C), dtype=_F32, device=dev)
             call.job, coef_hi = self._norm_bwd_job(cx, rec, gst, float(Dd * Hh * Ww), coef)
         had_job = call.job is not None
-        getattr(self, self._WGRAD_KERNELS[wgrad])(call)
+        self._launcher(2, wgrad)(call)
         if not rec.pre_norm:
             return dg, self._identity_coef(Nn, src.C, dev), None  # no GroupNorm on the conv input: dx = dg
         if not had_job or call.job is not None:  # (no job, or a weight-gradient family without a reduce launch to carry it)
@@ -1320,6 +1418,10 @@ class ConvLayers:
                         lib.u3d_subpixel_wgrad_workspace_floats(N, D // 2, H // 2, W // 2, sub[1], Cout),
                         lib.u3d_conv3d_workspace_floats(N, D, H, W, Cout, sub[0])] +
                        [lib.u3d_wgrad_workspace_floats(N, b[3] - b[0], b[4] - b[1], b[5] - b[2], sub[1], Cout) for b in boxes])
+        if family == "subpixel_bf16":  # (`bf16_subpixel`: skip slice + sub-pixel slice on the bf16 kernels' plans, the skip data gradient's split-K)
+            return max(lib.u3d_wgrad_bf16_workspace_floats(N, D, H, W, sub[0], Cout),
+                       lib.u3d_subpixel_wgrad_bf16_workspace_floats(N, D // 2, H // 2, W // 2, sub[1], Cout),
+                       lib.u3d_conv3d_bf16_workspace_floats(N, D, H, W, Cout, sub[0]))
         if family == "bf16":
             return max(lib.u3d_conv3d_bf16_workspace_floats(N, D, H, W, Cout, Cin), lib.u3d_wgrad_bf16_workspace_floats(N, D, H, W, Cin, Cout))
         if family in ("fp32", "f32s"):  # (the split data gradient grows the buffer itself, `_BwdCtx.ensure_ws`)

@@ -61,6 +61,10 @@ class Kind(enum.IntEnum):
     SKIP_BF16_DGRAD2D = enum.auto()
     UP_BF16_FWD2D = enum.auto()      # ... the parity-class images of the remaining C1 channels: taps pre-summed in fp32, rounded once
     UP_BF16_DGRAD2D = enum.auto()
+    SKIP_BF16_FWD = enum.auto()      # sub-pixel layer of a UNet3D in bf16 (`bf16_subpixel`): the first C0 (skip) input channels, 27 taps ...
+    SKIP_BF16_DGRAD = enum.auto()
+    UP_BF16_FWD = enum.auto()        # ... the parity-class images of the remaining C1 channels: taps pre-summed in fp32, rounded once
+    UP_BF16_DGRAD = enum.auto()
 
 
 @dataclass(frozen=True)
@@ -72,7 +76,7 @@ class _Spec:
     batch: Optional[int] = None   # C-ABI mode of the image's row in the per-step batch launch of its dtype (None: packed on demand)
     half: Optional[int] = None    # the image may be / is of one half of a sub-pixel pair (C0, C1): 0 = skip, 1 = upsampled channels
     transposed: bool = False      # ConvTranspose weight (Cin, Cout, ...): the entry point takes (Cin, Cout), else (Cout, Cin)
-    up2d: bool = False            # u3d_pack_subpixel2d_*: the entry point takes (Cout, Cin_total, c_off, C1[, mode])
+    up_args: bool = False         # u3d_pack_subpixel2d_* / u3d_pack_subpixel_weights_bf16: the entry point takes (Cout, Cin_total, c_off, C1[, mode])
 
 
 _f32 = lambda lib, ci, co, m: lib.u3d_packed_weight_floats(ci, co, m)  # noqa: E731
@@ -86,6 +90,7 @@ _2db = lambda lib, ci, co, m: lib.u3d_packed_weight2d_bf16_elems(ci, co, m)  # n
 _2db16 = lambda lib, ci, co, m: lib.u3d_packed_weight2d_bf16_c16_elems(ci, co, m)  # noqa: E731
 _tr2db = lambda lib, ci, co, m: lib.u3d_packed_convtr2d_bf16_elems(ci, co, m)  # noqa: E731
 _up2db = lambda lib, ci, co, m: lib.u3d_subpixel2d_bf16_packed_elems(ci, co, m)  # noqa: E731
+_up3db = lambda lib, ci, co, m: lib.u3d_subpixel_bf16_packed_elems(ci, co, m)  # noqa: E731
 
 # the C-ABI mode numbers of include/u3d.h live in this table (and `_BF16_BOTH`) and nowhere else in the package
 _KINDS = {
@@ -120,15 +125,19 @@ _KINDS = {
     Kind.SKIP_FWD2D: _Spec(_2d, _F32, "u3d_pack_weights2d_slice", 0, half=0),
     Kind.SKIP_DGRAD2D: _Spec(_2d, _F32, "u3d_pack_weights2d_slice", 1, half=0),
     Kind.UP_FWD2D: _Spec(lambda lib, ci, co, m: lib.u3d_subpixel2d_packed_floats(ci, co), _F32, "u3d_pack_subpixel2d_weights", None,
-                         half=1, up2d=True),
+                         half=1, up_args=True),
     Kind.UP_DGRAD2D: _Spec(lambda lib, ci, co, m: lib.u3d_subpixel2d_dgrad_packed_floats(co, ci), _F32,
-                           "u3d_pack_subpixel2d_dgrad_weights", None, half=1, up2d=True),
+                           "u3d_pack_subpixel2d_dgrad_weights", None, half=1, up_args=True),
     Kind.SLAB_FWD2D: _Spec(_2d, _F32, "u3d_pack_weights2d_slice", 0, half=1),
     Kind.SLAB_DGRAD2D: _Spec(_2d, _F32, "u3d_pack_weights2d_slice", 1, half=1),
     Kind.SKIP_BF16_FWD2D: _Spec(_2db, _BF16, "u3d_pack_weights2d_bf16_slice", 0, half=0),
     Kind.SKIP_BF16_DGRAD2D: _Spec(_2db, _BF16, "u3d_pack_weights2d_bf16_slice", 1, half=0),
-    Kind.UP_BF16_FWD2D: _Spec(_up2db, _BF16, "u3d_pack_subpixel2d_weights_bf16", 0, half=1, up2d=True),
-    Kind.UP_BF16_DGRAD2D: _Spec(_up2db, _BF16, "u3d_pack_subpixel2d_weights_bf16", 1, half=1, up2d=True),
+    Kind.UP_BF16_FWD2D: _Spec(_up2db, _BF16, "u3d_pack_subpixel2d_weights_bf16", 0, half=1, up_args=True),
+    Kind.UP_BF16_DGRAD2D: _Spec(_up2db, _BF16, "u3d_pack_subpixel2d_weights_bf16", 1, half=1, up_args=True),
+    Kind.SKIP_BF16_FWD: _Spec(_bf16, _BF16, "u3d_pack_weights_bf16_slice", 0, half=0),
+    Kind.SKIP_BF16_DGRAD: _Spec(_bf16, _BF16, "u3d_pack_weights_bf16_slice", 1, half=0),
+    Kind.UP_BF16_FWD: _Spec(_up3db, _BF16, "u3d_pack_subpixel_weights_bf16", 0, half=1, up_args=True),
+    Kind.UP_BF16_DGRAD: _Spec(_up3db, _BF16, "u3d_pack_subpixel_weights_bf16", 1, half=1, up_args=True),
 }
 # the images a sub-pixel layer reads, stated once: (forward, data-gradient) pair of the whole weight in a `repack` list -> the pairs of its
 # skip half, its upsampled half and — an n -> 2n + 1 level — the slab (None: the family takes exact-2x levels only)
@@ -136,6 +145,7 @@ _SUB_KINDS = {
     (Kind.FWD, Kind.DGRAD): ((Kind.SKIP_FWD, Kind.SKIP_DGRAD), (Kind.UP_FWD, Kind.UP_DGRAD), (Kind.SLAB_FWD, Kind.SLAB_DGRAD)),
     (Kind.FWD2D, Kind.DGRAD2D): ((Kind.SKIP_FWD2D, Kind.SKIP_DGRAD2D), (Kind.UP_FWD2D, Kind.UP_DGRAD2D), (Kind.SLAB_FWD2D, Kind.SLAB_DGRAD2D)),
     (Kind.BF16_FWD2D, Kind.BF16_DGRAD2D): ((Kind.SKIP_BF16_FWD2D, Kind.SKIP_BF16_DGRAD2D), (Kind.UP_BF16_FWD2D, Kind.UP_BF16_DGRAD2D), None),
+    (Kind.BF16_FWD, Kind.BF16_DGRAD): ((Kind.SKIP_BF16_FWD, Kind.SKIP_BF16_DGRAD), (Kind.UP_BF16_FWD, Kind.UP_BF16_DGRAD), None),
 }
 _BF16_BOTH = 6  # batch row that writes BF16_FWD and, right behind it in one buffer, BF16_DGRAD from one read of the weight
 
@@ -215,7 +225,7 @@ class WeightImages:
             args = (ci, co) if spec.transposed else (co, ci)
             args += () if spec.mode is None else (spec.mode,)
             args += (ld, off) if spec.half is not None else ()
-            if spec.up2d:
+            if spec.up_args:
                 args = (co, ld, off, ci) + (() if spec.mode is None else (spec.mode,))
             nat.call(spec.entry, dev.index, _stream(dev), _p(w.detach()), *args, _p(out))
         self._images[key] = (ver, out)
@@ -279,7 +289,7 @@ class WeightImages:
             for kind in (Kind.BF16_FWD2D_C16, Kind.BF16_DGRAD2D_C16)[:nd]:
                 self.get(w, kind, dev)
         if self._bf16 or self._t8:
-            self._repack_bf16(dev, nd)
+            self._repack_bf16(dev, nd, sub)
         refs = []
         for w in self._f32:
             pair, kinds = self._layer_kinds(w, nd, (Kind.FWD, Kind.DGRAD), sub)
@@ -308,7 +318,7 @@ class WeightImages:
         for (w, kind, pair), buf in zip(stale, bufs):
             self._images[(id(w), kind, pair)] = (self._ver(w), buf)
 
-    def _repack_bf16(self, dev, nd):
+    def _repack_bf16(self, dev, nd, sub=None):
         """bf16 fragment images of every bf16 layer whose parameter changed: ONE launch at HBM rate (u3d_pack_weights_bf16_batch)
         instead of one strided-read launch per layer and image (36 + 36 per config-4 step, 1.0 ms -> 0.25 ms).  The space-to-depth
         images of the transposed convolutions ride in the same launch (round 5; the per-weight kernel read 4 bytes per lane at a
@@ -316,6 +326,11 @@ class WeightImages:
         lib = nat.get_lib()
         refs = []
         for w in self._bf16:
+            if sub and id(w) in sub:  # (`bf16_subpixel`: the four images of the layer's two halves instead, one small launch each)
+                pair, kinds = self._layer_kinds(w, nd, (Kind.BF16_FWD, Kind.BF16_DGRAD), sub)
+                for kind in kinds:
+                    self.get(w, kind, dev, pair)
+                continue
             if w.data_ptr() % 16 == 0:  # (the batch kernel reads 16 bytes per lane; an unaligned view is packed on demand by `get`)
                 refs += [(w, kind, None) for kind in (Kind.BF16_FWD, Kind.BF16_DGRAD)[:nd]]
         for w in self._t8:

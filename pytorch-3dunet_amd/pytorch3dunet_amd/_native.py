@@ -1,6 +1,7 @@
 """ctypes binding of libu3d_hip.so (gfx950 HIP kernels), derived from include/u3d.h at import.
 
-The header is the only statement of the C-ABI: `parse_header` reads its declarations, the four `typedef struct`s and the `U3D_*`
+The header — include/u3d.h and the parts it includes (`PART_PATHS`, read by `read_part` into a second table, `_PART_PROTOS`) — is the only
+statement of the C-ABI: `parse_header` reads its declarations, the four `typedef struct`s and the `U3D_*`
 constants, and this module keeps no second copy of any of them.  One type rule: scalars map through `_SCALARS`; EVERY pointer argument
 and struct field is `c_void_p` (struct pointers too: two of the four structs travel as device arrays through `data_ptr()`, so a typed
 pointer cannot be the rule), which takes `ctypes.byref(struct)`, `(c_int * n)(...)`, an integer address and None alike; a
@@ -103,6 +104,27 @@ def read_header(path):
 
 _PROTOS, _structs, _consts = read_header(HEADER_PATH)  # name: (restype, argtypes), in header order
 EXPORTED_SYMBOLS = tuple(_PROTOS)
+
+
+def read_part(path, known):
+    """prototypes of a part of the C-ABI that u3d.h includes (`#include <u3d_*.h>` inside its extern "C" block): declarations only, in
+    u3d.h's form, read by the same strict reader; a name u3d.h already declares raises"""
+    if not os.path.exists(path):
+        raise U3DError(f"C-ABI header part {path} not found (include/u3d.h includes it)")
+    with open(path) as fh:
+        protos, structs, consts = parse_header(fh.read())
+    if structs or consts or set(protos) & set(known):
+        raise U3DError(f"{path}: a part of u3d.h holds function declarations only, none of them u3d.h's own")
+    return protos
+
+
+# the parts u3d.h includes, in its order: the sub-pixel bf16 entry points of a UNet3D (`bf16_subpixel`)
+PART_PATHS = (os.path.join(os.path.dirname(HEADER_PATH), "u3d_subpix_bf16.h"),)
+_PART_PROTOS = {}
+for _path in PART_PATHS:
+    _PART_PROTOS.update(read_part(_path, {**_PROTOS, **_PART_PROTOS}))
+PART_SYMBOLS = tuple(_PART_PROTOS)
+ALL_SYMBOLS = EXPORTED_SYMBOLS + PART_SYMBOLS  # every u3d_* the library exports: u3d.h's own declarations, then its parts'
 U3D_VERSION, U3D_OK, U3D_EINVAL, U3D_EHIP, U3D_EARCH, U3D_EWORKSPACE = (_consts[k] for k in _CONSTANTS)
 U3DSrc, U3DAdamDesc, U3DGnBwdJob, U3DPackDesc = (
     type(py, (ctypes.Structure,), {"_fields_": _structs[c], "__doc__": f"{c} of include/u3d.h"}) for c, py in _STRUCT_NAMES.items())
@@ -135,7 +157,7 @@ def get_lib():
         import torch  # noqa: F401
 
         lib = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in _PROTOS.items():
+        for name, (res, args) in {**_PROTOS, **_PART_PROTOS}.items():
             fn = getattr(lib, name)  # AttributeError if a declared symbol is missing
             fn.restype = res
             fn.argtypes = args

@@ -18,6 +18,12 @@ run them natively (resolved by unet3d/native2d.py, which says more about each):
 
 {native_2d_keys}
 
+`bf16_subpixel: true` (U3D_BF16_SUBPIXEL=1; a UNet3D, implies `compute_dtype: bf16`): the decoders' first convolutions at levels that
+upsample by exactly 2 on all three axes run the upsampled half of their concat as eight parity-class 2x2x2 convolutions over the LOW-RES
+tensor on the bf16 MFMA (csrc/u3d_subpix_bf16.hip; 8/27 of that half's multiply-adds, the concat is never written) and the skip half on
+channel-sliced images of the 27-tap bf16 kernels.  Other levels and models without such a level run as under plain `compute_dtype: bf16`,
+bit for bit.  Refuses an explicit fp32 / fp32_split compute_dtype, a 2-D model (that key is `native_2d_bf16_subpixel`) and `hip_graph`.
+
 Covered since round 2: every layer order with at most one
 GroupNorm / BatchNorm, one non-linearity and a trailing dropout, every `upsample` value the reference itself can run
 on a 3-D net, nn.DataParallel, activation checkpointing, and the opt-in compute modes `bf16` and `fp32_split`.
@@ -35,7 +41,7 @@ from .utils import get_class, number_of_features_per_level
 
 _THIS_MODULE = __name__
 __doc__ = __doc__.replace("{native_2d_keys}", native2d.TABLE)
-_OPT_IN_KEYS = ("compute_dtype", "checkpoint_encoders", "hip_graph", "activation_dtype", "checkpoint_levels") + native2d.NAMES
+_OPT_IN_KEYS = ("compute_dtype", "checkpoint_encoders", "hip_graph", "activation_dtype", "checkpoint_levels", "bf16_subpixel") + native2d.NAMES
 
 
 def _mark_engine_stale(module, incompatible_keys):
@@ -49,7 +55,7 @@ class AbstractUNet(nn.Module):
     def __init__(self, in_channels, out_channels, final_sigmoid, basic_module, f_maps=64, layer_order="gcr",
                  num_groups=8, num_levels=4, is_segmentation=True, conv_kernel_size=3, pool_kernel_size=2,
                  conv_padding=1, conv_upscale=2, upsample="default", dropout_prob=0.1, is3d=True, compute_dtype=None,
-                 checkpoint_encoders=None, hip_graph=None, activation_dtype=None, checkpoint_levels=None,
+                 checkpoint_encoders=None, hip_graph=None, activation_dtype=None, checkpoint_levels=None, bf16_subpixel=None,
                  **native_2d_keys):
         super().__init__()
         if isinstance(f_maps, int):
@@ -113,6 +119,18 @@ class AbstractUNet(nn.Module):
             reasons.append("head wider than 1024 outputs / 256 inputs")  # (> 16 outputs: the tiled wide-head kernels, round 5)
         # opt-in extras of the native executor (extra keys of the YAML's model section are swallowed by the reference's **kwargs):
         # bf16 MFMA operands with fp32 accumulation / master weights, and recomputation of the encoder blocks in backward
+        # `bf16_subpixel: true` / U3D_BF16_SUBPIXEL=1 (a 3-D model): exact-2x decoder levels of a UNet3D on the sub-pixel bf16 kernels
+        # (engine: `_bf16_subpixel3d`); implies compute_dtype bf16.  The environment only sets the default of a 3-D model's key
+        if bf16_subpixel is None:
+            bf16_subpixel = bool(is3d) and os.environ.get("U3D_BF16_SUBPIXEL", "0") == "1"
+        self.bf16_subpixel = bool(bf16_subpixel)
+        if self.bf16_subpixel:
+            if not is3d:
+                raise ValueError("u3d: bf16_subpixel is the 3-D key (UNet3D); a UNet2D takes native_2d_bf16_subpixel: true")
+            if compute_dtype is not None and str(compute_dtype).lower() not in ("bf16", "bfloat16"):
+                raise ValueError(f"u3d: bf16_subpixel runs bf16 MFMA operands; compute_dtype {compute_dtype!r} contradicts it "
+                                 "(drop one of the two keys)")
+            compute_dtype = "bf16"
         if compute_dtype is None:
             compute_dtype = ("bf16" if os.environ.get("U3D_BF16", "0") == "1"
                              else "fp32_split" if os.environ.get("U3D_F32_SPLIT", "0") == "1" else "fp32")
@@ -161,6 +179,9 @@ class AbstractUNet(nn.Module):
         if self.native_2d and self.hip_graph:
             raise ValueError("u3d: hip_graph is not available with native_2d (the captured training step is 3-D only); "
                              "drop one of the two keys")
+        if self.bf16_subpixel and self.hip_graph:
+            raise ValueError("u3d: hip_graph is not available with bf16_subpixel (the captured training step has not been held to the "
+                             "eager one with the sub-pixel bf16 kernels); drop one of the two keys")
         if self.keys_2d.native_2d_residual and (self.checkpoint_encoders or self.checkpoint_levels is not None):
             raise ValueError("u3d: checkpoint_encoders / checkpoint_levels are not available with native_2d_residual (the 2-D residual "
                              "executor keeps every activation); drop one of the keys")
