@@ -1,0 +1,43 @@
+/* u3d_ext.h — the C-ABI of libu3d_ext_hip.so, the extension library next to libu3d_hip.so (csrc/u3d_c16_bf16.hip).
+ *
+ * A header PART: declarations only — no guard, no C++ wrapper, no constants.  Include it after <u3d.h>, inside extern "C":
+ *     extern "C" {
+ *     #include <u3d.h>      (u3d.h carries its own wrapper; it does not include this file)
+ *     #include <u3d_ext.h>
+ *     }
+ * The extension links against the core library: error codes, u3d_last_error() and the device handling are the core's own.
+ *
+ * ---- 16-channel 3x3x3 convolutions of a UNet3D on the bf16 MFMA (`bf16_stem: true`) ------
+ * The twins of u3d_conv3d_bf16_ex (without `residual`) and u3d_conv3d_wgrad_bf16 on v_mfma_f32_32x32x16_bf16 for layers whose channel
+ * counts are multiples of 16 in EVERY role (forward, data gradient with the roles swapped, weight gradient).  Tensors are fp32 NDHWC,
+ * accumulation is fp32, pointers 16-byte aligned, N * D * H * W < 2^31.
+ * Rounding points: the weight is rounded once, nearest even, by the pack kernel; activations and dz are rounded once while staged to
+ * LDS, after the optional per-sample affine applied in fp32 as fmaf(x, a, b); zero padding applies after the affine and stays exactly 0.
+ *   u3d_conv3d_bf16_c16_supported            1 iff both counts > 0 and both % 16 == 0
+ *   u3d_packed_weight_bf16_c16_elems         2-byte elements of the image u3d_pack_weights_bf16_c16 writes; 0 outside the envelope
+ *   u3d_pack_weights_bf16_c16                w (Cout, Cin, 3, 3, 3) fp32 -> image [K / 16 chunk][27 taps][n-tile][64 lanes][8] of B[k][n];
+ *              mode 0 forward (B[k = ci][n = co] = w[co][ci][tap]), mode 1 data gradient (B[k = co][n = ci] = w[co][ci][26 - tap]); the
+ *              columns of a half n-tile (n >= the produced channel count) are zero
+ *   u3d_conv3d_bf16_c16_workspace_floats     always 0: no split-K (narrow layers sit at high resolution); workspace may be NULL
+ *   u3d_conv3d_bf16_c16                      out (N,D,H,W,Cout) = [relu](conv3d(bf16(a * x + b), bf16(w))); affine optional, (N, Cin, 2);
+ *              out_stats optional, double[N][Cout][2] += (sum y, sum y^2) of the stored values.  Data-gradient form: the mode-1 image,
+ *              relu = 0, x = dz, Cin / Cout swapped, gx = the layer's forward input: gstats double[N][Cout][2] += (sum y, sum y * gx).
+ *              out_stats and gstats are exclusive.
+ *   u3d_wgrad_bf16_c16_workspace_floats      floats of the plan that fills the current device; one slot is 27 * Cin * Cout floats
+ *   u3d_conv3d_wgrad_bf16_c16                dw (Cout, Cin, 3, 3, 3) = sum_v bf16(dz[v, co]) * bf16(g[v + tap - 1, ci]), g = a * x + b zero
+ *              padded; WRITTEN, not accumulated.  No atomics: every block writes its partial sums to its workspace slot and a second kernel
+ *              adds the slots in slot order — the same inputs and workspace size give the same bits.  A workspace smaller than the size
+ *              function's runs on as many splits as it holds; smaller than one slot: U3D_EINVAL.
+ * Outside the envelope, or with unaligned pointers, every launch returns U3D_EINVAL with u3d_last_error() set and launches nothing.
+ *   u3d_ext_version                          the extension's own version, compared by the Python host with its constant */
+int u3d_ext_version(void);
+int u3d_conv3d_bf16_c16_supported(int Cin, int Cout);
+long long u3d_packed_weight_bf16_c16_elems(int Cin, int Cout, int mode);
+int u3d_pack_weights_bf16_c16(int device, u3d_stream_t stream, const float* w, int Cout, int Cin, int mode, void* packed);
+long long u3d_conv3d_bf16_c16_workspace_floats(int N, int D, int H, int W, int Cin, int Cout);
+int u3d_conv3d_bf16_c16(int device, u3d_stream_t stream, const float* x, const float* affine, const void* packed_w, float* out, int N,
+                        int D, int H, int W, int Cin, int Cout, int relu, double* out_stats, const float* gx, double* gstats,
+                        float* workspace, long long workspace_floats);
+long long u3d_wgrad_bf16_c16_workspace_floats(int N, int D, int H, int W, int Cin, int Cout);
+int u3d_conv3d_wgrad_bf16_c16(int device, u3d_stream_t stream, const float* x, const float* affine, const float* dz, float* dw, int N,
+                              int D, int H, int W, int Cin, int Cout, float* workspace, long long workspace_floats);

@@ -62,7 +62,7 @@ class _ConvCall:
     affine_lo: Optional[torch.Tensor] = None  # sub-pixel layers: compact rows of `affine` for the skip / upsampled channels
     affine_hi: Optional[torch.Tensor] = None
     plus: tuple = (0, 0, 0)              # `_src_plus` of a sub-pixel layer's source
-    c16: bool = False                    # a `conv2d_bf16` layer on the `_c16` envelope
+    c16: bool = False                    # a `conv2d_bf16` (`native_2d_stem`) or 3-D `bf16` (`bf16_stem`) layer on the `_c16` envelope
 
     def take_stats(self, reps: int = 1) -> Optional[StatTable]:
         return self.pool.table(self.N, self.Cout, reps) if self.stats else None
@@ -321,10 +321,15 @@ class ConvLayers:
         and through `_bf16_routed` by `_fwd_family` (backward reads its answer from the record), and by `_cat_bf16` for a decoder's
         written-out concat.  Under `native_2d_stem`
         the rule widens to both channel counts % 16 (the net's 16-channel stem layers); a layer only inside the wider rule runs on the
-        `_c16` entry points with the `*_C16` images (`_c16`), a layer inside the old one keeps today's."""
+        `_c16` entry points with the `*_C16` images (`_c16`), a layer inside the old one keeps today's.
+        THE rule for a UNet3D in bf16 as well: `_bf16_layer`, widened under `bf16_stem` (`stem3d`: the key on a DoubleConv net with fp32
+        activation storage) to both channel counts % 16 — such a layer keeps family `bf16` with `c16` in its record and runs on the
+        u3d_*_bf16_c16 entry points of the extension library (include/u3d_ext.h) with the BF16_*_C16 images.  Asked by `_fwd_family`
+        (which adds the per-call conditions: one real source, no residual, fp32 tensors), `_weight_images`, `_cat_bf16` (a pre-norm
+        decoder's 48 -> 16 first convolution runs on its written-out concat) and `_layer_ws_floats`."""
         if virtual:
             return False
-        return self._bf16_layer(Cin, Cout) or bool(self.bf16 and self.stem and Cin % 16 == 0 and Cout % 16 == 0)
+        return self._bf16_layer(Cin, Cout) or bool(self.bf16 and (self.stem or self.stem3d) and Cin % 16 == 0 and Cout % 16 == 0)
 
     def _bf16_vcat(self, src: VSrc, Cout: int) -> bool:
         """THE rule for a decoder's first conv under `native_2d_bf16_vcat`, stated once: the layer runs on the `_src` entry points of the
@@ -554,7 +559,9 @@ class ConvLayers:
             return c.sub.family_of(id(c.conv.weight))
         if c.src.t1 is None and self._split_fwd(c.Ctot, c.Cout):
             return "f32s"
-        if c.src.t1 is None and self._bf16_layer(c.Ctot, c.Cout):
+        # (`_bf16_routed_weight`: under `bf16_stem` a 16-channel layer too — `c16` in its record — unless it carries a residual or bf16 tensors)
+        if c.src.t1 is None and self._bf16_routed_weight(c.Ctot, c.Cout, False) and (
+                self._bf16_layer(c.Ctot, c.Cout) or (residual is None and not c.b16)):
             return "bf16"
         return "fp32"
 
@@ -710,6 +717,12 @@ class ConvLayers:
         # bf16 MFMA operands, fp32 accumulation / epilogue (csrc/u3d_bf16.hip); with bf16 activation storage the input, the
         # output and the residual are bf16 tensors (`_b16` entry point)
         ystats = c.take_stats()
+        if c.c16:  # (`bf16_stem`: a 16-channel layer on the extension library's kernel, csrc/u3d_c16_bf16.hip: no residual, no split-K)
+            assert c.residual is None and not c.b16
+            nat.call("u3d_conv3d_bf16_c16", c.dev.index, _stream(c.dev), _p(c.src.t0), _p(c.affine),
+                     _p(self.images.get(c.conv.weight, Kind.BF16_FWD_C16, c.dev)), _p(c.y), c.N, c.D, c.H, c.W, c.Ctot, c.Cout, c.relu,
+                     _tab(ystats)[0], None, None, None, 0, flops=c.flops)
+            return ystats
         need = nat.get_lib().u3d_conv3d_bf16_workspace_floats(c.N, c.D, c.H, c.W, c.Ctot, c.Cout)  # split-K scratch at the bottom of the U
         kws = _empty(need, dtype=_F32, device=c.dev) if need > 0 else None
         nat.call("u3d_conv3d_bf16_ex" + ("_b16" if c.b16 else ""), c.dev.index, _stream(c.dev), _p(c.src.t0), _p(c.affine),
@@ -833,7 +846,7 @@ class ConvLayers:
         call = _ConvCall(dev, conv, src, affine, y, N, D, H, W, Ctot, Cout, relu, bool(want_stats and self.fused_stats), pool, conv_res,
                          sub, b16, *(split[1:] if split is not None else (None, None)), plus)
         family = self._fwd_family(call, residual)
-        call.c16 = family == "conv2d_bf16" and self._c16(Ctot, Cout)
+        call.c16 = family in ("conv2d_bf16", "bf16") and self._c16(Ctot, Cout)
         dmod = getattr(sc, "dropout", None) if spec.drop == "d" else (getattr(sc, "dropout2d", None) if spec.drop == "D" else None)
         rec = None
         if tape is not None:
@@ -945,7 +958,8 @@ class ConvLayers:
         src, Cout = rec.src, rec.y.shape[-1]
         if rec.family in ("f32s", "fp32") and src.t1 is None and self._split_dgrad(src.C, Cout):
             dgrad = "f32s"  # (the forward's channel rule with the roles swapped: 16 -> 32 is split forward only, 32 -> 16 backward only)
-        if wgrad == "bf16" and Cout % 32 != 0:  # (Cout % 64 == 32 since round 4: 64-column blocks with a zero upper half)
+        if wgrad == "bf16" and Cout % 32 != 0 and not rec.c16:  # (Cout % 64 == 32 since round 4: 64-column blocks with a zero upper half;
+            # a `c16` record's weight gradient is the extension library's, whose envelope is % 16)
             wgrad = "fp32"
         if wgrad == "fp32" and self.overlap_small_wgrad and src.N * src.D * src.H * src.W <= cx.SIDE_MAX_VOXELS and self.debug is None:
             wgrad = "fp32_side"  # (U3D_SIDE_VOXELS, off by default)
@@ -953,6 +967,11 @@ class ConvLayers:
 
     def _wgrad_bf16(self, c: "_BwdCall"):
         cx, dev, src, rec = c.cx, c.cx.dev, c.src, c.rec
+        if rec.c16:  # (`bf16_stem`: takes no GroupNorm-backward job — c.job stays set and _conv_bwd runs the reduction on its own)
+            ws = cx.ensure_ws(nat.get_ext_lib().u3d_wgrad_bf16_c16_workspace_floats(c.N, c.D, c.H, c.W, src.C, c.Cout))
+            nat.call("u3d_conv3d_wgrad_bf16_c16", dev.index, _stream(dev), _p(src.t0), _p(rec.affine), _p(c.dz), _p(cx.gview(rec.idx_w)),
+                     c.N, c.D, c.H, c.W, src.C, c.Cout, _p(ws), ws.numel(), flops=c.flops)
+            return
         need = nat.get_lib().u3d_wgrad_bf16_workspace_floats(c.N, c.D, c.H, c.W, src.C, c.Cout)
         ws = cx.ensure_ws(need)
         dw = cx.gview(rec.idx_w)
@@ -1091,6 +1110,10 @@ class ConvLayers:
         cx, dev, src, rec = c.cx, c.cx.dev, c.src, c.rec
         dg = _empty((c.N, c.D, c.H, c.W, src.C), dtype=c.dz.dtype if c.b16 else _F32, device=dev)
         gst = cx.pool.table(c.N, src.C)
+        if rec.c16:  # (`bf16_stem`: the same kernel with the mode-1 image, roles swapped)
+            nat.call("u3d_conv3d_bf16_c16", dev.index, _stream(dev), _p(c.dz), None, _p(self.images.get(rec.conv_w, Kind.BF16_DGRAD_C16, dev)),
+                     _p(dg), c.N, c.D, c.H, c.W, c.Cout, src.C, 0, None, _p(src.t0), _p(gst.t), None, 0, flops=c.flops)
+            return dg, (gst, None)
         need = nat.get_lib().u3d_conv3d_bf16_workspace_floats(c.N, c.D, c.H, c.W, c.Cout, src.C)
         kws = cx.ensure_ws(need) if need > 0 else None
         nat.call("u3d_conv3d_bf16_ex" + ("_b16" if c.b16 else ""), dev.index, _stream(dev), _p(c.dz), None,
@@ -1422,6 +1445,8 @@ class ConvLayers:
             return max(lib.u3d_wgrad_bf16_workspace_floats(N, D, H, W, sub[0], Cout),
                        lib.u3d_subpixel_wgrad_bf16_workspace_floats(N, D // 2, H // 2, W // 2, sub[1], Cout),
                        lib.u3d_conv3d_bf16_workspace_floats(N, D, H, W, Cout, sub[0]))
+        if family == "bf16" and c16:  # (`bf16_stem`: the extension library's plans; its convolution never splits)
+            return nat.get_ext_lib().u3d_wgrad_bf16_c16_workspace_floats(N, D, H, W, Cin, Cout)
         if family == "bf16":
             return max(lib.u3d_conv3d_bf16_workspace_floats(N, D, H, W, Cout, Cin), lib.u3d_wgrad_bf16_workspace_floats(N, D, H, W, Cin, Cout))
         if family in ("fp32", "f32s"):  # (the split data gradient grows the buffer itself, `_BwdCtx.ensure_ws`)
@@ -1452,8 +1477,8 @@ class ConvLayers:
         if self.is2d:
             family = "small2d" if small else ("conv2d_bf16" if self._bf16_routed_weight(Cin, Cout, False) else "conv2d")
         else:
-            family = "small" if small else ("bf16" if self._bf16_layer(Cin, Cout) else "fp32")
-        return self._family_ws_floats(family, N, D, H, W, Cin, Cout, c16=family == "conv2d_bf16" and self._c16(Cin, Cout))
+            family = "small" if small else ("bf16" if self._bf16_routed_weight(Cin, Cout, False) else "fp32")
+        return self._family_ws_floats(family, N, D, H, W, Cin, Cout, c16=family in ("conv2d_bf16", "bf16") and self._c16(Cin, Cout))
 
     def _wgrad_workspace_floats(self, convs):
         """scratch floats the backward kernels of these recorded layers need (one shared buffer, sized once per backward)"""

@@ -18,7 +18,7 @@ from ._native import U3DSrc
 
 from ._engine_base import *  # noqa: F401,F403  (explicit __all__: helpers, records, activation codes)
 from ._engine_conv import ConvLayers
-from ._engine_weights import WeightImages
+from ._engine_weights import Kind, WeightImages
 
 
 
@@ -41,6 +41,9 @@ class UNet3DEngine(ConvLayers):
         self.vcat = keys.native_2d_bf16_vcat  # a decoder's first conv reads its concat inside the bf16 kernels (`_bf16_vcat`)
         self.subpixel2d_bf16 = keys.native_2d_bf16_subpixel  # exact-2x decoder levels on the sub-pixel bf16 kernels (`_bf16_subpixel`)
         self.subpixel_bf16 = bool(getattr(model, "bf16_subpixel", False))  # a UNet3D's exact-2x decoder levels on the sub-pixel bf16 kernels (`_bf16_subpixel3d`)
+        # `bf16_stem`: a UNet3D's 16-channel layers on the bf16 kernels of the extension library (`_bf16_routed_weight`); a residual class
+        # accepts the key and routes no layer
+        self.stem3d = bool(getattr(model, "bf16_stem", False)) and not getattr(model, "_residual", False)
         self.bf16_deconv = keys.native_2d_residual_bf16_deconv  # the decoders' ConvTranspose2d on the bf16 matrix pipe (`_bf16_convtr2d`)
         self.children = 4.0 if self.is2d else 8.0  # full-res voxels a low-res voxel of an exact-2x level stands for
         self._up_scale_t = None  # `_up_scale`'s memo
@@ -142,11 +145,14 @@ class UNet3DEngine(ConvLayers):
             c16 = {id(w) for w in ws if id(w) in bf16 and self._c16(w.shape[1], w.shape[0])}  # (stem layers: the `*_C16` images)
             return WeightImages(each=[w for w in ws if id(w) not in bf16 | small], each_bf16=[w for w in ws if id(w) in bf16 - c16],
                                 each_bf16_c16=[w for w in ws if id(w) in c16])
-        bf16 = {id(w) for w in ws if self._bf16_layer(w.shape[1], w.shape[0])} - self._virtual_w
+        bf16 = {id(w) for w in ws if self._bf16_routed_weight(w.shape[1], w.shape[0], id(w) in self._virtual_w)}
+        # (`bf16_stem`: the 16-channel layers' BF16_*_C16 images, one launch per weight and image, not in the batch pack launch)
+        c16 = {id(w) for w in ws if id(w) in bf16 and self._c16(w.shape[1], w.shape[0])}
         return WeightImages(
             # (not the first layer: its dedicated kernels read the reference layout)
             f32=[w for w in ws if id(w) not in bf16 and not (self.small_cin and w.shape[1] <= 4 and w.shape[0] <= 32)],
-            bf16=[w for w in ws if id(w) in bf16], t8=self._t8_weights() if self.bf16 else ())
+            bf16=[w for w in ws if id(w) in bf16 - c16], t8=self._t8_weights() if self.bf16 else (),
+            each_bf16_c16=[w for w in ws if id(w) in c16], c16_kinds=(Kind.BF16_FWD_C16, Kind.BF16_DGRAD_C16))
 
     def _t8_weights(self) -> list:
         """ConvTranspose3d weights whose forward / data gradient may run in space-to-depth form (`_convtr_t8`)"""

@@ -49,6 +49,8 @@ class Kind(enum.IntEnum):
     BF16_DGRAD2D = enum.auto()
     BF16_FWD2D_C16 = enum.auto()    # ... the 16-channel stem layers among them (`native_2d_stem`): half n-tiles stored whole, zero upper columns
     BF16_DGRAD2D_C16 = enum.auto()
+    BF16_FWD_C16 = enum.auto()      # the 16-channel 3x3x3 layers of a UNet3D in bf16 (`bf16_stem`): images of the extension library's kernels
+    BF16_DGRAD_C16 = enum.auto()
     CONVTR2D_BF16_FWD = enum.auto()    # ConvTranspose2d on the bf16 kernels (`native_2d_residual_bf16_deconv`): B[ci][co] per tap ...
     CONVTR2D_BF16_DGRAD = enum.auto()  # ... B[co][ci] per tap
     SKIP_FWD2D = enum.auto()    # sub-pixel layer of a 2-D net (`native_2d_subpixel`): the first C0 (skip) input channels ...
@@ -88,6 +90,7 @@ _2d = lambda lib, ci, co, m: lib.u3d_packed_weight2d_floats(ci, co, m)  # noqa: 
 _tr2d = lambda lib, ci, co, m: lib.u3d_convtr2d_packed_floats(ci, co)  # noqa: E731
 _2db = lambda lib, ci, co, m: lib.u3d_packed_weight2d_bf16_elems(ci, co, m)  # noqa: E731
 _2db16 = lambda lib, ci, co, m: lib.u3d_packed_weight2d_bf16_c16_elems(ci, co, m)  # noqa: E731
+_3db16 = lambda lib, ci, co, m: nat.get_ext_lib().u3d_packed_weight_bf16_c16_elems(ci, co, m)  # noqa: E731  (include/u3d_ext.h)
 _tr2db = lambda lib, ci, co, m: lib.u3d_packed_convtr2d_bf16_elems(ci, co, m)  # noqa: E731
 _up2db = lambda lib, ci, co, m: lib.u3d_subpixel2d_bf16_packed_elems(ci, co, m)  # noqa: E731
 _up3db = lambda lib, ci, co, m: lib.u3d_subpixel_bf16_packed_elems(ci, co, m)  # noqa: E731
@@ -120,6 +123,8 @@ _KINDS = {
     Kind.BF16_DGRAD2D: _Spec(_2db, _BF16, "u3d_pack_weights2d_bf16", 1),
     Kind.BF16_FWD2D_C16: _Spec(_2db16, _BF16, "u3d_pack_weights2d_bf16_c16", 0),
     Kind.BF16_DGRAD2D_C16: _Spec(_2db16, _BF16, "u3d_pack_weights2d_bf16_c16", 1),
+    Kind.BF16_FWD_C16: _Spec(_3db16, _BF16, "u3d_pack_weights_bf16_c16", 0),
+    Kind.BF16_DGRAD_C16: _Spec(_3db16, _BF16, "u3d_pack_weights_bf16_c16", 1),
     Kind.CONVTR2D_BF16_FWD: _Spec(_tr2db, _BF16, "u3d_pack_convtr2d_bf16", 0, transposed=True),
     Kind.CONVTR2D_BF16_DGRAD: _Spec(_tr2db, _BF16, "u3d_pack_convtr2d_bf16", 1, transposed=True),
     Kind.SKIP_FWD2D: _Spec(_2d, _F32, "u3d_pack_weights2d_slice", 0, half=0),
@@ -156,9 +161,10 @@ class WeightImages:
     images, bf16 images of the layers on the bf16 kernels) at the start of a forward (`repack`); every other image is packed when `get`
     first misses it.  Constructing it does not touch the native library."""
 
-    def __init__(self, f32=(), bf16=(), t8=(), each=(), each_bf16=(), each_bf16_c16=()):
+    def __init__(self, f32=(), bf16=(), t8=(), each=(), each_bf16=(), each_bf16_c16=(), c16_kinds=(Kind.BF16_FWD2D_C16, Kind.BF16_DGRAD2D_C16)):
         self._f32, self._bf16, self._t8, self._each = list(f32), list(bf16), list(t8), list(each)
         self._each_bf16, self._each_bf16_c16 = list(each_bf16), list(each_bf16_c16)
+        self._c16_kinds = tuple(c16_kinds)  # (forward, data-gradient) image of an `each_bf16_c16` weight: the 2-D pair, or a UNet3D's (`bf16_stem`)
         self._images: dict = {}  # (id(weight), kind, sub-pixel pair or None) -> (version key, device buffer)
         self._tables: dict = {}  # batch launch -> (its stale set, descriptor tables + the buffers they point at): one live plan each
         self._salt = 0           # advanced by begin_forward / invalidate: see _ver
@@ -285,8 +291,8 @@ class WeightImages:
             pair, kinds = self._layer_kinds(w, nd, (Kind.BF16_FWD2D, Kind.BF16_DGRAD2D), sub)  # (`native_2d_bf16_subpixel`: likewise)
             for kind in kinds:
                 self.get(w, kind, dev, pair)
-        for w in self._each_bf16_c16:  # ... and of its 16-channel stem layers (u3d_pack_weights2d_bf16_c16)
-            for kind in (Kind.BF16_FWD2D_C16, Kind.BF16_DGRAD2D_C16)[:nd]:
+        for w in self._each_bf16_c16:  # ... and of its 16-channel stem layers (u3d_pack_weights2d_bf16_c16; a UNet3D's: u3d_pack_weights_bf16_c16)
+            for kind in self._c16_kinds[:nd]:
                 self.get(w, kind, dev)
         if self._bf16 or self._t8:
             self._repack_bf16(dev, nd, sub)

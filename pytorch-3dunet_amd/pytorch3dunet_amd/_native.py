@@ -1,4 +1,6 @@
-"""ctypes binding of libu3d_hip.so (gfx950 HIP kernels), derived from include/u3d.h at import.
+"""ctypes binding of libu3d_hip.so (gfx950 HIP kernels), derived from include/u3d.h at import — and of the extension library
+libu3d_ext_hip.so next to it, derived from include/u3d_ext.h into a third table (`_EXT_PROTOS`) and loaded lazily, on the first call of one
+of its names (`get_ext_lib`).
 
 The header — include/u3d.h and the parts it includes (`PART_PATHS`, read by `read_part` into a second table, `_PART_PROTOS`) — is the only
 statement of the C-ABI: `parse_header` reads its declarations, the four `typedef struct`s and the `U3D_*`
@@ -125,11 +127,19 @@ for _path in PART_PATHS:
     _PART_PROTOS.update(read_part(_path, {**_PROTOS, **_PART_PROTOS}))
 PART_SYMBOLS = tuple(_PART_PROTOS)
 ALL_SYMBOLS = EXPORTED_SYMBOLS + PART_SYMBOLS  # every u3d_* the library exports: u3d.h's own declarations, then its parts'
+# the extension library's C-ABI (include/u3d_ext.h, a header in the form of a part: u3d.h does NOT include it): the 16-channel bf16 entry
+# points of a UNet3D (`bf16_stem`).  The core's tables above do not know these names; `call` resolves them in `get_ext_lib()`.
+EXT_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "u3d_ext.h")
+EXT_LIB_PATH = os.environ.get("U3D_EXT_LIB_PATH") or os.path.join(os.path.dirname(LIB_PATH), "libu3d_ext_hip.so")
+_EXT_PROTOS = read_part(EXT_HEADER_PATH, {**_PROTOS, **_PART_PROTOS})
+EXT_SYMBOLS = tuple(_EXT_PROTOS)
+U3D_EXT_VERSION = 1  # what u3d_ext_version() of a matching libu3d_ext_hip.so returns
 U3D_VERSION, U3D_OK, U3D_EINVAL, U3D_EHIP, U3D_EARCH, U3D_EWORKSPACE = (_consts[k] for k in _CONSTANTS)
 U3DSrc, U3DAdamDesc, U3DGnBwdJob, U3DPackDesc = (
     type(py, (ctypes.Structure,), {"_fields_": _structs[c], "__doc__": f"{c} of include/u3d.h"}) for c, py in _STRUCT_NAMES.items())
 
 _lib = None
+_ext_lib = None  # stays None until the first call of an extension name: a model without `bf16_stem` never loads the library
 _lock = threading.Lock()
 launch_count = 0  # number of native calls issued (tests assert the HIP path really ran)
 
@@ -170,6 +180,32 @@ def get_lib():
                     raise U3DError(f"U3D_TUNE: bad knob {kv!r}")
         _lib = lib
     return _lib
+
+
+def get_ext_lib():
+    """Load libu3d_ext_hip.so (once, after the core library it links against).  Raises U3DError if it has not been built."""
+    global _ext_lib
+    if _ext_lib is not None:
+        return _ext_lib
+    get_lib()
+    with _lock:
+        if _ext_lib is not None:
+            return _ext_lib
+        if not os.path.exists(EXT_LIB_PATH):
+            raise U3DError(
+                f"native extension library {EXT_LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
+                "(hipcc --offload-arch=gfx950). The MI355X path has no CPU/PyTorch fallback."
+            )
+        lib = ctypes.CDLL(EXT_LIB_PATH)
+        for name, (res, args) in _EXT_PROTOS.items():
+            fn = getattr(lib, name)  # AttributeError if a declared symbol is missing
+            fn.restype = res
+            fn.argtypes = args
+        if lib.u3d_ext_version() != U3D_EXT_VERSION:
+            raise U3DError(f"libu3d_ext_hip.so has version {lib.u3d_ext_version()}, the Python host code expects {U3D_EXT_VERSION}: rebuild it "
+                           "with `python -c 'import __graft_entry__ as g; g.build()'`")
+        _ext_lib = lib
+    return _ext_lib
 
 
 def check(rc: int, what: str = "") -> None:
@@ -229,7 +265,7 @@ profiler = None
 def call(name: str, *args, flops: float = 0.0) -> None:
     """Call an int-returning entry point and raise on error."""
     global launch_count
-    fn = getattr(get_lib(), name)
+    fn = getattr(get_ext_lib() if name in _EXT_PROTOS else get_lib(), name)
     launch_count += 1
     rc = fn(*args) if profiler is None else profiler.wrap(name, fn, args, flops)
     if rc != U3D_OK:

@@ -24,6 +24,15 @@ tensor on the bf16 MFMA (csrc/u3d_subpix_bf16.hip; 8/27 of that half's multiply-
 channel-sliced images of the 27-tap bf16 kernels.  Other levels and models without such a level run as under plain `compute_dtype: bf16`,
 bit for bit.  Refuses an explicit fp32 / fp32_split compute_dtype, a 2-D model (that key is `native_2d_bf16_subpixel`) and `hip_graph`.
 
+`bf16_stem: true` (U3D_BF16_STEM=1; a UNet3D, implies `compute_dtype: bf16`, REDUCED precision like it): the 3x3x3 layers whose channel
+counts are multiples of 16 but not both of 32 — `encoders.0`'s 16 -> 32 convolution of an `f_maps: 32` net, the 16-channel layers and the
+48 -> 16 top decoder (on its written-out concat) of an `f_maps: 16` net — run forward, data gradient and weight gradient on the bf16 MFMA
+kernels of the extension library libu3d_ext_hip.so (csrc/u3d_c16_bf16.hip, include/u3d_ext.h) instead of the fp32 kernels.  Layers inside
+the 32-channel rule, models without such a layer and the residual classes (which accept the key and route no layer) run as under plain
+`compute_dtype: bf16`, bit for bit, and never load the extension.  Composes with `bf16_subpixel`, `checkpoint_encoders` /
+`checkpoint_levels` and nn.DataParallel.  Refuses an explicit fp32 / fp32_split compute_dtype, a 2-D model (that key is `native_2d_stem`)
+and `hip_graph`.
+
 Covered since round 2: every layer order with at most one
 GroupNorm / BatchNorm, one non-linearity and a trailing dropout, every `upsample` value the reference itself can run
 on a 3-D net, nn.DataParallel, activation checkpointing, and the opt-in compute modes `bf16` and `fp32_split`.
@@ -41,7 +50,7 @@ from .utils import get_class, number_of_features_per_level
 
 _THIS_MODULE = __name__
 __doc__ = __doc__.replace("{native_2d_keys}", native2d.TABLE)
-_OPT_IN_KEYS = ("compute_dtype", "checkpoint_encoders", "hip_graph", "activation_dtype", "checkpoint_levels", "bf16_subpixel") + native2d.NAMES
+_OPT_IN_KEYS = ("compute_dtype", "checkpoint_encoders", "hip_graph", "activation_dtype", "checkpoint_levels", "bf16_subpixel", "bf16_stem") + native2d.NAMES
 
 
 def _mark_engine_stale(module, incompatible_keys):
@@ -56,7 +65,7 @@ class AbstractUNet(nn.Module):
                  num_groups=8, num_levels=4, is_segmentation=True, conv_kernel_size=3, pool_kernel_size=2,
                  conv_padding=1, conv_upscale=2, upsample="default", dropout_prob=0.1, is3d=True, compute_dtype=None,
                  checkpoint_encoders=None, hip_graph=None, activation_dtype=None, checkpoint_levels=None, bf16_subpixel=None,
-                 **native_2d_keys):
+                 bf16_stem=None, **native_2d_keys):
         super().__init__()
         if isinstance(f_maps, int):
             f_maps = number_of_features_per_level(f_maps, num_levels=num_levels)
@@ -131,6 +140,18 @@ class AbstractUNet(nn.Module):
                 raise ValueError(f"u3d: bf16_subpixel runs bf16 MFMA operands; compute_dtype {compute_dtype!r} contradicts it "
                                  "(drop one of the two keys)")
             compute_dtype = "bf16"
+        # `bf16_stem: true` / U3D_BF16_STEM=1 (a 3-D model): the 16-channel 3x3x3 layers of a UNet3D on the bf16 MFMA kernels of the extension
+        # library (engine: `_bf16_stem_layer`); implies compute_dtype bf16.  The environment only sets the default of a 3-D model's key
+        if bf16_stem is None:
+            bf16_stem = bool(is3d) and os.environ.get("U3D_BF16_STEM", "0") == "1"
+        self.bf16_stem = bool(bf16_stem)
+        if self.bf16_stem:
+            if not is3d:
+                raise ValueError("u3d: bf16_stem is the 3-D key (UNet3D); a UNet2D takes native_2d_stem: true")
+            if compute_dtype is not None and str(compute_dtype).lower() not in ("bf16", "bfloat16"):
+                raise ValueError(f"u3d: bf16_stem runs bf16 MFMA operands; compute_dtype {compute_dtype!r} contradicts it "
+                                 "(drop one of the two keys)")
+            compute_dtype = "bf16"
         if compute_dtype is None:
             compute_dtype = ("bf16" if os.environ.get("U3D_BF16", "0") == "1"
                              else "fp32_split" if os.environ.get("U3D_F32_SPLIT", "0") == "1" else "fp32")
@@ -182,6 +203,9 @@ class AbstractUNet(nn.Module):
         if self.bf16_subpixel and self.hip_graph:
             raise ValueError("u3d: hip_graph is not available with bf16_subpixel (the captured training step has not been held to the "
                              "eager one with the sub-pixel bf16 kernels); drop one of the two keys")
+        if self.bf16_stem and self.hip_graph:
+            raise ValueError("u3d: hip_graph is not available with bf16_stem (the captured training step has not been held to the "
+                             "eager one with the 16-channel bf16 kernels); drop one of the two keys")
         if self.keys_2d.native_2d_residual and (self.checkpoint_encoders or self.checkpoint_levels is not None):
             raise ValueError("u3d: checkpoint_encoders / checkpoint_levels are not available with native_2d_residual (the 2-D residual "
                              "executor keeps every activation); drop one of the keys")
