@@ -1,4 +1,5 @@
-/* u3d_ext.h — the C-ABI of libu3d_ext_hip.so, the extension library next to libu3d_hip.so (csrc/u3d_c16_bf16.hip).
+/* u3d_ext.h — the C-ABI of libu3d_ext_hip.so, the extension library next to libu3d_hip.so (csrc/u3d_c16_bf16.hip,
+ * csrc/u3d_wgrad_f32s.hip).
  *
  * A header PART: declarations only — no guard, no C++ wrapper, no constants.  Include it after <u3d.h>, inside extern "C":
  *     extern "C" {
@@ -29,6 +30,21 @@
  *              adds the slots in slot order — the same inputs and workspace size give the same bits.  A workspace smaller than the size
  *              function's runs on as many splits as it holds; smaller than one slot: U3D_EINVAL.
  * Outside the envelope, or with unaligned pointers, every launch returns U3D_EINVAL with u3d_last_error() set and launches nothing.
+ *
+ * ---- the weight gradient of `compute_dtype: fp32_split` on the bf16 MFMA (`fp32_split_wgrad: true`; csrc/u3d_wgrad_f32s.hip) ------
+ * The contract of u3d_conv3d_wgrad_bf16_strided with fp32-grade arithmetic.  Both operands are split exactly into three bf16 values while
+ * staged, after the fp32 affine: h = bf16(g), m = bf16(g - h), l = bf16(g - h - m); the six products hh, hm, mh, hl, lh, mm run on
+ * v_mfma_f32_32x32x16_bf16 with fp32 accumulation; every voxel tile's MFMA chain starts from zero and is added to the running sums with
+ * the sign of dz alternating per tile, which cancels the MFMA's round-down accumulation drift.
+ *   u3d_conv3d_wgrad_f32s_supported          1 iff both counts > 0 and both % 32 == 0
+ *   u3d_wgrad_f32s_workspace_floats          floats of the plan that fills the current device; one slot is 27 * Cin * Cout floats; 0 outside
+ *              the envelope
+ *   u3d_conv3d_wgrad_f32s                    dw[co][ci][tap] = sum_v dz[v, co] * g[v + tap - 1, ci], g = fmaf(x, a, b) from the optional
+ *              (N, Cin, 2) affine, zero padded after it; WRITTEN, not accumulated, into channels [dw, dw + Cin) of a
+ *              (Cout, dw_cin_stride, 3, 3, 3) gradient (dw_cin_stride = Cin: the plain layout).  x, affine, dz and workspace 16-byte
+ *              aligned.  No atomics: every block writes its partial sums to its workspace slot and a second kernel adds the slots in a
+ *              fixed order — the same inputs and workspace size give the same bits.  A workspace smaller than the size function's runs
+ *              on as many splits as it holds; outside the envelope, or smaller than one slot: U3D_EINVAL, nothing launched.
  *   u3d_ext_version                          the extension's own version, compared by the Python host with its constant */
 int u3d_ext_version(void);
 int u3d_conv3d_bf16_c16_supported(int Cin, int Cout);
@@ -41,3 +57,7 @@ int u3d_conv3d_bf16_c16(int device, u3d_stream_t stream, const float* x, const f
 long long u3d_wgrad_bf16_c16_workspace_floats(int N, int D, int H, int W, int Cin, int Cout);
 int u3d_conv3d_wgrad_bf16_c16(int device, u3d_stream_t stream, const float* x, const float* affine, const float* dz, float* dw, int N,
                               int D, int H, int W, int Cin, int Cout, float* workspace, long long workspace_floats);
+int u3d_conv3d_wgrad_f32s_supported(int Cin, int Cout);
+long long u3d_wgrad_f32s_workspace_floats(int N, int D, int H, int W, int Cin, int Cout);
+int u3d_conv3d_wgrad_f32s(int device, u3d_stream_t stream, const float* x, const float* affine, const float* dz, float* dw, int dw_cin_stride,
+                          int N, int D, int H, int W, int Cin, int Cout, float* workspace, long long workspace_floats);

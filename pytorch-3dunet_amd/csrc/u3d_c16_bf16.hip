@@ -1,7 +1,7 @@
 // u3d_c16_bf16.hip — the 16-channel 3x3x3 convolutions of a UNet3D on the bf16 MFMA (`bf16_stem: true`): forward / data gradient and weight
 // gradient for layers whose channel counts are multiples of 16 but not both of 32 (16 -> 32 at full resolution, the 48 -> 16 top decoder
-// of an `f_maps: 16` net), the 3-D twins of the `_c16` entry points of csrc/u3d_conv2d_bf16.hip.  This is the ONE translation unit of
-// libu3d_ext_hip.so (include/u3d_ext.h), linked against libu3d_hip.so: u3d_set_err / u3d_last_error and u3d_device_guard are the core's.
+// of an `f_maps: 16` net), the 3-D twins of the `_c16` entry points of csrc/u3d_conv2d_bf16.hip.  This is the first translation unit of
+// libu3d_ext_hip.so (include/u3d_ext.h; the second is csrc/u3d_wgrad_f32s.hip), linked against libu3d_hip.so: u3d_set_err / u3d_last_error and u3d_device_guard are the core's.
 // Self-contained like csrc/u3d_subpix_bf16.hip: it restates the LDS record layout of csrc/u3d_bf16.hip instead of sharing templates.
 // Tensors in HBM are fp32 NDHWC, accumulation is fp32.  Rounding points: the weight is rounded ONCE to bf16, nearest even, by the pack
 // kernel; activations and dz are rounded once while staged to LDS, after the fp32 affine fmaf(x, a, b); zero padding applies after the
@@ -32,7 +32,7 @@ extern "C" {
 
 #include <algorithm>
 
-#define U3D_EXT_VERSION 1
+#define U3D_EXT_VERSION 2
 
 typedef __bf16 c16_bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 c16_bf16x4 __attribute__((ext_vector_type(4)));

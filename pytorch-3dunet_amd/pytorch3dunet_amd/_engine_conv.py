@@ -389,6 +389,21 @@ class ConvLayers:
         """data gradient of a (Cin -> Cout) conv: contraction over Cout, produces Cin channels"""
         return self.split and Cout % 16 == 0 and Cin % 32 == 0
 
+    def _split_wgrad(self, Cin: int, Cout: int) -> bool:
+        """THE rule for the split weight gradient under `fp32_split_wgrad`, stated once: a (Cin -> Cout) weight gradient over ONE real fp32
+        source — a single-source layer of the `fp32` weight-gradient family, or the skip slice of a `subpixel` layer — runs on
+        u3d_conv3d_wgrad_f32s of the extension library (csrc/u3d_wgrad_f32s.hip) when both channel counts lie in its envelope (% 32).
+        Asked by `_wgrad_fp32`, `_wgrad_subpixel`, `_conv_bwd` (that launch takes no GroupNorm-backward job) and `_family_ws_floats`;
+        with the key off the extension library is not even loaded."""
+        return bool(self.split_wgrad) and nat.get_ext_lib().u3d_conv3d_wgrad_f32s_supported(Cin, Cout) == 1
+
+    def _split_wgrad_call(self, c: "_BwdCall", x, affine, Cin: int, dw, dw_cin_stride: int):
+        """u3d_conv3d_wgrad_f32s of one real source into channels [dw, dw + Cin) of the layer's gradient; scratch through `ensure_ws`"""
+        cx, dev = c.cx, c.cx.dev
+        ws = cx.ensure_ws(nat.get_ext_lib().u3d_wgrad_f32s_workspace_floats(c.N, c.D, c.H, c.W, Cin, c.Cout))
+        nat.call("u3d_conv3d_wgrad_f32s", dev.index, _stream(dev), _p(x), _p(affine), _p(c.dz), _p(dw), dw_cin_stride, c.N, c.D, c.H, c.W,
+                 Cin, c.Cout, _p(ws), ws.numel(), flops=54.0 * Cin * c.Cout * c.N * c.D * c.H * c.W)
+
     def _convtr_t8(self, Cl: int, Cs: int) -> bool:
         """the transposed convolution and its gradients run in space-to-depth form on the bf16 MFMA kernels"""
         return self.bf16 and not self.is2d and nat.get_lib().u3d_convtr3d_t8_supported(Cl, Cs) == 1
@@ -1015,6 +1030,9 @@ class ConvLayers:
                      _p(c.dz), _p(dwv[C0 * 27:]), Ct, c.N, src.D1, src.H1, src.W1, C1, c.Cout, _p(ws), ws.numel(),
                      flops=128.0 * C1 * c.Cout * c.N * src.D1 * src.H1 * src.W1)
         a0 = rec.affine_lo if rec.affine_lo is not None else rec.affine[:, :C0].contiguous()
+        if self._split_wgrad(C0, c.Cout):  # (`fp32_split_wgrad`: the skip slice alone; no job — c.job stays set for _conv_bwd's finalize)
+            self._split_wgrad_call(c, src.t0, a0, C0, dwv, Ct)
+            return
         s0 = VSrc(src.t0).struct(a0)
         nat.call("u3d_conv3d_wgrad_job", dev.index, _stream(dev), ctypes.byref(s0), _p(c.dz), _p(dwv), Ct, c.N, c.D, c.H, c.W,
                  c.Cout, _p(ws), ws.numel(), ctypes.byref(c.job) if c.job is not None else None,
@@ -1037,6 +1055,10 @@ class ConvLayers:
 
     def _wgrad_fp32(self, c: "_BwdCall"):
         cx, dev, src, rec, ws = c.cx, c.cx.dev, c.src, c.rec, c.cx.ws
+        if src.t1 is None and self._split_wgrad(src.C, c.Cout):
+            # (`fp32_split_wgrad`: takes no GroupNorm-backward job — c.job stays set and _conv_bwd runs the reduction on its own)
+            self._split_wgrad_call(c, src.t0, rec.affine, src.C, cx.gview(rec.idx_w), src.C)
+            return
         s_aff = src.struct(rec.affine)
         nat.call("u3d_conv3d_wgrad_job", dev.index, _stream(dev), ctypes.byref(s_aff), _p(c.dz), _p(cx.gview(rec.idx_w)), 0, c.N, c.D,
                  c.H, c.W, c.Cout, _p(ws), ws.numel(), ctypes.byref(c.job) if c.job is not None else None, flops=c.flops)
@@ -1390,7 +1412,10 @@ class ConvLayers:
         # ---- data gradient (+ the GroupNorm-backward sums of the conv input), then weight gradient.  The one-block reduction of those
         # sums rides in the weight gradient's reduce launch where the family takes a job (round 6)
         # (replica rows for the sums only where the weight-gradient launch will take the reduction as a job: it reads them in that form)
-        if (self.stat_reps > 1 and rec.pre_norm and rec.norm == "g" and wgrad in ("fp32", "subpixel")
+        # (`fp32_split_wgrad`: the split launch takes no job — `_wgrad_fp32` / `_wgrad_subpixel` ask the same predicate)
+        split_w = (wgrad == "fp32" and src.t1 is None and self._split_wgrad(src.C, Cout)) or (
+            wgrad == "subpixel" and self._split_wgrad(rec.sub[0], Cout))
+        if (self.stat_reps > 1 and rec.pre_norm and rec.norm == "g" and wgrad in ("fp32", "subpixel") and not split_w
                 and nat.get_lib().u3d_conv3d_wgrad_job_supported(Nn, src.C, rec.G) == 1):
             call.greps = self.stat_reps
         dg, gst = self._launcher(1, dgrad)(call)
@@ -1437,7 +1462,7 @@ class ConvLayers:
             return lib.u3d_small_cin_bwd_workspace_floats(N, D, H, W, Cin, Cout)
         if family == "subpixel":  # skip slice (fp32 kernels) + sub-pixel slice + the slab boxes of an n -> 2n + 1 level
             boxes = slab_boxes((D, H, W), plus, 2)
-            return max([lib.u3d_wgrad_workspace_floats(N, D, H, W, sub[0], Cout),
+            return max([lib.u3d_wgrad_workspace_floats(N, D, H, W, sub[0], Cout), self._split_wgrad_ws_floats(N, D, H, W, sub[0], Cout),
                         lib.u3d_subpixel_wgrad_workspace_floats(N, D // 2, H // 2, W // 2, sub[1], Cout),
                         lib.u3d_conv3d_workspace_floats(N, D, H, W, Cout, sub[0])] +
                        [lib.u3d_wgrad_workspace_floats(N, b[3] - b[0], b[4] - b[1], b[5] - b[2], sub[1], Cout) for b in boxes])
@@ -1450,7 +1475,8 @@ class ConvLayers:
         if family == "bf16":
             return max(lib.u3d_conv3d_bf16_workspace_floats(N, D, H, W, Cout, Cin), lib.u3d_wgrad_bf16_workspace_floats(N, D, H, W, Cin, Cout))
         if family in ("fp32", "f32s"):  # (the split data gradient grows the buffer itself, `_BwdCtx.ensure_ws`)
-            return max(lib.u3d_wgrad_workspace_floats(N, D, H, W, Cin, Cout), lib.u3d_conv3d_workspace_floats(N, D, H, W, Cout, Cin))
+            return max(lib.u3d_wgrad_workspace_floats(N, D, H, W, Cin, Cout), lib.u3d_conv3d_workspace_floats(N, D, H, W, Cout, Cin),
+                       self._split_wgrad_ws_floats(N, D, H, W, Cin, Cout))
         if family == "subpixel2d_bf16":  # (`native_2d_bf16_subpixel`: the three of `subpixel2d` below on the bf16 kernels' plans)
             return max(lib.u3d_wgrad2d_bf16_workspace_floats(N, H, W, sub[0], Cout),
                        lib.u3d_subpixel2d_wgrad_bf16_workspace_floats(N, H // 2, W // 2, sub[1], Cout),
@@ -1470,6 +1496,11 @@ class ConvLayers:
             return max(need, lib.u3d_small_cin2d_bwd_workspace_floats(N, H, W, Cin, Cout))
         assert family == "conv2d", family
         return need
+
+    def _split_wgrad_ws_floats(self, N, D, H, W, Cin, Cout):
+        """the split weight gradient's plan under `fp32_split_wgrad` (0 with the key off or outside `_split_wgrad`: the extension library is
+        not loaded then)"""
+        return nat.get_ext_lib().u3d_wgrad_f32s_workspace_floats(N, D, H, W, Cin, Cout) if self._split_wgrad(Cin, Cout) else 0
 
     def _layer_ws_floats(self, N, D, H, W, Cin, Cout, small=False):
         """... by shape, of a single-source (Cin -> Cout) layer no forward has recorded yet (a checkpointed block that backward will

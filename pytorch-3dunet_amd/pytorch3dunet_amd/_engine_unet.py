@@ -67,6 +67,9 @@ class UNet3DEngine(ConvLayers):
         # into three bf16 values, six partial products per multiply accumulated in fp32 (csrc/u3d_bf16.hip, u3d_conv3d_f32s);
         # forward and data gradients only, weight gradients stay on the fp32 MFMA kernels
         self.split = model.compute_split
+        # opt-in `fp32_split_wgrad`: ... and the weight gradients inside `_split_wgrad` on the six-product kernel of the extension library
+        # (csrc/u3d_wgrad_f32s.hip, u3d_conv3d_wgrad_f32s)
+        self.split_wgrad = bool(getattr(model, "fp32_split_wgrad", False))
         self.checkpoint_encoders = model.checkpoint_encoders
         self.checkpoint_levels = model.checkpoint_levels  # None: every encoder level; k: the k highest-resolution ones
         # with activation checkpointing the tape is also RELEASED block by block during backward (ResUNetEngine.backward): a feature

@@ -128,18 +128,18 @@ for _path in PART_PATHS:
 PART_SYMBOLS = tuple(_PART_PROTOS)
 ALL_SYMBOLS = EXPORTED_SYMBOLS + PART_SYMBOLS  # every u3d_* the library exports: u3d.h's own declarations, then its parts'
 # the extension library's C-ABI (include/u3d_ext.h, a header in the form of a part: u3d.h does NOT include it): the 16-channel bf16 entry
-# points of a UNet3D (`bf16_stem`).  The core's tables above do not know these names; `call` resolves them in `get_ext_lib()`.
+# points of a UNet3D (`bf16_stem`) and the split weight gradient (`fp32_split_wgrad`).  The core's tables above do not know these names; `call` resolves them in `get_ext_lib()`.
 EXT_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "u3d_ext.h")
 EXT_LIB_PATH = os.environ.get("U3D_EXT_LIB_PATH") or os.path.join(os.path.dirname(LIB_PATH), "libu3d_ext_hip.so")
 _EXT_PROTOS = read_part(EXT_HEADER_PATH, {**_PROTOS, **_PART_PROTOS})
 EXT_SYMBOLS = tuple(_EXT_PROTOS)
-U3D_EXT_VERSION = 1  # what u3d_ext_version() of a matching libu3d_ext_hip.so returns
+U3D_EXT_VERSION = 2  # what u3d_ext_version() of a matching libu3d_ext_hip.so returns
 U3D_VERSION, U3D_OK, U3D_EINVAL, U3D_EHIP, U3D_EARCH, U3D_EWORKSPACE = (_consts[k] for k in _CONSTANTS)
 U3DSrc, U3DAdamDesc, U3DGnBwdJob, U3DPackDesc = (
     type(py, (ctypes.Structure,), {"_fields_": _structs[c], "__doc__": f"{c} of include/u3d.h"}) for c, py in _STRUCT_NAMES.items())
 
 _lib = None
-_ext_lib = None  # stays None until the first call of an extension name: a model without `bf16_stem` never loads the library
+_ext_lib = None  # stays None until the first call of an extension name: a model without `bf16_stem` / `fp32_split_wgrad` never loads the library
 _lock = threading.Lock()
 launch_count = 0  # number of native calls issued (tests assert the HIP path really ran)
 

@@ -33,6 +33,14 @@ the 32-channel rule, models without such a layer and the residual classes (which
 `checkpoint_levels` and nn.DataParallel.  Refuses an explicit fp32 / fp32_split compute_dtype, a 2-D model (that key is `native_2d_stem`)
 and `hip_graph`.
 
+`fp32_split_wgrad: true` (U3D_F32_SPLIT_WGRAD=1; the 3-D classes, implies `compute_dtype: fp32_split`, fp32-grade like it): the weight
+gradients of the 3x3x3 layers whose channel counts are both multiples of 32 — and the skip slice of a sub-pixel decoder convolution — run
+as six bf16 partial products of exactly split operands on the bf16 MFMA (u3d_conv3d_wgrad_f32s of the extension library,
+csrc/u3d_wgrad_f32s.hip) instead of the fp32 MFMA kernels; forward and data gradients are those of `fp32_split`, bit for bit.  Layers
+outside the envelope (1 -> 16, 16 -> 32), virtual-concat sources and the sub-pixel kernels' upsampled slice keep the fp32 kernels.  Composes
+with `checkpoint_encoders` / `checkpoint_levels` and nn.DataParallel.  Refuses an explicit fp32 / bf16 compute_dtype, `bf16_subpixel` and
+`bf16_stem` (they imply bf16), a 2-D model and `hip_graph`.
+
 Covered since round 2: every layer order with at most one
 GroupNorm / BatchNorm, one non-linearity and a trailing dropout, every `upsample` value the reference itself can run
 on a 3-D net, nn.DataParallel, activation checkpointing, and the opt-in compute modes `bf16` and `fp32_split`.
@@ -50,7 +58,8 @@ from .utils import get_class, number_of_features_per_level
 
 _THIS_MODULE = __name__
 __doc__ = __doc__.replace("{native_2d_keys}", native2d.TABLE)
-_OPT_IN_KEYS = ("compute_dtype", "checkpoint_encoders", "hip_graph", "activation_dtype", "checkpoint_levels", "bf16_subpixel", "bf16_stem") + native2d.NAMES
+_OPT_IN_KEYS = ("compute_dtype", "checkpoint_encoders", "hip_graph", "activation_dtype", "checkpoint_levels", "bf16_subpixel", "bf16_stem",
+                "fp32_split_wgrad") + native2d.NAMES
 
 
 def _mark_engine_stale(module, incompatible_keys):
@@ -65,7 +74,7 @@ class AbstractUNet(nn.Module):
                  num_groups=8, num_levels=4, is_segmentation=True, conv_kernel_size=3, pool_kernel_size=2,
                  conv_padding=1, conv_upscale=2, upsample="default", dropout_prob=0.1, is3d=True, compute_dtype=None,
                  checkpoint_encoders=None, hip_graph=None, activation_dtype=None, checkpoint_levels=None, bf16_subpixel=None,
-                 bf16_stem=None, **native_2d_keys):
+                 bf16_stem=None, fp32_split_wgrad=None, **native_2d_keys):
         super().__init__()
         if isinstance(f_maps, int):
             f_maps = number_of_features_per_level(f_maps, num_levels=num_levels)
@@ -152,6 +161,24 @@ class AbstractUNet(nn.Module):
                 raise ValueError(f"u3d: bf16_stem runs bf16 MFMA operands; compute_dtype {compute_dtype!r} contradicts it "
                                  "(drop one of the two keys)")
             compute_dtype = "bf16"
+        # `fp32_split_wgrad: true` / U3D_F32_SPLIT_WGRAD=1 (a 3-D model): the weight gradients of `fp32_split` on the six-product bf16 MFMA
+        # kernel of the extension library (engine: `_split_wgrad`); implies compute_dtype fp32_split.  The environment only sets the default
+        # of a 3-D model's key
+        if fp32_split_wgrad is None:
+            fp32_split_wgrad = bool(is3d) and os.environ.get("U3D_F32_SPLIT_WGRAD", "0") == "1"
+        self.fp32_split_wgrad = bool(fp32_split_wgrad)
+        if self.fp32_split_wgrad:
+            if not is3d:
+                raise ValueError("u3d: fp32_split_wgrad is a 3-D key (UNet3D, ResidualUNet3D, ResidualUNetSE3D); the native 2-D path has no "
+                                 "fp32_split mode")
+            for other in ("bf16_subpixel", "bf16_stem"):
+                if getattr(self, other):
+                    raise ValueError(f"u3d: fp32_split_wgrad runs fp32-grade split operands; {other} implies compute_dtype bf16 and "
+                                     "contradicts it (drop one of the two keys)")
+            if compute_dtype is not None and str(compute_dtype).lower() != "fp32_split":
+                raise ValueError(f"u3d: fp32_split_wgrad is the weight gradient of compute_dtype fp32_split; compute_dtype {compute_dtype!r} "
+                                 "contradicts it (drop one of the two keys)")
+            compute_dtype = "fp32_split"
         if compute_dtype is None:
             compute_dtype = ("bf16" if os.environ.get("U3D_BF16", "0") == "1"
                              else "fp32_split" if os.environ.get("U3D_F32_SPLIT", "0") == "1" else "fp32")
@@ -206,6 +233,9 @@ class AbstractUNet(nn.Module):
         if self.bf16_stem and self.hip_graph:
             raise ValueError("u3d: hip_graph is not available with bf16_stem (the captured training step has not been held to the "
                              "eager one with the 16-channel bf16 kernels); drop one of the two keys")
+        if self.fp32_split_wgrad and self.hip_graph:
+            raise ValueError("u3d: hip_graph is not available with fp32_split_wgrad (the captured training step has not been held to the "
+                             "eager one with the split weight-gradient kernel); drop one of the two keys")
         if self.keys_2d.native_2d_residual and (self.checkpoint_encoders or self.checkpoint_levels is not None):
             raise ValueError("u3d: checkpoint_encoders / checkpoint_levels are not available with native_2d_residual (the 2-D residual "
                              "executor keeps every activation); drop one of the keys")
