@@ -1,5 +1,5 @@
 /* u3d_ext.h — the C-ABI of libu3d_ext_hip.so, the extension library next to libu3d_hip.so (csrc/u3d_c16_bf16.hip,
- * csrc/u3d_wgrad_f32s.hip).
+ * csrc/u3d_wgrad_f32s.hip with its header csrc/u3d_conv2d_f32s.h).
  *
  * A header PART: declarations only — no guard, no C++ wrapper, no constants.  Include it after <u3d.h>, inside extern "C":
  *     extern "C" {
@@ -61,3 +61,48 @@ int u3d_conv3d_wgrad_f32s_supported(int Cin, int Cout);
 long long u3d_wgrad_f32s_workspace_floats(int N, int D, int H, int W, int Cin, int Cout);
 int u3d_conv3d_wgrad_f32s(int device, u3d_stream_t stream, const float* x, const float* affine, const float* dz, float* dw, int dw_cin_stride,
                           int N, int D, int H, int W, int Cin, int Cout, float* workspace, long long workspace_floats);
+/* ---- the 3x3 convolutions of a UNet2D in fp32_split (`native_2d_fp32_split: true`; csrc/u3d_conv2d_f32s.h, a header of
+ * csrc/u3d_wgrad_f32s.hip) ------
+ * The twins of u3d_conv2d_ex_reps / u3d_conv2d_wgrad with fp32-grade arithmetic on v_mfma_f32_32x32x16_bf16.  Tensors are fp32 NHWC,
+ * pointers 16-byte aligned, N * H * W < 2^31.  A source (p0, p1, ymap, xmap, C0, C1, H1, W1) is the virtual concat cat(skip,
+ * nearest(low)) of a decoder's first convolution: p0 (N,H,W,C0), channels [C0, C0 + C1) from p1 (N,H1,W1,C1) at (ymap[y], xmap[x]);
+ * p1 == NULL with C1 == 0 is a single tensor.  Virtual envelope: C0 % 32 == 0 and C1 % 32 == 0.
+ * Rounding points: every fp32 operand is split exactly into three bf16 values, h = bf16(g), m = bf16(g - h), l = bf16(g - h - m) — the
+ * weight by the pack kernel, activations and dz while staged to LDS, after the optional per-sample affine applied in fp32 as
+ * fmaf(x, a, b); zero padding applies after the affine and stays exactly 0.  The six products hh, hm, mh, hl, lh, mm run smallest class
+ * first with fp32 accumulation.  The MFMA's round-down accumulation drift is cancelled by sign alternation: forward / data gradient —
+ * the images carry (-1)^chunk and the sums are negated between 16-channel chunks; weight gradient — every 16 x 16 pixel tile's chain
+ * starts from zero and is added to the running sums, the sign of dz alternating per tile.  No split-K: workspace only in the weight gradient.
+ *   u3d_conv2d_f32s_supported                1 iff both counts > 0, contraction channels K % 16 == 0 and produced channels Nn % 32 == 0
+ *   u3d_conv2d_wgrad_f32s_supported          1 iff both counts > 0 and both % 32 == 0
+ *   u3d_packed_weight2d_f32s_elems           2-byte elements of the three images u3d_pack_weights2d_f32s writes; 0 outside the envelope
+ *   u3d_pack_weights2d_f32s                  w (Cout, Cin, 3, 3) fp32 -> three images (h | m | l of (-1)^chunk * w), each
+ *              [K / 16 chunk][9 taps][n-tile][64 lanes][8] of B[k][n]; mode 0 forward (B[k = ci][n = co] = w[co][ci][tap]), mode 1 data
+ *              gradient (B[k = co][n = ci] = w[co][ci][8 - tap])
+ *   u3d_conv2d_f32s                          out (N,H,W,Cout) = [relu](conv2d(a * src + b, w)) with the mode-0 images; affine optional,
+ *              (N, C0 + C1, 2); out_stats optional, double[stat_reps][N][Cout][2] += (sum y, sum y^2) of the stored values, a block
+ *              adding into replica row block % stat_reps
+ *   u3d_conv2d_f32s_dgrad                    dg (N,H,W,C0 + C1) = the data gradient of that layer from dz (N,H,W,Cout) with the mode-1
+ *              images (Cout % 16, C0 + C1 % 32); gstats optional, double[stat_reps][N][C0 + C1][2] += (sum dg, sum dg * gx), gx = the
+ *              layer's forward input (gx0, gx1, ymap, xmap: single or virtual, read only with gstats)
+ *   u3d_wgrad2d_f32s_workspace_floats        floats of the plan that fills the current device; one slot is 9 * Cin * Cout floats; 0 outside
+ *              the envelope
+ *   u3d_conv2d_wgrad_f32s                    dw (Cout, C0 + C1, 3, 3) = sum_v dz[v, co] * g[v + tap - 1, ci], g = fmaf(src, a, b) zero
+ *              padded; WRITTEN, not accumulated.  No atomics: every block writes its partial sums to its workspace slot and a second
+ *              kernel adds the slots in slot order — the same inputs and workspace size give the same bits.  A workspace smaller than the
+ *              size function's runs on as many splits as it holds; smaller than one slot: U3D_EINVAL.
+ * Outside the envelope, or with unaligned pointers, every launch returns U3D_EINVAL with u3d_last_error() set and launches nothing. */
+int u3d_conv2d_f32s_supported(int K, int Nn);
+int u3d_conv2d_wgrad_f32s_supported(int Cin, int Cout);
+long long u3d_packed_weight2d_f32s_elems(int Cin, int Cout, int mode);
+int u3d_pack_weights2d_f32s(int device, u3d_stream_t stream, const float* w, int Cout, int Cin, int mode, void* packed);
+int u3d_conv2d_f32s(int device, u3d_stream_t stream, const float* p0, const float* p1, const int32_t* ymap, const int32_t* xmap, int C0,
+                    int C1, int H1, int W1, const float* affine, const void* packed_w, float* out, int N, int H, int W, int Cout, int relu,
+                    double* out_stats, int stat_reps);
+int u3d_conv2d_f32s_dgrad(int device, u3d_stream_t stream, const float* dz, const void* packed_w, float* dg, int N, int H, int W, int Cout,
+                          const float* gx0, const float* gx1, const int32_t* ymap, const int32_t* xmap, int C0, int C1, int H1, int W1,
+                          double* gstats, int stat_reps);
+long long u3d_wgrad2d_f32s_workspace_floats(int N, int H, int W, int Cin, int Cout);
+int u3d_conv2d_wgrad_f32s(int device, u3d_stream_t stream, const float* p0, const float* p1, const int32_t* ymap, const int32_t* xmap,
+                          int C0, int C1, int H1, int W1, const float* affine, const float* dz, float* dw, int N, int H, int W, int Cout,
+                          float* workspace, long long workspace_floats);

@@ -1,7 +1,8 @@
 // u3d_wgrad_f32s.hip — the weight gradient of `compute_dtype: fp32_split` on the bf16 MFMA (`fp32_split_wgrad: true`): fp32-grade
 // arithmetic from six bf16 partial products, the weight-gradient twin of conv3d_f32s_kernel (csrc/u3d_bf16.hip).  The second translation
 // unit of libu3d_ext_hip.so (include/u3d_ext.h); u3d_set_err / u3d_last_error and u3d_device_guard are the core library's.
-// Self-contained like csrc/u3d_c16_bf16.hip, whose weight-gradient tiling it takes over.
+// Self-contained like csrc/u3d_c16_bf16.hip, whose weight-gradient tiling it takes over.  The unit also carries the 3x3 Conv2d kernels of
+// a UNet2D in fp32_split (`native_2d_fp32_split: true`): csrc/u3d_conv2d_f32s.h, included at the end of this file.
 //
 // dw[co][ci][tap] = sum_v dz[v][co] * g[v + tap - 1][ci], g = fmaf(x, a, b) zero padded after the affine.  Tensors are fp32 NDHWC.
 //
@@ -366,3 +367,6 @@ extern "C" int u3d_conv3d_wgrad_f32s(int device, u3d_stream_t stream, const floa
     U3D_LAUNCH_CHECK();
     return 0;
 }
+
+// the 3x3 Conv2d kernels of a UNet2D in fp32_split (`native_2d_fp32_split`): device code and entry points, on this file's helpers
+#include "u3d_conv2d_f32s.h"

@@ -417,6 +417,7 @@ class ConvRec:
     sub: Optional[tuple] = None  # (C0, C1): the upsampled half ran as a sub-pixel convolution (the `subpixel`, `subpixel2d`, `subpixel2d_bf16` rows)
     plus: tuple = (0, 0, 0)      # a sub-pixel layer: per axis 1 where its level upsamples n -> 2n + 1 (`ConvLayers._src_plus`)
     c16: bool = False            # a `conv2d_bf16` layer on the `_c16` entry points and `*_C16` images (`ConvLayers._c16`)
+    f32s: bool = False           # a `conv2d` layer on the six-product kernels of `native_2d_fp32_split` (`ConvLayers._split2d`): all three directions
     pre_norm: bool = True        # GroupNorm on the conv input ('gc…'); False: `affine` is the identity table
     post: Optional[tuple] = None  # post-norm order ('cg…'): (z = [f_inner](conv output), its GroupNorm affine table, f_inner, slope); y = f(a*z + b)
     norm: Optional[str] = "g"    # 'g' GroupNorm, 'b' BatchNorm3d (mean_rstd is (C,2)), None: conv bias (idx_gb = its index)

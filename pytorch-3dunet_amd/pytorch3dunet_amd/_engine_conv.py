@@ -1,6 +1,6 @@
 """One SingleConv / ResNetBlock convolution (reference buildingblocks.py:99-135) forward and backward on the native kernels: which
 kernel FAMILY runs a layer (first-layer small-Cin, sub-pixel decoder in fp32 or bf16, split-fp32, bf16 operands / bf16 storage, fp32 MFMA)
-is decided ONCE, in forward (`_fwd_family`), and kept in the layer's record: `ConvRec.family`, with `sub`, `plus`, `c16` beside it.  Backward maps
+is decided ONCE, in forward (`_fwd_family`), and kept in the layer's record: `ConvRec.family`, with `sub`, `plus`, `c16`, `f32s` beside it.  Backward maps
 the recorded family to its (data-gradient, weight-gradient) families in one place (`_BWD_FAMILY`; `_bwd_families` holds the few
 decisions that are backward's own), the shared scratch is sized from the same record (`_family_ws_floats`), and every launcher reads the
 record instead of asking the routing rules again — a new family is a new entry in the tables, not a new flag inside the layer code.
@@ -63,6 +63,7 @@ class _ConvCall:
     affine_hi: Optional[torch.Tensor] = None
     plus: tuple = (0, 0, 0)              # `_src_plus` of a sub-pixel layer's source
     c16: bool = False                    # a `conv2d_bf16` (`native_2d_stem`) or 3-D `bf16` (`bf16_stem`) layer on the `_c16` envelope
+    f32s: bool = False                   # a `conv2d` layer on the six-product kernels of the extension library (`_split2d`)
 
     def take_stats(self, reps: int = 1) -> Optional[StatTable]:
         return self.pool.table(self.N, self.Cout, reps) if self.stats else None
@@ -403,6 +404,29 @@ class ConvLayers:
         ws = cx.ensure_ws(nat.get_ext_lib().u3d_wgrad_f32s_workspace_floats(c.N, c.D, c.H, c.W, Cin, c.Cout))
         nat.call("u3d_conv3d_wgrad_f32s", dev.index, _stream(dev), _p(x), _p(affine), _p(c.dz), _p(dw), dw_cin_stride, c.N, c.D, c.H, c.W,
                  Cin, c.Cout, _p(ws), ws.numel(), flops=54.0 * Cin * c.Cout * c.N * c.D * c.H * c.W)
+
+    def _split2d_counts(self, C0: int, C1: int, Cout: int) -> bool:
+        """THE rule for a UNet2D under `native_2d_fp32_split`, stated once, on channel counts: a 3x3 layer of the `conv2d` family runs
+        forward, data gradient and weight gradient on the six-product kernels of the extension library (csrc/u3d_conv2d_f32s.h) when the key
+        is on and — a single source (C1 == 0) — both channel counts are multiples of 32, or — a decoder's virtual concat — C0, C1 and Cout
+        all are.  A 16 -> 32 layer, the first layer and odd counts keep the fp32 `conv2d` kernels.  Asked by `_split2d` (forward; backward
+        reads the record's `f32s`), `_split2d_weights` (which weights get F32S_*2D instead of FWD2D / DGRAD2D images) and
+        `_layer_ws_floats`; with the key off the extension library is not loaded."""
+        if not self.split2d or Cout <= 0 or Cout % 32 != 0 or C0 <= 0 or C0 % 32 != 0:
+            return False
+        return C1 == 0 or (C1 > 0 and C1 % 32 == 0)
+
+    def _split2d(self, src: VSrc, Cout: int) -> bool:
+        """`_split2d_counts` for a layer about to run on `src`, whose tensors must be fp32 (every activation of a 2-D net is)"""
+        return bool(self.split2d) and src.t0.dtype == _F32 and (src.t1 is None or src.t1.dtype == _F32) and \
+            self._split2d_counts(src.C0, src.C1, Cout)
+
+    @staticmethod
+    def _f32s_src(src: VSrc):
+        """the flat source arguments of the u3d_conv2d_*_f32s entry points: (p0, p1, ymap, xmap, C0, C1, H1, W1)"""
+        if src.t1 is None:
+            return _p(src.t0), None, None, None, src.C0, 0, 0, 0
+        return _p(src.t0), _p(src.t1), _p(src.maps[1]), _p(src.maps[2]), src.C0, src.C1, src.H1, src.W1
 
     def _convtr_t8(self, Cl: int, Cs: int) -> bool:
         """the transposed convolution and its gradients run in space-to-depth form on the bf16 MFMA kernels"""
@@ -749,6 +773,13 @@ class ConvLayers:
         # fp32 MFMA 3x3 implicit GEMM on the D = 1 tensors (virtual concat, fused affine, ReLU and statistics as the 3-D kernels);
         # with a residual (ResidualUNet2D's conv3): out = [relu](conv + residual) in the epilogue (u3d_conv2d_res_reps)
         assert c.D == 1
+        if c.f32s:  # (`native_2d_fp32_split`, `_split2d`: six bf16 products of split operands, csrc/u3d_conv2d_f32s.h; no split-K scratch)
+            assert c.residual is None
+            wp = self.images.get(c.conv.weight, Kind.F32S_FWD2D, c.dev)
+            ystats = c.take_stats(self.stat_reps)
+            nat.call("u3d_conv2d_f32s", c.dev.index, _stream(c.dev), *self._f32s_src(c.src), _p(c.affine), _p(wp), _p(c.y), c.N, c.H, c.W,
+                     c.Cout, c.relu, *_tab(ystats), flops=18.0 * c.Ctot * c.Cout * c.N * c.H * c.W)
+            return ystats
         wp = self.images.get(c.conv.weight, Kind.FWD2D, c.dev)
         ystats = c.take_stats(self.stat_reps)
         s = c.src.struct(c.affine)
@@ -862,6 +893,7 @@ class ConvLayers:
                          sub, b16, *(split[1:] if split is not None else (None, None)), plus)
         family = self._fwd_family(call, residual)
         call.c16 = family in ("conv2d_bf16", "bf16") and self._c16(Ctot, Cout)
+        call.f32s = family == "conv2d" and residual is None and self._split2d(src, Cout)
         dmod = getattr(sc, "dropout", None) if spec.drop == "d" else (getattr(sc, "dropout2d", None) if spec.drop == "D" else None)
         rec = None
         if tape is not None:
@@ -869,7 +901,7 @@ class ConvLayers:
             rec = ConvRec(name=name, src=src, affine=affine, mean_rstd=mean_rstd, y=y, gn_w=gn.weight if gn is not None else None,
                           conv_w=conv.weight, G=G, idx_gw=self._pindex[id(gn.weight)] if gn is not None else -1,
                           idx_gb=self._pindex[id(gn.bias)] if gn is not None else self._pindex[id(conv.bias)],
-                          idx_w=self._pindex[id(conv.weight)], family=family, sub=pair, plus=plus, c16=call.c16, pre_norm=not post,
+                          idx_w=self._pindex[id(conv.weight)], family=family, sub=pair, plus=plus, c16=call.c16, f32s=call.f32s, pre_norm=not post,
                           norm=spec.norm, bn_training=bn_training, affine_lo=call.affine_lo, affine_hi=call.affine_hi)
             tape.convs.append(rec)
         # record_only (recomputation under activation checkpointing, the block's LAST convolution): y_out still holds this layer's final
@@ -1146,15 +1178,25 @@ class ConvLayers:
     def _wgrad_conv2d(self, c: "_BwdCall"):
         # (takes no GroupNorm-backward job: c.job stays set and _conv_bwd runs the reduction on its own)
         cx, dev, src, rec, ws = c.cx, c.cx.dev, c.src, c.rec, c.cx.ws
+        if rec.f32s:  # (`_split2d`, read off the record: slots added in slot order, no atomics; takes no job either)
+            ws = cx.ensure_ws(nat.get_ext_lib().u3d_wgrad2d_f32s_workspace_floats(c.N, c.H, c.W, src.C, c.Cout))
+            nat.call("u3d_conv2d_wgrad_f32s", dev.index, _stream(dev), *self._f32s_src(src), _p(rec.affine), _p(c.dz),
+                     _p(cx.gview(rec.idx_w)), c.N, c.H, c.W, c.Cout, _p(ws), ws.numel(), flops=18.0 * src.C * c.Cout * c.N * c.H * c.W)
+            return
         s_aff = src.struct(rec.affine)
         nat.call("u3d_conv2d_wgrad", dev.index, _stream(dev), ctypes.byref(s_aff), _p(c.dz), _p(cx.gview(rec.idx_w)), c.N, c.H, c.W,
                  c.Cout, _p(ws), ws.numel(), flops=18.0 * src.C * c.Cout * c.N * c.H * c.W)
 
     def _dgrad_conv2d(self, c: "_BwdCall"):
         cx, dev, src, rec, ws = c.cx, c.cx.dev, c.src, c.rec, c.cx.ws
-        wpd = self.images.get(rec.conv_w, Kind.DGRAD2D, dev)
         dg = _empty((c.N, c.D, c.H, c.W, src.C), dtype=_F32, device=dev)
         gst = cx.pool.table(c.N, src.C, c.greps)
+        if rec.f32s:  # (`_split2d`, read off the record: the mode-1 images, gx the layer's — single or virtual — forward input)
+            wpd = self.images.get(rec.conv_w, Kind.F32S_DGRAD2D, dev)
+            nat.call("u3d_conv2d_f32s_dgrad", dev.index, _stream(dev), _p(c.dz), _p(wpd), _p(dg), c.N, c.H, c.W, c.Cout,
+                     *self._f32s_src(src), _p(gst.t), gst.reps, flops=18.0 * src.C * c.Cout * c.N * c.H * c.W)
+            return dg, (gst, None)
+        wpd = self.images.get(rec.conv_w, Kind.DGRAD2D, dev)
         s_dz = VSrc(c.dz).struct()
         s_x = src.struct()
         nat.call("u3d_conv2d_ex_reps", dev.index, _stream(dev), ctypes.byref(s_dz), _p(wpd), _p(dg), c.N, c.H, c.W, src.C, 0, None,
@@ -1454,10 +1496,12 @@ class ConvLayers:
     def _wgrad_workspace(self, tape, dev):
         return _empty(max(self._wgrad_workspace_floats(tape.convs), 4), dtype=_F32, device=dev)
 
-    def _family_ws_floats(self, family, N, D, H, W, Cin, Cout, sub=None, plus=(0, 0, 0), c16=False):
+    def _family_ws_floats(self, family, N, D, H, W, Cin, Cout, sub=None, plus=(0, 0, 0), c16=False, f32s=False):
         """scratch floats the backward of one layer of forward family `family` needs from the shared buffer: its weight gradient + its
-        data gradient's split-K scratch (roles swapped); `sub`, `plus`, `c16` as the layer's record holds them"""
+        data gradient's split-K scratch (roles swapped); `sub`, `plus`, `c16`, `f32s` as the layer's record holds them"""
         lib = nat.get_lib()
+        if family == "conv2d" and f32s:  # (`native_2d_fp32_split`: the extension library's plan; its convolutions never split)
+            return nat.get_ext_lib().u3d_wgrad2d_f32s_workspace_floats(N, H, W, Cin, Cout)
         if family == "small":
             return lib.u3d_small_cin_bwd_workspace_floats(N, D, H, W, Cin, Cout)
         if family == "subpixel":  # skip slice (fp32 kernels) + sub-pixel slice + the slab boxes of an n -> 2n + 1 level
@@ -1509,9 +1553,10 @@ class ConvLayers:
             family = "small2d" if small else ("conv2d_bf16" if self._bf16_routed_weight(Cin, Cout, False) else "conv2d")
         else:
             family = "small" if small else ("bf16" if self._bf16_routed_weight(Cin, Cout, False) else "fp32")
-        return self._family_ws_floats(family, N, D, H, W, Cin, Cout, c16=family in ("conv2d_bf16", "bf16") and self._c16(Cin, Cout))
+        return self._family_ws_floats(family, N, D, H, W, Cin, Cout, c16=family in ("conv2d_bf16", "bf16") and self._c16(Cin, Cout),
+                                      f32s=family == "conv2d" and self._split2d_counts(Cin, 0, Cout))
 
     def _wgrad_workspace_floats(self, convs):
         """scratch floats the backward kernels of these recorded layers need (one shared buffer, sized once per backward)"""
-        return int(max((self._family_ws_floats(r.family, r.src.N, r.src.D, r.src.H, r.src.W, r.src.C, r.y.shape[-1], r.sub, r.plus, r.c16)
+        return int(max((self._family_ws_floats(r.family, r.src.N, r.src.D, r.src.H, r.src.W, r.src.C, r.y.shape[-1], r.sub, r.plus, r.c16, r.f32s)
                         for r in convs), default=0))

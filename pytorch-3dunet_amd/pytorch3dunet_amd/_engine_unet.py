@@ -66,7 +66,12 @@ class UNet3DEngine(ConvLayers):
         # opt-in `compute_dtype: fp32_split`: FP32-grade convolutions on the bf16 matrix pipe — every fp32 operand split exactly
         # into three bf16 values, six partial products per multiply accumulated in fp32 (csrc/u3d_bf16.hip, u3d_conv3d_f32s);
         # forward and data gradients only, weight gradients stay on the fp32 MFMA kernels
-        self.split = model.compute_split
+        # (a 2-D net reaches fp32_split only through `native_2d_fp32_split`, whose flag is `split2d`: the 3-D image packing and the
+        # `_split_fwd` paths stay off)
+        self.split = model.compute_split and not self.is2d
+        # opt-in `native_2d_fp32_split`: the 3x3 layers of a UNet2D inside `_split2d` on the six-product Conv2d kernels of the extension
+        # library (csrc/u3d_conv2d_f32s.h: u3d_conv2d_f32s, u3d_conv2d_f32s_dgrad, u3d_conv2d_wgrad_f32s), all three directions
+        self.split2d = keys.native_2d_fp32_split
         # opt-in `fp32_split_wgrad`: ... and the weight gradients inside `_split_wgrad` on the six-product kernel of the extension library
         # (csrc/u3d_wgrad_f32s.hip, u3d_conv3d_wgrad_f32s)
         self.split_wgrad = bool(getattr(model, "fp32_split_wgrad", False))
@@ -146,7 +151,8 @@ class UNet3DEngine(ConvLayers):
             # (a small-family layer reads the reference layout: no image up front; a data-gradient fall-through packs its own on demand)
             small = {id(w) for w in ws if self._small2d(w.shape[1], w.shape[0], id(w) in self._virtual_w)}
             c16 = {id(w) for w in ws if id(w) in bf16 and self._c16(w.shape[1], w.shape[0])}  # (stem layers: the `*_C16` images)
-            return WeightImages(each=[w for w in ws if id(w) not in bf16 | small], each_bf16=[w for w in ws if id(w) in bf16 - c16],
+            f32s = self._split2d_weights()  # (`native_2d_fp32_split`: the routed layers read F32S_*2D images, packed when first asked for)
+            return WeightImages(each=[w for w in ws if id(w) not in bf16 | small | f32s], each_bf16=[w for w in ws if id(w) in bf16 - c16],
                                 each_bf16_c16=[w for w in ws if id(w) in c16])
         bf16 = {id(w) for w in ws if self._bf16_routed_weight(w.shape[1], w.shape[0], id(w) in self._virtual_w)}
         # (`bf16_stem`: the 16-channel layers' BF16_*_C16 images, one launch per weight and image, not in the batch pack launch)
@@ -156,6 +162,22 @@ class UNet3DEngine(ConvLayers):
             f32=[w for w in ws if id(w) not in bf16 and not (self.small_cin and w.shape[1] <= 4 and w.shape[0] <= 32)],
             bf16=[w for w in ws if id(w) in bf16 - c16], t8=self._t8_weights() if self.bf16 else (),
             each_bf16_c16=[w for w in ws if id(w) in c16], c16_kinds=(Kind.BF16_FWD_C16, Kind.BF16_DGRAD_C16))
+
+    def _split2d_weights(self) -> set:
+        """ids of the conv weights `_split2d` routes (`native_2d_fp32_split`; empty with the key off): from the layer table, a decoder's
+        first convolution with its skip / upsampled channel counts"""
+        if not self.split2d:
+            return set()
+        out = set()
+        for _, c1, c2 in self.enc:
+            out |= {id(c.conv.weight) for c in (c1, c2) if self._split2d_counts(c.conv.in_channels, 0, c.conv.out_channels)}
+        skips = [c2.conv.out_channels for _, _, c2 in self.enc][:-1][::-1]
+        for (c1, c2), C0 in zip(self.dec, skips):
+            if self._split2d_counts(C0, c1.conv.in_channels - C0, c1.conv.out_channels):
+                out.add(id(c1.conv.weight))
+            if self._split2d_counts(c2.conv.in_channels, 0, c2.conv.out_channels):
+                out.add(id(c2.conv.weight))
+        return out
 
     def _t8_weights(self) -> list:
         """ConvTranspose3d weights whose forward / data gradient may run in space-to-depth form (`_convtr_t8`)"""

@@ -49,6 +49,8 @@ class Kind(enum.IntEnum):
     BF16_DGRAD2D = enum.auto()
     BF16_FWD2D_C16 = enum.auto()    # ... the 16-channel stem layers among them (`native_2d_stem`): half n-tiles stored whole, zero upper columns
     BF16_DGRAD2D_C16 = enum.auto()
+    F32S_FWD2D = enum.auto()        # ... of a UNet2D in fp32_split (`native_2d_fp32_split`): three bf16 images of the layers `_split2d` routes,
+    F32S_DGRAD2D = enum.auto()      # written by the extension library (u3d_pack_weights2d_f32s)
     BF16_FWD_C16 = enum.auto()      # the 16-channel 3x3x3 layers of a UNet3D in bf16 (`bf16_stem`): images of the extension library's kernels
     BF16_DGRAD_C16 = enum.auto()
     CONVTR2D_BF16_FWD = enum.auto()    # ConvTranspose2d on the bf16 kernels (`native_2d_residual_bf16_deconv`): B[ci][co] per tap ...
@@ -91,6 +93,7 @@ _tr2d = lambda lib, ci, co, m: lib.u3d_convtr2d_packed_floats(ci, co)  # noqa: E
 _2db = lambda lib, ci, co, m: lib.u3d_packed_weight2d_bf16_elems(ci, co, m)  # noqa: E731
 _2db16 = lambda lib, ci, co, m: lib.u3d_packed_weight2d_bf16_c16_elems(ci, co, m)  # noqa: E731
 _3db16 = lambda lib, ci, co, m: nat.get_ext_lib().u3d_packed_weight_bf16_c16_elems(ci, co, m)  # noqa: E731  (include/u3d_ext.h)
+_2df32s = lambda lib, ci, co, m: nat.get_ext_lib().u3d_packed_weight2d_f32s_elems(ci, co, m)  # noqa: E731  (include/u3d_ext.h)
 _tr2db = lambda lib, ci, co, m: lib.u3d_packed_convtr2d_bf16_elems(ci, co, m)  # noqa: E731
 _up2db = lambda lib, ci, co, m: lib.u3d_subpixel2d_bf16_packed_elems(ci, co, m)  # noqa: E731
 _up3db = lambda lib, ci, co, m: lib.u3d_subpixel_bf16_packed_elems(ci, co, m)  # noqa: E731
@@ -123,6 +126,8 @@ _KINDS = {
     Kind.BF16_DGRAD2D: _Spec(_2db, _BF16, "u3d_pack_weights2d_bf16", 1),
     Kind.BF16_FWD2D_C16: _Spec(_2db16, _BF16, "u3d_pack_weights2d_bf16_c16", 0),
     Kind.BF16_DGRAD2D_C16: _Spec(_2db16, _BF16, "u3d_pack_weights2d_bf16_c16", 1),
+    Kind.F32S_FWD2D: _Spec(_2df32s, _BF16, "u3d_pack_weights2d_f32s", 0),
+    Kind.F32S_DGRAD2D: _Spec(_2df32s, _BF16, "u3d_pack_weights2d_f32s", 1),
     Kind.BF16_FWD_C16: _Spec(_3db16, _BF16, "u3d_pack_weights_bf16_c16", 0),
     Kind.BF16_DGRAD_C16: _Spec(_3db16, _BF16, "u3d_pack_weights_bf16_c16", 1),
     Kind.CONVTR2D_BF16_FWD: _Spec(_tr2db, _BF16, "u3d_pack_convtr2d_bf16", 0, transposed=True),

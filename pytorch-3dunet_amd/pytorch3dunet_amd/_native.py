@@ -128,7 +128,8 @@ for _path in PART_PATHS:
 PART_SYMBOLS = tuple(_PART_PROTOS)
 ALL_SYMBOLS = EXPORTED_SYMBOLS + PART_SYMBOLS  # every u3d_* the library exports: u3d.h's own declarations, then its parts'
 # the extension library's C-ABI (include/u3d_ext.h, a header in the form of a part: u3d.h does NOT include it): the 16-channel bf16 entry
-# points of a UNet3D (`bf16_stem`) and the split weight gradient (`fp32_split_wgrad`).  The core's tables above do not know these names; `call` resolves them in `get_ext_lib()`.
+# points of a UNet3D (`bf16_stem`), the split weight gradient (`fp32_split_wgrad`) and the 3x3 convolutions of a UNet2D in fp32_split
+# (`native_2d_fp32_split`).  The core's tables above do not know these names; `call` resolves them in `get_ext_lib()`.
 EXT_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "u3d_ext.h")
 EXT_LIB_PATH = os.environ.get("U3D_EXT_LIB_PATH") or os.path.join(os.path.dirname(LIB_PATH), "libu3d_ext_hip.so")
 _EXT_PROTOS = read_part(EXT_HEADER_PATH, {**_PROTOS, **_PART_PROTOS})
@@ -139,7 +140,7 @@ U3DSrc, U3DAdamDesc, U3DGnBwdJob, U3DPackDesc = (
     type(py, (ctypes.Structure,), {"_fields_": _structs[c], "__doc__": f"{c} of include/u3d.h"}) for c, py in _STRUCT_NAMES.items())
 
 _lib = None
-_ext_lib = None  # stays None until the first call of an extension name: a model without `bf16_stem` / `fp32_split_wgrad` never loads the library
+_ext_lib = None  # stays None until the first call of an extension name: a model without `bf16_stem` / `fp32_split_wgrad` / `native_2d_fp32_split` never loads the library
 _lock = threading.Lock()
 launch_count = 0  # number of native calls issued (tests assert the HIP path really ran)
 
@@ -198,7 +199,10 @@ def get_ext_lib():
             )
         lib = ctypes.CDLL(EXT_LIB_PATH)
         for name, (res, args) in _EXT_PROTOS.items():
-            fn = getattr(lib, name)  # AttributeError if a declared symbol is missing
+            fn = getattr(lib, name, None)
+            if fn is None:  # (a library from before include/u3d_ext.h gained the name: its version alone would not say so)
+                raise U3DError(f"libu3d_ext_hip.so does not export {name}, which include/u3d_ext.h declares: rebuild it "
+                               "with `python -c 'import __graft_entry__ as g; g.build()'`")
             fn.restype = res
             fn.argtypes = args
         if lib.u3d_ext_version() != U3D_EXT_VERSION:

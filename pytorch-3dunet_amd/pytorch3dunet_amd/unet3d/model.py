@@ -105,7 +105,8 @@ class AbstractUNet(nn.Module):
             if basic_module is not DoubleConv and not self.keys_2d.native_2d_residual:
                 reasons.append(f"2-D model with {basic_module.__name__} (native_2d covers DoubleConv blocks; a ResidualUNet2D needs "
                                "native_2d_residual: true)")
-            if not (self.keys_2d.native_2d_bf16 or self.keys_2d.native_2d_residual_bf16) and (compute_dtype not in (None, "fp32", "float32") or
+            if not (self.keys_2d.native_2d_bf16 or self.keys_2d.native_2d_residual_bf16 or self.keys_2d.native_2d_fp32_split) and (
+                    compute_dtype not in (None, "fp32", "float32") or
                     os.environ.get("U3D_BF16", "0") == "1" or os.environ.get("U3D_F32_SPLIT", "0") == "1"):
                 reasons.append(f"2-D model with compute_dtype {compute_dtype!r} (native_2d is fp32; a UNet2D in bf16 needs "
                                "native_2d_bf16: true, a ResidualUNet2D native_2d_residual_bf16: true)")
@@ -169,8 +170,8 @@ class AbstractUNet(nn.Module):
         self.fp32_split_wgrad = bool(fp32_split_wgrad)
         if self.fp32_split_wgrad:
             if not is3d:
-                raise ValueError("u3d: fp32_split_wgrad is a 3-D key (UNet3D, ResidualUNet3D, ResidualUNetSE3D); the native 2-D path has no "
-                                 "fp32_split mode")
+                raise ValueError("u3d: fp32_split_wgrad is a 3-D key (UNet3D, ResidualUNet3D, ResidualUNetSE3D); a UNet2D takes "
+                                 "native_2d_fp32_split: true")
             for other in ("bf16_subpixel", "bf16_stem"):
                 if getattr(self, other):
                     raise ValueError(f"u3d: fp32_split_wgrad runs fp32-grade split operands; {other} implies compute_dtype bf16 and "

@@ -3,7 +3,8 @@
 A 2-D model stays outside the native executor unless a key is set in the YAML's model section (`key: true`) or its environment
 variable is "1" (the variable is the key's DEFAULT: an explicit `key: false` beats it).  A key means something only to the 2-D class
 built from its block type; every other class ignores it entirely, a contradicting compute_dtype next to it included.  A fp32 key next
-to compute_dtype bf16 WITHOUT the bf16 key of its class stays on the warning path.
+to compute_dtype bf16 WITHOUT the bf16 key of its class stays on the warning path (and next to compute_dtype fp32_split without
+`native_2d_fp32_split`).  Two keys that force different precisions contradict each other.
 
 A new key is one row of KEYS (and one kernel-family entry in _engine_conv.py); `unet3d.model` derives its keyword list from the rows."""
 import dataclasses
@@ -45,14 +46,18 @@ KEYS = (
         "also the levels that upsample n -> 2n + 1 along H and / or W: the same kernels on a shifted window + 3x3 box launches on the 2-pixel slab"),
     Key("native_2d_subpixel", "U3D_NATIVE_2D_SUBPIXEL", DoubleConv, "native_2d", None, ("native_2d_bf16", "the fp32 sub-pixel decoder path"),
         "u3d_subpix2d.hip", "the upsampled half of a decoder's first convolution at an exact-2x level as four 2x2 convolutions; no bf16 form"),
+    Key("native_2d_fp32_split", "U3D_NATIVE_2D_FP32_SPLIT", DoubleConv, "native_2d", "fp32_split",
+        ("native_2d_subpixel", "the fp32_split 2-D path, which has no sub-pixel kernels"), "u3d_conv2d_f32s.h",
+        "the 3x3 layers with all channel counts % 32 (a decoder's virtual concat: both halves) on six bf16 MFMA products of exactly "
+        "split fp32 operands, all three directions, fp32-grade; everything else stays on the fp32 kernels"),
     Key("native_2d", "U3D_NATIVE_2D", None, None, None, None, "u3d_conv2d.hip",
         "a fp32 UNet2D with nearest upsampling on the DoubleConv executor at D = 1"),
 )
 _BY_NAME = {k.name: k for k in KEYS}
 NAMES = tuple(k.name for k in KEYS)
-_DTYPE_NAMES = {"bf16": ("bf16", "bfloat16")}  # how compute_dtype may spell a row's precision
+_DTYPE_NAMES = {"bf16": ("bf16", "bfloat16"), "fp32_split": ("fp32_split",)}  # how compute_dtype may spell a row's precision
 _CLASS = {DoubleConv: "UNet2D", ResNetBlock: "ResidualUNet2D", None: "any 2-D class"}
-_ROW = "  {:<30}  {:<34}  {:<14}  {:<23}  {:<9}  {}"
+_ROW = "  {:<30}  {:<34}  {:<14}  {:<23}  {:<10}  {}"
 TABLE = "\n".join([_ROW.format("key", "variable", "class", "implies", "precision", "kernels (csrc/)")] +
                   [_ROW.format(k.name, k.env, _CLASS[k.block], k.implies or "-", k.precision or "-", k.kernels) for k in KEYS] +
                   [""] + [f"  {k.name}: {k.does}" for k in KEYS])
@@ -78,6 +83,11 @@ def resolve(values: dict, is3d: bool, basic_module: type, compute_dtype):
         if (bool(v) or k.name in implied) and not is3d and k.block in (None, basic_module):
             on.append(k)
             implied.add(k.implies)
+    forced = [k for k in on if k.precision is not None]
+    for k in forced[1:]:  # (two keys that force different precisions: named as such, before either meets the other's compute_dtype)
+        if k.precision != forced[0].precision:
+            raise ValueError(f"u3d: {forced[0].name} runs {forced[0].precision} operands and {k.name} runs {k.precision} operands — drop "
+                             "one of the two keys")
     for k in on:  # (a refusing key stands after the keys it refuses: a precision contradiction comes first)
         if k.precision is not None:
             if compute_dtype is not None and str(compute_dtype).lower() not in _DTYPE_NAMES[k.precision]:

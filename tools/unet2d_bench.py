@@ -54,7 +54,15 @@ shifted window, the 2-pixel slab on box launches of csrc/u3d_conv2d.hip).  The r
 `native_2d_subpixel` arm of the same run and the verdict against the same bar (more than 5 % faster than that arm), the levels it took, the
 FLOPs it executes, its convolution launches by entry point and torch.cuda.max_memory_allocated over one step of every fp32 arm.
 
-  python tools/unet2d_bench.py [--configs confocal,dsb2018] [--batch N] [--steps 10] [--warmup 3] [--bf16] [--stem] [--vcat] [--bf16-subpixel] [--subpixel] [--subpixel-plus]   (--batch: every config's own default)"""
+With --fp32-split (UNet2D configurations) the alternation gains the arm `native_2d_fp32_split: true` (the 3x3 layers with all channel counts
+% 32 on the six-product bf16 MFMA kernels of csrc/u3d_conv2d_f32s.h, fp32 grade) and, next to --stem, the same with `native_2d_stem`.  The
+record adds the arm's ms per step of every round with its median and range next to the `native_2d` arm's, whether the two ranges are
+disjoint, the speed-up of the medians and the verdict against the project's bar for a speed mode (more than 5 % faster than the
+`native_2d` arm of the same run), the new entry points per call next to the fp32 launches they replace (difference of the two arms'
+totals), peak memory of one step per arm, and the three launches of ONE full-resolution 32 -> 32 layer on the new kernels against the
+three fp32 launches they replace (HIP events around each launch, median of 5, same process).
+
+  python tools/unet2d_bench.py [--configs confocal,dsb2018] [--fp32-split] [--batch N] [--steps 10] [--warmup 3] [--bf16] [--stem] [--vcat] [--bf16-subpixel] [--subpixel] [--subpixel-plus]   (--batch: every config's own default)"""
 import argparse
 import json
 import os
@@ -150,7 +158,9 @@ def make(cfg, native, dev):
 
     torch.manual_seed(0)
     extra = {}
-    if native == "subpixel":
+    if native in ("f32s", "f32s_stem"):
+        extra, native = dict(native_2d_fp32_split=True, **(dict(native_2d_stem=True) if native == "f32s_stem" else {})), True
+    elif native == "subpixel":
         extra, native = dict(native_2d_subpixel=True), True
     elif native == "subpixel_plus":
         extra, native = dict(native_2d_subpixel_plus=True), True
@@ -189,6 +199,66 @@ def timed(model, opt, x, target, loss_fn, steps):
     return st.elapsed_time(en) / steps
 
 
+def layer_times_f32s(batch, hw, C=32, reps=5):
+    """ms of the three launches of one (C -> C) 3x3 layer at (batch, H, W) on the six-product kernels and on the fp32 kernels they
+    replace: HIP events around each launch, median of `reps` after one warm-up launch"""
+    import ctypes
+    import statistics
+
+    from pytorch3dunet_amd import _native as nat
+    from pytorch3dunet_amd.engine import VSrc, _p, _stream
+
+    dev = torch.device("cuda", 0)
+    lib, ext, st = nat.get_lib(), nat.get_ext_lib(), _stream(dev)
+    H, W = hw
+    g = torch.Generator().manual_seed(2)
+    x = torch.randn((batch, 1, H, W, C), generator=g).to(dev)
+    dz = torch.randn((batch, 1, H, W, C), generator=g).to(dev)
+    w = (torch.randn((C, C, 3, 3), generator=g) / (9 * C) ** 0.5).to(dev)
+    aff = torch.stack((1.0 + 0.1 * torch.randn(batch, C, generator=g), 0.1 * torch.randn(batch, C, generator=g)), dim=-1).contiguous().to(dev)
+    y, dw = torch.empty_like(x), torch.empty_like(w)
+    stats = torch.zeros(8 * batch * C * 2, dtype=torch.float64, device=dev)
+    img = {}
+    for mode in (0, 1):
+        img["s", mode] = torch.empty(ext.u3d_packed_weight2d_f32s_elems(C, C, mode), dtype=torch.bfloat16, device=dev)
+        nat.call("u3d_pack_weights2d_f32s", 0, st, _p(w), C, C, mode, _p(img["s", mode]))
+        img["f", mode] = torch.empty(lib.u3d_packed_weight2d_floats(C, C, mode), dtype=torch.float32, device=dev)
+        nat.call("u3d_pack_weights2d", 0, st, _p(w), C, C, mode, _p(img["f", mode]))
+    need = max(ext.u3d_wgrad2d_f32s_workspace_floats(batch, H, W, C, C), lib.u3d_wgrad2d_workspace_floats(batch, H, W, C, C),
+               lib.u3d_conv2d_workspace_floats(batch, H, W, C, C), 4)
+    ws = torch.empty(need, dtype=torch.float32, device=dev)
+    sx, sdz, sgx = VSrc(x).struct(aff), VSrc(dz).struct(), VSrc(x).struct()
+    single = (None, None, None, C, 0, 0, 0)
+    launches = {
+        "u3d_conv2d_f32s": lambda: nat.call("u3d_conv2d_f32s", 0, st, _p(x), *single, _p(aff), _p(img["s", 0]), _p(y), batch, H, W, C, 1,
+                                            _p(stats), 8),
+        "u3d_conv2d_f32s_dgrad": lambda: nat.call("u3d_conv2d_f32s_dgrad", 0, st, _p(dz), _p(img["s", 1]), _p(y), batch, H, W, C, _p(x),
+                                                  *single, _p(stats), 8),
+        "u3d_conv2d_wgrad_f32s": lambda: nat.call("u3d_conv2d_wgrad_f32s", 0, st, _p(x), *single, _p(aff), _p(dz), _p(dw), batch, H, W, C,
+                                                  _p(ws), ws.numel()),
+        "u3d_conv2d_ex_reps (forward)": lambda: nat.call("u3d_conv2d_ex_reps", 0, st, ctypes.byref(sx), _p(img["f", 0]), _p(y), batch, H, W,
+                                                         C, 1, _p(stats), None, None, _p(ws), ws.numel(), 8),
+        "u3d_conv2d_ex_reps (data gradient)": lambda: nat.call("u3d_conv2d_ex_reps", 0, st, ctypes.byref(sdz), _p(img["f", 1]), _p(y), batch,
+                                                               H, W, C, 0, None, ctypes.byref(sgx), _p(stats), _p(ws), ws.numel(), 8),
+        "u3d_conv2d_wgrad": lambda: nat.call("u3d_conv2d_wgrad", 0, st, ctypes.byref(sx), _p(dz), _p(dw), batch, H, W, C, _p(ws), ws.numel()),
+    }
+    out = {}
+    for name, fn in launches.items():
+        fn()
+        torch.cuda.synchronize()
+        ts = []
+        for _ in range(reps):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            torch.cuda.synchronize()
+            ts.append(a.elapsed_time(b))
+        out[name] = {"ms_median": round(statistics.median(ts), 4), "ms_range": [round(min(ts), 4), round(max(ts), 4)],
+                     "tflops_executed": round(18.0 * C * C * batch * H * W / statistics.median(ts) / 1e9, 2)}
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--configs", default="confocal,dsb2018")
@@ -203,6 +273,7 @@ def main():
     ap.add_argument("--bf16-subpixel", action="store_true", help="with --bf16 --stem --vcat: also time the UNet2D step with native_2d_bf16_subpixel on top of them")
     ap.add_argument("--subpixel", action="store_true", help="also time the UNet2D step with native_2d_subpixel next to native_2d")
     ap.add_argument("--subpixel-plus", action="store_true", help="also time the UNet2D step with native_2d_subpixel_plus (next to --subpixel)")
+    ap.add_argument("--fp32-split", action="store_true", help="also time the UNet2D step with native_2d_fp32_split next to native_2d (and, with --stem, with native_2d_stem)")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "unet2d_bench measures on the GPU"
     from pytorch3dunet_amd import _native as nat
@@ -230,6 +301,10 @@ def main():
                     paths.insert(paths.index("bf16_stem") + 1, "bf16_stem_vcat")
                     if a.bf16_subpixel:
                         paths.insert(paths.index("bf16_stem_vcat") + 1, "bf16_stem_vcat_subpixel")
+        if a.fp32_split and not _residual(cfg):
+            paths.insert(1, "f32s")
+            if a.stem:
+                paths.insert(2, "f32s_stem")
         if a.subpixel_plus and not _residual(cfg):
             paths.insert(1, "subpixel_plus")
         if a.subpixel and not _residual(cfg):
@@ -293,6 +368,39 @@ def main():
             return {k: {"calls": v["calls"], "ms": round(v["ms"], 3), "tflops_executed": round(v["flops"] / v["ms"] / 1e9, 2) if v["ms"] else None}
                     for k, v in d.items()}
 
+        if "f32s" in ms:
+            # the fp32_split arm(s) against the native_2d arm of the same run: every round's ms, medians and ranges; the new entry points
+            # per call and the fp32 launches they replace (difference of the two arms' totals); peak memory; one full-resolution layer
+            import statistics
+
+            def f32s_peak(path):
+                torch.cuda.synchronize()
+                torch.cuda.reset_peak_memory_stats(dev)
+                step(*runs[path], x, target, loss_fn)
+                torch.cuda.synchronize()
+                return torch.cuda.max_memory_allocated(dev)
+
+            def spread(v):
+                return {"median": round(statistics.median(v), 3), "range": [round(min(v), 3), round(max(v), 3)]}
+
+            base_med = statistics.median(ms[True])
+            rec.update(native_ms=spread(ms[True]), fp32_split_bar="more than 1.05x the native_2d arm of the same run (medians)")
+            for arm in [p for p in ("f32s", "f32s_stem") if p in ms]:
+                afam = family_step(arm)
+                new = {k: v for k, v in afam.items() if "f32s" in k}
+                old = {k: {"calls": fam[k]["calls"] - afam.get(k, {"calls": 0})["calls"],
+                           "ms": round(fam[k]["ms"] - afam.get(k, {"ms": 0.0})["ms"], 3)}
+                       for k in ("u3d_conv2d_ex_reps", "u3d_conv2d_wgrad") if k in fam}
+                ratio = base_med / statistics.median(ms[arm])
+                key = "fp32_split" if arm == "f32s" else "fp32_split_stem"
+                rec.update({f"{key}_ms_per_step": [round(v, 3) for v in ms[arm]], f"{key}_ms": spread(ms[arm]),
+                            f"{key}_images_per_s": round(batch * 1000.0 / statistics.median(ms[arm]), 2),
+                            f"{key}_ranges_disjoint_from_native": bool(max(ms[arm]) < min(ms[True]) or min(ms[arm]) > max(ms[True])),
+                            f"{key}_speedup_over_native_fp32": round(ratio, 4), f"{key}_meets_bar": bool(ratio > 1.05),
+                            f"{key}_new_calls": calls(new), f"{key}_replaced_fp32_calls": old,
+                            f"{key}_routed_layers": len(runs[arm][0]._get_engine()._split2d_weights())})
+            rec.update(fp32_split_peak_memory_bytes={str(p): f32s_peak(p) for p in paths if p in (True, "stem", "f32s", "f32s_stem")},
+                       fp32_split_layer_32_to_32_full_resolution=layer_times_f32s(batch, hw))
         if "subpixel" in ms:
             # the sub-pixel arm against the native_2d arm of the same run; its convolution launches by entry point (the three new ones
             # and the skip halves on the conv2d family), and the 3x3 FLOPs per image it executes
