@@ -1,9 +1,11 @@
 """Static-shape step runner: the launch sequences of one training step captured in hipGraphs (hip_graph: true / U3D_GRAPH=1)."""
 from __future__ import annotations
 
+import contextlib
 import copy
 import ctypes
 import dataclasses
+import gc
 import os
 import threading
 from dataclasses import dataclass, field
@@ -19,6 +21,24 @@ from ._engine_base import *  # noqa: F401,F403  (explicit __all__: helpers, reco
 from ._engine_unet import UNet3DEngine
 
 
+
+
+@contextlib.contextmanager
+def _quiet_gc():
+    """Around a stream capture: Python's cycle collector runs NOW and not before the capture is over.  A model and its executor
+    point at each other, so a dropped model with captured steps (its hipGraphs, their private pool, streams and events) is freed by
+    the cycle collector, whenever its allocation counters trip — inside another model's capture as readily as anywhere, where the
+    finalizers' HIP calls hit a capturing thread (the process aborted there).  torch.cuda.graph() itself stopped collecting before
+    a capture in torch 2.9 (torch.compiler.config.force_cudagraph_gc).  Tensors whose last reference goes away during the capture
+    are still freed at once: that is reference counting, and part of the captured allocation pattern."""
+    was = gc.isenabled()
+    gc.collect()
+    gc.disable()
+    try:
+        yield
+    finally:
+        if was:
+            gc.enable()
 
 
 class GraphStep:
@@ -64,6 +84,17 @@ class GraphStep:
             engine.grad_sync = self.sync
         cur.wait_stream(side)
         torch.cuda.synchronize(dev)
+        with _quiet_gc():
+            self._capture(engine, dev, need_dx)
+        # Strong references to every PRE-CAPTURE device buffer the graphs dereference (ADVICE r03, medium): the pack descriptor
+        # tables' only other owner is a one-entry memo that the next eager forward with a different stale set replaces
+        # (WeightImages._plan: validation between training steps does exactly that), the packed
+        # images can be replaced in the cache, constants can be rebuilt — the caching allocator (or torch.cuda.empty_cache())
+        # would then hand the blocks to someone else while every later replay still reads / writes them.
+        self._pins = engine.graph_pins()
+
+    def _capture(self, engine: "UNet3DEngine", dev, need_dx: bool):
+        """both directions of the warmed-up step into `g_fwd` / `g_bwds`, one private pool"""
         self.pool = torch.cuda.graph_pool_handle()
         self.g_fwd = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.g_fwd, pool=self.pool, capture_error_mode="thread_local"):
@@ -94,12 +125,6 @@ class GraphStep:
             torch.cuda.synchronize(dev)
         finally:
             engine.grad_sync = self.sync
-        # Strong references to every PRE-CAPTURE device buffer the graphs dereference (ADVICE r03, medium): the pack descriptor
-        # tables' only other owner is a one-entry memo that the next eager forward with a different stale set replaces
-        # (WeightImages._plan: validation between training steps does exactly that), the packed
-        # images can be replaced in the cache, constants can be rebuilt — the caching allocator (or torch.cuda.empty_cache())
-        # would then hand the blocks to someone else while every later replay still reads / writes them.
-        self._pins = engine.graph_pins()
 
     def forward(self, x: torch.Tensor):
         self.static_x.copy_(x)

@@ -22,7 +22,7 @@ def _mk(name, **kw):
     from pytorch3dunet_amd.unet3d.model import get_model
 
     torch.manual_seed(0)
-    m = get_model(dict(name=name, in_channels=1, out_channels=1, final_sigmoid=True, layer_order="gcr", **kw))
+    m = get_model({**dict(name=name, in_channels=1, out_channels=1, final_sigmoid=True, layer_order="gcr"), **kw})
     with torch.no_grad():
         for k, p in m.named_parameters():
             if "groupnorm" in k:
@@ -39,20 +39,28 @@ def _batches(shapes, seed):
     return out
 
 
-def _train(model, batches, lr=1e-2):
+def _train(model, batches, lr=1e-2, loss=None, xgrads=None, opt=None):
+    """SGD-with-momentum steps over `batches`; `loss(probs, logits, target)` defaults to the fused BCEDiceLoss on the logits.  An input
+    that requires grad has its gradient appended to `xgrads` (and cleared) every step; `opt` continues an earlier call's optimizer."""
     from pytorch3dunet_amd.unet3d.losses import BCEDiceLoss
 
-    crit = BCEDiceLoss()
-    opt = torch.optim.SGD(model.parameters(), lr=lr, momentum=0.9)
+    if loss is None:
+        crit = BCEDiceLoss()
+        loss = lambda probs, logits, t: crit(logits, t)  # noqa: E731
+    if opt is None:
+        opt = torch.optim.SGD(model.parameters(), lr=lr, momentum=0.9)
     model.train()
     losses, grads = [], []
     for x, t in batches:
         out, logits = model(x, return_logits=True)
-        loss = crit(logits, t)
+        value = loss(out, logits, t)
         opt.zero_grad()
-        loss.backward()
+        value.backward()
         grads.append([p.grad.detach().clone() for p in model.parameters()])
-        losses.append(loss.detach().clone())
+        losses.append(value.detach().clone())
+        if x.grad is not None and xgrads is not None:
+            xgrads.append(x.grad.detach().clone())
+            x.grad = None
         opt.step()
     torch.cuda.synchronize()
     return losses, grads
