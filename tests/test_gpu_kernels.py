@@ -818,6 +818,8 @@ def test_replica_rows_of_the_other_statistics_producers():
 
 @pytest.mark.parametrize("N,C,size", [(2, 8, (8, 12, 16)), (1, 5, (9, 13, 11)), (1, 32, (4, 6, 2)), (2, 64, (8, 16, 16))])
 def test_maxpool_forward_backward_merge(N, C, size):
+    """pool forward + the merge with a plain skip gradient, no fused GroupNorm backward, ReLU mask on.
+    The remaining arms (coef table, no / fused skip gradient, relu_mask = 0, the scalar kernel forced by Cdg) are in test_gpu_pass_kernels.py."""
     U, nat, VSrc, _p, _stream = _mods()
     torch.manual_seed(C)
     D, H, W = size
