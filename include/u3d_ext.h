@@ -61,6 +61,16 @@ int u3d_conv3d_wgrad_f32s_supported(int Cin, int Cout);
 long long u3d_wgrad_f32s_workspace_floats(int N, int D, int H, int W, int Cin, int Cout);
 int u3d_conv3d_wgrad_f32s(int device, u3d_stream_t stream, const float* x, const float* affine, const float* dz, float* dw, int dw_cin_stride,
                           int N, int D, int H, int W, int Cin, int Cout, float* workspace, long long workspace_floats);
+/* ---- the residual epilogue of a ResidualUNet2D in fp32_split (`native_2d_residual_fp32_split: true`; csrc/u3d_conv2d_f32s.h) ------
+ * u3d_conv2d_f32s (below: arithmetic, rounding points, mode-0 images of u3d_pack_weights2d_f32s, envelope of u3d_conv2d_f32s_supported,
+ * replica rows, no split-K) on ONE real source x (N,H,W,Cin), plus the tail of a ResNetBlock: the twin of u3d_conv2d_res_reps.
+ *   u3d_conv2d_f32s_res                      out (N,H,W,Cout) = [relu](conv2d(a * x + b, w) + residual); residual (N,H,W,Cout) fp32, 16-byte
+ *              aligned, added in fp32 to the signed accumulator — before the ReLU and before the statistics, never rounded to bf16;
+ *              out_stats optional, double[stat_reps][N][Cout][2] += (sum y, sum y^2) of the STORED values.  residual may alias out: the
+ *              lane that writes an element has read it first.  A NULL or unaligned residual, or channel counts outside the envelope:
+ *              U3D_EINVAL with u3d_last_error() set, nothing launched. */
+int u3d_conv2d_f32s_res(int device, u3d_stream_t stream, const float* x, const float* affine, const void* packed_w, float* out, int N,
+                        int H, int W, int Cin, int Cout, int relu, double* out_stats, int stat_reps, const float* residual);
 /* ---- the 3x3 convolutions of a UNet2D in fp32_split (`native_2d_fp32_split: true`; csrc/u3d_conv2d_f32s.h, a header of
  * csrc/u3d_wgrad_f32s.hip) ------
  * The twins of u3d_conv2d_ex_reps / u3d_conv2d_wgrad with fp32-grade arithmetic on v_mfma_f32_32x32x16_bf16.  Tensors are fp32 NHWC,

@@ -20,6 +20,8 @@
 // conflict-free ds_read_b128 pattern of that kernel), double-buffered: 63936 bytes per block, two blocks per CU.  Per tap a wave reads
 // 3 x 2 A fragments and 3 x NT B fragments for 6 * 2 * NT MFMAs; the B fragments stream from the packed images one tap ahead.
 // NO split-K in this version: a small grid at the bottom of the U runs its whole channel reduction in one block.
+// The RES variants (u3d_conv2d_f32s_res, `native_2d_residual_fp32_split: true`: conv3 of a ResidualUNet2D's ResNetBlock) add the fp32
+// residual to the signed sum in the epilogue, before the ReLU and the statistics.
 //
 // Weight gradient (c2s_wgrad_kernel): a block of 9 waves owns one (32 co, 32 ci) cell and a contiguous range of 16 x 16 pixel tiles; the
 // three parts of the 18 x 18 halo of g and of the 256 pixels of dz sit in LDS as [part][pixel][32 channels] (3 x 20736 + 3 x 16384 =
@@ -118,6 +120,7 @@ struct C2sParams {
     int C0, C1, H1, W1;
     int nchunks, ntg, ncb, ty, tx;
     int relu, stat_reps;
+    const float* residual;  // RES: (N,H,W,Cout) fp32, added to the signed sum before the ReLU and the statistics; may alias `out`
 };
 
 // per-block statistics, as c2b_flush_stats of csrc/u3d_conv2d_bf16.hip: column sums s[nt][0..3] = (sum v, sum v^2, sum v, sum v * gx)
@@ -159,7 +162,9 @@ __device__ __forceinline__ void c2s_flush_stats(const C2sParams& p, float* red, 
 }
 
 // V = 0: single tensors.  V = 1 / 2: x / gx is a virtual concat (C0 and C1 multiples of 32: a staged chunk / an n-tile lies in one source)
-template <int NT, int V>
+// RES (u3d_conv2d_f32s_res, V = 0 only): out = [relu](conv + residual), the tail of a ResNetBlock — the fp32 residual is read with the
+// store's access pattern (lane = channel, register = pixel row) by the lane that then writes the element, so it may alias `out`
+template <int NT, int V, bool RES = false>
 __global__ __launch_bounds__(256, 2) void c2s_conv_kernel(const C2sParams p) {
     constexpr bool VX = V == 1, VG = V == 2;
     using namespace c2s;
@@ -321,6 +326,7 @@ __global__ __launch_bounds__(256, 2) void c2s_conv_kernel(const C2sParams p) {
                 if (y >= H || x >= W) continue;
                 float v = sgn * acc[mt][nt][r];
                 const size_t o = ((size_t)(n * H + y) * W + x) * p.Cout + co;
+                if constexpr (RES) v += p.residual[o];
                 if (p.relu) v = fmaxf(v, 0.f);
                 p.out[o] = v;
                 s[nt][0] += v;
@@ -341,16 +347,17 @@ __global__ __launch_bounds__(256, 2) void c2s_conv_kernel(const C2sParams p) {
     if (p.out_stats || p.gstats) c2s_flush_stats<NT>(p, reinterpret_cast<float*>(lds), s, n, cb, t);  // (the loop ended on a barrier)
 }
 
-template <int NT, int V>
+template <int NT, int V, bool RES = false>
 int c2s_conv_launch_as(const C2sParams& p, long long blocks, hipStream_t stream) {
-    U3D_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&c2s_conv_kernel<NT, V>), hipFuncAttributeMaxDynamicSharedMemorySize,
+    U3D_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&c2s_conv_kernel<NT, V, RES>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 c2s::LDS_BYTES));
-    hipLaunchKernelGGL((c2s_conv_kernel<NT, V>), dim3((unsigned)blocks), dim3(256), c2s::LDS_BYTES, stream, p);
+    hipLaunchKernelGGL((c2s_conv_kernel<NT, V, RES>), dim3((unsigned)blocks), dim3(256), c2s::LDS_BYTES, stream, p);
     U3D_LAUNCH_CHECK();
     return 0;
 }
 
-// the one launcher of u3d_conv2d_f32s (vmode 0 / 1) and u3d_conv2d_f32s_dgrad (vmode 0 / 2); K contraction, Nn produced channels
+// the one launcher of u3d_conv2d_f32s (vmode 0 / 1), u3d_conv2d_f32s_dgrad (vmode 0 / 2) and u3d_conv2d_f32s_res (vmode 0 with
+// p.residual: the RES variants); K contraction, Nn produced channels
 int c2s_conv_launch(const char* who, C2sParams p, int vmode, u3d_stream_t stream) {
     p.nchunks = p.Cin / c2s::CC;
     p.ntg = p.Cout / 32;
@@ -362,6 +369,7 @@ int c2s_conv_launch(const char* who, C2sParams p, int vmode, u3d_stream_t stream
     const long long blocks = (long long)p.N * p.ty * p.tx * p.ncb;
     U3D_REQUIRE(blocks < (1LL << 31), "%s: grid too large", who);
     hipStream_t s = (hipStream_t)stream;
+    if (p.residual) return nt == 2 ? c2s_conv_launch_as<2, 0, true>(p, blocks, s) : c2s_conv_launch_as<1, 0, true>(p, blocks, s);
     if (nt == 2) return vmode == 0 ? c2s_conv_launch_as<2, 0>(p, blocks, s) : vmode == 1 ? c2s_conv_launch_as<2, 1>(p, blocks, s)
                                                                                          : c2s_conv_launch_as<2, 2>(p, blocks, s);
     return vmode == 0 ? c2s_conv_launch_as<1, 0>(p, blocks, s) : vmode == 1 ? c2s_conv_launch_as<1, 1>(p, blocks, s)
@@ -623,6 +631,29 @@ extern "C" int u3d_conv2d_f32s(int device, u3d_stream_t stream, const float* p0,
     p.relu = relu ? 1 : 0;
     p.stat_reps = stat_reps;
     return c2s_conv_launch("u3d_conv2d_f32s", p, virt ? 1 : 0, stream);
+}
+
+extern "C" int u3d_conv2d_f32s_res(int device, u3d_stream_t stream, const float* x, const float* affine, const void* packed_w, float* out,
+                                   int N, int H, int W, int Cin, int Cout, int relu, double* out_stats, int stat_reps, const float* residual) {
+    U3D_ENTER(device);
+    U3D_REQUIRE(c2s_fwd_ok(Cin, Cout), "u3d_conv2d_f32s_res: (%d -> %d) channels are outside the split envelope (Cin %% 16, Cout %% 32)", Cin,
+                Cout);
+    U3D_REQUIRE(residual != nullptr, "u3d_conv2d_f32s_res: residual is NULL (u3d_conv2d_f32s is the convolution without one)");
+    U3D_REQUIRE(x && packed_w && out && stat_reps >= 1 && c2s_dims_ok(N, H, W), "u3d_conv2d_f32s_res: bad argument (N * H * W must be < 2^31)");
+    U3D_REQUIRE(wf_aligned(x) && wf_aligned(affine) && wf_aligned(packed_w) && wf_aligned(out) && wf_aligned(residual),
+                "u3d_conv2d_f32s_res: pointers must be 16-byte aligned");
+    C2sParams p = {};
+    p.x = x;
+    p.affine = affine;
+    p.wp = reinterpret_cast<const wf_bf16x8*>(packed_w);
+    p.out = out;
+    p.out_stats = out_stats;
+    p.residual = residual;
+    p.N = N, p.H = H, p.W = W, p.Cin = Cin, p.Cout = Cout;
+    p.C0 = Cin;
+    p.relu = relu ? 1 : 0;
+    p.stat_reps = stat_reps;
+    return c2s_conv_launch("u3d_conv2d_f32s_res", p, 0, stream);
 }
 
 extern "C" int u3d_conv2d_f32s_dgrad(int device, u3d_stream_t stream, const float* dz, const void* packed_w, float* dg, int N, int H, int W,

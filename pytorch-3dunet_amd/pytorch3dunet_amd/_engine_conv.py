@@ -406,7 +406,8 @@ class ConvLayers:
                  Cin, c.Cout, _p(ws), ws.numel(), flops=54.0 * Cin * c.Cout * c.N * c.D * c.H * c.W)
 
     def _split2d_counts(self, C0: int, C1: int, Cout: int) -> bool:
-        """THE rule for a UNet2D under `native_2d_fp32_split`, stated once, on channel counts: a 3x3 layer of the `conv2d` family runs
+        """THE rule for a UNet2D under `native_2d_fp32_split` (and for conv2 / conv3 of a ResidualUNet2D's blocks under
+        `native_2d_residual_fp32_split`: always a single source), stated once, on channel counts: a 3x3 layer of the `conv2d` family runs
         forward, data gradient and weight gradient on the six-product kernels of the extension library (csrc/u3d_conv2d_f32s.h) when the key
         is on and — a single source (C1 == 0) — both channel counts are multiples of 32, or — a decoder's virtual concat — C0, C1 and Cout
         all are.  A 16 -> 32 layer, the first layer and odd counts keep the fp32 `conv2d` kernels.  Asked by `_split2d` (forward; backward
@@ -774,9 +775,13 @@ class ConvLayers:
         # with a residual (ResidualUNet2D's conv3): out = [relu](conv + residual) in the epilogue (u3d_conv2d_res_reps)
         assert c.D == 1
         if c.f32s:  # (`native_2d_fp32_split`, `_split2d`: six bf16 products of split operands, csrc/u3d_conv2d_f32s.h; no split-K scratch)
-            assert c.residual is None
             wp = self.images.get(c.conv.weight, Kind.F32S_FWD2D, c.dev)
             ystats = c.take_stats(self.stat_reps)
+            if c.residual is not None:  # (`native_2d_residual_fp32_split`: a ResNetBlock's conv3 in a pre-norm order, one real source)
+                assert c.src.t1 is None
+                nat.call("u3d_conv2d_f32s_res", c.dev.index, _stream(c.dev), _p(c.src.t0), _p(c.affine), _p(wp), _p(c.y), c.N, c.H, c.W,
+                         c.Ctot, c.Cout, c.relu, *_tab(ystats), _p(c.residual), flops=18.0 * c.Ctot * c.Cout * c.N * c.H * c.W)
+                return ystats
             nat.call("u3d_conv2d_f32s", c.dev.index, _stream(c.dev), *self._f32s_src(c.src), _p(c.affine), _p(wp), _p(c.y), c.N, c.H, c.W,
                      c.Cout, c.relu, *_tab(ystats), flops=18.0 * c.Ctot * c.Cout * c.N * c.H * c.W)
             return ystats
@@ -893,7 +898,7 @@ class ConvLayers:
                          sub, b16, *(split[1:] if split is not None else (None, None)), plus)
         family = self._fwd_family(call, residual)
         call.c16 = family in ("conv2d_bf16", "bf16") and self._c16(Ctot, Cout)
-        call.f32s = family == "conv2d" and residual is None and self._split2d(src, Cout)
+        call.f32s = family == "conv2d" and self._split2d(src, Cout)  # (a residual rides in `u3d_conv2d_f32s_res`'s epilogue)
         dmod = getattr(sc, "dropout", None) if spec.drop == "d" else (getattr(sc, "dropout2d", None) if spec.drop == "D" else None)
         rec = None
         if tape is not None:

@@ -32,7 +32,8 @@ class ResUNetEngine(UNet3DEngine):
     convolution run on the FP32 vector units (csrc/u3d_res.hip).
 
     ResidualUNet2D under `native_2d_residual` and the keys that imply it (unet3d/native2d.py; `self.is2d`): (N,C,H,W) runs as (N,C,1,H,W);
-    the 3x3 convolutions take the `conv2d` / `conv2d_bf16` families (`_bf16_routed`; both fuse `out += residual`), the pools the
+    the 3x3 convolutions take the `conv2d` / `conv2d_bf16` families (`_bf16_routed`; both fuse `out += residual`; under
+    `native_2d_residual_fp32_split` the `conv2d` layers inside `_split2d_counts` run the six-product kernels, u3d_conv2d_f32s_res), the pools the
     u3d_maxpool2d_* twins and the decoders ConvTranspose2d (u3d_convtr2d_*; `_bf16_convtr2d`: the bf16 twins) before the same joining
     kernels at D = 1; the t8 and sub-pixel branches stay off, the 1x1 convolutions and every activation tensor stay fp32."""
 
@@ -83,6 +84,14 @@ class ResUNetEngine(UNet3DEngine):
 
     def _virtual_weights(self):
         return set()  # summation joining: every 3x3x3 conv reads one real tensor
+
+    def _split2d_weights(self) -> set:
+        """ids of the conv weights `_split2d` routes (`native_2d_residual_fp32_split`; empty with the key off): conv2 and conv3 of every
+        block, each on one real source of the block's width"""
+        if not self.split2d:
+            return set()
+        return {id(sc.conv.weight) for _, bm in self.enc + self.dec for sc in (bm.conv2, bm.conv3)
+                if self._split2d_counts(sc.conv.in_channels, 0, sc.conv.out_channels)}
 
     def _t8_weights(self):
         # (`_up_family`'s "t8" row without the library's word on the channel counts: the cache packs those the library takes)

@@ -70,8 +70,9 @@ class UNet3DEngine(ConvLayers):
         # `_split_fwd` paths stay off)
         self.split = model.compute_split and not self.is2d
         # opt-in `native_2d_fp32_split`: the 3x3 layers of a UNet2D inside `_split2d` on the six-product Conv2d kernels of the extension
-        # library (csrc/u3d_conv2d_f32s.h: u3d_conv2d_f32s, u3d_conv2d_f32s_dgrad, u3d_conv2d_wgrad_f32s), all three directions
-        self.split2d = keys.native_2d_fp32_split
+        # library (csrc/u3d_conv2d_f32s.h: u3d_conv2d_f32s, u3d_conv2d_f32s_dgrad, u3d_conv2d_wgrad_f32s), all three directions;
+        # `native_2d_residual_fp32_split`: the same for conv2 / conv3 of a ResidualUNet2D's blocks (u3d_conv2d_f32s_res: the residual epilogue)
+        self.split2d = keys.native_2d_fp32_split or keys.native_2d_residual_fp32_split
         # opt-in `fp32_split_wgrad`: ... and the weight gradients inside `_split_wgrad` on the six-product kernel of the extension library
         # (csrc/u3d_wgrad_f32s.hip, u3d_conv3d_wgrad_f32s)
         self.split_wgrad = bool(getattr(model, "fp32_split_wgrad", False))

@@ -129,7 +129,7 @@ PART_SYMBOLS = tuple(_PART_PROTOS)
 ALL_SYMBOLS = EXPORTED_SYMBOLS + PART_SYMBOLS  # every u3d_* the library exports: u3d.h's own declarations, then its parts'
 # the extension library's C-ABI (include/u3d_ext.h, a header in the form of a part: u3d.h does NOT include it): the 16-channel bf16 entry
 # points of a UNet3D (`bf16_stem`), the split weight gradient (`fp32_split_wgrad`) and the 3x3 convolutions of a UNet2D in fp32_split
-# (`native_2d_fp32_split`).  The core's tables above do not know these names; `call` resolves them in `get_ext_lib()`.
+# (`native_2d_fp32_split`; with the residual epilogue: a ResidualUNet2D's, `native_2d_residual_fp32_split`).  The core's tables above do not know these names; `call` resolves them in `get_ext_lib()`.
 EXT_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "u3d_ext.h")
 EXT_LIB_PATH = os.environ.get("U3D_EXT_LIB_PATH") or os.path.join(os.path.dirname(LIB_PATH), "libu3d_ext_hip.so")
 _EXT_PROTOS = read_part(EXT_HEADER_PATH, {**_PROTOS, **_PART_PROTOS})

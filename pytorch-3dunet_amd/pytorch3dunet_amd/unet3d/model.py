@@ -105,7 +105,8 @@ class AbstractUNet(nn.Module):
             if basic_module is not DoubleConv and not self.keys_2d.native_2d_residual:
                 reasons.append(f"2-D model with {basic_module.__name__} (native_2d covers DoubleConv blocks; a ResidualUNet2D needs "
                                "native_2d_residual: true)")
-            if not (self.keys_2d.native_2d_bf16 or self.keys_2d.native_2d_residual_bf16 or self.keys_2d.native_2d_fp32_split) and (
+            if not (self.keys_2d.native_2d_bf16 or self.keys_2d.native_2d_residual_bf16 or self.keys_2d.native_2d_fp32_split
+                    or self.keys_2d.native_2d_residual_fp32_split) and (
                     compute_dtype not in (None, "fp32", "float32") or
                     os.environ.get("U3D_BF16", "0") == "1" or os.environ.get("U3D_F32_SPLIT", "0") == "1"):
                 reasons.append(f"2-D model with compute_dtype {compute_dtype!r} (native_2d is fp32; a UNet2D in bf16 needs "

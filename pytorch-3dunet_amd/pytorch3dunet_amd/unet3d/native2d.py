@@ -4,7 +4,7 @@ A 2-D model stays outside the native executor unless a key is set in the YAML's 
 variable is "1" (the variable is the key's DEFAULT: an explicit `key: false` beats it).  A key means something only to the 2-D class
 built from its block type; every other class ignores it entirely, a contradicting compute_dtype next to it included.  A fp32 key next
 to compute_dtype bf16 WITHOUT the bf16 key of its class stays on the warning path (and next to compute_dtype fp32_split without
-`native_2d_fp32_split`).  Two keys that force different precisions contradict each other.
+`native_2d_fp32_split` / `native_2d_residual_fp32_split`).  Two keys that force different precisions contradict each other.
 
 A new key is one row of KEYS (and one kernel-family entry in _engine_conv.py); `unet3d.model` derives its keyword list from the rows."""
 import dataclasses
@@ -32,6 +32,10 @@ KEYS = (
         "u3d_conv2d_bf16.hip", "also the decoders' ConvTranspose2d with both channel counts % 32 take bf16 operands, all three directions"),
     Key("native_2d_residual_bf16", "U3D_NATIVE_2D_RESIDUAL_BF16", ResNetBlock, "native_2d_residual", "bf16", None, "u3d_conv2d_bf16.hip",
         "the 3x3 layers with both channel counts % 32 take bf16 MFMA operands (fp32 residual epilogue); everything else stays fp32"),
+    Key("native_2d_residual_fp32_split", "U3D_NATIVE_2D_RESIDUAL_FP32_SPLIT", ResNetBlock, "native_2d_residual", "fp32_split", None,
+        "u3d_conv2d_f32s.h",
+        "the 3x3 layers (conv2, conv3) of the blocks whose width is % 32 on six bf16 MFMA products of exactly split fp32 operands, all "
+        "three directions, fp32-grade (fp32 residual epilogue); conv1, ConvTranspose2d and everything else stay on the fp32 kernels"),
     Key("native_2d_residual", "U3D_NATIVE_2D_RESIDUAL", ResNetBlock, "native_2d", None, None, "u3d_conv2d.hip, u3d_res.hip",
         "a fp32 ResidualUNet2D on the residual executor at D = 1; native_2d alone leaves it on the warning path"),
     Key("native_2d_bf16_vcat", "U3D_NATIVE_2D_BF16_VCAT", DoubleConv, "native_2d_bf16", "bf16", None, "u3d_conv2d_bf16.hip",

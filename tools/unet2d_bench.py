@@ -60,7 +60,10 @@ record adds the arm's ms per step of every round with its median and range next 
 disjoint, the speed-up of the medians and the verdict against the project's bar for a speed mode (more than 5 % faster than the
 `native_2d` arm of the same run), the new entry points per call next to the fp32 launches they replace (difference of the two arms'
 totals), peak memory of one step per arm, and the three launches of ONE full-resolution 32 -> 32 layer on the new kernels against the
-three fp32 launches they replace (HIP events around each launch, median of 5, same process).
+three fp32 launches they replace (HIP events around each launch, median of 5, same process).  On the ResidualUNet2D configurations
+(`--configs resunet2d_515,resunet2d --fp32-split`) the arm is `native_2d_residual_fp32_split: true` against the `native_2d_residual` arm
+(conv2 / conv3 of every block on the six-product kernels, conv3 with the residual epilogue u3d_conv2d_f32s_res): the same record — with
+the stock arm's median and range next to them — without the one-layer timing.
 
   python tools/unet2d_bench.py [--configs confocal,dsb2018] [--fp32-split] [--batch N] [--steps 10] [--warmup 3] [--bf16] [--stem] [--vcat] [--bf16-subpixel] [--subpixel] [--subpixel-plus]   (--batch: every config's own default)"""
 import argparse
@@ -158,7 +161,9 @@ def make(cfg, native, dev):
 
     torch.manual_seed(0)
     extra = {}
-    if native in ("f32s", "f32s_stem"):
+    if native == "f32s" and _residual(cfg):
+        extra, native = dict(native_2d_residual_fp32_split=True), True
+    elif native in ("f32s", "f32s_stem"):
         extra, native = dict(native_2d_fp32_split=True, **(dict(native_2d_stem=True) if native == "f32s_stem" else {})), True
     elif native == "subpixel":
         extra, native = dict(native_2d_subpixel=True), True
@@ -273,7 +278,8 @@ def main():
     ap.add_argument("--bf16-subpixel", action="store_true", help="with --bf16 --stem --vcat: also time the UNet2D step with native_2d_bf16_subpixel on top of them")
     ap.add_argument("--subpixel", action="store_true", help="also time the UNet2D step with native_2d_subpixel next to native_2d")
     ap.add_argument("--subpixel-plus", action="store_true", help="also time the UNet2D step with native_2d_subpixel_plus (next to --subpixel)")
-    ap.add_argument("--fp32-split", action="store_true", help="also time the UNet2D step with native_2d_fp32_split next to native_2d (and, with --stem, with native_2d_stem)")
+    ap.add_argument("--fp32-split", action="store_true", help="also time the UNet2D step with native_2d_fp32_split next to native_2d (and, with --stem, with native_2d_stem); "
+                    "a ResidualUNet2D step with native_2d_residual_fp32_split next to native_2d_residual")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "unet2d_bench measures on the GPU"
     from pytorch3dunet_amd import _native as nat
@@ -301,9 +307,9 @@ def main():
                     paths.insert(paths.index("bf16_stem") + 1, "bf16_stem_vcat")
                     if a.bf16_subpixel:
                         paths.insert(paths.index("bf16_stem_vcat") + 1, "bf16_stem_vcat_subpixel")
-        if a.fp32_split and not _residual(cfg):
+        if a.fp32_split:  # (a ResidualUNet2D: `native_2d_residual_fp32_split`, no stem arm)
             paths.insert(1, "f32s")
-            if a.stem:
+            if a.stem and not _residual(cfg):
                 paths.insert(2, "f32s_stem")
         if a.subpixel_plus and not _residual(cfg):
             paths.insert(1, "subpixel_plus")
@@ -384,13 +390,16 @@ def main():
                 return {"median": round(statistics.median(v), 3), "range": [round(min(v), 3), round(max(v), 3)]}
 
             base_med = statistics.median(ms[True])
-            rec.update(native_ms=spread(ms[True]), fp32_split_bar="more than 1.05x the native_2d arm of the same run (medians)")
+            fp32_key = "native_2d_residual" if _residual(cfg) else "native_2d"
+            rec.update(native_ms=spread(ms[True]), fp32_split_bar=f"more than 1.05x the {fp32_key} arm of the same run (medians)")
+            if False in ms:
+                rec.update(stock_ms=spread(ms[False]))
             for arm in [p for p in ("f32s", "f32s_stem") if p in ms]:
                 afam = family_step(arm)
                 new = {k: v for k, v in afam.items() if "f32s" in k}
                 old = {k: {"calls": fam[k]["calls"] - afam.get(k, {"calls": 0})["calls"],
                            "ms": round(fam[k]["ms"] - afam.get(k, {"ms": 0.0})["ms"], 3)}
-                       for k in ("u3d_conv2d_ex_reps", "u3d_conv2d_wgrad") if k in fam}
+                       for k in ("u3d_conv2d_ex_reps", "u3d_conv2d_res_reps", "u3d_conv2d_wgrad") if k in fam}
                 ratio = base_med / statistics.median(ms[arm])
                 key = "fp32_split" if arm == "f32s" else "fp32_split_stem"
                 rec.update({f"{key}_ms_per_step": [round(v, 3) for v in ms[arm]], f"{key}_ms": spread(ms[arm]),
@@ -399,8 +408,9 @@ def main():
                             f"{key}_speedup_over_native_fp32": round(ratio, 4), f"{key}_meets_bar": bool(ratio > 1.05),
                             f"{key}_new_calls": calls(new), f"{key}_replaced_fp32_calls": old,
                             f"{key}_routed_layers": len(runs[arm][0]._get_engine()._split2d_weights())})
-            rec.update(fp32_split_peak_memory_bytes={str(p): f32s_peak(p) for p in paths if p in (True, "stem", "f32s", "f32s_stem")},
-                       fp32_split_layer_32_to_32_full_resolution=layer_times_f32s(batch, hw))
+            rec.update(fp32_split_peak_memory_bytes={str(p): f32s_peak(p) for p in paths if p in (True, "stem", "f32s", "f32s_stem")})
+            if not _residual(cfg):  # (a UNet2D's first routed layer; the residual configurations start at 64 channels)
+                rec.update(fp32_split_layer_32_to_32_full_resolution=layer_times_f32s(batch, hw))
         if "subpixel" in ms:
             # the sub-pixel arm against the native_2d arm of the same run; its convolution launches by entry point (the three new ones
             # and the skip halves on the conv2d family), and the 3x3 FLOPs per image it executes
